@@ -15,12 +15,16 @@ one per GPU, before anything in the parent touches the GPU) and relays rank 0's 
 --gpus, or fewer visible devices than ranks, is an error (non-zero exit), never a silently smaller run.
 
 Rank 0 prints ONE JSON line.  `value` is measured with every matrix product in exact fp32 (`--gemm fp32`, the reference's
-arithmetic); the split-bf16 policies are reported beside it under `other_gemm_arithmetic` with their measured gradient
+arithmetic).  A plain run sets up, warms up, times the --steps steps and prints the headline (`metric`, `value`, `unit`,
+`ms_per_step`, `dtype`, `config`, ...): nothing else runs.  `--dump-outputs DIR` writes what the last timed step computed
+(dump_outputs below).  `--full` adds every other measurement, each after the headline steps:
+the split-bf16 policies are reported beside it under `other_gemm_arithmetic` with their measured gradient
 error.  `roofline` is measured live with HIP events around the dominant kernel (the fp32-MFMA GEMM);
 `roofline_graph_attention` is the HBM-bound object->frame graph kernel the north_star names; `cpu_baseline` times the
 oracle (CPU port of the reference path) on a bounded sample on the host cores; `vs_pytorch_rocm_eager` is BASELINE
 configs[1]'s comparator: the same step run by PyTorch-ROCm eager (the oracle's torch modules moved to the GPU) in the
-same process; `batch_128` is the N = 1 figure at configs[3]'s per-GPU batch.
+same process; `batch_128` is the N = 1 figure at configs[3]'s per-GPU batch; with N > 1, `bucket_timeline`.  The `--no-*`
+options switch single legs of a `--full` run off.
 """
 import argparse
 import json
@@ -39,6 +43,27 @@ import torch  # noqa: E402
 PEAK_FP32_MFMA_TFLOPS = 157.3   # MI355X_MICROARCH.md: v_mfma_f32_32x32x2_f32 dense peak
 PEAK_BF16_MFMA_TFLOPS = 2500.0  # MI355X_MICROARCH.md: dense bf16 MFMA peak; a bf16x3 product costs 3 MFMA flops per flop
 PEAK_HBM_GBS = 8000.0           # MI355X_MICROARCH.md: HBM3E spec
+DUMP_SAMPLE = 1 << 21           # --dump-outputs: entries of the weights and of the gradient written (8 MB each in fp32)
+
+
+def dump_outputs(path, net, loss):
+    """--dump-outputs: what the last timed step handed its caller -- the loss, and the model it updated: the weights after
+    Adam and the gradient the step computed, both in named_parameters() order, as a fixed, seeded sample of DUMP_SAMPLE
+    entries (one per stride, the same positions in every run).  float64 loss.npy, float32 weights_sample.npy and
+    grads_sample.npy: 16 MB in all."""
+    import numpy as np
+    named = list(net.named_parameters())
+    G = net.grad_views()
+    w = torch.cat([p.detach().reshape(-1) for _, p in named])
+    g = torch.cat([G[n].reshape(-1) for n, _ in named])
+    k = min(DUMP_SAMPLE, w.numel())
+    stride = w.numel() // k
+    idx = np.arange(k, dtype=np.int64) * stride + np.random.RandomState(0).randint(0, stride, size=k)
+    idx = torch.from_numpy(idx).to(w.device)
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, 'loss.npy'), loss.detach().double().reshape(-1).cpu().numpy())
+    np.save(os.path.join(path, 'weights_sample.npy'), w[idx].float().cpu().numpy())
+    np.save(os.path.join(path, 'grads_sample.npy'), g[idx].float().cpu().numpy())
 
 
 def usable_cores():
@@ -736,6 +761,11 @@ def main():
     ap.add_argument('--gpus', type=int, default=1)
     ap.add_argument('--steps', type=int, default=10)
     ap.add_argument('--warmup', type=int, default=3)
+    ap.add_argument('--full', action='store_true',
+                    help='after the headline, also run every other measurement (roofline, other GEMM arithmetic, batch 128, side '
+                         'legs, CPU and PyTorch-ROCm eager baselines, the bucket timeline with N > 1)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write the loss and a fixed sample of the weights and gradient of the last timed step to DIR/*.npy')
     ap.add_argument('--batch', type=int, default=64, help='clips per GPU (BASELINE configs[1]: 64)')
     ap.add_argument('--shape', default='msvd', choices=['msvd', 'msrvtt'])
     ap.add_argument('--no-pass', action='store_true', help='skip the isolated graph-attention pass measurement')
@@ -864,15 +894,18 @@ def main():
     barrier()
     dt = time.perf_counter() - t0
     loss_v = float(loss)
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, net, loss)          # before anything below steps the model again
     launch = launch_mode(tr, not a.no_graphs)
     comm_info.update(tr.collectives_info())
-    # per-kernel HIP-event timing for the roofline objects (every rank runs it: the step has collectives)
-    nprof = max(1, min(5, a.steps))
-    prof = profile_eager_steps(net, tr, (frames, regions, caps, lens), eps, nprof)
-    barrier()
+    nprof, prof = max(1, min(5, a.steps)), None
+    if a.full:
+        # per-kernel HIP-event timing for the roofline objects (every rank runs it: the step has collectives)
+        prof = profile_eager_steps(net, tr, (frames, regions, caps, lens), eps, nprof)
+        barrier()
     # the same step under the other GEMM arithmetic policies (informational; `value` is the --gemm policy)
     other = {}
-    if world == 1:
+    if world == 1 and a.full:
         for mode in ('fp32', 'x3_bwd', 'x3_all'):
             if mode == a.gemm:
                 continue
@@ -907,7 +940,7 @@ def main():
         del probe, grads
         net.gemm_precision = a.gemm
     b128 = None
-    if world == 1 and not a.no_batch128 and a.batch != 128 and a.shape == 'msvd':
+    if a.full and world == 1 and not a.no_batch128 and a.batch != 128 and a.shape == 'msvd':
       try:                                   # (a side leg: its failure must not cost the headline line)
         # BASELINE configs[3] runs 128 clips per GPU: its "8 GPUs vs 1" needs the N = 1 number at that batch
         torch.cuda.empty_cache()
@@ -954,7 +987,8 @@ def main():
         every = [None] * world
         dist.all_gather_object(every, per_rank_ms[0])
         per_rank_ms = every
-        timeline = bucket_timeline(tr, (frames, regions, caps, lens), eps, dev, world)
+        if a.full:
+            timeline = bucket_timeline(tr, (frames, regions, caps, lens), eps, dev, world)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
     dt = float(tmax.item())
 
@@ -978,143 +1012,146 @@ def main():
         }
         if world > 1:
             out['per_rank_ms_per_step'] = per_rank_ms
-            out['bucket_timeline'] = timeline
-        gemm_flops = prof.pop('__gemm_flops_per_step__', None)
-        out['kernel_time_ms_per_step'] = {k: round(v['ms_total'] / nprof, 3) for k, v in prof.items()}
-        rl = gemm_roofline(prof, nprof)
-        if rl:
-            out['roofline'] = rl
-        sk = {}
-        for k in sorted(prof):
-            if 'streamk' in k:
-                r1 = gemm_roofline({k: prof[k]}, nprof)
-                st_ = r1['symbol_total']          # (per operand layout: the symbol-wide figures; every shape below)
-                sk[k] = {'achieved': st_['achieved'], 'peak': r1['peak'], 'unit': r1['unit'], 'frac': st_['frac'], 'traffic': st_['traffic'],
-                         'avg_launch_ms': st_['avg_launch_ms'], 'ms_per_step_in_this_kernel': r1['ms_per_step_in_this_kernel'],
-                         'launch_shapes': r1['launch_shapes']}
-        if sk:
-            out['roofline_stream_k'] = dict(sk, kernel='gemm_sk_kernel<...> (csrc/gemm_sk.hip): each call is ONE persistent launch; one entry per '
-                                                        'operand layout, with every launch shape of the step')
-        if gemm_flops:
-            # what the step EXECUTES: every dlsg_gemm call's 2 M N K as launched (the decoder's K / V projections hoisted out of the word
-            # loop, no input gradients for regions / frames) + the MFMA work outside dlsg_gemm: the persistent BiLSTM recurrence
-            # (forward and backward through time, 2 B 4H H per step and direction) and the object->frame graph kernels
-            Hh = args.visual_hidden_size
-            Tt = args.max_frames
-            bil = 2.0 * a.batch * 4 * Hh * Hh * Tt * 2 * 2 if bool(getattr(net.ops, 'persistent_bilstm', False)) else 0.0
-            graph = a.batch * 2 * (44.3e6 + 133e6) * (args.num_obj / 16.0)
-            tot = gemm_flops + bil + graph
-            out['whole_step_mfma_frac'] = {'executed_flops_per_step': tot, 'dlsg_gemm_calls': gemm_flops, 'persistent_bilstm': bil,
-                                           'graph_kernels': graph, 'TFLOPs': round(tot / (dt / a.steps) / 1e12, 2), 'peak': PEAK_FP32_MFMA_TFLOPS,
-                                           'frac': round(tot / (dt / a.steps) / 1e12 / PEAK_FP32_MFMA_TFLOPS, 4),
-                                           'flops_per_clip': round(tot / a.batch / 1e9, 3)}
-        tj = {}
-        try:
-            tj = json.load(open(os.path.join(ROOT, 'profiles', 'traffic.json'))).get('per_launch_shape', {})
-        except Exception:
+            if timeline is not None:
+                out['bucket_timeline'] = timeline
+        if a.full:
+            gemm_flops = prof.pop('__gemm_flops_per_step__', None)
+            out['kernel_time_ms_per_step'] = {k: round(v['ms_total'] / nprof, 3) for k, v in prof.items()}
+            rl = gemm_roofline(prof, nprof)
+            if rl:
+                out['roofline'] = rl
+            sk = {}
+            for k in sorted(prof):
+                if 'streamk' in k:
+                    r1 = gemm_roofline({k: prof[k]}, nprof)
+                    st_ = r1['symbol_total']          # (per operand layout: the symbol-wide figures; every shape below)
+                    sk[k] = {'achieved': st_['achieved'], 'peak': r1['peak'], 'unit': r1['unit'], 'frac': st_['frac'], 'traffic': st_['traffic'],
+                             'avg_launch_ms': st_['avg_launch_ms'], 'ms_per_step_in_this_kernel': r1['ms_per_step_in_this_kernel'],
+                             'launch_shapes': r1['launch_shapes']}
+            if sk:
+                out['roofline_stream_k'] = dict(sk, kernel='gemm_sk_kernel<...> (csrc/gemm_sk.hip): each call is ONE persistent launch; one entry per '
+                                                            'operand layout, with every launch shape of the step')
+            if gemm_flops:
+                # what the step EXECUTES: every dlsg_gemm call's 2 M N K as launched (the decoder's K / V projections hoisted out of the word
+                # loop, no input gradients for regions / frames) + the MFMA work outside dlsg_gemm: the persistent BiLSTM recurrence
+                # (forward and backward through time, 2 B 4H H per step and direction) and the object->frame graph kernels
+                Hh = args.visual_hidden_size
+                Tt = args.max_frames
+                bil = 2.0 * a.batch * 4 * Hh * Hh * Tt * 2 * 2 if bool(getattr(net.ops, 'persistent_bilstm', False)) else 0.0
+                graph = a.batch * 2 * (44.3e6 + 133e6) * (args.num_obj / 16.0)
+                tot = gemm_flops + bil + graph
+                out['whole_step_mfma_frac'] = {'executed_flops_per_step': tot, 'dlsg_gemm_calls': gemm_flops, 'persistent_bilstm': bil,
+                                               'graph_kernels': graph, 'TFLOPs': round(tot / (dt / a.steps) / 1e12, 2), 'peak': PEAK_FP32_MFMA_TFLOPS,
+                                               'frac': round(tot / (dt / a.steps) / 1e12 / PEAK_FP32_MFMA_TFLOPS, 4),
+                                               'flops_per_clip': round(tot / a.batch / 1e9, 3)}
             tj = {}
-
-        def o2v_traffic(key):
-            shp = list(prof[key]['shapes'])
-            ent = tj.get(key + ' | ' + shp[0]) if len(shp) == 1 else None
-            return ent.get('hbm_bytes_per_launch') if ent else None
-        o = prof.get('o2v_graph_fwd')
-        if o and o['ms_total'] > 0:
-            ach = o['work_total'] / (o['ms_total'] * 1e-3) / 1e9
-            out['roofline_graph_attention'] = {'kernel': 'o2v16_kernel (both encoder streams in one launch) + o2v_combine_kernel', 'bound': 'hbm',
-                                               'achieved': round(ach, 1), 'peak': PEAK_HBM_GBS, 'unit': 'GB/s',
-                                               'frac': round(ach / PEAK_HBM_GBS, 4), 'traffic': o2v_traffic('o2v_graph_fwd'),
-                                               'avg_launch_ms': round(o['ms_total'] / o['launches'], 4)}
-        ob = prof.get('o2v_graph_bwd')
-        if ob and ob['ms_total'] > 0:
-            ach = ob['work_total'] / (ob['ms_total'] * 1e-3) / 1e9
-            out['roofline_graph_attention_bwd'] = {'kernel': O2V_BWD_KERNELS, 'bound': 'hbm',
-                                                   'achieved': round(ach, 1), 'peak': PEAK_HBM_GBS, 'unit': 'GB/s',
-                                                   'frac': round(ach / PEAK_HBM_GBS, 4), 'traffic': o2v_traffic('o2v_graph_bwd'),
-                                                   'avg_launch_ms': round(ob['ms_total'] / ob['launches'], 4)}
-        if world == 1 and not a.no_pass:
-            # the graph-attention pass (object->frame graph x2, LatentPSL x2, self-attention core, decoder
-            # attention over cached K',V' x 26 steps) in isolation, 1024 clips in flight, algorithmic bytes 8.79 MB/clip
-            from dlsg_amd.passbench import run_graph_attention_pass
-            torch.cuda.empty_cache()
-            pr = run_graph_attention_pass(net.ops, B=1024)
-            ptraffic = None
             try:
-                ptraffic = (json.load(open(os.path.join(ROOT, 'profiles', 'traffic.json'))).get('graph_attention_pass_hbm_part_1024') or {}).get(
-                    'hbm_bytes_per_launch')
+                tj = json.load(open(os.path.join(ROOT, 'profiles', 'traffic.json'))).get('per_launch_shape', {})
             except Exception:
-                ptraffic = None
-            hs = pr['hbm_streaming_part']
-            try:                                   # the same part with 2048 clips in flight (launch ramp and tail amortised further)
-                torch.cuda.empty_cache()
-                pr2 = run_graph_attention_pass(net.ops, B=2048)['hbm_streaming_part']
-                more = {'clips': 2048, 'ms': pr2['ms'], 'achieved': pr2['achieved_GBps'], 'unit': 'GB/s',
-                        'frac': round(pr2['achieved_GBps'] / PEAK_HBM_GBS, 4)}
-            except Exception as e:                 # noqa: BLE001
-                more = {'error': '%s: %s' % (type(e).__name__, e)}
-                torch.cuda.synchronize()
-            torch.cuda.empty_cache()
-            out['roofline_graph_attention_pass'] = {
-                'kernel': 'o2v_fwd x2 + latent_psl_fwd x2 + sa_core_fwd: the HBM-streaming part of the SURVEY.md 8d forward pass '
-                          '(4.96 MB/clip), product kernels, 1024 clips in flight', 'bound': 'hbm',
-                'achieved': hs['achieved_GBps'], 'peak': PEAK_HBM_GBS, 'unit': 'GB/s',
-                'frac': round(hs['achieved_GBps'] / PEAK_HBM_GBS, 4), 'traffic': ptraffic, 'clips_per_s': hs['clips_per_s'],
-                'ms': hs['ms'], 'bytes_per_clip': hs['bytes_per_clip'], 'parts_ms': pr['parts_ms'], 'parts_GBps': pr['parts_GBps'],
-                'decoder_term_cache_resident': pr['decoder_term'], 'with_2048_clips_in_flight': more,
-                'whole_pass_incl_decoder_term': {'bytes_per_clip': pr['bytes_per_clip'], 'ms': pr['ms'],
-                                                 'GBps': pr['achieved_GBps'], 'clips_per_s': pr['clips_per_s']}}
-        if b128 is not None:
-            out['batch_128'] = b128
-        # the side legs must never cost the headline line: a failure in one of them is reported in its field
-        def leg(name, fn):
-            try:
-                out[name] = fn()
-            except Exception as e:                                   # noqa: BLE001
-                out[name] = {'error': '%s: %s' % (type(e).__name__, e)}
-                torch.cuda.synchronize()
+                tj = {}
 
-        def eager_leg():
-            eb = gpu_eager_baseline(dev, a.batch)
-            eb['speedup'] = round(out['value'] / eb['clips_per_s'], 2)
-            return eb
-        side = world == 1 and a.shape == 'msvd' and a.batch == 64
-        if side and not a.no_inference:
-            leg('inference', lambda: inference_leg(dev, a))
-        if side and not a.no_msrvtt:
-            leg('msrvtt_b64', lambda: msrvtt_leg(dev, a))
-        if side and not a.no_sustained:
-            def sus():
-                r = sustained_leg(dev, a)
-                r['vs_headline_ms_per_step'] = round(r['ms_per_step'] / out['ms_per_step'], 4)
-                return r
-            leg('sustained', sus)
-        if side and not a.no_dp_schedule and not a.no_graphs:
-            def dps():
-                r = dp_schedule_leg(dev, a, batches=(64, 128))
-                r['one_rank_ms_per_step'] = {'batch_64': out['ms_per_step'], 'batch_128': (out.get('batch_128') or {}).get('ms_per_step')}
-                return r
-            leg('dp_schedule_world1', dps)
-        if world == 1 and not a.no_eager_baseline and a.shape == 'msvd':
-            leg('vs_pytorch_rocm_eager', eager_leg)
-        if world == 1 and not a.no_gan and a.shape == 'msvd' and a.gemm == 'fp32' and not a.no_graphs:
-            # the product's GAN iteration runs here, in this process (every launch one of this repo's kernels); only the COMPARATOR
-            # -- the oracle stepped by PyTorch-ROCm eager: autograd's double backward over rocBLAS / MIOpen -- runs in a child
-            def gan_leg():
-                g = gan_iteration_leg(dev, a.batch, with_eager=False)
-                if not a.no_eager_baseline:
-                    e = child_leg('gan_eager', ['--batch', str(a.batch)], 900)
-                    g['vs_pytorch_rocm_eager'] = e.get('vs_pytorch_rocm_eager', e)
-                    if 'ms_per_iteration' in g['vs_pytorch_rocm_eager']:
-                        g['vs_pytorch_rocm_eager']['speedup'] = round(g['vs_pytorch_rocm_eager']['ms_per_iteration'] / g['ms_per_iteration'], 2)
-                return g
-            leg('gan_iteration', gan_leg)
-        if world == 1 and not a.no_cpu_baseline:
-            leg('cpu_baseline', cpu_baseline)
+            def o2v_traffic(key):
+                shp = list(prof[key]['shapes'])
+                ent = tj.get(key + ' | ' + shp[0]) if len(shp) == 1 else None
+                return ent.get('hbm_bytes_per_launch') if ent else None
+            o = prof.get('o2v_graph_fwd')
+            if o and o['ms_total'] > 0:
+                ach = o['work_total'] / (o['ms_total'] * 1e-3) / 1e9
+                out['roofline_graph_attention'] = {'kernel': 'o2v16_kernel (both encoder streams in one launch) + o2v_combine_kernel', 'bound': 'hbm',
+                                                   'achieved': round(ach, 1), 'peak': PEAK_HBM_GBS, 'unit': 'GB/s',
+                                                   'frac': round(ach / PEAK_HBM_GBS, 4), 'traffic': o2v_traffic('o2v_graph_fwd'),
+                                                   'avg_launch_ms': round(o['ms_total'] / o['launches'], 4)}
+            ob = prof.get('o2v_graph_bwd')
+            if ob and ob['ms_total'] > 0:
+                ach = ob['work_total'] / (ob['ms_total'] * 1e-3) / 1e9
+                out['roofline_graph_attention_bwd'] = {'kernel': O2V_BWD_KERNELS, 'bound': 'hbm',
+                                                       'achieved': round(ach, 1), 'peak': PEAK_HBM_GBS, 'unit': 'GB/s',
+                                                       'frac': round(ach / PEAK_HBM_GBS, 4), 'traffic': o2v_traffic('o2v_graph_bwd'),
+                                                       'avg_launch_ms': round(ob['ms_total'] / ob['launches'], 4)}
+            if world == 1 and not a.no_pass:
+                # the graph-attention pass (object->frame graph x2, LatentPSL x2, self-attention core, decoder
+                # attention over cached K',V' x 26 steps) in isolation, 1024 clips in flight, algorithmic bytes 8.79 MB/clip
+                from dlsg_amd.passbench import run_graph_attention_pass
+                torch.cuda.empty_cache()
+                pr = run_graph_attention_pass(net.ops, B=1024)
+                ptraffic = None
+                try:
+                    ptraffic = (json.load(open(os.path.join(ROOT, 'profiles', 'traffic.json'))).get('graph_attention_pass_hbm_part_1024') or {}).get(
+                        'hbm_bytes_per_launch')
+                except Exception:
+                    ptraffic = None
+                hs = pr['hbm_streaming_part']
+                try:                                   # the same part with 2048 clips in flight (launch ramp and tail amortised further)
+                    torch.cuda.empty_cache()
+                    pr2 = run_graph_attention_pass(net.ops, B=2048)['hbm_streaming_part']
+                    more = {'clips': 2048, 'ms': pr2['ms'], 'achieved': pr2['achieved_GBps'], 'unit': 'GB/s',
+                            'frac': round(pr2['achieved_GBps'] / PEAK_HBM_GBS, 4)}
+                except Exception as e:                 # noqa: BLE001
+                    more = {'error': '%s: %s' % (type(e).__name__, e)}
+                    torch.cuda.synchronize()
+                torch.cuda.empty_cache()
+                out['roofline_graph_attention_pass'] = {
+                    'kernel': 'o2v_fwd x2 + latent_psl_fwd x2 + sa_core_fwd: the HBM-streaming part of the SURVEY.md 8d forward pass '
+                              '(4.96 MB/clip), product kernels, 1024 clips in flight', 'bound': 'hbm',
+                    'achieved': hs['achieved_GBps'], 'peak': PEAK_HBM_GBS, 'unit': 'GB/s',
+                    'frac': round(hs['achieved_GBps'] / PEAK_HBM_GBS, 4), 'traffic': ptraffic, 'clips_per_s': hs['clips_per_s'],
+                    'ms': hs['ms'], 'bytes_per_clip': hs['bytes_per_clip'], 'parts_ms': pr['parts_ms'], 'parts_GBps': pr['parts_GBps'],
+                    'decoder_term_cache_resident': pr['decoder_term'], 'with_2048_clips_in_flight': more,
+                    'whole_pass_incl_decoder_term': {'bytes_per_clip': pr['bytes_per_clip'], 'ms': pr['ms'],
+                                                     'GBps': pr['achieved_GBps'], 'clips_per_s': pr['clips_per_s']}}
+            if b128 is not None:
+                out['batch_128'] = b128
+            # the side legs must never cost the headline line: a failure in one of them is reported in its field
+            def leg(name, fn):
+                try:
+                    out[name] = fn()
+                except Exception as e:                                   # noqa: BLE001
+                    out[name] = {'error': '%s: %s' % (type(e).__name__, e)}
+                    torch.cuda.synchronize()
+
+            def eager_leg():
+                eb = gpu_eager_baseline(dev, a.batch)
+                eb['speedup'] = round(out['value'] / eb['clips_per_s'], 2)
+                return eb
+            side = world == 1 and a.shape == 'msvd' and a.batch == 64
+            if side and not a.no_inference:
+                leg('inference', lambda: inference_leg(dev, a))
+            if side and not a.no_msrvtt:
+                leg('msrvtt_b64', lambda: msrvtt_leg(dev, a))
+            if side and not a.no_sustained:
+                def sus():
+                    r = sustained_leg(dev, a)
+                    r['vs_headline_ms_per_step'] = round(r['ms_per_step'] / out['ms_per_step'], 4)
+                    return r
+                leg('sustained', sus)
+            if side and not a.no_dp_schedule and not a.no_graphs:
+                def dps():
+                    r = dp_schedule_leg(dev, a, batches=(64, 128))
+                    r['one_rank_ms_per_step'] = {'batch_64': out['ms_per_step'], 'batch_128': (out.get('batch_128') or {}).get('ms_per_step')}
+                    return r
+                leg('dp_schedule_world1', dps)
+            if world == 1 and not a.no_eager_baseline and a.shape == 'msvd':
+                leg('vs_pytorch_rocm_eager', eager_leg)
+            if world == 1 and not a.no_gan and a.shape == 'msvd' and a.gemm == 'fp32' and not a.no_graphs:
+                # the product's GAN iteration runs here, in this process (every launch one of this repo's kernels); only the COMPARATOR
+                # -- the oracle stepped by PyTorch-ROCm eager: autograd's double backward over rocBLAS / MIOpen -- runs in a child
+                def gan_leg():
+                    g = gan_iteration_leg(dev, a.batch, with_eager=False)
+                    if not a.no_eager_baseline:
+                        e = child_leg('gan_eager', ['--batch', str(a.batch)], 900)
+                        g['vs_pytorch_rocm_eager'] = e.get('vs_pytorch_rocm_eager', e)
+                        if 'ms_per_iteration' in g['vs_pytorch_rocm_eager']:
+                            g['vs_pytorch_rocm_eager']['speedup'] = round(g['vs_pytorch_rocm_eager']['ms_per_iteration'] / g['ms_per_iteration'], 2)
+                    return g
+                leg('gan_iteration', gan_leg)
+            if world == 1 and not a.no_cpu_baseline:
+                leg('cpu_baseline', cpu_baseline)
         out['dtype_note'] = {'fp32': 'all products on fp32-input MFMA (exact fp32)',
                              'x3_bwd': 'forward: exact fp32 MFMA; backward products: fp32 operands split into bf16 hi+lo, 3 bf16 '
                                        'MFMAs per product, fp32 accumulate (rel. error ~1e-5)',
                              'x3_all': 'all products: fp32 operands split into bf16 hi+lo, 3 bf16 MFMAs per product, fp32 accumulate'}[a.gemm]
-        out['other_gemm_arithmetic'] = other
+        if a.full:
+            out['other_gemm_arithmetic'] = other
         # what the contract names first, then the legs the round's review asked for, then the rest (a reader that keeps only the
         # head or the tail of a long line still sees the headline objects)
         first = ['metric', 'value', 'unit', 'n_gpus', 'steps', 'warmup', 'ms_per_step', 'higher_is_better', 'scaling', 'vs_baseline',

@@ -25,7 +25,7 @@ def test_bench_two_ranks_prints_one_contract_line():
     env = dict(os.environ, DLSG_BENCH_ALL_RANKS_ON_DEVICE0='1', DLSG_BENCH_BACKEND='gloo', HSA_ENABLE_IPC_MODE_LEGACY='0')
     cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '2', '--master-addr', '127.0.0.1',
            '--master-port', str(_free_port()), os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '3', '--warmup', '2',
-           '--batch', '16']
+           '--batch', '16', '--full']
     r = subprocess.run(cmd, env=env, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=800)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith('{')]
@@ -35,6 +35,7 @@ def test_bench_two_ranks_prints_one_contract_line():
     assert d['unit'] == 'clips/s' and d['higher_is_better'] is True
     assert abs(d['value'] - 2 * 16 * 3 / (d['ms_per_step'] * 3 / 1e3)) <= 0.02 * d['value']   # whole-job aggregate
     assert d['config']['launch'] == 'hipGraph replay'
+    assert d['bucket_timeline'] and len(d['per_rank_ms_per_step']) == 2                        # (--full: the N > 1 extras)
 
 
 @pytest.mark.timeout(900)
