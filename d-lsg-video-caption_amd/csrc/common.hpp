@@ -83,11 +83,13 @@ __device__ __forceinline__ uint32_t mix32(uint32_t x) {
     x ^= x >> 16; x *= 0x7feb352dU; x ^= x >> 15; x *= 0x846ca68bU; x ^= x >> 16;
     return x;
 }
+__device__ __forceinline__ uint32_t counter_hash(uint64_t seed, uint32_t site, uint64_t idx) {
+    const uint32_t h = mix32((uint32_t)idx ^ mix32((uint32_t)(idx >> 32) + 0x9e3779b9U * site + (uint32_t)seed));
+    return mix32(h ^ (uint32_t)(seed >> 32));
+}
 __device__ __forceinline__ float drop_scale(uint64_t seed, uint32_t site, uint64_t idx, float p) {
     // returns 0 (dropped) or 1/(1-p) (kept)
-    uint32_t h = mix32((uint32_t)idx ^ mix32((uint32_t)(idx >> 32) + 0x9e3779b9U * site + (uint32_t)seed));
-    h = mix32(h ^ (uint32_t)(seed >> 32));
-    const float u = (float)(h >> 8) * (1.0f / 16777216.0f);
+    const float u = (float)(counter_hash(seed, site, idx) >> 8) * (1.0f / 16777216.0f);
     return u < p ? 0.f : 1.f / (1.f - p);
 }
 

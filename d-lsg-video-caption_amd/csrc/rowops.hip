@@ -625,6 +625,82 @@ __global__ __launch_bounds__(256) void select_embed_kernel(const float* __restri
     }
 }
 
+// (m, s) of an online log-sum-exp merged with (om, os); an empty side (max -inf) contributes nothing
+__device__ __forceinline__ void lse_merge(float& m, float& s, float om, float os) {
+    const float nm = fmaxf(m, om);
+    s = (m == -INFINITY ? 0.f : s * __expf(m - nm)) + (om == -INFINITY ? 0.f : os * __expf(om - nm));
+    m = nm;
+}
+
+// sampled word step (self-critical training): id = argmax_j (x_j / tau + g_j) with Gumbel noise g_j = -log(-log u_j), u_j from
+// the counter hash keyed (seed, site_sample, (row0 + r) * V + j) -- one pass over the row, the same word whatever the reduction
+// order (a replayed graph draws what the eager launch drew).  The same pass keeps an online max / sum-exp of x / tau for
+// logp[r] = log softmax(x / tau)[id].  tau == 0: argmax_kernel's choice (first maximum), logp of the untempered softmax.  Then
+// the gather of E[id] under the word-dropout stream of embed_fwd / select_embed (row row0 + r), and lens[r] (L on entry)
+// becomes t + 1 at the row's first end_id.  One block of 256 per row.
+__global__ __launch_bounds__(256) void sample_embed_kernel(const float* __restrict__ logits, int64_t ld, int V, float tau,
+                                                           const float* __restrict__ E, int64_t* __restrict__ ids_out,
+                                                           float* __restrict__ out, int64_t ldo, int W, float* __restrict__ logp,
+                                                           int64_t* __restrict__ lens, int t, int64_t end_id, float p,
+                                                           uint64_t seed, uint32_t site_word, uint32_t site_sample, int64_t row0,
+                                                           const uint64_t* seed_ptr) {
+    __shared__ float bv[4], bm[4], bs[4];
+    __shared__ int bi[4];
+    __shared__ int64_t chosen;
+    if (seed_ptr) seed += *seed_ptr;
+    const int r = blockIdx.x;
+    const float* x = logits + (int64_t)r * ld;
+    const bool gumbel = tau > 0.f;
+    const float sc = gumbel ? 1.f / tau : 1.f;
+    const uint64_t key0 = (uint64_t)(row0 + r) * (uint64_t)V;
+    float best = -INFINITY, m = -INFINITY, s = 0.f;
+    int idx = 0x7fffffff;
+    for (int j = threadIdx.x; j < V; j += blockDim.x) {
+        const float z = x[j] * sc;
+        float key = z;
+        if (gumbel) {
+            // u = (hi + 1/2) 2^-24 in (0, 1).  hi + 1/2 needs 25 bits above 2^23: there -log u = -log1p(-(1 - u)) with
+            // 1 - u = (2^24 - 1 - hi + 1/2) 2^-24 exact, so u never rounds to 1 and the noise stays finite
+            const uint32_t hi = counter_hash(seed, site_sample, key0 + j) >> 8;
+            const float e = hi < (1u << 23) ? -logf(((float)hi + 0.5f) * (1.0f / 16777216.0f))
+                                            : -log1pf(-((float)(0xFFFFFFu - hi) + 0.5f) * (1.0f / 16777216.0f));
+            key = z - logf(e);                          // a -inf logit stays -inf: never drawn
+        }
+        if (key > best || (key == best && j < idx)) { best = key; idx = j; }
+        if (z > m) { s = s * __expf(m - z) + 1.f; m = z; }
+        else if (z > -INFINITY) s += __expf(z - m);
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const float ov = __shfl_xor(best, o, 64);
+        const int oi = __shfl_xor(idx, o, 64);
+        if (ov > best || (ov == best && oi < idx)) { best = ov; idx = oi; }
+        const float om = __shfl_xor(m, o, 64), os = __shfl_xor(s, o, 64);
+        lse_merge(m, s, om, os);
+    }
+    const int w = threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 0) { bv[w] = best; bi[w] = idx; bm[w] = m; bs[w] = s; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int k = 1; k < 4; ++k) {
+            if (bv[k] > best || (bv[k] == best && bi[k] < idx)) { best = bv[k]; idx = bi[k]; }
+            lse_merge(m, s, bm[k], bs[k]);
+        }
+        const int64_t id = idx == 0x7fffffff ? 0 : idx;   // no maximum (a row of NaN / -inf): word 0, not an out-of-range row of E
+        chosen = id;
+        ids_out[r] = id;
+        logp[r] = x[id] * sc - m - logf(s);
+        if (id == end_id && lens[r] > t) lens[r] = t + 1;
+    }
+    __syncthreads();
+    const int64_t id = chosen;
+    for (int j = threadIdx.x; j < W; j += blockDim.x) {
+        float v = E[id * W + j];
+        if (p > 0.f) v *= drop_scale(seed, site_word, (uint64_t)(row0 + r) * W + j, p);
+        out[(int64_t)r * ldo + j] = v;
+    }
+}
+
 __global__ void copy2d_kernel(const float* __restrict__ src, int64_t lds_, float* __restrict__ dst, int64_t ldd, int rows,
                               int n, int accum) {
     const int64_t total = (int64_t)rows * n;
@@ -685,9 +761,13 @@ __global__ void fill_kernel(float* __restrict__ dst, int64_t n, float v) {
 }
 
 // ------------------------------------------------------------------------------------------------ ragged CE
+// WEIGHTED: caption b's rows scaled by weights[b] (the self-critical advantage); the unweighted instantiation is dlsg_ce_ragged,
+// and with weights of 1 the weighted one gives the same bits (1.f * (1 / ntot) == 1 / ntot, same summation order)
+template <bool WEIGHTED>
 __global__ __launch_bounds__(256) void ce_ragged_kernel(const float* __restrict__ logits, const int64_t* __restrict__ targets,
-                                                        const int64_t* __restrict__ lens, float* __restrict__ dlogits,
-                                                        float* __restrict__ row_loss, int B, int L, int V, int tm) {
+                                                        const int64_t* __restrict__ lens, const float* __restrict__ weights,
+                                                        float* __restrict__ dlogits, float* __restrict__ row_loss, int B, int L,
+                                                        int V, int tm) {
     __shared__ float red[16];
     const int row = blockIdx.x;
     const int b = tm ? row % B : row / L, t = tm ? row / B : row % L;
@@ -712,7 +792,9 @@ __global__ __launch_bounds__(256) void ce_ragged_kernel(const float* __restrict_
     // a target outside [0, V) (torch's CrossEntropyLoss raises): no out-of-bounds read; the row's loss -- hence the step's
     // loss -- and its gradient are NaN, which no caller can miss
     const bool bad = tgt < 0 || tgt >= V;
-    const float inv = bad ? NAN : 1.f / s, invn = 1.f / (float)ntot;
+    const float inv = bad ? NAN : 1.f / s;
+    float invn = 1.f / (float)ntot;
+    if constexpr (WEIGHTED) invn = weights[b] * invn;
     for (int j = threadIdx.x; j < V; j += blockDim.x) {
         float p = __expf(x[j] - m) * inv;
         if (j == tgt) p -= 1.f;
@@ -1132,6 +1214,16 @@ extern "C" int dlsg_select_embed(const float* logits, int64_t ld, int V, const i
     DLSG_CHECK_LAUNCH();
     return DLSG_OK;
 }
+extern "C" int dlsg_sample_embed(const float* logits, int64_t ld, int V, float temperature, const float* E, int64_t* ids_out, float* out,
+                                 int64_t ldo, int W, float* logp, int64_t* lens, int t, int64_t end_id, int rows, float p, uint64_t seed,
+                                 uint32_t site_word, uint32_t site_sample, int64_t row0, const uint64_t* seed_ptr, void* stream) {
+    if (rows == 0) return DLSG_OK;
+    if (V < 1 || W < 0 || !(temperature >= 0.f)) return DLSG_EINVAL;
+    hipLaunchKernelGGL(sample_embed_kernel, dim3(rows), dim3(256), 0, ST(stream), logits, ld, V, temperature, E, ids_out, out, ldo, W,
+                       logp, lens, t, end_id, p, seed, site_word, site_sample, row0, seed_ptr);
+    DLSG_CHECK_LAUNCH();
+    return DLSG_OK;
+}
 extern "C" int dlsg_argmax(const float* logits, int64_t ld, int64_t* ids, int rows, int V, void* stream) {
     if (rows == 0) return DLSG_OK;
     hipLaunchKernelGGL(argmax_kernel, dim3(rows), dim3(256), 0, ST(stream), logits, ld, ids, V);
@@ -1179,8 +1271,18 @@ extern "C" int dlsg_permute_tb(const float* src, float* dst, int T, int B, int n
 extern "C" int dlsg_ce_ragged(const float* logits, const int64_t* targets, const int64_t* lens, float* dlogits, float* row_loss,
                               float* loss, int B, int L, int V, int time_major, void* stream) {
     if (B * L == 0) return DLSG_OK;
-    hipLaunchKernelGGL(ce_ragged_kernel, dim3(B * L), dim3(256), 0, ST(stream), logits, targets, lens, dlogits, row_loss, B, L, V,
-                       time_major);
+    hipLaunchKernelGGL(ce_ragged_kernel<false>, dim3(B * L), dim3(256), 0, ST(stream), logits, targets, lens, nullptr, dlogits, row_loss,
+                       B, L, V, time_major);
+    hipLaunchKernelGGL(sum_to_scalar_kernel, dim3(1), dim3(256), 0, ST(stream), row_loss, B * L, loss);
+    DLSG_CHECK_LAUNCH();
+    return DLSG_OK;
+}
+extern "C" int dlsg_ce_ragged_weighted(const float* logits, const int64_t* targets, const int64_t* lens, const float* weights,
+                                       float* dlogits, float* row_loss, float* loss, int B, int L, int V, int time_major, void* stream) {
+    if (B * L == 0) return DLSG_OK;
+    if (!weights) return DLSG_EINVAL;
+    hipLaunchKernelGGL(ce_ragged_kernel<true>, dim3(B * L), dim3(256), 0, ST(stream), logits, targets, lens, weights, dlogits, row_loss,
+                       B, L, V, time_major);
     hipLaunchKernelGGL(sum_to_scalar_kernel, dim3(1), dim3(256), 0, ST(stream), row_loss, B * L, loss);
     DLSG_CHECK_LAUNCH();
     return DLSG_OK;

@@ -29,6 +29,8 @@ V_SK = 7        # include/dlsg.h DLSG_GEMM_V_SK: the persistent stream-K kernel
 SITE_PSL_OBJ, SITE_PSL_MOT, SITE_LSTM, SITE_PE, SITE_SA, SITE_WORD, SITE_QUERY, SITE_ATT1, SITE_ATT2, SITE_LANG = range(1, 11)
 # per-step sites add STEP_SITE*(t+1)
 STEP_SITE = 64
+# Gumbel noise of sampled decoding (hip.sample_embed): keyed like a dropout mask, on a site no mask uses
+SITE_SAMPLE = 11
 
 
 def _empty(ref, *shape, dtype=torch.float32):
@@ -1093,6 +1095,33 @@ def dec_fwd(ops, dec, mems, sv, captions, L, coins, training, seed, dev_coins=No
             ops.embed_fwd(E, ids[t + 1], s['WE'][t + 1], p=pw, seed=seed, site=SITE_WORD, row0=(t + 1) * B)
     if any(coins[t] for t in range(L)):
         dec_logits(ops, dec, s, 0, L)          # (greedy inference: every step's logits were already written above)
+    return s
+
+
+def dec_sample(ops, dec, mems, sv, L, training, seed, temperature):
+    """Sampled decoding for self-critical training: step t feeds a word drawn from softmax(logits_t / temperature) to step t+1
+    (`sample_embed`, Gumbel noise keyed by (seed, SITE_SAMPLE, row); temperature 0 is greedy).  Fills IDS (slots 1..L: the
+    words), LOGP (L, B) their log-probabilities and LENS (B,): first <end> position + 1, else L.  The word-dropout rows are those
+    of dec_fwd, so a teacher-forced pass over the sampled words with the same seed sees the same masks.  No host
+    synchronisation: capturable, the seed may be a device word."""
+    s = dec_prepare(ops, dec, mems, sv, training, seed)
+    ref = mems[0]
+    B = ref.shape[0]
+    dec_alloc(dec, s, ref, B, L)
+    E = dec.word_embed.weight
+    pw = dec.p_drop if training else 0.0
+    ids = s['IDS']
+    ids[0].fill_(dec.vocab('<start>'))
+    s['pw'] = pw
+    s['LOGP'] = _empty(ref, L, B)
+    s['LENS'] = torch.full((B,), L, dtype=torch.int64, device=ref.device)
+    end = dec.vocab('<end>')
+    ops.embed_fwd(E, ids[0], s['WE'][0], p=pw, seed=seed, site=SITE_WORD, row0=0)
+    for t in range(L):
+        dec_step(ops, dec, s, t, ref, training, seed, B)
+        dec_logits(ops, dec, s, t, t + 1)
+        ops.sample_embed(s['LOGITS'][t], E, ids[t + 1], s['WE'][t + 1], s['LOGP'][t], s['LENS'], t, end, temperature=temperature,
+                         p=pw, seed=seed, site=SITE_WORD, site_sample=SITE_SAMPLE, row0=(t + 1) * B)
     return s
 
 

@@ -231,7 +231,7 @@ SYMBOLS = ['dlsg_abi_version', 'dlsg_struct_size', 'dlsg_gemm', 'dlsg_gemm_varia
            'dlsg_rowln_bwd_nblk', 'dlsg_colsum', 'dlsg_colsum2', 'dlsg_colsum_ws_floats', 'dlsg_colsum_multi', 'dlsg_colsum_multi_ok', 'dlsg_o2v_workspace_bytes', 'dlsg_o2v_fwd', 'dlsg_o2v_fwd_multi',
            'dlsg_softmax_fwd', 'dlsg_softmax_bwd', 'dlsg_decatt_fwd', 'dlsg_decatt_bwd', 'dlsg_lstm_pw_fwd',
            'dlsg_lstm_pw_bwd', 'dlsg_lstm_pw_fwd_n', 'dlsg_lstm_pw_bwd_n', 'dlsg_mean_rows_fwd', 'dlsg_mean_rows_bwd', 'dlsg_embed_fwd', 'dlsg_embed_bwd',
-           'dlsg_argmax', 'dlsg_select_embed', 'dlsg_copy2d', 'dlsg_dropout', 'dlsg_fill', 'dlsg_ce_ragged', 'dlsg_log_softmax',
+           'dlsg_argmax', 'dlsg_select_embed', 'dlsg_sample_embed', 'dlsg_ce_ragged_weighted', 'dlsg_copy2d', 'dlsg_dropout', 'dlsg_fill', 'dlsg_ce_ragged', 'dlsg_log_softmax',
            'dlsg_adam', 'dlsg_permute_tb', 'dlsg_gather_rows', 'dlsg_dec_mid_fwd', 'dlsg_dec_tail_fwd',
            'dlsg_dec_mid_bwd', 'dlsg_decatt_cache_grads', 'dlsg_o2v_bwd', 'dlsg_o2v_bwd_multi',
            'dlsg_latent_psl_fwd', 'dlsg_sa_core_fwd', 'dlsg_beam_select', 'dlsg_gather_rows_multi',
@@ -289,6 +289,8 @@ def load_library(path=LIB_PATH):
         'dlsg_embed_bwd': [vp, i64, vp, vp, i32, i32, f32, u64, u32, i64, vp, vp],
         'dlsg_select_embed': [vp, i64, i32, vp, i32, i32, vp, vp, vp, vp, i64, i32, i32, f32, u64, u32, i64, vp, i32, vp],
         'dlsg_argmax': [vp, i64, vp, i32, i32, vp],
+        'dlsg_sample_embed': [vp, i64, i32, f32, vp, vp, vp, i64, i32, vp, vp, i32, i64, i32, f32, u64, u32, u32, i64, vp, vp],
+        'dlsg_ce_ragged_weighted': [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp],
         'dlsg_copy2d': [vp, i64, vp, i64, i32, i32, i32, vp],
         'dlsg_dropout': [vp, i64, vp, i64, i32, i32, f32, u64, u32, vp, vp],
         'dlsg_fill': [vp, i64, f32, vp],
@@ -1282,6 +1284,19 @@ class HipOps(object):
         rows, V = logits.shape
         self._check(self.lib.dlsg_argmax(_p(logits), i64(logits.stride(0)), _p(ids), rows, V, self._stream()), 'argmax')
 
+    def sample_embed(self, logits, E, ids_out, out, logp, lens, t, end_id, temperature=1.0, p=0.0, seed=0, site=0, site_sample=0,
+                     row0=0):
+        """ids_out[r] ~ softmax(logits[r] / temperature) (Gumbel-max on the (seed, site_sample, row0 + r) noise; 0: argmax),
+        logp[r] = its log-probability, out[r] = drop(E[id]) on the word-dropout rows row0 + r, lens[r] = t + 1 at the first end_id
+        (the caller sets lens to L)."""
+        rows, V = logits.shape
+        assert E.shape[0] >= V and E.is_contiguous() and ids_out.numel() == rows and logp.numel() == rows and lens.numel() == rows
+        assert ids_out.dtype == torch.int64 and lens.dtype == torch.int64 and out.shape == (rows, E.shape[1])
+        sd, sp = _seed(seed)
+        self._check(self.lib.dlsg_sample_embed(_p(logits), i64(logits.stride(0)), V, f32(temperature), _p(E), _p(ids_out), _p(out),
+                                               i64(out.stride(0)), out.shape[1], _p(logp), _p(lens), int(t), i64(end_id), rows, f32(p),
+                                               u64(sd), u32(site), u32(site_sample), i64(row0), sp, self._stream()), 'sample_embed')
+
     def copy2d(self, src, dst, accum=False):
         rows, n = src.shape
         self._check(self.lib.dlsg_copy2d(_p(src), i64(src.stride(0)), _p(dst), i64(dst.stride(0)), rows, n, int(accum),
@@ -1605,6 +1620,16 @@ class HipOps(object):
             B, L, V = logits.shape
         self._check(self.lib.dlsg_ce_ragged(_p(logits), _p(targets), _p(lens), _p(dlogits), _p(row_loss), _p(loss), B, L, V,
                                             int(time_major), self._stream()), 'ce_ragged')
+
+    def ce_ragged_weighted(self, logits, targets, lens, weights, dlogits, row_loss, loss, time_major):
+        """ce_ragged with caption b's rows weighted by weights[b] (float32 device tensor, (B,))"""
+        if time_major:
+            L, B, V = logits.shape
+        else:
+            B, L, V = logits.shape
+        assert weights.dtype == torch.float32 and weights.numel() == B and weights.is_contiguous()
+        self._check(self.lib.dlsg_ce_ragged_weighted(_p(logits), _p(targets), _p(lens), _p(weights), _p(dlogits), _p(row_loss), _p(loss),
+                                                     B, L, V, int(time_major), self._stream()), 'ce_ragged_weighted')
 
     def log_softmax(self, logits, out):
         rows, V = logits.shape

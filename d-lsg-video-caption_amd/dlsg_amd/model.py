@@ -169,6 +169,9 @@ class _HipModel(_ArenaModule):
     def _engine_backward(self, sv, dlogits_tm, dobj, dmot, dalpha_tm, training, seed):
         raise NotImplementedError
 
+    def sample(self, visual_feats, region_feats, n=1, temperature=1.0, seed=None):
+        raise NotImplementedError('sampled decoding (self-critical training) is implemented for CapGnnModel only')
+
     def _draw_coins(self, L, infer, tf_ratio):
         # reference draws one coin per step only when not inferring (layer.py:432)
         if infer:
@@ -362,6 +365,19 @@ class CapGnnModel(_HipModel):
         if on_bucket:
             on_bucket(('encoder.motion_encoder', 'encoder.obj_encoder'))
 
+    def _sample_forward(self, frames, regions, L, training, seed, temperature, sv):
+        """encoder + sampled decoding (engine.dec_sample) -> the decoder state (IDS, LOGP, LENS)"""
+        ops = self.ops
+        self._gemm_policy(False)
+        if getattr(ops, 'colsum_defer', None) is not None:
+            ops.colsum_defer = None
+        frames = frames.contiguous().float()
+        regions = regions.contiguous().float()
+        obj, mot = self._encode(frames, regions, training, seed, sv)
+        sv['frames'], sv['regions'] = frames, regions
+        sv['dec_gsrc'] = [obj, mot]
+        return E.dec_sample(ops, self.decoder, [obj, mot], sv, L, training, seed, temperature)
+
     # ------------------------------------------------------------------ public forward
     def forward(self, visual_feats, region_feats, caption, max_words=None, teacher_forcing_ratio=1.0):
         self.flatten_parameters_()
@@ -385,6 +401,22 @@ class CapGnnModel(_HipModel):
             with torch.no_grad():
                 return self._engine_forward(visual_feats, region_feats, caption, L, coins, self.training, seed, {})
         return _ModelFn.apply(self, visual_feats, region_feats, caption, L, coins, seed, *params)
+
+    @torch.no_grad()
+    def sample(self, visual_feats, region_feats, n=1, temperature=1.0, seed=None):
+        """Draw n captions per clip from softmax(logits / temperature) (self-critical training; temperature 0 is greedy).
+        Returns (ids (B*n, L) int64, logp (B*n, L) float32 log-probabilities of the drawn words, lens (B*n,) int64: first
+        <end> position + 1, else L); clip b's samples are rows b*n .. b*n + n - 1.  The clips are repeated n times before the
+        encoder (it runs on B*n rows, with their own dropout rows).  Dropout follows `self.training`.  seed None draws the next
+        seed of the model's sequence; a given seed reproduces the draw -- and the dropout masks of a train step on the same
+        rows with that seed, so the sampled words are on-policy for it."""
+        self.flatten_parameters_()
+        if seed is None:
+            seed = self.next_seed()
+        sv = {}
+        s = self._sample_forward(expand_rows(visual_feats, n), expand_rows(region_feats, n), self.decoder.max_words, self.training,
+                                 seed, temperature, sv)
+        return s['IDS'][1:].t().contiguous(), s['LOGP'].t().contiguous(), s['LENS']
 
 
 class CapBaseline1(_HipModel):
@@ -576,6 +608,54 @@ class GreedyGraph(object):
         return self.ids
 
 
+def expand_rows(x, n):
+    """x.repeat_interleave(n, 0) as one copy (row b*n + i = x[b]): no host synchronisation, so it may be captured"""
+    if n == 1:
+        return x
+    return x.unsqueeze(1).expand(x.shape[0], n, *x.shape[1:]).reshape(x.shape[0] * n, *x.shape[1:])
+
+
+class SampleGraph(object):
+    """hipGraph-captured `CapGnnModel.sample`: the n-fold expansion of the batch, the encoder on B*n rows and the sampled decode
+    steps, captured once for a batch shape (and for the model's train / eval mode at construction) and replayed.  The seed is
+    read from a device word, so every replay draws fresh samples; a replay with seed s gives the bits of
+    `model.sample(frames, regions, n, temperature, seed=s)`.  Outputs are static buffers, valid until the next replay."""
+
+    def __init__(self, model, frames, regions, n=1, temperature=1.0):
+        self.model, self.n, self.temperature = model, n, temperature
+        model.flatten_parameters_()
+        self.arena = model._flat
+        self.training = model.training
+        dev = frames.device
+        self.frames, self.regions = frames.clone(), regions.clone()
+        self.seed = torch.zeros(1, dtype=torch.int64, device=dev)
+        L = model.decoder.max_words
+        side = _capture_stream(dev)
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side), torch.no_grad():
+            def run():
+                s = model._sample_forward(expand_rows(self.frames, n), expand_rows(self.regions, n), L, self.training, self.seed,
+                                          temperature, {})
+                return s['IDS'][1:].t().contiguous(), s['LOGP'].t().contiguous(), s['LENS']
+            run()                                                                                      # warm-up
+            side.synchronize()
+            self.graph = torch.cuda.CUDAGraph()
+            self.graph.capture_begin(capture_error_mode='thread_local')
+            self.ids, self.logp, self.lens = run()
+            self.graph.capture_end()
+        torch.cuda.current_stream().wait_stream(side)
+
+    @torch.no_grad()
+    def __call__(self, frames, regions, seed):
+        if frames.data_ptr() != self.frames.data_ptr():
+            self.frames.copy_(frames, non_blocking=True)
+        if regions.data_ptr() != self.regions.data_ptr():
+            self.regions.copy_(regions, non_blocking=True)
+        _copy_h2d(self.seed, [int(seed)])
+        self.graph.replay()
+        return self.ids, self.logp, self.lens
+
+
 class BeamGraph(object):
     """hipGraph-captured beam search (BASELINE configs[4]): encoder + all max_words beam steps (decode step, `beam_select`,
     state reorder) captured once for a batch shape; a replay has no host synchronisation, the early stop of the reference is
@@ -675,6 +755,7 @@ class Trainer(object):
         self._graphs = None
         self._contact_checked = False
         self._hook_mode, self._hook_sv = False, None
+        self._weighted_mode = False     # the captured graphs weight the CrossEntropy per caption (step(seq_weights=...))
         self.m = self.v = None
         if world_size > 1 or self.rehearse_ranks > 1:
             assert world_size == 1 or not self.rehearse_ranks, 'rehearse_ranks is for one-rank runs'
@@ -987,7 +1068,7 @@ class Trainer(object):
             self._rccl = None
 
     # ------------------------------------------------------------------ one step, as a schedule
-    def _schedule(self, frames, regions, captions, cap_lens, coins, seed, dev_coins, on_bucket, extra_dlogits=None):
+    def _schedule(self, frames, regions, captions, cap_lens, coins, seed, dev_coins, on_bucket, extra_dlogits=None, seq_weights=None):
         model, ops = self.model, self.model.ops
         L = captions.shape[1]
         sv = {}
@@ -1000,7 +1081,11 @@ class Trainer(object):
         dl = torch.empty_like(s['LOGITS'])
         row_loss = torch.empty(L * Bn, dtype=torch.float32, device=dl.device)
         loss = torch.empty(1, dtype=torch.float32, device=dl.device)
-        ops.ce_ragged(s['LOGITS'], captions, cap_lens, dl, row_loss, loss, time_major=True)
+        if seq_weights is None:
+            ops.ce_ragged(s['LOGITS'], captions, cap_lens, dl, row_loss, loss, time_major=True)
+        else:
+            # policy gradient of self-critical training: caption b's CrossEntropy weighted by its advantage
+            ops.ce_ragged_weighted(s['LOGITS'], captions, cap_lens, seq_weights, dl, row_loss, loss, time_major=True)
         if extra_dlogits is not None:
             # another loss on the logits (the GAN term of run_gun.py:218-231): its gradient joins the CrossEntropy's
             sv['loss_dev'] = loss
@@ -1015,12 +1100,16 @@ class Trainer(object):
         return [self.lr / (1.0 - b1 ** self.t), math.sqrt(1.0 - b2 ** self.t)]
 
     @torch.no_grad()
-    def step(self, frames, regions, captions, cap_lens, tf_ratio, max_len=26, extra_dlogits=None):
+    def step(self, frames, regions, captions, cap_lens, tf_ratio, max_len=26, extra_dlogits=None, seed=None, seq_weights=None):
         """One optimisation step.  Returns the (device) scalar loss of this rank's shard.
         extra_dlogits: optional callable (logits (L,B,V) time-major, saved-state dict) -> (L,B,V) gradient of an additional
         loss on the logits, added to the CrossEntropy's before the backward.  With use_graphs the captured step is cut at
         that point: forward + CrossEntropy replay, the callable runs (on the graphs' static logits / saved state), its result
-        is copied into a static buffer that the replayed backward adds to the CrossEntropy gradient."""
+        is copied into a static buffer that the replayed backward adds to the CrossEntropy gradient.
+        seed: the dropout seed of the step (None: the model's next one) -- a self-critical step passes the seed its samples were
+        drawn with, so that the masks are those of the sampling pass.
+        seq_weights: optional (B,) per-caption weights of the CrossEntropy (`ce_ragged_weighted`; the advantages of self-critical
+        training); with use_graphs that form of the step is captured on its own, the weights read from a static device buffer."""
         model, ops = self.model, self.model.ops
         self._check_binding()
         captions = captions[:, :max_len].contiguous()
@@ -1028,19 +1117,24 @@ class Trainer(object):
             cap_lens = _h2d(cap_lens, torch.int64, captions.device)
         L = captions.shape[1]
         coins = model._draw_coins(L, False, tf_ratio)
-        seed = model.next_seed()
+        seed = model.next_seed() if seed is None else int(seed)
         self.t += 1
         hook = extra_dlogits is not None
-        if self.use_graphs and (self._graphs is None or self._hook_mode == hook):
-            loss = self._step_graphs(frames, regions, captions, cap_lens, coins, seed, extra_dlogits)
+        weighted = seq_weights is not None
+        if weighted and not (torch.is_tensor(seq_weights) and seq_weights.device == captions.device
+                             and seq_weights.dtype == torch.float32):
+            seq_weights = _h2d(seq_weights, torch.float32, captions.device)
+        if self.use_graphs and (self._graphs is None or (self._hook_mode == hook and self._weighted_mode == weighted)):
+            loss = self._step_graphs(frames, regions, captions, cap_lens, coins, seed, extra_dlogits, seq_weights)
         else:
-            # (a trainer's graphs are captured for one of the two forms of the step; the other form runs kernel by kernel)
-            loss = self._eager_step(frames, regions, captions, cap_lens, coins, seed, counted=True, extra_dlogits=extra_dlogits)
+            # (a trainer's graphs are captured for one form of the step; the other forms run kernel by kernel)
+            loss = self._eager_step(frames, regions, captions, cap_lens, coins, seed, counted=True, extra_dlogits=extra_dlogits,
+                                    seq_weights=seq_weights)
         if self.check_every and self.t % self.check_every == 0:
             self.check()
         return loss
 
-    def _eager_step(self, frames, regions, captions, cap_lens, coins, seed, counted=False, extra_dlogits=None):
+    def _eager_step(self, frames, regions, captions, cap_lens, coins, seed, counted=False, extra_dlogits=None, seq_weights=None):
         model, ops = self.model, self.model.ops
         if not counted:
             self.t += 1
@@ -1048,7 +1142,7 @@ class Trainer(object):
         if self.device_coins:
             dev_coins = _h2d([int(c) for c in coins], torch.int32, captions.device)
         self._works = []
-        loss = self._schedule(frames, regions, captions, cap_lens, coins, seed, dev_coins, self._allreduce, extra_dlogits)
+        loss = self._schedule(frames, regions, captions, cap_lens, coins, seed, dev_coins, self._allreduce, extra_dlogits, seq_weights)
         self._reduce_guard()
         for w in self._works:
             w.wait()
@@ -1057,12 +1151,14 @@ class Trainer(object):
         return loss
 
     # ------------------------------------------------------------------ hipGraph path
-    def _capture(self, frames, regions, captions, cap_lens, hook=False):
+    def _capture(self, frames, regions, captions, cap_lens, hook=False, weighted=False):
         dev = frames.device
         L = captions.shape[1]
         self._hook_mode, self._hook_sv = hook, None
+        self._weighted_mode = weighted
         st = self._static = dict(frames=frames.clone(), regions=regions.clone(), captions=captions.clone(),
                                  lens=cap_lens.clone())
+        st['weights'] = torch.ones(captions.shape[0], dtype=torch.float32, device=dev) if weighted else None
         # what changes every step besides the batch -- the scheduled-sampling coins, the dropout seed, Adam's bias corrections --
         # lives in ONE device buffer (int32 words: coins | seed (int64) | hyper (2 x float32)), so that a step sends it as one copy
         Lp = (L + 1) // 2 * 2
@@ -1084,7 +1180,7 @@ class Trainer(object):
             # (with RCCL the warm-up also runs the collectives once: channel buffers are set up before the capture;
             #  nothing is updated: Adam is not part of the schedule)
             self._schedule(st['frames'], st['regions'], st['captions'], st['lens'], None, st['seed'], st['coins'],
-                           self._allreduce if mode == 'rccl' else None)
+                           self._allreduce if mode == 'rccl' else None, seq_weights=st['weights'])
             if mode == 'rccl':
                 self._reduce_guard()
             self._join_comm()
@@ -1123,7 +1219,7 @@ class Trainer(object):
                     return st['extra']
 
                 loss = self._schedule(st['frames'], st['regions'], st['captions'], st['lens'], None, st['seed'], st['coins'], cut,
-                                      placeholder if hook else None)
+                                      placeholder if hook else None, st['weights'])
                 if mode != 'torch':
                     # no host-issued collective between backward and update: Adam is part of the graph, behind the join of the
                     # side stream's collectives; with host-issued collectives it follows their waits
@@ -1147,13 +1243,13 @@ class Trainer(object):
         self._graphs, self._loss = graphs, loss
         self._adam_in_graph = mode != 'torch'
 
-    def _capture_agreed(self, frames, regions, captions, cap_lens, hook):
+    def _capture_agreed(self, frames, regions, captions, cap_lens, hook, weighted=False):
         """`_capture`, and with several ranks the agreement on its outcome: returns None when EVERY rank captured, else the error
         (this rank's own, or a stand-in when only another rank failed) after dropping this rank's graphs -- so that all ranks take
         the same fallback together"""
         err = None
         try:
-            self._capture(frames, regions, captions, cap_lens, hook)
+            self._capture(frames, regions, captions, cap_lens, hook, weighted)
         except Exception as e:            # (any failure votes: an AssertionError on one rank must not leave the others in the vote)
             err = e
         if self.world_size > 1:
@@ -1216,11 +1312,12 @@ class Trainer(object):
         st = self._static
         return st['frames'], st['regions'], st['captions'], st['lens']
 
-    def _step_graphs(self, frames, regions, captions, cap_lens, coins, seed, extra_dlogits=None):
+    def _step_graphs(self, frames, regions, captions, cap_lens, coins, seed, extra_dlogits=None, seq_weights=None):
         model, ops = self.model, self.model.ops
         hook = extra_dlogits is not None
+        weighted = seq_weights is not None
         if self._graphs is None:
-            err = self._capture_agreed(frames, regions, captions, cap_lens, hook)
+            err = self._capture_agreed(frames, regions, captions, cap_lens, hook, weighted)
             if err is not None and self.graph_fallback and self._comm_mode() == 'rccl' and self.world_size > 1:
                 # the in-graph RCCL capture was refused somewhere: EVERY rank retries the segmented form (torch.distributed
                 # collectives issued by the host between graph segments) -- a rank replaying graphs that hold private-communicator
@@ -1230,7 +1327,7 @@ class Trainer(object):
                               'torch.distributed collectives between graph segments' % (type(err).__name__, err))
                 torch.cuda.synchronize()
                 self.comm = 'torch'
-                err = self._capture_agreed(frames, regions, captions, cap_lens, hook)
+                err = self._capture_agreed(frames, regions, captions, cap_lens, hook, weighted)
             if err is not None:
                 if not self.graph_fallback:
                     raise err
@@ -1239,14 +1336,18 @@ class Trainer(object):
                 warnings.warn('hipGraph capture failed (%s: %s); continuing with eager launches' % (type(err).__name__, err))
                 torch.cuda.synchronize()
                 self.use_graphs, self._graphs = False, None
-                return self._eager_step(frames, regions, captions, cap_lens, coins, seed, counted=True, extra_dlogits=extra_dlogits)
+                return self._eager_step(frames, regions, captions, cap_lens, coins, seed, counted=True, extra_dlogits=extra_dlogits,
+                                        seq_weights=seq_weights)
         st = self._static
         if (frames.shape, regions.shape, captions.shape) != (st['frames'].shape, st['regions'].shape, st['captions'].shape):
             # a batch of another shape (the short last batch of an epoch): the captured graphs are for one shape only
-            return self._eager_step(frames, regions, captions, cap_lens, coins, seed, counted=True, extra_dlogits=extra_dlogits)
+            return self._eager_step(frames, regions, captions, cap_lens, coins, seed, counted=True, extra_dlogits=extra_dlogits,
+                                    seq_weights=seq_weights)
         for k, src in (('frames', frames), ('regions', regions), ('captions', captions), ('lens', cap_lens)):
             if src.data_ptr() != st[k].data_ptr():
                 st[k].copy_(src, non_blocking=True)
+        if weighted:
+            st['weights'].copy_(seq_weights, non_blocking=True)
         self._send_scalars(coins, seed, self._hyper())
         self._works = []
         for g, key in self._graphs:

@@ -17,6 +17,8 @@ import collections
 import math
 import re
 
+import numpy as np
+
 PUNCTUATIONS = frozenset(["''", "'", "``", "`", "-LRB-", "-RRB-", "-LCB-", "-RCB-", ".", "?", "!", ",", ":", "-", "--", "...", ";"])
 _TOKEN = re.compile(r"\.\.\.|--|``|''|[A-Za-z0-9]+(?:'[a-z]+)?|[^\sA-Za-z0-9]")
 
@@ -137,6 +139,64 @@ def cider(gts, res, n=4, sigma=6.0):
                 tot[k] += s * pen
         per.append(sum(tot) / n / len(rs) * 10.0)
     return sum(per) / len(per), per
+
+
+class CiderD(object):
+    """CIDEr-D as a reward (self-critical training): `refs` {vid: [tokenized caption, ...]} is the training corpus; document
+    frequencies, log N and every reference's tf-idf vectors are computed once here, so `scores` only vectorises the hypotheses.
+    Same arithmetic as `cider` (clipping, sigma = 6 length penalty, x10): with the corpus equal to the scored set,
+    scores(sorted ids, hyps) == cider(gts, res)[1]."""
+
+    def __init__(self, refs, n=4, sigma=6.0):
+        self.n, self.sigma = n, sigma
+        grams = {v: [_ngrams(r.split(), n) for r in refs[v]] for v in sorted(refs)}
+        df = collections.Counter()
+        for rs in grams.values():
+            for g in set(g for r in rs for g in r):
+                df[g] += 1
+        self.df = df
+        self.log_n = math.log(float(len(grams)))
+        self.ref_vecs = {v: [self._vec(r) for r in rs] for v, rs in grams.items()}
+
+    def _vec(self, cnt):
+        n, df, log_n = self.n, self.df, self.log_n
+        v = [dict() for _ in range(n)]
+        norm = [0.0] * n
+        length = 0
+        for g, tf in cnt.items():
+            k = len(g) - 1
+            w = float(tf) * (log_n - math.log(max(1.0, df.get(g, 0.0))))
+            v[k][g] = w
+            norm[k] += w * w
+            if k == 1:
+                length += tf               # bigrams, as in `cider`
+        return v, [math.sqrt(x) for x in norm], length
+
+    def _score(self, vid, hyp):
+        n, sigma = self.n, self.sigma
+        vh, nh, lh = self._vec(_ngrams(hyp.split(), n))
+        rs = self.ref_vecs[vid]
+        tot = [0.0] * n
+        for vr, nr, lr in rs:
+            pen = math.e ** (-(float(lh - lr) ** 2) / (2 * sigma ** 2))
+            for k in range(n):
+                s = sum(min(w, vr[k].get(g, 0.0)) * vr[k].get(g, 0.0) for g, w in vh[k].items())
+                if nh[k] != 0 and nr[k] != 0:
+                    s /= nh[k] * nr[k]
+                tot[k] += s * pen
+        return sum(tot) / n / len(rs) * 10.0
+
+    def scores(self, vids, hyps):
+        """CIDEr-D of hyps[i] (tokenized, space-joined) against the references of vids[i] -> float64 array.  A (vid, caption)
+        pair that repeats within the call (n samples of a clip often agree) is scored once."""
+        memo = {}
+        out = np.empty(len(hyps), dtype=np.float64)
+        for i, (v, h) in enumerate(zip(vids, hyps)):
+            key = (v, h)
+            if key not in memo:
+                memo[key] = self._score(v, h)
+            out[i] = memo[key]
+        return out
 
 
 # ------------------------------------------------------------------------------------------------ driver (evaluate.py)

@@ -1,0 +1,97 @@
+"""Self-critical sequence training (SCST): fine-tuning on the metric the model is judged by, after cross-entropy.
+
+One step: draw n captions per clip in train mode (`CapGnnModel.sample`, or its captured form `SampleGraph`), score them with
+CIDEr-D on the host (`scoring.CiderD`), subtract a baseline, and take the policy-gradient step
+    loss = -sum_b A_b sum_{t < len_b} log p(w_bt) / sum_b len_b,   A_b = reward_b - baseline_b
+as the Trainer's fused step teacher-forced on the sampled words with the CrossEntropy weighted per caption by A_b
+(`ce_ragged_weighted`).  The train pass uses the sampling pass's seed and rows, hence its dropout masks: the gradient is
+on-policy up to the tiling of the vocabulary product.
+"""
+import numpy as np
+import torch
+
+from .model import Trainer, GreedyGraph, SampleGraph, expand_rows, _h2d
+
+
+class SCSTTrainer(object):
+    """reward: an object with `scores(vids, hyps) -> np.ndarray` (a `scoring.CiderD` over the training references).
+    baseline: 'mean' -- the leave-one-out mean of the clip's other n - 1 rewards (needs n_samples >= 2); 'greedy' -- the reward
+    of the clip's eval-mode greedy caption.  The remaining keywords go to the owned `Trainer` (lr, use_graphs, data parallel,
+    ...), whose Adam state, gradient buckets and graphs the step reuses."""
+
+    def __init__(self, model, reward, n_samples=5, baseline='mean', temperature=1.0, **trainer_kwargs):
+        if baseline not in ('mean', 'greedy'):
+            raise ValueError("baseline must be 'mean' or 'greedy', not %r" % (baseline,))
+        if baseline == 'mean' and n_samples < 2:
+            raise ValueError("the 'mean' baseline needs n_samples >= 2 (leave-one-out over the clip's samples)")
+        self.model, self.reward = model, reward
+        self.n, self.baseline, self.temperature = int(n_samples), baseline, float(temperature)
+        self.trainer = Trainer(model, **trainer_kwargs)
+        self._sampler = self._greedy = None
+
+    def _graph_ok(self, g, frames, regions):
+        return g is not None and g.frames.shape == frames.shape and g.regions.shape == regions.shape and \
+            g.arena is self.model._flat
+
+    def _sample(self, frames, regions, seed):
+        model = self.model
+        if not self.trainer.use_graphs:
+            return model.sample(frames, regions, n=self.n, temperature=self.temperature, seed=seed)
+        model.flatten_parameters_()
+        if not self._graph_ok(self._sampler, frames, regions) or self._sampler.training != model.training:
+            self._sampler = SampleGraph(model, frames, regions, self.n, self.temperature)
+        return self._sampler(frames, regions, seed)
+
+    def _greedy_ids(self, frames, regions):
+        """eval-mode greedy captions of the B clips (no dropout, so the seed is immaterial)"""
+        model = self.model
+        model.flatten_parameters_()
+        if self.trainer.use_graphs:
+            if not self._graph_ok(self._greedy, frames, regions):
+                self._greedy = GreedyGraph(model, frames, regions)
+                self._greedy.arena = model._flat
+            return self._greedy(frames, regions)
+        L = model.decoder.max_words
+        sv = {}
+        model._engine_forward(frames, regions, None, L, [False] * L, False, 0, sv)
+        return sv['dec']['IDS'][1:].t().contiguous()
+
+    def _expanded_inputs(self, frames, regions):
+        """the batch repeated n times, written straight into the Trainer's static graph inputs when they have that shape"""
+        n = self.n
+        st = self.trainer.static_inputs()
+        B = frames.shape[0]
+        if st is not None and st[0].shape == (B * n,) + tuple(frames.shape[1:]) and st[1].shape == (B * n,) + tuple(regions.shape[1:]):
+            fx, rx = st[0], st[1]
+            fx.view(B, n, *frames.shape[1:]).copy_(frames.unsqueeze(1).expand(B, n, *frames.shape[1:]))
+            rx.view(B, n, *regions.shape[1:]).copy_(regions.unsqueeze(1).expand(B, n, *regions.shape[1:]))
+            return fx, rx
+        return expand_rows(frames, n), expand_rows(regions, n)
+
+    @torch.no_grad()
+    def step(self, frames, regions, vids):
+        """One SCST step on clips `vids` (B ids of the reward's corpus).  Returns {'loss' (device scalar), 'reward_mean',
+        'baseline_mean', 'mean_len'}.  The one host synchronisation is the copy of the sampled words to the host: the reward is
+        computed there."""
+        model = self.model
+        dec = model.decoder
+        n, B = self.n, frames.shape[0]
+        assert len(vids) == B, (len(vids), B)
+        seed = model.next_seed()
+        ids, _, lens = self._sample(frames, regions, seed)
+        greedy = self._greedy_ids(frames, regions) if self.baseline == 'greedy' else None
+        host = torch.cat([ids, lens.unsqueeze(1)] + ([expand_rows(greedy, n)] if greedy is not None else []), 1).cpu()
+        L = ids.shape[1]
+        vids_x = [v for v in vids for _ in range(n)]
+        r = np.asarray(self.reward.scores(vids_x, [dec.decode_tokens(row) for row in host[:, :L]]), dtype=np.float64)
+        if greedy is not None:
+            g = np.asarray(self.reward.scores(list(vids), [dec.decode_tokens(row) for row in host[::n, L + 1:]]), dtype=np.float64)
+            b = np.repeat(g, n)
+        else:
+            R = r.reshape(B, n)
+            b = ((R.sum(1, keepdims=True) - R) / (n - 1)).reshape(-1)
+        adv = (r - b).astype(np.float32)
+        fx, rx = self._expanded_inputs(frames, regions)
+        loss = self.trainer.step(fx, rx, ids, lens, 1.0, max_len=L, seed=seed, seq_weights=_h2d(adv, torch.float32, ids.device))
+        return {'loss': loss, 'reward_mean': float(r.mean()), 'baseline_mean': float(b.mean()),
+                'mean_len': float(host[:, L].double().mean())}

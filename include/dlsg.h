@@ -468,6 +468,16 @@ int dlsg_select_embed(const float* logits, int64_t ld, int V, const int64_t* cap
                       uint32_t site, int64_t row0, const uint64_t* seed_ptr, int prefilled, void* stream);
 /* argmax over logits rows (first max wins, like torch.max) */
 int dlsg_argmax(const float* logits, int64_t ld, int64_t* ids, int rows, int V, void* stream);
+/* sampled decoding (self-critical training): ids_out[r] = a word drawn from softmax(logits[r, :] / temperature) by Gumbel-max,
+ * argmax_j (x_j / temperature + g_j) with g_j = -log(-log u_j) and u_j from the dropout hash keyed (seed (+ *seed_ptr),
+ * site_sample, (row0 + r) * V + j) -- stateless, so a replayed graph with the same seed draws the same words;
+ * logp[r] = log softmax(logits[r, :] / temperature)[id]; out[r, :] = drop(E[id, :]) with the word-dropout mask of
+ * dlsg_embed_fwd (seed, site_word, row0 + r); lens[r] (int64, set to L by the caller) becomes t + 1 when id == end_id and
+ * lens[r] > t.  temperature 0: the id of dlsg_argmax (first maximum) and logp of the untempered softmax.  A row without a
+ * maximum (all NaN / -inf) gives id 0; a -inf logit is never drawn.  E has at least V rows of W floats. */
+int dlsg_sample_embed(const float* logits, int64_t ld, int V, float temperature, const float* E, int64_t* ids_out, float* out,
+                      int64_t ldo, int W, float* logp, int64_t* lens, int t, int64_t end_id, int rows, float p, uint64_t seed,
+                      uint32_t site_word, uint32_t site_sample, int64_t row0, const uint64_t* seed_ptr, void* stream);
 /* strided 2-d copy / add: dst[r*ldd + j] (+)= src[r*lds + j] */
 int dlsg_copy2d(const float* src, int64_t lds, float* dst, int64_t ldd, int rows, int n, int accum, void* stream);
 /* elementwise dropout with the stateless mask: y = x * keep(seed, site, r*n+j)/(1-p) */
@@ -656,6 +666,11 @@ int dlsg_crit_colsum(const dlsg_crit_colsum_desc* d, int count, void* stream);
  * dlogits are laid out (L,B,V) (the decoder's internal layout) instead of (B,L,V); targets stay (B,L). */
 int dlsg_ce_ragged(const float* logits, const int64_t* targets, const int64_t* lens, float* dlogits, float* row_loss,
                    float* loss, int B, int L, int V, int time_major, void* stream);
+/* dlsg_ce_ragged with one weight per caption (the policy gradient of self-critical training, weights = reward - baseline):
+ * dlogits = weights[b] * (softmax - onehot) / ntot, row_loss = weights[b] * CE / ntot, ntot = sum of lens as above.
+ * With every weight 1 the results are bit-identical to dlsg_ce_ragged. */
+int dlsg_ce_ragged_weighted(const float* logits, const int64_t* targets, const int64_t* lens, const float* weights, float* dlogits,
+                            float* row_loss, float* loss, int B, int L, int V, int time_major, void* stream);
 int dlsg_log_softmax(const float* logits, float* out, int rows, int V, void* stream);
 /* One beam-search step for every batch item (BeamSearch.search, allennlp_beamsearch.py:140-260, per-node k == k):
  * log-softmax + per-beam top-k over the vocabulary + top-k over the k*k summed candidates, in one launch.

@@ -1,0 +1,128 @@
+"""Self-critical training at the MSVD shape (batch 64, n = 5 samples per clip, vocabulary 1000, train mode), one JSON line:
+  * `sample_graph_ms` -- a replay of SampleGraph (encoder on 320 rows + 26 sampled word steps) against `greedy_graph_ms`, a
+    GreedyGraph replay on the same 320 rows (the clips repeated 5 times): the cost of sampling over argmax in the word loop;
+  * `ciderd_ms` -- host ms of CiderD.scores for 320 hypotheses (a corpus of 64 clips x 20 references);
+  * `scst_step_ms` -- one SCSTTrainer step (use_graphs), split into `sample_ms` (SampleGraph replay + copy of the words to the
+    host), `reward_ms` (decode + CIDEr-D + advantages, host) and `train_ms` (the Trainer's weighted step on 320 rows).
+usage: python3 tools/scst_bench.py [steps=10] [batch=64] [n=5]
+       python3 tools/scst_bench.py kernels      (rocprofv3 --kernel-trace --stats target: eager greedy and sampled decodes)"""
+import json
+import os
+import random
+import sys
+import time
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for p in (ROOT, os.path.join(ROOT, 'd-lsg-video-caption_amd')):
+    if p not in sys.path:
+        sys.path.insert(0, p)
+
+import dlsg_amd  # noqa: E402
+from dlsg_amd import scst as SC  # noqa: E402
+from dlsg_amd.synth import synth_state_dict, synth_batch  # noqa: E402
+
+
+def setup(B, V=1000):
+    args = dlsg_amd.msvd_shaped()
+    vocab = dlsg_amd.make_vocab(V)
+    torch.manual_seed(0)
+    net = dlsg_amd.CapGnnModel(args, vocab)
+    net.load_state_dict(synth_state_dict(net.state_dict(), 0))
+    net = net.to('cuda').train()
+    net.update_beam_size(1)
+    frames, regions, _, _ = synth_batch(args, V, B, 1)
+    rng = random.Random(0)
+    words = [vocab.idx2word[i] for i in range(4, V)]
+    refs = {str(b): [' '.join(rng.choice(words) for _ in range(rng.randint(5, 12))) for _ in range(20)] for b in range(B)}
+    return net, vocab, frames.cuda(), regions.cuda(), refs
+
+
+def timed(fn, steps):
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(steps):
+        fn()
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t0) / steps * 1e3
+
+
+def kernels(B=64, n=5):
+    """eager greedy decode and eager sampled decode on B*n rows, 3 each: argmax_kernel and sample_embed_kernel side by side"""
+    net, vocab, frames, regions, refs = setup(B)
+    fx, rx = SC.expand_rows(frames, n), SC.expand_rows(regions, n)
+    L = net.decoder.max_words
+    with torch.no_grad():
+        for k in range(3):
+            net._engine_forward(fx, rx, None, L, [False] * L, True, 100 + k, {})
+            net.sample(frames, regions, n=n, seed=200 + k)
+    torch.cuda.synchronize()
+    print('kernels: 3 greedy + 3 sampled decodes of %d rows' % (B * n))
+
+
+def main(steps=10, B=64, n=5):
+    net, vocab, frames, regions, refs = setup(B)
+    rows = B * n
+    fx, rx = SC.expand_rows(frames, n).contiguous(), SC.expand_rows(regions, n).contiguous()
+    sg = dlsg_amd.SampleGraph(net, frames, regions, n=n)
+    net.eval()
+    gg = dlsg_amd.GreedyGraph(net, fx, rx)
+    net.train()
+    seeds = iter(range(1, 10 ** 6))
+    sample_ms = timed(lambda: sg(frames, regions, next(seeds)), steps)
+    greedy_ms = timed(lambda: gg(fx, rx), steps)
+    del gg, sg
+    reward = dlsg_amd.CiderD(refs)
+    ids = net.sample(frames, regions, n=n, seed=3)[0].cpu()
+    hyps = [net.decoder.decode_tokens(x) for x in ids]
+    vids = [str(b) for b in range(B) for _ in range(n)]
+    t0 = time.perf_counter()
+    for _ in range(3):
+        reward.scores(vids, hyps)
+    cider_ms = (time.perf_counter() - t0) / 3 * 1e3
+
+    tr = SC.SCSTTrainer(net, reward, n_samples=n, use_graphs=True)
+    parts = {'sample': 0.0, 'reward': 0.0, 'train': 0.0}
+    inner_sample, inner_scores, inner_step = tr._sample, reward.scores, tr.trainer.step
+
+    def clock(key, fn, sync):
+        def f(*a, **k):
+            if sync:
+                torch.cuda.synchronize()
+            t = time.perf_counter()
+            out = fn(*a, **k)
+            if sync:
+                torch.cuda.synchronize()
+            parts[key] += time.perf_counter() - t
+            return out
+        return f
+    vb = [str(b) for b in range(B)]
+    for _ in range(2):
+        tr.step(frames, regions, vb)                   # captures
+    step_ms = timed(lambda: tr.step(frames, regions, vb), steps)
+    tr._sample = clock('sample', inner_sample, True)
+    reward.scores = clock('reward', inner_scores, False)
+    tr.trainer.step = clock('train', inner_step, True)
+    for _ in range(steps):
+        out = tr.step(frames, regions, vb)
+    torch.cuda.synchronize()
+    tr.trainer.check()
+    print(json.dumps({
+        'what': 'SCST at the MSVD shape: batch %d x %d samples = %d rows, vocabulary 1000, train mode, hipGraph replays' % (B, n, rows),
+        'sample_graph_ms': round(sample_ms, 3), 'greedy_graph_ms': round(greedy_ms, 3),
+        'sample_over_greedy': round(sample_ms / greedy_ms, 3),
+        'ciderd_ms': round(cider_ms, 2), 'ciderd_hyps': rows,
+        'scst_step_ms': round(step_ms, 2),
+        'parts_ms': {k: round(v / steps * 1e3, 2) for k, v in parts.items()},
+        'parts_note': 'separate steps with a device synchronisation around sample and train: they add up to more than scst_step_ms',
+        'last_step': {k: (float(v) if k == 'loss' else v) for k, v in out.items()},
+        'steps': steps}))
+
+
+if __name__ == '__main__':
+    if len(sys.argv) > 1 and sys.argv[1] == 'kernels':
+        kernels()
+    else:
+        main(*[int(x) for x in sys.argv[1:4]])
