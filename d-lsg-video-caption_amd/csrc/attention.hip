@@ -260,6 +260,7 @@ extern "C" int dlsg_struct_size(int which) {
         case 27: return (int)sizeof(dlsg_crit_score_args);
         case 28: return (int)sizeof(dlsg_crit_colsum_desc);
         case 29: return (int)sizeof(dlsg_crit_reduce_desc);
+        case 30: return (int)sizeof(dlsg_cider_tables);
         default: return -1;
     }
 }

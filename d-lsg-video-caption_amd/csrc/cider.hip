@@ -1,0 +1,207 @@
+// Self-critical training's reward on the device (gfx950): CIDEr-D of caption rows given as vocabulary ids against the fixed
+// corpus tables of scoring.DeviceCiderD, and the baseline / advantages that turn the rewards into the CrossEntropy's weights.
+// Everything in float64 like the host scorer, every reduction in a fixed order: the same inputs give the same bits on every
+// launch and on graph replay.
+#include <math.h>
+
+#include "common.hpp"
+#include "dlsg.h"
+
+namespace {
+
+constexpr int CIDER_THREADS = 256;      // wave k holds the n-grams of order k + 1: n <= 4
+constexpr int CIDER_MAXL = 64;          // lane i holds word position i
+constexpr int CIDER_STAGE = 2048;       // reference entries staged in LDS per pass (16 KiB keys + 16 KiB weights)
+constexpr uint32_t CIDER_NONE = 0xFFFFu;
+
+// every lane gets the same bits: a butterfly adds the same two partial sums in every lane (a + b == b + a)
+__device__ __forceinline__ double wave_sum_f64(double v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+
+// index of `key` in keys[0, n) (sorted ascending), -1 if absent; reads only inside [0, n)
+__device__ __forceinline__ int64_t find_key(const uint64_t* keys, int64_t n, uint64_t key) {
+    int64_t lo = 0, hi = n;
+    while (lo < hi) {
+        const int64_t mid = (lo + hi) >> 1;
+        if (keys[mid] < key) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo < n && keys[lo] == key ? lo : -1;
+}
+
+// One workgroup per row.  Lane i of every wave holds word i; wave k builds the row's order-(k + 1) n-grams (position i = lane),
+// counts each one's occurrences, and keeps it at its first position only.  Per reference of the row's clip each kept n-gram
+// looks itself up in the reference's sorted entries (staged in LDS) and adds min(w_h, w_r) w_r, divided by the two norms when
+// both are nonzero, times the length penalty.  The n per-order sums are added in order by one thread.
+__global__ __launch_bounds__(CIDER_THREADS) void cider_d_kernel(const int64_t* __restrict__ ids, int64_t ld, int L,
+                                                                const int32_t* __restrict__ clip_idx, int64_t end_id,
+                                                                const dlsg_cider_tables t, double* __restrict__ scores) {
+    __shared__ uint64_t skey[CIDER_STAGE];
+    __shared__ double sw[CIDER_STAGE];
+    __shared__ double stot[4];
+    const int row = blockIdx.x;
+    const int lane = threadIdx.x & 63, k = threadIdx.x >> 6;
+    const int n = t.n;
+    const int c = clip_idx[row];
+    const int64_t rb = (c >= 0 && c < t.n_clips) ? t.clip_off[c] : 0;
+    const int64_t re = (c >= 0 && c < t.n_clips) ? t.clip_off[c + 1] : 0;
+    if (re <= rb) {                                           // the same for the whole workgroup: no barrier is skipped by some
+        if (threadIdx.x == 0) scores[row] = NAN;
+        return;
+    }
+    // the row's words (decode_tokens): those before the first end_id, all L without one
+    const int64_t id = lane < L ? ids[(int64_t)row * ld + lane] : end_id;
+    const unsigned long long ends = __ballot(lane >= L || id == end_id);
+    const int len = ends ? __builtin_ctzll(ends) : CIDER_MAXL;
+    const bool bad = id < 0 || id >= t.vocab;                 // outside the vocabulary: matches nothing, never indexes a table
+    const uint32_t w = bad ? CIDER_NONE : (uint32_t)id;
+
+    uint64_t key = 0;
+    bool kbad = false;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const uint32_t wj = (uint32_t)__shfl((int)w, (lane + j) & 63, 64);
+        const int bj = __shfl((int)bad, (lane + j) & 63, 64);
+        const bool used = j <= k;
+        key |= (uint64_t)(used ? wj : CIDER_NONE) << (16 * j);
+        kbad |= used && bj;
+    }
+    const bool live = k < n;                                  // wave-uniform
+    const bool active = live && lane + k < len;
+    // term frequency, and whether this is the n-gram's first position (an n-gram with a word outside the vocabulary keeps the
+    // 0xFFFF of that word in a used slot: equal keys within one order still mean equal word sequences)
+    int tf = 0;
+    bool first = active;
+    for (int j = 0; j < CIDER_MAXL; ++j) {
+        const uint64_t kj = __shfl(key, j, 64);
+        if (j + k < len && kj == key) {
+            ++tf;
+            if (j < lane) first = false;
+        }
+    }
+    const bool look = first && !kbad;                         // a key with a bad word may alias a shorter n-gram's: no lookups
+    double idf = t.log_n;                                     // not in the corpus: df = 0, max(1, df) = 1
+    if (look && t.n_grams > 0) {
+        const int64_t p = find_key(t.gram_keys, t.n_grams, key);
+        if (p >= 0) idf = t.gram_idf[p];
+    }
+    const double wh = first ? (double)tf * idf : 0.0;
+    const double nh = sqrt(wave_sum_f64(wh * wh));
+    const int lh = n >= 2 ? (len > 0 ? len - 1 : 0) : 0;     // the reference scorer's "length": the bigram count
+    const double two_s2 = 2.0 * (t.sigma * t.sigma);
+
+    double acc = 0.0;
+    for (int64_t r = rb; r < re;) {
+        // as many whole references as fit in LDS; one that does not fit alone is searched in HBM
+        const int64_t e0 = t.ref_off[r];
+        int64_t r1 = r + 1;
+        while (r1 < re && t.ref_off[r1 + 1] - e0 <= CIDER_STAGE) ++r1;
+        const int64_t cnt = t.ref_off[r1] - e0;
+        const bool staged = cnt <= CIDER_STAGE;
+        if (staged) {
+            for (int64_t i = threadIdx.x; i < cnt; i += CIDER_THREADS) {
+                skey[i] = t.ent_keys[e0 + i];
+                sw[i] = t.ent_w[e0 + i];
+            }
+        }
+        __syncthreads();
+        if (live) {
+            for (int64_t q = r; q < r1; ++q) {
+                const int64_t a = t.ref_off[q], m = t.ref_off[q + 1] - a;
+                const double nr = t.ref_norm[4 * q + k];
+                const double d = (double)(lh - t.ref_len[q]);
+                const double pen = exp(-(d * d) / two_s2);
+                double cq = 0.0;
+                if (look) {
+                    double wr = 0.0;
+                    if (staged) {
+                        const int64_t p = find_key(skey + (a - e0), m, key);
+                        if (p >= 0) wr = sw[a - e0 + p];
+                    } else {
+                        const int64_t p = find_key(t.ent_keys + a, m, key);
+                        if (p >= 0) wr = t.ent_w[a + p];
+                    }
+                    cq = fmin(wh, wr) * wr;
+                }
+                if (nh != 0.0 && nr != 0.0) cq /= nh * nr;
+                acc += cq * pen;
+            }
+        }
+        __syncthreads();
+        r = r1;
+    }
+    const double tot = wave_sum_f64(acc);
+    if (lane == 0 && live) stot[k] = tot;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double s = 0.0;
+        for (int kk = 0; kk < n; ++kk) s += stot[kk];
+        scores[row] = s / (double)n / (double)(re - rb) * 10.0;
+    }
+}
+
+// One workgroup of 256: thread-strided rows, then wave and workgroup sums in a fixed order.
+__global__ __launch_bounds__(256) void scst_advantage_kernel(const double* __restrict__ r, const int64_t* __restrict__ lens,
+                                                             const double* __restrict__ greedy, int B, int n,
+                                                             float* __restrict__ adv, double* __restrict__ stats) {
+    __shared__ double red[3][4];
+    const int N = B * n;
+    double sr = 0.0, sb = 0.0, sl = 0.0;
+    for (int i = threadIdx.x; i < N; i += 256) {
+        const int b = i / n;
+        double base;
+        if (greedy) {
+            base = greedy[b];
+        } else {
+            double s = 0.0;
+            for (int j = 0; j < n; ++j) s += r[b * n + j];
+            base = (s - r[i]) / (double)(n - 1);
+        }
+        adv[i] = (float)(r[i] - base);
+        sr += r[i];
+        sb += base;
+        sl += (double)lens[i];
+    }
+    sr = wave_sum_f64(sr);
+    sb = wave_sum_f64(sb);
+    sl = wave_sum_f64(sl);
+    const int wv = threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 0) {
+        red[0][wv] = sr;
+        red[1][wv] = sb;
+        red[2][wv] = sl;
+    }
+    __syncthreads();
+    if (threadIdx.x < 3) {
+        const double* v = red[threadIdx.x];
+        stats[threadIdx.x] = ((v[0] + v[1]) + (v[2] + v[3])) / (double)N;
+    }
+}
+
+}  // namespace
+
+#define ST(s) reinterpret_cast<hipStream_t>(s)
+
+extern "C" int dlsg_cider_d(const int64_t* ids, int64_t ld, int rows, int L, const int32_t* clip_idx, int64_t end_id,
+                            const dlsg_cider_tables* t, double* scores, void* stream) {
+    if (rows == 0) return DLSG_OK;
+    if (!t || !ids || !clip_idx || !scores || rows < 0 || L < 0 || L > CIDER_MAXL || (L > 0 && ld < L)) return DLSG_EINVAL;
+    if (t->n < 1 || t->n > 4 || t->vocab < 1 || t->vocab > 65535 || t->n_clips < 0 || t->n_grams < 0) return DLSG_EINVAL;
+    if (t->n_clips > 0 && (!t->clip_off || !t->ref_off || !t->ref_norm || !t->ref_len)) return DLSG_EINVAL;
+    if (t->n_grams > 0 && (!t->gram_keys || !t->gram_idf)) return DLSG_EINVAL;
+    hipLaunchKernelGGL(cider_d_kernel, dim3(rows), dim3(CIDER_THREADS), 0, ST(stream), ids, ld, L, clip_idx, end_id, *t, scores);
+    DLSG_CHECK_LAUNCH();
+    return DLSG_OK;
+}
+
+extern "C" int dlsg_scst_advantage(const double* rewards, const int64_t* lens, const double* greedy, int B, int n, float* adv,
+                                   double* stats, void* stream) {
+    if (B < 0 || n < 1 || (!greedy && n < 2) || !rewards || !lens || !adv || !stats) return DLSG_EINVAL;
+    if (B == 0) return DLSG_OK;
+    hipLaunchKernelGGL(scst_advantage_kernel, dim3(1), dim3(256), 0, ST(stream), rewards, lens, greedy, B, n, adv, stats);
+    DLSG_CHECK_LAUNCH();
+    return DLSG_OK;
+}

@@ -159,6 +159,12 @@ class CritColsumDesc(C.Structure):
                 ('out', c_f32p), ('out_b', c_f32p), ('scale', f32), ('pad2_', f32)]
 
 
+class CiderTables(C.Structure):
+    _fields_ = [('gram_keys', C.c_void_p), ('gram_idf', C.c_void_p), ('clip_off', C.c_void_p), ('ref_off', C.c_void_p),
+                ('ref_norm', C.c_void_p), ('ref_len', C.c_void_p), ('ent_keys', C.c_void_p), ('ent_w', C.c_void_p), ('n_grams', i64),
+                ('log_n', C.c_double), ('sigma', C.c_double), ('n_clips', i32), ('vocab', i32), ('n', i32), ('pad_', i32)]
+
+
 class ColsumDesc(C.Structure):
     _fields_ = [('part', c_f32p), ('ld', i64), ('out_a', c_f32p), ('out_b', c_f32p), ('rows', i32), ('n', i32), ('split', i32),
                 ('dup', i32), ('accum', i32), ('pad_', i32)]
@@ -231,7 +237,7 @@ SYMBOLS = ['dlsg_abi_version', 'dlsg_struct_size', 'dlsg_gemm', 'dlsg_gemm_varia
            'dlsg_rowln_bwd_nblk', 'dlsg_colsum', 'dlsg_colsum2', 'dlsg_colsum_ws_floats', 'dlsg_colsum_multi', 'dlsg_colsum_multi_ok', 'dlsg_o2v_workspace_bytes', 'dlsg_o2v_fwd', 'dlsg_o2v_fwd_multi',
            'dlsg_softmax_fwd', 'dlsg_softmax_bwd', 'dlsg_decatt_fwd', 'dlsg_decatt_bwd', 'dlsg_lstm_pw_fwd',
            'dlsg_lstm_pw_bwd', 'dlsg_lstm_pw_fwd_n', 'dlsg_lstm_pw_bwd_n', 'dlsg_mean_rows_fwd', 'dlsg_mean_rows_bwd', 'dlsg_embed_fwd', 'dlsg_embed_bwd',
-           'dlsg_argmax', 'dlsg_select_embed', 'dlsg_sample_embed', 'dlsg_ce_ragged_weighted', 'dlsg_copy2d', 'dlsg_dropout', 'dlsg_fill', 'dlsg_ce_ragged', 'dlsg_log_softmax',
+           'dlsg_argmax', 'dlsg_select_embed', 'dlsg_sample_embed', 'dlsg_ce_ragged_weighted', 'dlsg_cider_d', 'dlsg_scst_advantage', 'dlsg_copy2d', 'dlsg_dropout', 'dlsg_fill', 'dlsg_ce_ragged', 'dlsg_log_softmax',
            'dlsg_adam', 'dlsg_permute_tb', 'dlsg_gather_rows', 'dlsg_dec_mid_fwd', 'dlsg_dec_tail_fwd',
            'dlsg_dec_mid_bwd', 'dlsg_decatt_cache_grads', 'dlsg_o2v_bwd', 'dlsg_o2v_bwd_multi',
            'dlsg_latent_psl_fwd', 'dlsg_sa_core_fwd', 'dlsg_beam_select', 'dlsg_gather_rows_multi',
@@ -291,6 +297,8 @@ def load_library(path=LIB_PATH):
         'dlsg_argmax': [vp, i64, vp, i32, i32, vp],
         'dlsg_sample_embed': [vp, i64, i32, f32, vp, vp, vp, i64, i32, vp, vp, i32, i64, i32, f32, u64, u32, u32, i64, vp, vp],
         'dlsg_ce_ragged_weighted': [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp],
+        'dlsg_cider_d': [vp, i64, i32, i32, vp, i64, P(CiderTables), vp, vp],
+        'dlsg_scst_advantage': [vp, vp, vp, i32, i32, vp, vp, vp],
         'dlsg_copy2d': [vp, i64, vp, i64, i32, i32, i32, vp],
         'dlsg_dropout': [vp, i64, vp, i64, i32, i32, f32, u64, u32, vp, vp],
         'dlsg_fill': [vp, i64, f32, vp],
@@ -365,7 +373,7 @@ STRUCTS = [GemmArgs, RowLnArgs, RowLnBwdArgs, O2VArgs, DecAttArgs, DecAttBwdArgs
            DecTailArgs, DecMidBwdArgs, DecattCacheGradsArgs, O2VBwdArgs, LatentPslArgs,
            SaCoreArgs, BeamSelectArgs, GatherMultiArgs, SaCoreBwdArgs,
            LatentPslBwdArgs, BilstmArgs, BilstmBwdArgs, ColsumDesc, LstmSeqArgs, ClnArgs, CritSaArgs, CritPattnArgs, CritTsumArgs,
-           CritScoreArgs, CritColsumDesc, CritReduceDesc]
+           CritScoreArgs, CritColsumDesc, CritReduceDesc, CiderTables]
 
 
 def _p(t):
@@ -382,6 +390,14 @@ def _seed(seed):
     if torch.is_tensor(seed):
         return 0, C.c_void_p(seed.data_ptr())
     return int(seed), None
+
+
+def cider_tables(tb):
+    """the dlsg_cider_tables of a scoring.DeviceCiderD (device pointers; an empty table is NULL)"""
+    def p(t):
+        return t.data_ptr() if t.numel() else None
+    return CiderTables(p(tb.gram_keys), p(tb.gram_idf), p(tb.clip_off), p(tb.ref_off), p(tb.ref_norm), p(tb.ref_len), p(tb.ent_keys),
+                       p(tb.ent_w), tb.gram_keys.numel(), tb.log_n, tb.sigma, tb.n_clips, tb.V, tb.n, 0)
 
 
 def host_to_device(values, dtype, device):
@@ -1630,6 +1646,28 @@ class HipOps(object):
         assert weights.dtype == torch.float32 and weights.numel() == B and weights.is_contiguous()
         self._check(self.lib.dlsg_ce_ragged_weighted(_p(logits), _p(targets), _p(lens), _p(weights), _p(dlogits), _p(row_loss), _p(loss),
                                                      B, L, V, int(time_major), self._stream()), 'ce_ragged_weighted')
+
+    def cider_d(self, ids, clip_idx, end_id, tables, out):
+        """out[r] (float64) = CIDEr-D of the words of ids[r] (int64 (R, L), L <= 64, unit column stride; the words before the first
+        end_id) against the references of clip clip_idx[r] (int32) in `tables` (a scoring.DeviceCiderD)"""
+        R, L = ids.shape
+        assert ids.dtype == torch.int64 and (ids.stride(1) == 1 or L <= 1), (ids.dtype, ids.stride())
+        assert clip_idx.dtype == torch.int32 and clip_idx.is_contiguous() and clip_idx.numel() == R
+        assert out.dtype == torch.float64 and out.is_contiguous() and out.numel() == R
+        self._check(self.lib.dlsg_cider_d(_p(ids), i64(ids.stride(0)), R, L, _p(clip_idx), i64(end_id), C.byref(cider_tables(tables)),
+                                          _p(out), self._stream()), 'cider_d')
+
+    def scst_advantage(self, rewards, lens, greedy, n, adv, stats):
+        """adv = (float32) rewards - baseline over B clips x n samples: greedy[b] (float64 (B,)) or, greedy None, the leave-one-out
+        mean of the clip's other samples; stats (float64 (3,)) = mean reward, mean baseline, mean of lens (int64)"""
+        N = rewards.numel()
+        assert n >= 1 and N % n == 0 and rewards.dtype == torch.float64 and rewards.is_contiguous()
+        assert lens.dtype == torch.int64 and lens.is_contiguous() and lens.numel() == N
+        assert greedy is None or (greedy.dtype == torch.float64 and greedy.is_contiguous() and greedy.numel() == N // n)
+        assert adv.dtype == torch.float32 and adv.is_contiguous() and adv.numel() == N
+        assert stats.dtype == torch.float64 and stats.numel() == 3
+        self._check(self.lib.dlsg_scst_advantage(_p(rewards), _p(lens), _p(greedy), N // n, int(n), _p(adv), _p(stats), self._stream()),
+                    'scst_advantage')
 
     def log_softmax(self, logits, out):
         rows, V = logits.shape

@@ -1,5 +1,6 @@
 """caption scoring and the evaluation driver (reference evaluate.py:16-98 and the pure-Python
-metrics of caption-eval/pycocoevalcap: BLEU-1..4, ROUGE_L, CIDEr-D).  CPU-side, off the GPU critical path.
+metrics of caption-eval/pycocoevalcap: BLEU-1..4, ROUGE_L, CIDEr-D).  CPU-side, off the GPU critical path, except for
+`DeviceCiderD`: the self-critical reward scored on the GPU (`dlsg_cider_d`) against tables built from `CiderD`'s.
 
 Not reproduced: METEOR and the Stanford PTB tokenizer (caption-eval/pycocoevalcap/{meteor,tokenizer}) shell out to Java with
 jars that are not in the reference tree; `tokenize` below is a regular-expression stand-in that lower-cases, splits
@@ -196,6 +197,134 @@ class CiderD(object):
             if key not in memo:
                 memo[key] = self._score(v, h)
             out[i] = memo[key]
+        return out
+
+    def to_device(self, vocab, device='cuda'):
+        """the same scorer with device tables over `vocab`'s ids (`DeviceCiderD`); the corpus statistics are not recomputed"""
+        return DeviceCiderD(None, vocab, self.n, self.sigma, device, _cider=self)
+
+
+NGRAM_NONE = 0xFFFF             # the key slot of a position past the n-gram's order (and the bound on the vocabulary size)
+
+
+def pack_ngram(ids):
+    """the 64-bit key of an n-gram of word ids (n <= 4): sum_j s_j << 16 j, s_j = ids[j] for j < n, NGRAM_NONE past it"""
+    key = 0
+    for j in range(4):
+        key |= (ids[j] if j < len(ids) else NGRAM_NONE) << (16 * j)
+    return key
+
+
+class DeviceCiderD(object):
+    """CIDEr-D of captions given as vocabulary ids, scored on the GPU (`dlsg_cider_d`): the self-critical reward without a trip
+    through the host.  The corpus statistics are those of `CiderD(refs, n, sigma)`, built once on the host and copied to HBM:
+      * the corpus n-gram table -- every n-gram of the references made only of in-vocabulary words (`vocab.word2idx`: no
+        `<unk>` mapping, so an out-of-vocabulary reference word never meets a sampled `<unk>`), keyed by `pack_ngram`, sorted,
+        with its idf log_n - log(max(1, df)) (float64);
+      * the references -- per reference its in-vocabulary n-grams (sorted keys, tf-idf weights), its n norms and its length
+        (bigram count), the norms and lengths being CiderD's own, out-of-vocabulary n-grams included; CSR offsets from clip to
+        references (clips in sorted vid order) and from reference to entries.
+    `scores_device(ids, clip_idx)` scores id rows with decode_tokens' rule (the words before the first <end>) and gives what
+    `CiderD.scores` gives for the decoded strings (to rounding, 1e-12); an id outside [0, len(vocab)) is a word that matches no
+    reference.  `scores(vids, hyps)` (strings) is the host CiderD's, so this object serves wherever a CiderD does.
+    `ops`: the kernel binding (None: a `hip.HipOps` made on first use)."""
+
+    def __init__(self, refs, vocab, n=4, sigma=6.0, device='cuda', _cider=None):
+        import torch
+        V = len(vocab)
+        if V > NGRAM_NONE:
+            raise ValueError('DeviceCiderD packs 16 bits per word: a vocabulary of %d words is over the %d limit' % (V, NGRAM_NONE))
+        if not 1 <= int(n) <= 4:
+            raise ValueError('DeviceCiderD scores n-grams of orders 1..n with n <= 4, not n = %r' % (n,))
+        cd = _cider if _cider is not None else CiderD(refs, n, sigma)
+        self.cider, self.vocab, self.device = cd, vocab, torch.device(device)
+        self.n, self.sigma, self.V, self.log_n = int(cd.n), float(cd.sigma), V, float(cd.log_n)
+        self.end_id = vocab('<end>')
+        self.ops = None
+        w2i = vocab.word2idx
+        keyof = {}
+
+        def key(g):
+            k = keyof.get(g, False)
+            if k is False:
+                ids = [w2i.get(w) for w in g]
+                k = keyof[g] = None if any(i is None for i in ids) else pack_ngram(ids)
+            return k
+        gk, gi = [], []
+        for g, d in cd.df.items():
+            k = key(g)
+            if k is not None:
+                gk.append(k)
+                gi.append(cd.log_n - math.log(max(1.0, d)))
+        gk = np.array(gk, dtype=np.uint64)
+        order = np.argsort(gk, kind='stable')
+        self.vids = sorted(cd.ref_vecs)
+        self.vid_index = {v: i for i, v in enumerate(self.vids)}
+        clip_off, norms, lens, ent_ref, ek, ew = [0], [], [], [], [], []
+        q = 0
+        for v in self.vids:
+            for vr, nr, lr in cd.ref_vecs[v]:
+                for k in range(self.n):
+                    for g, w in vr[k].items():
+                        kk = key(g)
+                        if kk is not None:
+                            ent_ref.append(q)
+                            ek.append(kk)
+                            ew.append(w)
+                norms.append(list(nr) + [0.0] * (4 - len(nr)))
+                lens.append(lr)
+                q += 1
+            clip_off.append(q)
+        ek, ent_ref = np.array(ek, dtype=np.uint64), np.array(ent_ref, dtype=np.int64)
+        eo = np.lexsort((ek, ent_ref))                               # by reference, then by key
+        ref_off = np.zeros(q + 1, dtype=np.int64)
+        np.cumsum(np.bincount(ent_ref, minlength=q), out=ref_off[1:])
+
+        def dev(a, dtype):
+            return torch.from_numpy(np.ascontiguousarray(a)).to(dtype).to(self.device)
+        self.gram_keys = dev(gk[order].view(np.int64), torch.int64)  # uint64 bits
+        self.gram_idf = dev(np.array(gi, dtype=np.float64)[order], torch.float64)
+        self.clip_off = dev(np.array(clip_off, dtype=np.int64), torch.int64)
+        self.ref_off = dev(ref_off, torch.int64)
+        self.ref_norm = dev(np.array(norms, dtype=np.float64).reshape(q, 4), torch.float64)
+        self.ref_len = dev(np.array(lens, dtype=np.int32), torch.int32)
+        self.ent_keys = dev(ek[eo].view(np.int64), torch.int64)
+        self.ent_w = dev(np.array(ew, dtype=np.float64)[eo], torch.float64)
+        self.n_clips = len(self.vids)
+
+    def __getattr__(self, name):                                     # df, log_n, ref_vecs, ...: the host scorer's
+        if name == 'cider':
+            raise AttributeError(name)
+        return getattr(self.cider, name)
+
+    def scores(self, vids, hyps):
+        """CiderD.scores: tokenized strings on the host"""
+        return self.cider.scores(vids, hyps)
+
+    def index(self, vids):
+        """clip indices of `vids` (int32 tensor on the tables' device, one asynchronous host-to-device copy); KeyError for a vid
+        outside the corpus"""
+        import torch
+        from .hip import host_to_device
+        return host_to_device(np.array([self.vid_index[v] for v in vids], dtype=np.int32), torch.int32, self.device)
+
+    _hip_ops = None
+
+    def _ops(self):
+        if self.ops is not None:
+            return self.ops
+        if DeviceCiderD._hip_ops is None:
+            from .hip import HipOps
+            DeviceCiderD._hip_ops = HipOps()
+        return DeviceCiderD._hip_ops
+
+    def scores_device(self, ids, clip_idx, end_id=None):
+        """CIDEr-D of the id rows ids (int64 (R, L), L <= 64, any row stride) against the references of clips clip_idx (int32 (R,),
+        from `index`) -> float64 (R,) tensor on ids' device.  The words of a row are those before its first end_id (default the
+        vocabulary's <end>), all L without one.  One launch, no host synchronisation (capturable)."""
+        import torch
+        out = torch.empty(ids.shape[0], dtype=torch.float64, device=ids.device)
+        self._ops().cider_d(ids, clip_idx, self.end_id if end_id is None else int(end_id), self, out)
         return out
 
 

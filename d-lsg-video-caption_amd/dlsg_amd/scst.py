@@ -1,7 +1,8 @@
 """Self-critical sequence training (SCST): fine-tuning on the metric the model is judged by, after cross-entropy.
 
 One step: draw n captions per clip in train mode (`CapGnnModel.sample`, or its captured form `SampleGraph`), score them with
-CIDEr-D on the host (`scoring.CiderD`), subtract a baseline, and take the policy-gradient step
+CIDEr-D (on the host with `scoring.CiderD`, on the GPU with `scoring.DeviceCiderD`), subtract a baseline, and take the
+policy-gradient step
     loss = -sum_b A_b sum_{t < len_b} log p(w_bt) / sum_b len_b,   A_b = reward_b - baseline_b
 as the Trainer's fused step teacher-forced on the sampled words with the CrossEntropy weighted per caption by A_b
 (`ce_ragged_weighted`).  The train pass uses the sampling pass's seed and rows, hence its dropout masks: the gradient is
@@ -14,7 +15,9 @@ from .model import Trainer, GreedyGraph, SampleGraph, expand_rows, _h2d
 
 
 class SCSTTrainer(object):
-    """reward: an object with `scores(vids, hyps) -> np.ndarray` (a `scoring.CiderD` over the training references).
+    """reward: an object with `scores(vids, hyps) -> np.ndarray` (a `scoring.CiderD` over the training references), or one that
+    also has `index(vids)` and `scores_device(ids, clip_idx, end_id)` (a `scoring.DeviceCiderD`): the reward is then computed on
+    the GPU (see `step`).
     baseline: 'mean' -- the leave-one-out mean of the clip's other n - 1 rewards (needs n_samples >= 2); 'greedy' -- the reward
     of the clip's eval-mode greedy caption.  The remaining keywords go to the owned `Trainer` (lr, use_graphs, data parallel,
     ...), whose Adam state, gradient buckets and graphs the step reuses."""
@@ -71,8 +74,13 @@ class SCSTTrainer(object):
     @torch.no_grad()
     def step(self, frames, regions, vids):
         """One SCST step on clips `vids` (B ids of the reward's corpus).  Returns {'loss' (device scalar), 'reward_mean',
-        'baseline_mean', 'mean_len'}.  The one host synchronisation is the copy of the sampled words to the host: the reward is
-        computed there."""
+        'baseline_mean', 'mean_len'}.
+        Host reward (an object with `scores` only, e.g. `scoring.CiderD`): the one host synchronisation is the copy of the sampled
+        words to the host, where the reward, the baseline and the advantages are computed; the three statistics are floats.
+        Device reward (an object with `scores_device`, e.g. `scoring.DeviceCiderD`): the sampled rows -- and for the greedy
+        baseline the greedy rows -- are scored on the GPU (`dlsg_cider_d`), the baseline and advantages come from
+        `dlsg_scst_advantage` and go to the Trainer's step as they are: the step makes no device-to-host transfer of its own, and
+        'reward_mean', 'baseline_mean' and 'mean_len' are 0-d float64 device tensors, like 'loss'."""
         model = self.model
         dec = model.decoder
         n, B = self.n, frames.shape[0]
@@ -80,6 +88,8 @@ class SCSTTrainer(object):
         seed = model.next_seed()
         ids, _, lens = self._sample(frames, regions, seed)
         greedy = self._greedy_ids(frames, regions) if self.baseline == 'greedy' else None
+        if hasattr(self.reward, 'scores_device'):
+            return self._device_reward_step(frames, regions, vids, seed, ids, lens, greedy)
         host = torch.cat([ids, lens.unsqueeze(1)] + ([expand_rows(greedy, n)] if greedy is not None else []), 1).cpu()
         L = ids.shape[1]
         vids_x = [v for v in vids for _ in range(n)]
@@ -95,3 +105,19 @@ class SCSTTrainer(object):
         loss = self.trainer.step(fx, rx, ids, lens, 1.0, max_len=L, seed=seed, seq_weights=_h2d(adv, torch.float32, ids.device))
         return {'loss': loss, 'reward_mean': float(r.mean()), 'baseline_mean': float(b.mean()),
                 'mean_len': float(host[:, L].double().mean())}
+
+    def _device_reward_step(self, frames, regions, vids, seed, ids, lens, greedy):
+        model, reward = self.model, self.reward
+        n, B = self.n, len(vids)
+        L = ids.shape[1]
+        end = model.decoder.vocab('<end>')
+        # the clip indices of the B*n sampled rows, then of the B greedy rows: one asynchronous copy
+        cidx = reward.index([v for v in vids for _ in range(n)] + (list(vids) if greedy is not None else []))
+        r = reward.scores_device(ids, cidx[:B * n], end_id=end)
+        g = reward.scores_device(greedy.contiguous(), cidx[B * n:], end_id=end) if greedy is not None else None
+        adv = torch.empty(B * n, dtype=torch.float32, device=ids.device)
+        stats = torch.empty(3, dtype=torch.float64, device=ids.device)
+        model.ops.scst_advantage(r, lens, g, n, adv, stats)
+        fx, rx = self._expanded_inputs(frames, regions)
+        loss = self.trainer.step(fx, rx, ids, lens, 1.0, max_len=L, seed=seed, seq_weights=adv)
+        return {'loss': loss, 'reward_mean': stats[0], 'baseline_mean': stats[1], 'mean_len': stats[2]}

@@ -671,6 +671,32 @@ int dlsg_ce_ragged(const float* logits, const int64_t* targets, const int64_t* l
  * With every weight 1 the results are bit-identical to dlsg_ce_ragged. */
 int dlsg_ce_ragged_weighted(const float* logits, const int64_t* targets, const int64_t* lens, const float* weights, float* dlogits,
                             float* row_loss, float* loss, int B, int L, int V, int time_major, void* stream);
+/* CIDEr-D corpus tables of a training run (self-critical reward on the device; built once by scoring.DeviceCiderD).  An n-gram
+ * of word ids w_0..w_{k-1} (k <= 4) is the key sum_j s_j << 16 j with s_j = w_j for j < k and 0xFFFF past the order; only
+ * n-grams made of in-vocabulary words are listed.  Corpus table: the sorted keys and their idf, log_n - log(max(1, df)).
+ * References: clip c owns references [clip_off[c], clip_off[c + 1]); reference q owns entries [ref_off[q], ref_off[q + 1])
+ * (keys sorted, tf-idf weights), its n norms ref_norm[4 q + k] and its length ref_len[q] (bigram count) over ALL of its n-grams,
+ * out-of-vocabulary ones included. */
+typedef struct {
+    const uint64_t* gram_keys; const double* gram_idf;
+    const int64_t* clip_off; const int64_t* ref_off; const double* ref_norm; const int32_t* ref_len;
+    const uint64_t* ent_keys; const double* ent_w;
+    int64_t n_grams;
+    double log_n, sigma;
+    int32_t n_clips, vocab, n, pad_;
+} dlsg_cider_tables;
+/* scores[r] = CIDEr-D (x10, Gaussian length penalty sigma, orders 1..n) of row r of ids (int64, row stride ld) against the
+ * references of clip clip_idx[r], in float64, as scoring.CiderD scores decode_tokens(ids[r]): the row's words are those before
+ * its first end_id (all L without one).  An id outside [0, vocab) is a word outside the vocabulary (it matches no reference
+ * n-gram); a clip index outside [0, n_clips), or a clip without references, scores NaN.  One workgroup per row, fixed-order
+ * reductions (bit-identical on every launch).  L <= 64. */
+int dlsg_cider_d(const int64_t* ids, int64_t ld, int rows, int L, const int32_t* clip_idx, int64_t end_id,
+                 const dlsg_cider_tables* t, double* scores, void* stream);
+/* self-critical advantages of B clips x n samples: baseline b_i = greedy[i / n] when greedy is set, else the leave-one-out mean
+ * (sum_j r[(i / n) n + j] - r_i) / (n - 1); adv[i] = (float)(r_i - b_i); stats = {mean r, mean b, mean lens} (float64).
+ * One workgroup, fixed-order sums.  Without greedy n >= 2. */
+int dlsg_scst_advantage(const double* rewards, const int64_t* lens, const double* greedy, int B, int n, float* adv, double* stats,
+                        void* stream);
 int dlsg_log_softmax(const float* logits, float* out, int rows, int V, void* stream);
 /* One beam-search step for every batch item (BeamSearch.search, allennlp_beamsearch.py:140-260, per-node k == k):
  * log-softmax + per-beam top-k over the vocabulary + top-k over the k*k summed candidates, in one launch.

@@ -4,8 +4,12 @@
   * `ciderd_ms` -- host ms of CiderD.scores for 320 hypotheses (a corpus of 64 clips x 20 references);
   * `scst_step_ms` -- one SCSTTrainer step (use_graphs), split into `sample_ms` (SampleGraph replay + copy of the words to the
     host), `reward_ms` (decode + CIDEr-D + advantages, host) and `train_ms` (the Trainer's weighted step on 320 rows).
+  * `device_reward` -- the same with the reward on the GPU (`scoring.DeviceCiderD`, vocabulary 1000): `cider_kernel_ms` (HIP
+    events around `dlsg_cider_d` on the 320 rows), `advantage_kernel_ms` (`dlsg_scst_advantage`), `scst_step_ms` and its split
+    (`reward_ms`: the CIDEr-D and advantage launches, no host transfer), and the scores' largest difference to the host scorer.
 usage: python3 tools/scst_bench.py [steps=10] [batch=64] [n=5]
-       python3 tools/scst_bench.py kernels      (rocprofv3 --kernel-trace --stats target: eager greedy and sampled decodes)"""
+       python3 tools/scst_bench.py kernels      (rocprofv3 --kernel-trace --stats target: eager greedy and sampled decodes)
+       python3 tools/scst_bench.py reward-kernels   (rocprofv3 target: 20 launches each of dlsg_cider_d and dlsg_scst_advantage)"""
 import json
 import os
 import random
@@ -62,6 +66,79 @@ def kernels(B=64, n=5):
     print('kernels: 3 greedy + 3 sampled decodes of %d rows' % (B * n))
 
 
+def event_ms(fn, reps=20):
+    fn()
+    torch.cuda.synchronize()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(reps):
+        fn()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) / reps
+
+
+def reward_kernels(B=64, n=5):
+    """the reward launches alone on B*n sampled rows: 20 x dlsg_cider_d, 20 x dlsg_scst_advantage"""
+    net, vocab, frames, regions, refs = setup(B)
+    dc = dlsg_amd.DeviceCiderD(refs, vocab)
+    ids, _, lens = net.sample(frames, regions, n=n, seed=3)
+    cidx = dc.index([str(b) for b in range(B) for _ in range(n)])
+    adv = torch.empty(B * n, dtype=torch.float32, device='cuda')
+    stats = torch.empty(3, dtype=torch.float64, device='cuda')
+    for _ in range(20):
+        r = dc.scores_device(ids, cidx)
+        net.ops.scst_advantage(r, lens, None, n, adv, stats)
+    torch.cuda.synchronize()
+    print('reward kernels: 20 x %d rows' % (B * n))
+
+
+def device_leg(net, vocab, frames, regions, refs, steps, B, n):
+    dc = dlsg_amd.DeviceCiderD(refs, vocab)
+    vids = [str(b) for b in range(B) for _ in range(n)]
+    ids, _, lens = net.sample(frames, regions, n=n, seed=3)
+    cidx = dc.index(vids)
+    adv = torch.empty(B * n, dtype=torch.float32, device='cuda')
+    stats = torch.empty(3, dtype=torch.float64, device='cuda')
+    r = dc.scores_device(ids, cidx)
+    kernel_ms = event_ms(lambda: dc.scores_device(ids, cidx))
+    adv_ms = event_ms(lambda: net.ops.scst_advantage(r, lens, None, n, adv, stats))
+    host = dc.cider.scores(vids, [net.decoder.decode_tokens(x) for x in ids.cpu()])
+    err = float(np.abs(r.cpu().numpy() - host).max())
+
+    tr = SC.SCSTTrainer(net, dc, n_samples=n, use_graphs=True)
+    vb = [str(b) for b in range(B)]
+    for _ in range(2):
+        tr.step(frames, regions, vb)                   # captures
+    step_ms = timed(lambda: tr.step(frames, regions, vb), steps)
+    parts = {'sample': 0.0, 'reward': 0.0, 'train': 0.0}
+    inner_sample, inner_step = tr._sample, tr.trainer.step
+    inner_scores, inner_adv = dc.scores_device, net.ops.scst_advantage
+
+    def clock(key, fn):
+        def f(*a, **k):
+            torch.cuda.synchronize()
+            t = time.perf_counter()
+            out = fn(*a, **k)
+            torch.cuda.synchronize()
+            parts[key] += time.perf_counter() - t
+            return out
+        return f
+    tr._sample = clock('sample', inner_sample)
+    dc.scores_device = clock('reward', inner_scores)
+    net.ops.scst_advantage = clock('reward', inner_adv)
+    tr.trainer.step = clock('train', inner_step)
+    for _ in range(steps):
+        out = tr.step(frames, regions, vb)
+    torch.cuda.synchronize()
+    del net.ops.scst_advantage
+    tr.trainer.check()
+    return {'cider_kernel_ms': round(kernel_ms, 4), 'advantage_kernel_ms': round(adv_ms, 4), 'rows': B * n,
+            'refs_per_clip': len(refs['0']), 'max_abs_diff_to_host': err, 'scst_step_ms': round(step_ms, 2),
+            'parts_ms': {k: round(v / steps * 1e3, 2) for k, v in parts.items()},
+            'last_step': {k: float(v) for k, v in out.items()}}
+
+
 def main(steps=10, B=64, n=5):
     net, vocab, frames, regions, refs = setup(B)
     rows = B * n
@@ -109,6 +186,7 @@ def main(steps=10, B=64, n=5):
         out = tr.step(frames, regions, vb)
     torch.cuda.synchronize()
     tr.trainer.check()
+    dev = device_leg(net, vocab, frames, regions, refs, steps, B, n)
     print(json.dumps({
         'what': 'SCST at the MSVD shape: batch %d x %d samples = %d rows, vocabulary 1000, train mode, hipGraph replays' % (B, n, rows),
         'sample_graph_ms': round(sample_ms, 3), 'greedy_graph_ms': round(greedy_ms, 3),
@@ -118,11 +196,14 @@ def main(steps=10, B=64, n=5):
         'parts_ms': {k: round(v / steps * 1e3, 2) for k, v in parts.items()},
         'parts_note': 'separate steps with a device synchronisation around sample and train: they add up to more than scst_step_ms',
         'last_step': {k: (float(v) if k == 'loss' else v) for k, v in out.items()},
+        'device_reward': dev,
         'steps': steps}))
 
 
 if __name__ == '__main__':
     if len(sys.argv) > 1 and sys.argv[1] == 'kernels':
         kernels()
+    elif len(sys.argv) > 1 and sys.argv[1] == 'reward-kernels':
+        reward_kernels()
     else:
         main(*[int(x) for x in sys.argv[1:4]])
