@@ -77,6 +77,60 @@ def check_grads(get_grad, named_parameters, g, rel, abs_=2e-5):
             assert abs(n - ref) <= 2.5 * rel * max(ref, 1e-6) + 1e-6, (k, n, ref)
 
 
+GRAD_ABS, GRAD_REL, GRAD_NORM_REL, GRAD_NORM_ABS = 2e-5, 2e-3, 1e-3, 1e-7
+
+
+def compare_grads(got, want, tag='', check=True):
+    """Element-wise gradient comparison: {name: gradient} against {name: oracle gradient or None}.
+
+    For every parameter with an oracle gradient, both
+        max|g - g_ref|      <= 2e-5 + 2e-3 * max|g_ref|
+        ||g - g_ref||_2     <= 1e-3 * ||g_ref||_2 + 1e-7        (the norm OF THE DIFFERENCE)
+    and a parameter the oracle leaves without a gradient must be exactly zero in `got` (or missing / None).
+    Differences are taken in float64 on the device of `got[name]`.  Returns a report: the worst ratio of error to bound for
+    each criterion with the parameter that produced it, the number of parameters checked and the failures; with check=True
+    a failure raises AssertionError naming the parameters."""
+    rep = dict(tag=tag, max_ratio=0.0, max_param=None, norm_ratio=0.0, norm_param=None, checked=0, failures=[])
+    for k, ref in want.items():
+        try:
+            g = got[k]                                                  # (a dict, or a model's grad_views())
+        except KeyError:
+            g = None
+        if ref is None:
+            if g is not None and bool((g != 0).any()):
+                rep['failures'].append((k, 'no oracle gradient, but nonzero here'))
+            continue
+        assert g is not None, (tag, k, 'gradient missing')
+        assert tuple(g.shape) == tuple(ref.shape), (tag, k, tuple(g.shape), tuple(ref.shape))
+        g = g.detach().double()
+        r = ref.detach().to(g.device, torch.float64)
+        d = g - r
+        err_max, ref_max = float(d.abs().max()), float(r.abs().max())
+        err_norm, ref_norm = float(d.norm()), float(r.norm())
+        rmax = err_max / (GRAD_ABS + GRAD_REL * ref_max)
+        rnorm = err_norm / (GRAD_NORM_REL * ref_norm + GRAD_NORM_ABS)
+        rmax, rnorm = [r if r == r else float('inf') for r in (rmax, rnorm)]       # a NaN anywhere is the worst ratio
+        if rmax > 1.0:
+            rep['failures'].append((k, 'max|dg| %.3g, max|g_ref| %.3g' % (err_max, ref_max)))
+        if rnorm > 1.0:
+            rep['failures'].append((k, '|dg| %.3g, |g_ref| %.3g' % (err_norm, ref_norm)))
+        if rmax > rep['max_ratio']:
+            rep['max_ratio'], rep['max_param'] = rmax, k
+        if rnorm > rep['norm_ratio']:
+            rep['norm_ratio'], rep['norm_param'] = rnorm, k
+        rep['checked'] += 1
+    print('compare_grads %s: %d parameters, worst max-element ratio %.3g (%s), worst difference-norm ratio %.3g (%s)'
+          % (tag, rep['checked'], rep['max_ratio'], rep['max_param'], rep['norm_ratio'], rep['norm_param']))
+    if check:
+        assert not rep['failures'], (tag, rep['failures'][:8])
+    return rep
+
+
+def oracle_grads(model):
+    """{name: p.grad (float32, host) or None} of a module the oracle has just differentiated"""
+    return {k: (p.grad.detach().float().cpu() if p.grad is not None else None) for k, p in model.named_parameters()}
+
+
 def graft_and_step(make_model, device, tmp_path, make_trainer):
     """CapGnnModel.load_encoder (models/model.py:45-53) followed by one optimisation step: returns (model, word-embedding
     before the step, loss).  make_model(args, vocab) -> model; make_trainer(model) -> object with .step(...)."""

@@ -8,7 +8,9 @@ configuration and shared by the schedules below.
 Compared (run_gun.py:183-198 semantics, dropout off so that both sides see the same arithmetic):
   * teacher-forced logits: max |dlogit| <= 1e-3 (north_star), the proposals and attention weights likewise;
   * greedy ids: bit-exact;
-  * CrossEntropy over the ragged rows: |dloss| <= 1e-3; every parameter's gradient norm within 5e-3 relative;
+  * CrossEntropy over the ragged rows: |dloss| <= 1e-3; every parameter's gradient norm within 5e-3 relative, and every
+    gradient element-wise (helpers.compare_grads: max|dg| and the norm of the difference -- a norm alone misses a dropped
+    or swapped tile);
   * the same under scheduled sampling (tf = 0.6, random.seed(12): 11 of 26 steps feed their own argmax).
 
 Two schedules of the train step are held to that:
@@ -27,6 +29,7 @@ import torch
 import dlsg_amd
 from dlsg_amd.config import make_vocab, msvd_shaped, msrvtt_shaped
 from dlsg_amd.synth import synth_state_dict, synth_batch
+from helpers import compare_grads, oracle_grads
 
 pytestmark = pytest.mark.gpu
 
@@ -38,7 +41,8 @@ def _grad_norms_oracle(orc, frames, regions, caps, lens, tf, R):
     loss = R.ragged_ce(out[0], caps, lens)
     loss.backward()
     return [o.detach() for o in out], float(loss.detach()), \
-        {k: (float(p.grad.double().norm()) if p.grad is not None else None) for k, p in orc.named_parameters()}
+        {k: (float(p.grad.double().norm()) if p.grad is not None else None) for k, p in orc.named_parameters()}, \
+        oracle_grads(orc)
 
 
 @functools.lru_cache(maxsize=None)
@@ -60,7 +64,7 @@ def _case(shape, B):
     orc.update_beam_size(1)
     with torch.no_grad():
         ids = orc(frames, regions, None)[0]
-    return dict(args=args, vocab=vocab, sd=sd, batch=(frames, regions, caps, lens), tf=tf, ss=ss, ids=ids)
+    return dict(tag='%s B=%d' % (shape, B), args=args, vocab=vocab, sd=sd, batch=(frames, regions, caps, lens), tf=tf, ss=ss, ids=ids)
 
 
 def _net(c):
@@ -88,7 +92,7 @@ def _trainer(net, schedule):
     return tr
 
 
-def _check_step(net, c, schedule, tf, want_loss, want_gn, tag):
+def _check_step(net, c, schedule, tf, want_loss, want_gn, want_g, tag):
     frames, regions, caps, lens = c['batch']
     fg, rg, cg = frames.cuda(), regions.cuda(), caps.cuda()
     net.load_state_dict({k: v.cuda() for k, v in c['sd'].items()})
@@ -109,6 +113,7 @@ def _check_step(net, c, schedule, tf, want_loss, want_gn, tag):
         rel = abs(gn - ref) / max(ref, 1e-12)
         worst = max(worst, rel)
         assert rel <= 5e-3, (tag, k, gn, ref)
+    compare_grads(G, want_g, '%s %s' % (c['tag'], tag))
     tr.check()
     flat = net._gflat.clone()
     tr.close()
@@ -123,7 +128,7 @@ def test_bench_configuration_against_the_oracle(shape, B):
     fg, rg, cg = frames.cuda(), regions.cuda(), caps.cuda()
 
     # ---- teacher-forced forward
-    want, want_loss, want_gn = c['tf']
+    want, want_loss, want_gn, want_g = c['tf']
     with torch.no_grad():
         got = net(fg, rg, cg, 26, 1.0)
     err = (got[0].cpu() - want[0]).abs().max().item()
@@ -138,32 +143,32 @@ def test_bench_configuration_against_the_oracle(shape, B):
     assert torch.equal(ids_got, c['ids']), int((ids_got != c['ids']).sum())
 
     # ---- loss and gradients of one step (the trainer's own schedule: fused CE, Adam behind it)
-    _check_step(net, c, 'one_rank', 1.0, want_loss, want_gn, 'teacher-forced')
+    _check_step(net, c, 'one_rank', 1.0, want_loss, want_gn, want_g, 'teacher-forced')
 
     # ---- scheduled sampling: the coin order of random.seed(12) on both sides (models/layer.py:432)
-    want_ss, want_loss_ss, want_gn_ss = c['ss']
+    want_ss, want_loss_ss, want_gn_ss, want_g_ss = c['ss']
     net.load_state_dict({k: v.cuda() for k, v in c['sd'].items()})            # (the trainer's Adam step above moved the weights)
     random.seed(12)
     with torch.no_grad():
         got_ss = net(fg, rg, cg, 26, 0.6)[0].cpu()
     assert (got_ss - want_ss[0]).abs().max().item() <= 1e-3
     random.seed(12)
-    _check_step(net, c, 'one_rank', 0.6, want_loss_ss, want_gn_ss, 'scheduled sampling')
+    _check_step(net, c, 'one_rank', 0.6, want_loss_ss, want_gn_ss, want_g_ss, 'scheduled sampling')
 
 
 @pytest.mark.parametrize('shape,B', [('msvd', 64), ('msvd', 128), ('msrvtt', 64)])
 def test_data_parallel_rank_schedule_against_the_oracle(shape, B):
     """configs[2] / [3]'s per-GPU step AS A RANK RUNS IT, replayed from one hipGraph with the RCCL calls inside"""
     c = _case(shape, B)
-    want, want_loss, want_gn = c['tf']
+    want, want_loss, want_gn, want_g = c['tf']
     net = _net(c)
-    g_plain = _check_step(net, c, 'dp_rank', 1.0, want_loss, want_gn, 'dp rank, teacher-forced')
+    g_plain = _check_step(net, c, 'dp_rank', 1.0, want_loss, want_gn, want_g, 'dp rank, teacher-forced')
     # a co-tenant of an all-reduce's shape on the side stream under the backward: same gradients, bit for bit
     net2 = _net(c)
-    g_co = _check_step(net2, c, 'dp_rank_cotenant', 1.0, want_loss, want_gn, 'dp rank + co-tenant')
+    g_co = _check_step(net2, c, 'dp_rank_cotenant', 1.0, want_loss, want_gn, want_g, 'dp rank + co-tenant')
     assert torch.equal(g_plain, g_co)
     if (shape, B) == ('msvd', 64):
-        _check_step(_net(c), c, 'dp_rank_cu_budget', 1.0, want_loss, want_gn, 'dp rank, stream-K on a CU budget')
-    want_ss, want_loss_ss, want_gn_ss = c['ss']
+        _check_step(_net(c), c, 'dp_rank_cu_budget', 1.0, want_loss, want_gn, want_g, 'dp rank, stream-K on a CU budget')
+    want_ss, want_loss_ss, want_gn_ss, want_g_ss = c['ss']
     random.seed(12)
-    _check_step(net, c, 'dp_rank', 0.6, want_loss_ss, want_gn_ss, 'dp rank, scheduled sampling')
+    _check_step(net, c, 'dp_rank', 0.6, want_loss_ss, want_gn_ss, want_g_ss, 'dp rank, scheduled sampling')

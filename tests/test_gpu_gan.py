@@ -190,3 +190,74 @@ def test_replayed_generator_forward_equals_the_model_call():
     for a, b in zip(got, want):
         assert a.shape == b.shape and torch.equal(a, b)
     assert it.trainer.forward_only(frames[:2], regions[:2], caps[:2], 0.7) is None       # another batch shape: the model call
+
+
+def test_gan_iteration_at_the_bench_shape_against_the_oracle():
+    """bench.py gan_iteration_leg's shape -- MSVD-shaped with the visual GAN, V = 1000, B = 64, num_D = 5 -- against
+    oracle/gan_ref.py, dropout off (eval) and recorded penalty epsilons.  (1) The critic's first update through
+    CriticEngine.update_gradients, both sides on the same generator outputs: real / fake / mixed logits, penalty, loss_D and
+    every critic gradient element-wise (helpers.compare_grads) against critic_losses(...) + loss_D.backward().  (2) One whole
+    iteration with lr = 0 on both sides, so all five critic updates and the generator step see the same weights: the logged
+    losses, and the generator's gradient (caption loss + lambda * the critic's term) element-wise."""
+    import copy
+    from oracle import torch_ref as R
+    from oracle import gan_ref
+    from dlsg_amd.synth import synth_state_dict, synth_batch
+    from helpers import compare_grads, oracle_grads
+    V, B, num_D, lam = 1000, 64, 5, 0.01                                # bench.py: GanTrainer's default gan_lambda
+    args = dlsg_amd.msvd_shaped(use_visual_gan=True)
+    vocab = dlsg_amd.make_vocab(V)
+    torch.manual_seed(0)
+    G = dlsg_amd.CapGnnModel(args, vocab)
+    sd = synth_state_dict(G.state_dict(), 21)
+    G.load_state_dict(sd)
+    D = dlsg_amd.DiscV2(args, V)
+    dsd = synth_state_dict(D.state_dict(), 22)
+    D.load_state_dict(dsd)
+    frames, regions, caps, lens = synth_batch(args, V, B, 23)
+    caps = caps[:, :26].contiguous()
+    for j in range(B):
+        caps[j, int(lens[j]):] = 0
+    eps = torch.rand(num_D, B, 1, 1, generator=torch.Generator().manual_seed(24))
+    orc = R.CapGnnModelRef(args, vocab).eval()
+    orc.load_state_dict(sd)
+    Dr = gan_ref.DiscV2Ref(args, V).eval()
+    Dr.load_state_dict(dsd)
+    G, D = G.cuda().eval(), D.cuda().eval()
+    fg, rg, cg, eg = frames.cuda(), regions.cuda(), caps.cuda(), eps.cuda()
+
+    # ---- (1) the first critic update
+    with torch.no_grad():
+        f_caption, obj, mot, alpha = G(fg, rg, cg, 26, 1.0)
+    D0 = copy.deepcopy(D)
+    L = caps.shape[1]
+    smask = (cg > 0).float()
+    eng = D0.engine
+    ws = eng.prepare(cg.device, B, L, V, smask, 4)
+    eng.proposals(ws, obj, mot, alpha, smask)
+    stats = eng.update_gradients(ws, cg, f_caption.transpose(0, 1).contiguous(), eg[0].reshape(B), 0).cpu()
+    outv = eng._bufs(ws)['outv'].cpu()
+    loss_D, r_loss, f_loss, gp, logits = gan_ref.critic_losses(
+        Dr, gan_ref.to_onehot(caps, V), f_caption.cpu(), obj.cpu(), mot.cpu(), gan_ref.attention_mask(caps), alpha.cpu(), eps[0])
+    loss_D.backward()
+    for got, want in zip((outv[:B], outv[B:2 * B], outv[2 * B:]), logits):
+        assert (got - want.detach()).abs().max().item() <= 2e-4
+    assert abs(float(stats[3]) - float(gp)) <= 1e-3 * max(1.0, float(gp))
+    assert abs(float(stats[0]) - float(loss_D)) <= 2e-3
+    compare_grads(D0.grad_views(), oracle_grads(Dr), 'critic, first update at B=64 V=1000')
+
+    # ---- (2) one whole iteration, lr = 0
+    it = dlsg_amd.GanTrainer(G, D, lr=0.0, num_D=num_D, gan_lambda=lam)
+    it.eps_source = lambda k: eg[k]
+    res = it.iteration(fg, rg, cg, lens, 1.0)
+    Dr.zero_grad(set_to_none=True)
+    opt_G = R.make_optimizer(orc, 0.0)
+    opt_D = torch.optim.Adam(Dr.parameters(), lr=0.0, betas=(0.5, 0.9))
+    want = gan_ref.gan_iteration(orc, Dr, opt_G, opt_D, frames, regions, caps, lens, 1.0, lam, num_D, list(eps))
+    assert abs(res['loss_D'] - want['loss_D']) <= 3e-3, (res['loss_D'], want['loss_D'])
+    assert abs(res['wasserstein'] - want['wasserstein']) <= 3e-3, (res['wasserstein'], want['wasserstein'])
+    assert abs(res['cap_loss'] - want['cap_loss']) <= 1e-4, (res['cap_loss'], want['cap_loss'])
+    assert abs(res['loss_G'] - want['loss_G']) <= 2e-3, (res['loss_G'], want['loss_G'])
+    assert abs(res['total_loss'] - want['total_loss']) <= 2e-4, (res['total_loss'], want['total_loss'])
+    compare_grads(G.grad_views(), oracle_grads(orc), 'generator, whole iteration at B=64 V=1000')
+    G.ops.check_persistent()

@@ -721,6 +721,20 @@ def test_out_of_range_caption_id_poisons_the_loss():
     assert torch.isfinite(loss).item() and torch.isfinite(dl).all().item()
 
 
+def _oracle_hyp_logp(orc, frames, regions, hyp, end, upto):
+    """the beam score of the hypothesis hyp[:upto + 1] of one clip under the oracle: the sum of its words' log-probabilities,
+    teacher-forced, nothing added after the first <end> (allennlp_beamsearch.py: an ended beam only appends <end> at 0)"""
+    with torch.no_grad():
+        logits = orc(frames, regions, hyp[:upto + 1].unsqueeze(0), upto + 1, 1.0)[0][0].double()
+    lp = torch.log_softmax(logits, -1).gather(1, hyp[:upto + 1].view(-1, 1)).view(-1)
+    s = 0.0
+    for t in range(upto + 1):
+        s += float(lp[t])
+        if int(hyp[t]) == end:
+            break
+    return s
+
+
 @pytest.mark.parametrize('end_bias', [0.0, 9.0])
 def test_beam5_at_batch128_config4_as_stated(end_bias):
     """BASELINE configs[4] as it is stated: allennlp-style beam search with beam 5 at batch 128, MSVD-shaped, one GPU
@@ -728,8 +742,9 @@ def test_beam5_at_batch128_config4_as_stated(end_bias):
     gathers and `beam_select`.  Asserted: (1) the hipGraph-captured search (no host sync inside) returns exactly the ids
     of the eager search with its host-side early exit -- also when every beam ends early (`end_bias` lifts <end>'s logit so
     the whole batch stops after a few words and the cut of `beam_finish` is exercised); (2) a clip's beam ids do not depend on
-    which other clips share its batch (alone, among 3, among 128) beyond the common length of the two results; (3) three clips
-    agree with the oracle's beam search (CPU restatement of the reference) token for token."""
+    which other clips share its batch (alone, among 3, among 128) beyond the common length of the two results; (3) all 128 clips
+    agree with the oracle's beam search (CPU restatement of the reference) token for token: the same common prefix and only <end>
+    beyond it.  At most two clips other than 3, 64 and 127 may differ, and only at a demonstrated near-tie."""
     from dlsg_amd.synth import synth_state_dict, synth_batch
     from oracle import torch_ref as R
     args = dlsg_amd.msvd_shaped()
@@ -768,13 +783,22 @@ def test_beam5_at_batch128_config4_as_stated(end_bias):
     orc = R.CapGnnModelRef(args, vocab).eval()
     orc.load_state_dict(sd)
     orc.update_beam_size(5)
-    sel = [3, 64, 127]
     with torch.no_grad():
-        want = orc(frames[sel], regions[sel], None)[0]
-    n = min(want.shape[1], ids_eager.shape[1])
-    got = ids_eager[torch.tensor(sel, device='cuda')].cpu()
-    assert torch.equal(got[:, :n], want[:, :n])
-    assert bool((got[:, n:] == end).all()) and bool((want[:, n:] == end).all())
+        want = orc(frames, regions, None)[0]
+    got = ids_eager.cpu()
+    L = max(want.shape[1], got.shape[1])
+    pad = lambda x: torch.cat([x, torch.full((Bn, L - x.shape[1]), end, dtype=x.dtype)], 1)
+    # exact common prefix, only <end> beyond it: the padded rows are equal
+    differ = [b for b in range(Bn) if not torch.equal(pad(got)[b], pad(want)[b])]
+    print('beam-5 at batch 128, end_bias %g: %d of %d clips differ from the oracle %s' % (end_bias, len(differ), Bn, differ))
+    assert len(differ) <= 2 and not set(differ) & {3, 64, 127}, differ
+    for b in differ:
+        # the only excuse is a near-tie: at the first differing step the oracle's own cumulative log-probabilities of the two
+        # competing hypotheses (teacher-forced through the oracle) agree within 1e-5 relative
+        x, y = pad(got)[b], pad(want)[b]
+        d = int((x != y).nonzero()[0])
+        lp = [_oracle_hyp_logp(orc, frames[b:b + 1], regions[b:b + 1], h, end, d) for h in (x, y)]
+        assert abs(lp[0] - lp[1]) <= 1e-5 * abs(lp[1]), (b, d, lp)
 
 
 def test_single_long_clip_with_many_objects_stays_inside_the_graph_kernel_limits():

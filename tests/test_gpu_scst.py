@@ -172,15 +172,20 @@ def test_sampler_logp_is_on_policy(msvd):
     assert err <= 2e-4, err
 
 
-def test_scst_step_gradient_equals_oracle():
+@pytest.mark.parametrize('msvd', [False, True], ids=['small_3x3', 'msvd_64x5'])
+def test_scst_step_gradient_equals_oracle(msvd):
+    """The weighted CrossEntropy and the sampled-id backward of one SCST step against oracle autograd on the same weights, ids
+    and advantages: a small model with 3 clips x 3 samples, and the MSVD-shaped one at the shape tools/scst_bench.py measures
+    (64 clips x 5 samples = 320 rows), every gradient element-wise (helpers.compare_grads)."""
     from oracle import torch_ref as R
-    net, sd, args, vocab, frames, regions, _, _ = gpu_net(dropout=0.0)
-    n = 3
+    from helpers import compare_grads, oracle_grads
+    nb, n = (64, 5) if msvd else (3, 3)
+    net, sd, args, vocab, frames, regions, _, _ = gpu_net(dropout=0.0, msvd=msvd, n_batch=nb)
     tr = dlsg_amd.SCSTTrainer(net, LengthReward(), n_samples=n, lr=0.0)
     seen = []
     inner = tr.trainer.step
     tr.trainer.step = lambda *a, **k: seen.append((a, k)) or inner(*a, **k)
-    tr.step(frames, regions, ['0', '1', '2'])
+    tr.step(frames, regions, [str(i) for i in range(nb)])
     torch.cuda.synchronize()
     (fx, rx, ids, lens, _), kw = seen[0]
     A = kw['seq_weights'].cpu()
@@ -201,6 +206,8 @@ def test_scst_step_gradient_equals_oracle():
         assert err <= 2e-5 + 2e-3 * float(p.grad.abs().max()), (k, err)
         checked += 1
     assert checked > 20
+    assert ids.shape[0] == nb * n and float(A.abs().max()) > 0
+    compare_grads(G, oracle_grads(orc), 'SCST step, %d clips x %d samples' % (nb, n))
 
 
 @pytest.mark.parametrize('baseline', ['mean', 'greedy'])
