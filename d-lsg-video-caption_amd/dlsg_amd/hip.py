@@ -1,4 +1,6 @@
-"""ctypes binding of libdlsg_hip.so (include/dlsg.h) -- the only device compute path of this package.
+"""ctypes binding of libdlsg_hip.so -- the only device compute path of this package.  The argument structs, the prototypes and
+the DLSG_* constants are not written down here: dlsg_amd/abi.py reads them from include/dlsg.h, and this module refers to a
+struct by its header name (abi.dlsg_gemm_args).
 
 There is no CPU or eager-PyTorch fallback here: constructing `HipOps` raises if the library is missing or no
 MI355X is visible.  Tensors are only device memory + strides; every op is a hand-written HIP kernel launched on
@@ -12,368 +14,40 @@ import os
 
 import torch
 
+from . import abi
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, 'libdlsg_hip.so')
 
-ABI_VERSION = 8            # include/dlsg.h DLSG_ABI_VERSION this binding was written against
-GEMM_NT, GEMM_NN, GEMM_TN = 0, 1, 2
-F_ACCUM, F_BIAS, F_TANH = 1, 2, 4
-F_FORCE64, F_FORCE128, F_BF16X3, F_TILE256, F_SK, F_NOSK, F_SK_BM128, F_SK_BM256 = 256, 512, 1024, 2048, 4096, 8192, 16384, 32768
-F_SK_BN128 = 262144
-F_SK_NOXMAP = 131072
-F_SK_GIVEAWAY = 65536      # test hook (include/dlsg.h): the split tiles are finished by their last contributor alone
-MAXG = 16
-
-c_f32p = C.c_void_p
-i32, i64, u32, u64, f32 = C.c_int32, C.c_int64, C.c_uint32, C.c_uint64, C.c_float
-
-
-class GemmGroup(C.Structure):
-    _fields_ = [('A', c_f32p), ('B', c_f32p), ('C', c_f32p), ('lda', i64), ('ldb', i64), ('K', i32), ('N', i32),
-                ('bias', c_f32p), ('ldc', i64)]
-
-
-class GemmArgs(C.Structure):
-    _fields_ = [('mode', i32), ('M', i32), ('N', i32), ('ldc', i32), ('ngroups', i32), ('nbatch', i32), ('flags', i32),
-                ('cu_budget', i32), ('bsa', i64), ('bsb', i64), ('bsc', i64), ('alpha', f32), ('pad2_', i32),
-                ('bias', c_f32p), ('skip_if', c_f32p), ('ws', c_f32p), ('ws_bytes', i64), ('err', c_f32p), ('g', GemmGroup * MAXG)]
-
-
-class RowLnArgs(C.Structure):
-    _fields_ = [('x', c_f32p), ('ldx', i64), ('res', c_f32p), ('ldres', i64), ('gamma', c_f32p), ('beta', c_f32p),
-                ('y', c_f32p), ('ldy', i64), ('stats', c_f32p), ('pe', c_f32p), ('pe_rows', i32), ('rows', i32),
-                ('n', i32), ('pre_tanh', i32), ('post_tanh', i32), ('eps', f32), ('p1', f32), ('p2', f32),
-                ('seed', u64), ('site1', u32), ('site2', u32), ('seed_ptr', c_f32p)]
-
-
-class RowLnBwdArgs(C.Structure):
-    _fields_ = [('f', RowLnArgs), ('dy', c_f32p), ('lddy', i64), ('dx', c_f32p), ('lddx', i64), ('accum_dx', i32),
-                ('dgb_part', c_f32p), ('nblk', i32)]
-
-
-class O2VArgs(C.Structure):
-    _fields_ = [('y', c_f32p), ('v', c_f32p), ('g_obj', c_f32p), ('b_obj', c_f32p), ('z', c_f32p), ('ml', c_f32p),
-                ('ostats', c_f32p), ('S', c_f32p), ('ws', c_f32p), ('ws_bytes', i64), ('B', i32), ('T', i32),
-                ('NO', i32), ('H', i32), ('nsplit', i32), ('scale', f32), ('eps', f32)]
-
-
-class O2VBwdArgs(C.Structure):
-    _fields_ = [(n, c_f32p) for n in ('y', 'ostats', 'g_obj', 'b_obj', 'v', 'z', 'dz', 'S', 'ml', 'pd', 'm12', 'dy', 'dv',
-                                      'part', 'ws')] + [('ws_bytes', i64), ('B', i32), ('T', i32), ('NO', i32), ('H', i32),
-                                                        ('nsplit', i32), ('scale', f32), ('dysum', c_f32p)]
-
-
-class LatentPslArgs(C.Structure):
-    _fields_ = [(n, c_f32p) for n in ('ov', 'theta', 'gamma', 'beta', 'adj', 'u', 'out', 'stats')] + \
-               [('B', i32), ('T', i32), ('P', i32), ('H', i32), ('p', f32), ('site', u32), ('eps', f32), ('pad_', f32),
-                ('seed', u64), ('seed_ptr', c_f32p)]
-
-
-class SaCoreArgs(C.Structure):
-    _fields_ = [(n, c_f32p) for n in ('K', 'Q', 'V', 'mask', 'w', 'out')] + [('B', i32), ('T', i32), ('D', i32), ('scale', f32)]
-
-
-class BeamSelectArgs(C.Structure):
-    _fields_ = [('logits', c_f32p), ('ld', i64), ('last', c_f32p), ('last_lp', c_f32p), ('pred', c_f32p), ('new_lp', c_f32p),
-                ('back', c_f32p), ('rows', c_f32p), ('ended_count', c_f32p), ('B', i32), ('k', i32), ('V', i32), ('end', i32),
-                ('first', i32), ('pad_', i32)]
-
-
-class GatherMultiArgs(C.Structure):
-    _fields_ = [('src', C.c_void_p * 4), ('dst', C.c_void_p * 4), ('n', i32 * 4), ('rows', c_f32p), ('nrows', i32),
-                ('count', i32)]
-
-
-class SaCoreBwdArgs(C.Structure):
-    _fields_ = [(n, c_f32p) for n in ('w', 'K', 'Q', 'V', 'dout', 'dK', 'dQ', 'dV')] + [('B', i32), ('T', i32), ('D', i32),
-                                                                                          ('scale', f32)]
-
-
-class LatentPslBwdArgs(C.Structure):
-    _fields_ = [(n, c_f32p) for n in ('dout', 'u', 'stats', 'gamma', 'adj', 'ov', 'theta', 'dov', 'dtheta_part', 'part')] + \
-               [('B', i32), ('T', i32), ('P', i32), ('H', i32), ('p', f32), ('site', u32), ('seed', u64), ('seed_ptr', c_f32p)]
-
-
-class BilstmArgs(C.Structure):
-    _fields_ = [('xg', C.c_void_p * 2), ('ldxg', i64), ('w_hh', C.c_void_p * 2), ('b_ih', C.c_void_p * 2), ('b_hh', C.c_void_p * 2),
-                ('out', c_f32p), ('hprev', C.c_void_p * 2), ('c', C.c_void_p * 2), ('gates', C.c_void_p * 2), ('hx', c_f32p),
-                ('flags', c_f32p), ('err', c_f32p), ('B', i32), ('T', i32), ('H', i32), ('pad_', i32)]
-
-
-class BilstmBwdArgs(C.Structure):
-    _fields_ = [('gates', C.c_void_p * 2), ('c', C.c_void_p * 2), ('dout', c_f32p), ('w_hh', C.c_void_p * 2),
-                ('dgates', C.c_void_p * 2), ('gx', c_f32p), ('px', c_f32p), ('flags', c_f32p), ('err', c_f32p),
-                ('B', i32), ('T', i32), ('H', i32), ('pad_', i32)]
-
-
-class LstmSeqArgs(C.Structure):
-    _fields_ = [(n, c_f32p) for n in ('addend', 'addend_out', 'W', 'As', 'Hs', 'Cs', 'dHs', 'dAs', 'dCs', 'DA', 'DH', 'DC',
-                                      'gA', 'gC', 'gDH', 'gDC', 'xbuf', 'xbuf2', 'flags', 'err')] + \
-               [('L', i32), ('n', i32), ('H', i32), ('batch_major', i32)] + \
-               [(n, c_f32p) for n in ('b_ih', 'b_hh', 'Hprev', 'gDHprev')]
-
-
-_P4 = c_f32p * 4
-_P2 = c_f32p * 2
-
-
-class ClnArgs(C.Structure):
-    _fields_ = [('x', _P4), ('gamma', _P4), ('beta', _P4), ('y', _P4), ('dy', _P4 * 3), ('dx', _P4), ('dgamma', _P4), ('dbeta', _P4),
-                ('extra', _P4), ('U', _P4), ('gx', _P4), ('gdy', _P4), ('gpart', _P4), ('ws', c_f32p),
-                ('rows', i32), ('N', i32), ('groups', i32), ('pre_tanh', i32), ('ndy', i32), ('acc_lo', i32), ('acc_hi', i32), ('defer', i32),
-                ('eps', f32), ('p_pre', f32), ('p_post', f32), ('site_pre', u32), ('site_post', u32), ('pad2_', u32),
-                ('seed', u64), ('seed_ptr', C.c_void_p), ('row0', i64)]
-
-
-class CritSaArgs(C.Structure):
-    _fields_ = [(n, c_f32p) for n in ('KQV', 'smask', 'w', 'ctx', 'dctx', 'dKQV', 'U', 'Uctx', 'gKQV')] + \
-               [('n', i32), ('B', i32), ('L', i32), ('acc_lo', i32), ('acc_hi', i32), ('pad_', i32), ('scale', f32), ('pad2_', f32)]
-
-
-class CritPattnArgs(C.Structure):
-    _fields_ = [('a', _P2), ('e', _P2), ('smask', c_f32p), ('P', _P2), ('wgt', _P2), ('aggpre', _P2), ('d_agg', _P2), ('d_wgt', _P2),
-                ('da', _P2), ('de', _P2), ('Ua', _P2), ('Uagg', _P2), ('Uwgt', _P2), ('ga', _P2), ('ge', _P2),
-                ('n', i32), ('B', i32), ('L', i32), ('T', i32), ('acc_lo', i32), ('acc_hi', i32), ('scale', f32), ('pad_', f32)]
-
-
-class CritTsumArgs(C.Structure):
-    _fields_ = [(n, c_f32p) for n in ('words', 'theta', 'gamma', 'beta', 'fusion', 'adj', 'u', 'sent', 'fus', 'd_fus', 'dwords', 'part',
-                                      'U', 'Ufus', 'gwords', 'gpart')] + \
-               [('n', i32), ('L', i32), ('acc_lo', i32), ('acc_hi', i32), ('eps', f32), ('p', f32), ('site', u32), ('pad_', u32),
-                ('seed', u64), ('seed_ptr', C.c_void_p), ('row0', i64)]
-
-
-class CritScoreArgs(C.Structure):
-    _fields_ = [('v', _P2), ('s', _P2), ('wc', _P2), ('bc', _P2), ('wgt', _P2), ('fus', c_f32p), ('pair', _P2), ('score', _P2),
-                ('both', c_f32p), ('out', c_f32p), ('d_out', c_f32p), ('d_fus', c_f32p), ('c_spre', _P2), ('c_vpre', _P2), ('d_wgt', _P2),
-                ('part_wc', _P2), ('dbc', c_f32p), ('Uspre', _P2), ('Uwgt', _P2), ('Ufus', c_f32p), ('scratch', c_f32p),
-                ('n', i32), ('B', i32), ('T', i32), ('ng', i32), ('acc_lo', i32), ('acc_hi', i32)]
-
-
-class CritReduceDesc(C.Structure):
-    _fields_ = [('src', c_f32p), ('stride', i64), ('n', i64), ('nslab', i32), ('scale', f32), ('out', c_f32p)]
-
-
-class CritColsumDesc(C.Structure):
-    _fields_ = [('part', c_f32p), ('ld', i64), ('rows', i32), ('n', i32), ('part_b', c_f32p), ('ld_b', i64), ('rows_b', i32), ('pad_', i32),
-                ('out', c_f32p), ('out_b', c_f32p), ('scale', f32), ('pad2_', f32)]
-
-
-class CiderTables(C.Structure):
-    _fields_ = [('gram_keys', C.c_void_p), ('gram_idf', C.c_void_p), ('clip_off', C.c_void_p), ('ref_off', C.c_void_p),
-                ('ref_norm', C.c_void_p), ('ref_len', C.c_void_p), ('ent_keys', C.c_void_p), ('ent_w', C.c_void_p), ('n_grams', i64),
-                ('log_n', C.c_double), ('sigma', C.c_double), ('n_clips', i32), ('vocab', i32), ('n', i32), ('pad_', i32)]
-
-
-class ColsumDesc(C.Structure):
-    _fields_ = [('part', c_f32p), ('ld', i64), ('out_a', c_f32p), ('out_b', c_f32p), ('rows', i32), ('n', i32), ('split', i32),
-                ('dup', i32), ('accum', i32), ('pad_', i32)]
-
-
-class DecAttArgs(C.Structure):
-    _fields_ = [('Kp', c_f32p * 2), ('Vp', c_f32p * 2), ('q', c_f32p), ('ldq', i64), ('c', c_f32p * 2), ('ldc', i64),
-                ('alpha', c_f32p), ('B', i32), ('P', i32), ('Q', i32), ('H', i32), ('nstream', i32), ('scale', f32)]
-
-
-class DecAttBwdArgs(C.Structure):
-    _fields_ = [('f', DecAttArgs), ('dc', c_f32p * 2), ('lddc', i64), ('dalpha', c_f32p), ('dKp', c_f32p * 2),
-                ('dVp', c_f32p * 2), ('dq', c_f32p), ('lddq', i64), ('accum_dq', i32)]
-
-
-class LstmPwArgs(C.Structure):
-    _fields_ = [('slabs', c_f32p), ('nslab', i32), ('pad_', i32), ('slab_stride', i64), ('addend', c_f32p),
-                ('ldadd', i64), ('b_ih', c_f32p), ('b_hh', c_f32p), ('c_prev', c_f32p), ('ldcp', i64), ('c', c_f32p),
-                ('ldc_', i64), ('h', c_f32p), ('ldh', i64), ('h2', c_f32p), ('ldh2', i64), ('gates', c_f32p), ('ldg', i64),
-                ('B', i32), ('H', i32), ('p', f32), ('site', u32), ('seed', u64), ('seed_ptr', c_f32p)]
-
-
-class LstmPwBwdArgs(C.Structure):
-    _fields_ = [('gates', c_f32p), ('ldg', i64), ('c', c_f32p), ('ldc_', i64), ('c_prev', c_f32p), ('ldcp', i64), ('dh', c_f32p),
-                ('lddh', i64), ('dh2', c_f32p), ('lddh2', i64), ('dh3', c_f32p), ('lddh3', i64), ('dh4', c_f32p), ('lddh4', i64),
-                ('dh4_nslab', i32), ('pad4_', i32), ('dh4_slab_stride', i64),
-                ('dc_next', c_f32p), ('lddcn', i64),
-                ('dgates', c_f32p), ('lddg', i64), ('dc_prev', c_f32p), ('lddcp', i64), ('B', i32), ('H', i32), ('p', f32),
-                ('site', u32), ('seed', u64), ('seed_ptr', c_f32p)]
-
-
-class DecMidArgs(C.Structure):
-    _fields_ = [('slabs', c_f32p), ('nslab', i32), ('pad_', i32), ('slab_stride', i64), ('addend', c_f32p), ('ldadd', i64),
-                ('b_ih', c_f32p), ('b_hh', c_f32p), ('c_prev', c_f32p), ('c', c_f32p), ('h', c_f32p), ('gates', c_f32p),
-                ('lnq_g', c_f32p), ('lnq_b', c_f32p), ('qcur', c_f32p), ('st_q', c_f32p), ('p_q', f32), ('site_q', u32),
-                ('Kp', C.c_void_p * 2), ('Vp', C.c_void_p * 2), ('lnc_g', C.c_void_p * 2), ('lnc_b', C.c_void_p * 2),
-                ('cpre', C.c_void_p * 2), ('ctx', C.c_void_p * 2), ('st_c', C.c_void_p * 2), ('alpha', c_f32p),
-                ('p_att', f32 * 2), ('site_att', u32 * 2), ('B', i32), ('Q', i32), ('H', i32), ('P', i32), ('nstream', i32),
-                ('scale', f32), ('eps', f32), ('kv_div', i32), ('seed', u64), ('seed_ptr', c_f32p)]
-
-
-class DecTailArgs(C.Structure):
-    _fields_ = [('slabs', c_f32p), ('nslab', i32), ('pad_', i32), ('slab_stride', i64), ('b_ih', c_f32p), ('b_hh', c_f32p),
-                ('c_prev', c_f32p), ('c', c_f32p), ('hd', c_f32p), ('gates', c_f32p), ('ln_g', c_f32p), ('ln_b', c_f32p),
-                ('dout', c_f32p), ('st_l', c_f32p), ('p', f32), ('site', u32), ('B', i32), ('D', i32), ('eps', f32),
-                ('seed', u64), ('seed_ptr', c_f32p),
-                ('s_coins', c_f32p), ('s_t', i32), ('s_V', i32), ('s_W', c_f32p), ('s_b', c_f32p), ('s_E', c_f32p), ('s_Wd', i32),
-                ('s_site', u32), ('s_ids', c_f32p), ('s_we', c_f32p), ('s_ldwe', i64), ('s_row0', i64), ('s_p', f32), ('pad2_', f32)]
-
-
-class DecMidBwdArgs(C.Structure):
-    _fields_ = [('slabs', c_f32p), ('nslab', i32), ('write_rec', i32), ('slab_stride', i64), ('dlh_rec', c_f32p),
-                ('cpre', C.c_void_p * 2), ('st_c', C.c_void_p * 2), ('lnc_g', C.c_void_p * 2), ('part_c', C.c_void_p * 2),
-                ('dcpre', C.c_void_p * 2), ('p_att', f32 * 2), ('site_att', u32 * 2), ('Kp', C.c_void_p * 2),
-                ('Vp', C.c_void_p * 2), ('alpha', c_f32p), ('dalpha', c_f32p), ('ds', c_f32p), ('qh', c_f32p),
-                ('st_q', c_f32p), ('lnq_g', c_f32p), ('part_q', c_f32p), ('p_q', f32), ('site_q', u32),
-                ('rec_slabs', c_f32p), ('rec_nslab', i32), ('pad_', i32), ('rec_slab_stride', i64), ('rec_ld', i64),
-                ('gates', c_f32p), ('c', c_f32p), ('c_prev', c_f32p), ('dc', c_f32p), ('dgates', c_f32p),
-                ('B', i32), ('Q', i32), ('H', i32), ('D', i32), ('P', i32), ('nstream', i32), ('scale', f32), ('pad2_', f32),
-                ('seed', u64), ('seed_ptr', c_f32p)]
-
-
-class DecattCacheGradsArgs(C.Structure):
-    _fields_ = [('alpha', c_f32p), ('ds', c_f32p), ('qcur', c_f32p), ('dcpre', C.c_void_p * 2), ('dKp', C.c_void_p * 2),
-                ('dVp', C.c_void_p * 2), ('L', i32), ('B', i32), ('Q', i32), ('H', i32), ('P', i32), ('nstream', i32)]
-
-
-# every symbol include/dlsg.h declares (checked by tests/test_abi.py against the header text)
-SYMBOLS = ['dlsg_abi_version', 'dlsg_struct_size', 'dlsg_gemm', 'dlsg_gemm_variant', 'dlsg_gemm_ws_bytes', 'dlsg_slab_reduce', 'dlsg_rowln_fwd', 'dlsg_rowln_bwd', 'dlsg_rowln_fwd_multi', 'dlsg_rowln_bwd_multi',
-           'dlsg_rowln_bwd_nblk', 'dlsg_colsum', 'dlsg_colsum2', 'dlsg_colsum_ws_floats', 'dlsg_colsum_multi', 'dlsg_colsum_multi_ok', 'dlsg_o2v_workspace_bytes', 'dlsg_o2v_fwd', 'dlsg_o2v_fwd_multi',
-           'dlsg_softmax_fwd', 'dlsg_softmax_bwd', 'dlsg_decatt_fwd', 'dlsg_decatt_bwd', 'dlsg_lstm_pw_fwd',
-           'dlsg_lstm_pw_bwd', 'dlsg_lstm_pw_fwd_n', 'dlsg_lstm_pw_bwd_n', 'dlsg_mean_rows_fwd', 'dlsg_mean_rows_bwd', 'dlsg_embed_fwd', 'dlsg_embed_bwd',
-           'dlsg_argmax', 'dlsg_select_embed', 'dlsg_sample_embed', 'dlsg_ce_ragged_weighted', 'dlsg_cider_d', 'dlsg_scst_advantage', 'dlsg_copy2d', 'dlsg_dropout', 'dlsg_fill', 'dlsg_ce_ragged', 'dlsg_log_softmax',
-           'dlsg_adam', 'dlsg_permute_tb', 'dlsg_gather_rows', 'dlsg_dec_mid_fwd', 'dlsg_dec_tail_fwd',
-           'dlsg_dec_mid_bwd', 'dlsg_decatt_cache_grads', 'dlsg_o2v_bwd', 'dlsg_o2v_bwd_multi',
-           'dlsg_latent_psl_fwd', 'dlsg_sa_core_fwd', 'dlsg_beam_select', 'dlsg_gather_rows_multi',
-           'dlsg_sa_core_bwd', 'dlsg_latent_psl_bwd', 'dlsg_latent_psl_fwd_multi', 'dlsg_latent_psl_bwd_multi',
-           'dlsg_crit_embed_mix', 'dlsg_crit_embed_mix_bwd', 'dlsg_crit_vocab_scatter', 'dlsg_crit_relu_taps', 'dlsg_crit_relu_taps_bwd',
-           'dlsg_cln_ws_floats', 'dlsg_cln_fwd', 'dlsg_cln_bwd', 'dlsg_cln_bwd2', 'dlsg_crit_sa_fwd', 'dlsg_crit_sa_bwd', 'dlsg_crit_sa_bwd2',
-           'dlsg_crit_pattn_fwd', 'dlsg_crit_pattn_bwd', 'dlsg_crit_pattn_bwd2', 'dlsg_crit_tsum_fwd', 'dlsg_crit_tsum_bwd',
-           'dlsg_crit_tsum_bwd2', 'dlsg_crit_score_fwd', 'dlsg_crit_score_bwd', 'dlsg_crit_score_bwd2', 'dlsg_crit_gp', 'dlsg_crit_topk',
-           'dlsg_crit_unselect', 'dlsg_crit_colsum', 'dlsg_crit_reduce',
-           'dlsg_bilstm_supported', 'dlsg_bilstm_hx_floats', 'dlsg_bilstm_flag_words', 'dlsg_bilstm_fwd', 'dlsg_bilstm_bwd_x_floats', 'dlsg_bilstm_bwd',
-           'dlsg_lstm_seq_supported', 'dlsg_lstm_seq_x_floats', 'dlsg_lstm_seq_flag_words', 'dlsg_lstm_seq',
-           'dlsg_comm_unique_id', 'dlsg_comm_init', 'dlsg_comm_destroy', 'dlsg_comm_info', 'dlsg_allreduce_bucket',
-           'dlsg_allreduce_buckets', 'dlsg_allreduce_max_i32', 'dlsg_comm_rehearsal', 'dlsg_comm_async_error']
+# numeric aliases of the header's #defines: a value cannot disagree with include/dlsg.h, a renamed define is a KeyError here
+_D = abi.defines
+ABI_VERSION = _D['DLSG_ABI_VERSION']
+MAXG = _D['DLSG_GEMM_MAXG']
+GEMM_NT, GEMM_NN, GEMM_TN = _D['DLSG_GEMM_NT'], _D['DLSG_GEMM_NN'], _D['DLSG_GEMM_TN']
+F_ACCUM, F_BIAS, F_TANH = _D['DLSG_GEMM_ACCUM'], _D['DLSG_GEMM_BIAS'], _D['DLSG_GEMM_TANH']
+F_FORCE64, F_FORCE128, F_TILE256, F_BF16X3 = (_D['DLSG_GEMM_' + n] for n in ('FORCE64', 'FORCE128', 'TILE256', 'BF16X3'))
+F_SK, F_NOSK, F_SK_BM128, F_SK_BM256, F_SK_BN128, F_SK_NOXMAP = (_D['DLSG_GEMM_' + n] for n in (
+    'SK', 'NOSK', 'SK_BM128', 'SK_BM256', 'SK_BN128', 'SK_NOXMAP'))
+F_SK_GIVEAWAY = _D['DLSG_GEMM_SK_GIVEAWAY']   # test hook (include/dlsg.h): the split tiles are finished by their last contributor alone
+
+i64, u32, u64, f32 = C.c_int64, C.c_uint32, C.c_uint64, C.c_float
 
 
 def load_library(path=LIB_PATH):
+    """libdlsg_hip.so with the argtypes and restype of every entry point include/dlsg.h declares (dlsg_amd/abi.py reads them)"""
     if not os.path.exists(path):
         raise RuntimeError('libdlsg_hip.so not built (%s): run `python -c "import __graft_entry__ as g; g.build()"` '
                            'or `make -C d-lsg-video-caption_amd/csrc`; there is no fallback path' % path)
     lib = C.CDLL(path)
-    for s in SYMBOLS:
-        getattr(lib, s)  # AttributeError if the library does not export what the header declares
-    vp, P = C.c_void_p, C.POINTER
-    sig = {
-        'dlsg_abi_version': [],
-        'dlsg_struct_size': [i32],
-        'dlsg_gemm': [P(GemmArgs), vp],
-        'dlsg_gemm_variant': [P(GemmArgs)],
-        'dlsg_gemm_ws_bytes': [],
-        'dlsg_slab_reduce': [vp, i32, i64, vp, vp, i64, i32, i32, i32, vp],
-        'dlsg_rowln_fwd': [P(RowLnArgs), vp],
-        'dlsg_rowln_bwd': [P(RowLnBwdArgs), vp],
-        'dlsg_rowln_fwd_multi': [P(RowLnArgs), i32, vp],
-        'dlsg_rowln_bwd_multi': [P(RowLnBwdArgs), i32, vp],
-        'dlsg_rowln_bwd_nblk': [i32],
-        'dlsg_colsum_ws_floats': [i32, i32],
-        'dlsg_colsum': [vp, i64, i32, i32, vp, i32, vp, vp],
-        'dlsg_colsum2': [vp, i64, i32, i32, vp, vp, i32, i32, i32, vp, vp],
-        'dlsg_colsum_multi': [P(ColsumDesc), i32, vp],
-        'dlsg_colsum_multi_ok': [vp, i64, i32, i32],
-        'dlsg_o2v_workspace_bytes': [i32, i32, i32, i32],
-        'dlsg_o2v_fwd': [P(O2VArgs), vp],
-        'dlsg_o2v_fwd_multi': [P(O2VArgs), i32, vp],
-        'dlsg_softmax_fwd': [vp, vp, vp, i64, i32, i32, vp],
-        'dlsg_softmax_bwd': [vp, vp, vp, i64, i32, i32, vp],
-        'dlsg_decatt_fwd': [P(DecAttArgs), vp],
-        'dlsg_decatt_bwd': [P(DecAttBwdArgs), vp],
-        'dlsg_lstm_pw_fwd': [P(LstmPwArgs), vp],
-        'dlsg_lstm_pw_bwd': [P(LstmPwBwdArgs), vp],
-        'dlsg_lstm_pw_fwd_n': [P(LstmPwArgs), i32, vp],
-        'dlsg_lstm_pw_bwd_n': [P(LstmPwBwdArgs), i32, vp],
-        'dlsg_mean_rows_fwd': [vp, vp, i64, i32, i32, i32, vp],
-        'dlsg_mean_rows_bwd': [vp, i64, vp, i32, i32, i32, i32, vp],
-        'dlsg_embed_fwd': [vp, vp, vp, i64, i32, i32, f32, u64, u32, i64, vp, vp],
-        'dlsg_embed_bwd': [vp, i64, vp, vp, i32, i32, f32, u64, u32, i64, vp, vp],
-        'dlsg_select_embed': [vp, i64, i32, vp, i32, i32, vp, vp, vp, vp, i64, i32, i32, f32, u64, u32, i64, vp, i32, vp],
-        'dlsg_argmax': [vp, i64, vp, i32, i32, vp],
-        'dlsg_sample_embed': [vp, i64, i32, f32, vp, vp, vp, i64, i32, vp, vp, i32, i64, i32, f32, u64, u32, u32, i64, vp, vp],
-        'dlsg_ce_ragged_weighted': [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp],
-        'dlsg_cider_d': [vp, i64, i32, i32, vp, i64, P(CiderTables), vp, vp],
-        'dlsg_scst_advantage': [vp, vp, vp, i32, i32, vp, vp, vp],
-        'dlsg_copy2d': [vp, i64, vp, i64, i32, i32, i32, vp],
-        'dlsg_dropout': [vp, i64, vp, i64, i32, i32, f32, u64, u32, vp, vp],
-        'dlsg_fill': [vp, i64, f32, vp],
-        'dlsg_ce_ragged': [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp],
-        'dlsg_log_softmax': [vp, vp, i32, i32, vp],
-        'dlsg_adam': [vp, vp, vp, vp, i64, f32, f32, f32, f32, i32, f32, vp, vp, vp],
-        'dlsg_permute_tb': [vp, vp, i32, i32, i32, vp],
-        'dlsg_gather_rows': [vp, i64, vp, vp, i64, i32, i32, vp],
-        'dlsg_dec_mid_fwd': [P(DecMidArgs), vp],
-        'dlsg_dec_tail_fwd': [P(DecTailArgs), vp],
-        'dlsg_dec_mid_bwd': [P(DecMidBwdArgs), vp],
-        'dlsg_decatt_cache_grads': [P(DecattCacheGradsArgs), vp],
-        'dlsg_o2v_bwd': [P(O2VBwdArgs), vp],
-        'dlsg_o2v_bwd_multi': [P(O2VBwdArgs), i32, vp],
-        'dlsg_latent_psl_fwd': [P(LatentPslArgs), vp],
-        'dlsg_latent_psl_fwd_multi': [P(LatentPslArgs), i32, vp],
-        'dlsg_sa_core_fwd': [P(SaCoreArgs), vp],
-        'dlsg_beam_select': [P(BeamSelectArgs), vp],
-        'dlsg_gather_rows_multi': [P(GatherMultiArgs), vp],
-        'dlsg_sa_core_bwd': [P(SaCoreBwdArgs), vp],
-        'dlsg_latent_psl_bwd': [P(LatentPslBwdArgs), vp],
-        'dlsg_latent_psl_bwd_multi': [P(LatentPslBwdArgs), i32, vp],
-        'dlsg_bilstm_supported': [i32, i32, i32],
-        'dlsg_bilstm_hx_floats': [i32, i32],
-        'dlsg_bilstm_flag_words': [i32, i32],
-        'dlsg_bilstm_fwd': [P(BilstmArgs), vp],
-        'dlsg_bilstm_bwd_x_floats': [i32, i32],
-        'dlsg_bilstm_bwd': [P(BilstmBwdArgs), vp],
-        'dlsg_comm_unique_id': [vp],
-        'dlsg_lstm_seq_supported': [i32, i32, i32],
-        'dlsg_lstm_seq_x_floats': [i32, i32, i32],
-        'dlsg_lstm_seq_flag_words': [i32, i32, i32],
-        'dlsg_lstm_seq': [P(LstmSeqArgs), i32, vp],
-        'dlsg_crit_embed_mix': [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp],
-        'dlsg_crit_embed_mix_bwd': [vp, vp, vp, vp, i32, i32, i32, vp],
-        'dlsg_crit_vocab_scatter': [vp, vp, vp, i32, i32, vp],
-        'dlsg_crit_relu_taps': [vp, vp, vp, f32, vp, vp, i32, i32, vp],
-        'dlsg_crit_relu_taps_bwd': [vp, vp, vp, vp, i32, i32, vp],
-        'dlsg_cln_ws_floats': [i32, i32],
-        'dlsg_cln_fwd': [P(ClnArgs), vp], 'dlsg_cln_bwd': [P(ClnArgs), vp], 'dlsg_cln_bwd2': [P(ClnArgs), vp],
-        'dlsg_crit_sa_fwd': [P(CritSaArgs), vp], 'dlsg_crit_sa_bwd': [P(CritSaArgs), vp], 'dlsg_crit_sa_bwd2': [P(CritSaArgs), vp],
-        'dlsg_crit_pattn_fwd': [P(CritPattnArgs), vp], 'dlsg_crit_pattn_bwd': [P(CritPattnArgs), vp],
-        'dlsg_crit_pattn_bwd2': [P(CritPattnArgs), vp],
-        'dlsg_crit_tsum_fwd': [P(CritTsumArgs), vp], 'dlsg_crit_tsum_bwd': [P(CritTsumArgs), vp], 'dlsg_crit_tsum_bwd2': [P(CritTsumArgs), vp],
-        'dlsg_crit_score_fwd': [P(CritScoreArgs), vp], 'dlsg_crit_score_bwd': [P(CritScoreArgs), vp],
-        'dlsg_crit_score_bwd2': [P(CritScoreArgs), vp],
-        'dlsg_crit_gp': [vp, vp, vp, vp, vp, vp, vp, i32, i32, vp],
-        'dlsg_crit_topk': [vp, i64, i64, i32, vp, vp, i32, i32, i32, i32, vp],
-        'dlsg_crit_unselect': [vp, vp, vp, i32, i32, i32, i32, vp],
-        'dlsg_crit_colsum': [P(CritColsumDesc), i32, vp],
-        'dlsg_crit_reduce': [P(CritReduceDesc), i32, vp],
-        'dlsg_comm_init': [P(vp), vp, i32, i32],
-        'dlsg_comm_destroy': [vp],
-        'dlsg_comm_info': [vp, P(i32), P(i32), P(i32)],
-        'dlsg_allreduce_bucket': [vp, vp, i64, vp],
-        'dlsg_allreduce_buckets': [vp, P(vp), P(i64), i32, vp],
-        'dlsg_allreduce_max_i32': [vp, vp, i64, vp],
-        'dlsg_comm_async_error': [vp, P(i32)],
-        'dlsg_comm_rehearsal': [vp, i64, i32, i32, vp],
-    }
-    assert sorted(sig) == sorted(SYMBOLS)
-    for name, args in sig.items():
-        fn = getattr(lib, name)
-        fn.argtypes = args
-        fn.restype = C.c_int64 if name in ('dlsg_gemm_ws_bytes', 'dlsg_o2v_workspace_bytes', 'dlsg_cln_ws_floats', 'dlsg_colsum_ws_floats',
-                                            'dlsg_bilstm_hx_floats', 'dlsg_bilstm_flag_words', 'dlsg_bilstm_bwd_x_floats',
-                                            'dlsg_lstm_seq_x_floats', 'dlsg_lstm_seq_flag_words') else C.c_int
+    for name, (restype, argtypes) in abi.functions.items():
+        fn = getattr(lib, name)  # AttributeError if the library does not export what the header declares
+        fn.restype, fn.argtypes = restype, argtypes
+    if lib.dlsg_abi_version() != ABI_VERSION:
+        raise RuntimeError('libdlsg_hip.so ABI mismatch: library %d, include/dlsg.h %d (rebuild: make -C d-lsg-video-caption_amd/csrc)'
+                           % (lib.dlsg_abi_version(), ABI_VERSION))
     return lib
 
 
-STRUCTS = [GemmArgs, RowLnArgs, RowLnBwdArgs, O2VArgs, DecAttArgs, DecAttBwdArgs, LstmPwArgs, LstmPwBwdArgs, DecMidArgs,
-           DecTailArgs, DecMidBwdArgs, DecattCacheGradsArgs, O2VBwdArgs, LatentPslArgs,
-           SaCoreArgs, BeamSelectArgs, GatherMultiArgs, SaCoreBwdArgs,
-           LatentPslBwdArgs, BilstmArgs, BilstmBwdArgs, ColsumDesc, LstmSeqArgs, ClnArgs, CritSaArgs, CritPattnArgs, CritTsumArgs,
-           CritScoreArgs, CritColsumDesc, CritReduceDesc, CiderTables]
 
 
 def _p(t):
@@ -396,8 +70,8 @@ def cider_tables(tb):
     """the dlsg_cider_tables of a scoring.DeviceCiderD (device pointers; an empty table is NULL)"""
     def p(t):
         return t.data_ptr() if t.numel() else None
-    return CiderTables(p(tb.gram_keys), p(tb.gram_idf), p(tb.clip_off), p(tb.ref_off), p(tb.ref_norm), p(tb.ref_len), p(tb.ent_keys),
-                       p(tb.ent_w), tb.gram_keys.numel(), tb.log_n, tb.sigma, tb.n_clips, tb.V, tb.n, 0)
+    return abi.dlsg_cider_tables(p(tb.gram_keys), p(tb.gram_idf), p(tb.clip_off), p(tb.ref_off), p(tb.ref_norm), p(tb.ref_len),
+                                 p(tb.ent_keys), p(tb.ent_w), tb.gram_keys.numel(), tb.log_n, tb.sigma, tb.n_clips, tb.V, tb.n, 0)
 
 
 def host_to_device(values, dtype, device):
@@ -436,9 +110,6 @@ class HipOps(object):
         if not torch.cuda.is_available():
             raise RuntimeError('dlsg_amd needs an MI355X (gfx950) device: torch.cuda.is_available() is False and '
                                'there is no CPU fallback')
-        if self.lib.dlsg_abi_version() != ABI_VERSION:
-            raise RuntimeError('libdlsg_hip.so ABI mismatch: library %d, binding %d (rebuild: make -C d-lsg-video-caption_amd/csrc)'
-                               % (self.lib.dlsg_abi_version(), ABI_VERSION))
         self.prof = None          # set to {} by bench.py: key -> list of (start event, end event, algorithmic work)
         self.extra_flags = 0      # OR-ed into every dlsg_gemm call (precision policy: F_BF16X3), set by the model
         self.prof_min_flops = 2e9  # dlsg_gemm calls below this are not bracketed by profile events (tools/pmc_step_target.py: 0)
@@ -543,7 +214,7 @@ class HipOps(object):
     def gemm(self, mode, groups, alpha=1.0, flags=0, bias=None, skip_if=None, plan_only=False):
         """groups: list of (A, B, C[, bias]) views (2-d, or 3-d batched with identical batch strides across groups).
         plan_only: nothing is launched; returns the tile family the library would run the call on (dlsg_gemm_variant)."""
-        a = GemmArgs()
+        a = abi.dlsg_gemm_args()
         A0, B0, C0 = groups[0][:3]
         batched = A0.dim() == 3
         if batched:
@@ -637,7 +308,7 @@ class HipOps(object):
 
     # ------------------------------------------------------------------ row kernels
     def _rowln_args(self, x, gamma, beta, y, stats, res, pe, pre_tanh, post_tanh, p1, site1, p2, site2, seed, eps):
-        a = RowLnArgs()
+        a = abi.dlsg_rowln_args()
         _chk2(x)
         a.x, a.ldx = _p(x), x.stride(0)
         a.res, a.ldres = _p(res), (res.stride(0) if res is not None else 0)
@@ -661,7 +332,7 @@ class HipOps(object):
         n = len(items)
         if n == 1:
             return self.rowln_fwd(**items[0])
-        arr = (RowLnArgs * n)()
+        arr = (abi.dlsg_rowln_args * n)()
         for i, it in enumerate(items):
             d = dict(stats=None, res=None, pe=None, pre_tanh=0, post_tanh=0, p1=0.0, site1=0, p2=0.0, site2=0, seed=0, eps=1e-5)
             d.update(it)
@@ -674,7 +345,7 @@ class HipOps(object):
         n = len(items)
         if n == 1:
             return self.rowln_bwd(**items[0])
-        arr = (RowLnBwdArgs * n)()
+        arr = (abi.dlsg_rowln_bwd_args * n)()
         for i, it in enumerate(items):
             d = dict(stats=None, res=None, pe=None, pre_tanh=0, post_tanh=0, p1=0.0, site1=0, p2=0.0, site2=0, seed=0, eps=1e-5,
                      dgb_part=None, accum_dx=False)
@@ -693,7 +364,7 @@ class HipOps(object):
 
     def rowln_bwd(self, dy, x, gamma, beta, dx, stats=None, res=None, pe=None, pre_tanh=0, post_tanh=0, p1=0.0,
                   site1=0, p2=0.0, site2=0, seed=0, eps=1e-5, dgb_part=None, accum_dx=False):
-        b = RowLnBwdArgs()
+        b = abi.dlsg_rowln_bwd_args()
         b.f = self._rowln_args(x, gamma, beta, None, stats, res, pe, pre_tanh, post_tanh, p1, site1, p2, site2, seed,
                                eps)
         b.dy, b.lddy, b.dx, b.lddx = _p(dy), dy.stride(0), _p(dx), dx.stride(0)
@@ -728,7 +399,7 @@ class HipOps(object):
                     batch.append(it); seen |= dests
                 else:
                     rest.append(it)
-            arr = (ColsumDesc * len(batch))()
+            arr = (abi.dlsg_colsum_desc * len(batch))()
             for d, (part, out_a, out_b, split, dup, accum) in zip(arr, batch):
                 d.part, d.ld, d.out_a, d.out_b = _p(part), part.stride(0), _p(out_a), _p(out_b)
                 d.rows, d.n, d.split, d.dup, d.accum = part.size(0), part.size(1), split, int(dup), int(accum)
@@ -774,7 +445,7 @@ class HipOps(object):
         n = len(items)
         B, NO, H = items[0]['y'].shape
         T = items[0]['v'].shape[1]
-        arr = (O2VArgs * n)()
+        arr = (abi.dlsg_o2v_args * n)()
         wsb = self.lib.dlsg_o2v_workspace_bytes(B, T, H, nsplit)
         keep = []
         for a, it in zip(arr, items):
@@ -804,7 +475,7 @@ class HipOps(object):
         B, NO, H = items[0]['y'].shape
         T = items[0]['v'].shape[1]
         dev = items[0]['y'].device
-        arr = (O2VBwdArgs * n)()
+        arr = (abi.dlsg_o2v_bwd_args * n)()
         wsb = int(self.lib.dlsg_o2v_workspace_bytes(B, T, H, nsplit))
         keep, parts = [], []
         for a, it in zip(arr, items):
@@ -834,7 +505,7 @@ class HipOps(object):
     # ------------------------------------------------------------------ beam search
     def beam_select(self, logits, last, last_lp, pred, new_lp, back, rows, k, end, first=False, ended_count=None):
         """one beam-search step for every batch item (see include/dlsg.h): logits (B*k,V) -> pred/new_lp/back/rows (B*k)."""
-        a = BeamSelectArgs()
+        a = abi.dlsg_beam_select_args()
         R, V = logits.shape
         a.logits, a.ld = _p(logits), logits.stride(0)
         a.last, a.last_lp = _p(last), _p(last_lp)
@@ -844,7 +515,7 @@ class HipOps(object):
 
     def gather_rows_multi(self, srcs, rows, dsts):
         """dsts[i][r] = srcs[i][rows[r]] for up to 4 dense (R, n_i) arrays in one launch."""
-        a = GatherMultiArgs()
+        a = abi.dlsg_gather_multi_args()
         for i, (sr, ds) in enumerate(zip(srcs, dsts)):
             _chkc(sr); _chkc(ds)
             a.src[i], a.dst[i], a.n[i] = sr.data_ptr(), ds.data_ptr(), sr.shape[1]
@@ -867,14 +538,14 @@ class HipOps(object):
 
     def latent_psl_fwd(self, ov, theta, gamma, beta, adj, u, out, stats, p=0.0, site=0, seed=0, eps=1e-5):
         """ov (B,T,H), theta (P,H) -> adj (B,T,P), u (B*P,H) pre-activation, out (B*P,H), stats (B*P,2); one launch."""
-        a = LatentPslArgs()
+        a = abi.dlsg_latent_psl_args()
         self._psl_args(a, ov, theta, gamma, beta, adj, u, out, stats, p, site, seed, eps)
         self._check(self.lib.dlsg_latent_psl_fwd(C.byref(a), self._stream()), 'dlsg_latent_psl_fwd')
 
     def latent_psl_fwd_multi(self, items):
         """several LatentPSL modules of one shape in ONE launch; items: dicts of latent_psl_fwd's arguments"""
         n = len(items)
-        arr = (LatentPslArgs * n)()
+        arr = (abi.dlsg_latent_psl_args * n)()
         for i, it in enumerate(items):
             self._psl_args(arr[i], **it)
         self._check(self.lib.dlsg_latent_psl_fwd_multi(arr, n, self._stream()), 'dlsg_latent_psl_fwd_multi')
@@ -894,14 +565,14 @@ class HipOps(object):
 
     def latent_psl_bwd(self, dout, u, stats, gamma, adj, ov, theta, dov, dtheta_part, part, p=0.0, site=0, seed=0):
         """backward of latent_psl_fwd: dout (B*P,H) -> dov (B*T,H), dtheta_part (B,P,H), part (B,2,H); one launch."""
-        a = LatentPslBwdArgs()
+        a = abi.dlsg_latent_psl_bwd_args()
         self._psl_bwd_args(a, dout, u, stats, gamma, adj, ov, theta, dov, dtheta_part, part, p, site, seed)
         self._check(self.lib.dlsg_latent_psl_bwd(C.byref(a), self._stream()), 'dlsg_latent_psl_bwd')
 
     def latent_psl_bwd_multi(self, items):
         """several LatentPSL backwards of one shape in ONE launch; items: dicts of latent_psl_bwd's arguments"""
         n = len(items)
-        arr = (LatentPslBwdArgs * n)()
+        arr = (abi.dlsg_latent_psl_bwd_args * n)()
         for i, it in enumerate(items):
             self._psl_bwd_args(arr[i], **it)
         self._check(self.lib.dlsg_latent_psl_bwd_multi(arr, n, self._stream()), 'dlsg_latent_psl_bwd_multi')
@@ -914,7 +585,7 @@ class HipOps(object):
         B, T, D = K.shape
         for t in (K, Q, V, w, out):
             _chkc(t)
-        a = SaCoreArgs()
+        a = abi.dlsg_sa_core_args()
         a.K, a.Q, a.V, a.mask, a.w, a.out = _p(K), _p(Q), _p(V), _p(mask), _p(w), _p(out)
         a.B, a.T, a.D, a.scale = B, T, D, scale
         self._check(self.lib.dlsg_sa_core_fwd(C.byref(a), self._stream()), 'dlsg_sa_core_fwd')
@@ -924,14 +595,14 @@ class HipOps(object):
         B, T, D = K.shape
         for t in (w, K, Q, V, dout, dK, dQ, dV):
             _chkc(t)
-        a = SaCoreBwdArgs()
+        a = abi.dlsg_sa_core_bwd_args()
         a.w, a.K, a.Q, a.V, a.dout, a.dK, a.dQ, a.dV = _p(w), _p(K), _p(Q), _p(V), _p(dout), _p(dK), _p(dQ), _p(dV)
         a.B, a.T, a.D, a.scale = B, T, D, scale
         self._check(self.lib.dlsg_sa_core_bwd(C.byref(a), self._stream()), 'dlsg_sa_core_bwd')
 
     # ------------------------------------------------------------------ decoder attention
     def _decatt_args(self, Kp, Vp, q, c, alpha, scale):
-        a = DecAttArgs()
+        a = abi.dlsg_decatt_args()
         ns = len(Kp)
         B, P, Q = Kp[0].shape
         H = Vp[0].shape[2]
@@ -950,7 +621,7 @@ class HipOps(object):
         self._check(self.lib.dlsg_decatt_fwd(C.byref(a), self._stream()), 'dlsg_decatt_fwd')
 
     def decatt_bwd(self, Kp, Vp, q, alpha, dc, dKp, dVp, dq, scale, accum_dq=False, dalpha=None):
-        b = DecAttBwdArgs()
+        b = abi.dlsg_decatt_bwd_args()
         b.f = self._decatt_args(Kp, Vp, q, None, alpha, scale)
         for s in range(len(Kp)):
             b.dc[s], b.dKp[s], b.dVp[s] = dc[s].data_ptr(), dKp[s].data_ptr(), dVp[s].data_ptr()
@@ -965,7 +636,7 @@ class HipOps(object):
         """query cell pointwise -> LN(+dropout) -> attention over Kp/Vp (per stream) -> tanh -> LN(+dropout); one launch.
         lnq = (gamma, beta); lnc = [(gamma, beta)] per stream.  kv_div = k > 1: Kp / Vp hold one block per k consecutive rows
         (beam search: the k beams of a clip share their clip's K', V')."""
-        a = DecMidArgs()
+        a = abi.dlsg_dec_mid_args()
         a.kv_div = kv_div
         assert Kp[0].size(0) * max(1, kv_div) == c.size(0), (Kp[0].shape, c.shape, kv_div)
         a.slabs, a.nslab, a.slab_stride = _p(slabs), slabs.size(0), slabs.stride(0)
@@ -1002,7 +673,7 @@ class HipOps(object):
         """language cell pointwise (+dropout on h) -> tanh(LN(h)); one launch.
         sample: optional dict(coins (int32 device vector), t, W (V,D), b (V) or None, E (V,Wd), ids_out (B) int64, we_out (B,Wd),
         p, site, row0): the next step's word is sampled inside the launch when coins[t] == 0 (include/dlsg.h)."""
-        a = DecTailArgs()
+        a = abi.dlsg_dec_tail_args()
         if sample is not None:
             sm = sample
             for t_ in (sm['W'], sm['E'], sm['ids_out']):
@@ -1025,7 +696,7 @@ class HipOps(object):
                     st_q, lnq_g, part_q, p_q, site_q, rec_slabs, gates, c, c_prev, dc, dgates, scale, seed=0):
         """backward of dec_mid_fwd for one word step (see include/dlsg.h).  slabs (S,B,ns*H+Q+D); dlh_rec (B,D) or None;
         rec_slabs (S',B,Q) view of the query cell's input-gradient slabs of step t+1, or None."""
-        a = DecMidBwdArgs()
+        a = abi.dlsg_dec_mid_bwd_args()
         ns = len(Kp)
         B, Q = c.shape
         H, P = Vp[0].size(2), Kp[0].size(1)
@@ -1054,7 +725,7 @@ class HipOps(object):
 
     def decatt_cache_grads(self, alpha, ds, qcur, dcpre, dKp, dVp):
         """dK'[s] = sum_t ds_t (x) q_cur_t, dV'[s] = sum_t alpha_t (x) dcpre_t  (time-major (L,B,.) inputs)."""
-        a = DecattCacheGradsArgs()
+        a = abi.dlsg_decatt_cache_grads_args()
         L, B, Q = qcur.shape
         ns = len(dKp)
         for t in (alpha, ds, qcur):
@@ -1117,7 +788,7 @@ class HipOps(object):
         hprev[d] (B,T,H) zero-filled by the caller; c[d] (B,T,H); gates[d] (B,T,4H).  Returns the int32 error word (device)."""
         B, T, H2 = out.shape
         H = H2 // 2
-        a = BilstmArgs()
+        a = abi.dlsg_bilstm_args()
         dev = out.device
         hx = torch.empty(int(self.lib.dlsg_bilstm_hx_floats(T, H)), dtype=torch.float32, device=dev)
         flags = torch.empty(int(self.lib.dlsg_bilstm_flag_words(T, H)), dtype=torch.int32, device=dev)
@@ -1139,7 +810,7 @@ class HipOps(object):
         """backward through time of bilstm_fwd in one launch: dout (B,T,2H) -> dgates[d] (B,T,4H).  Returns the error word."""
         B, T, H2 = dout.shape
         H = H2 // 2
-        a = BilstmBwdArgs()
+        a = abi.dlsg_bilstm_bwd_args()
         dev = dout.device
         nx = int(self.lib.dlsg_bilstm_bwd_x_floats(T, H))
         gx = torch.empty(nx, dtype=torch.float32, device=dev)
@@ -1181,7 +852,7 @@ class HipOps(object):
                 assert v.dtype == torch.float32 and v.shape[:2] == (n, L) and v.shape[2] in (H, 4 * H), (name, v.shape)
         for lo in range(0, n, chunk):
             hi = min(n, lo + chunk)
-            a = LstmSeqArgs()
+            a = abi.dlsg_lstm_seq_args()
             nx = int(self.lib.dlsg_lstm_seq_x_floats(L, hi - lo, H))
             xbuf = torch.empty(nx, dtype=torch.float32, device=dev)
             xbuf2 = torch.empty(nx, dtype=torch.float32, device=dev) if level == 1 else None
@@ -1225,13 +896,13 @@ class HipOps(object):
         a.seed, a.seed_ptr = _seed(seed)
 
     def lstm_pw_fwd(self, slabs, c, B, H, **kw):
-        a = LstmPwArgs()
+        a = abi.dlsg_lstm_pw_args()
         self._pw_fwd_args(a, slabs, c, B, H, **kw)
         self._check(self.lib.dlsg_lstm_pw_fwd(C.byref(a), self._stream()), 'dlsg_lstm_pw_fwd')
 
     def lstm_pw_fwd_multi(self, calls):
         """calls: 1 or 2 dicts of lstm_pw_fwd arguments (same B, H) -> one launch (both directions of a BiLSTM step)."""
-        arr = (LstmPwArgs * len(calls))()
+        arr = (abi.dlsg_lstm_pw_args * len(calls))()
         for a, kw in zip(arr, calls):
             self._pw_fwd_args(a, **kw)
         self._check(self.lib.dlsg_lstm_pw_fwd_n(arr, len(calls), self._stream()), 'dlsg_lstm_pw_fwd_n')
@@ -1255,12 +926,12 @@ class HipOps(object):
         a.seed, a.seed_ptr = _seed(seed)
 
     def lstm_pw_bwd(self, gates, c, dgates, B, H, **kw):
-        a = LstmPwBwdArgs()
+        a = abi.dlsg_lstm_pw_bwd_args()
         self._pw_bwd_args(a, gates, c, dgates, B, H, **kw)
         self._check(self.lib.dlsg_lstm_pw_bwd(C.byref(a), self._stream()), 'dlsg_lstm_pw_bwd')
 
     def lstm_pw_bwd_multi(self, calls):
-        arr = (LstmPwBwdArgs * len(calls))()
+        arr = (abi.dlsg_lstm_pw_bwd_args * len(calls))()
         for a, kw in zip(arr, calls):
             self._pw_bwd_args(a, **kw)
         self._check(self.lib.dlsg_lstm_pw_bwd_n(arr, len(calls), self._stream()), 'dlsg_lstm_pw_bwd_n')
@@ -1356,7 +1027,7 @@ class HipOps(object):
         self._check(self.lib.dlsg_crit_relu_taps_bwd(_p(dy), _p(dtaps), _p(ref), _p(dx), n, L, self._stream()), 'crit_relu_taps_bwd')
 
     def _cln_args(self, x, gamma, pre_tanh, eps, p_pre, site_pre, p_post, site_post, seed, row0):
-        a = ClnArgs()
+        a = abi.dlsg_cln_args()
         G = len(x)
         rows, N = x[0].shape
         for g in range(G):
@@ -1437,7 +1108,7 @@ class HipOps(object):
         self._check(self.lib.dlsg_cln_bwd2(C.byref(a), self._stream()), 'cln_bwd2')
 
     def _sa_args(self, KQV, smask, scale, acc=None):
-        a = CritSaArgs()
+        a = abi.dlsg_crit_sa_args()
         _chkc(KQV); _chkc(smask)
         a.KQV, a.smask = _p(KQV), _p(smask)
         a.n, a.L, a.B, a.scale = KQV.shape[0], KQV.shape[1], smask.shape[0], scale
@@ -1475,7 +1146,7 @@ class HipOps(object):
                 arr[h] = _p(pair[h])
 
     def _pattn_args(self, a_, e, smask, scale, acc=None):
-        a = CritPattnArgs()
+        a = abi.dlsg_crit_pattn_args()
         self._set2(a, a=a_, e=e)
         _chkc(smask)
         a.smask = _p(smask)
@@ -1499,7 +1170,7 @@ class HipOps(object):
         self._check(self.lib.dlsg_crit_pattn_bwd2(C.byref(a), self._stream()), 'crit_pattn_bwd2')
 
     def _tsum_args(self, words, theta, gamma, beta, fusion, eps, p, site, seed, row0, acc=None):
-        a = CritTsumArgs()
+        a = abi.dlsg_crit_tsum_args()
         for t in (words, theta, gamma, fusion):
             _chkc(t)
         a.words, a.theta, a.gamma, a.beta, a.fusion = _p(words), _p(theta), _p(gamma), _p(beta), _p(fusion)
@@ -1531,7 +1202,7 @@ class HipOps(object):
         self._check(self.lib.dlsg_crit_tsum_bwd2(C.byref(a), self._stream()), 'crit_tsum_bwd2')
 
     def _score_args(self, v, s, wc, wgt, fus, pair, score, ng, acc=None):
-        a = CritScoreArgs()
+        a = abi.dlsg_crit_score_args()
         self._set2(a, v=v, s=s, wc=wc, wgt=wgt, pair=pair, score=score)
         _chkc(fus)
         a.fus = _p(fus)
@@ -1592,7 +1263,7 @@ class HipOps(object):
         """descs: list of (slabs (S, ...) contiguous, out): out = sum over the S slabs, in slab order; one launch per 16"""
         for lo in range(0, len(descs), 16):
             chunk = descs[lo:lo + 16]
-            arr = (CritReduceDesc * len(chunk))()
+            arr = (abi.dlsg_crit_reduce_desc * len(chunk))()
             for d, (slabs, out) in zip(arr, chunk):
                 _chkc(slabs); _chkc(out)
                 assert out.numel() * slabs.shape[0] == slabs.numel() and out.numel() % 4 == 0
@@ -1604,7 +1275,7 @@ class HipOps(object):
         stride); out_b (or None) receives a copy.  One launch per 48 descriptors, fixed order of additions."""
         for lo in range(0, len(descs), 48):
             chunk = descs[lo:lo + 48]
-            arr = (CritColsumDesc * len(chunk))()
+            arr = (abi.dlsg_crit_colsum_desc * len(chunk))()
             for d, (srcs, out, out_b, scale) in zip(arr, chunk):
                 a = srcs[0]
                 assert a.dim() == 2 and (a.stride(1) == 1 or a.shape[1] == 1) and out.numel() == a.shape[1] and out.is_contiguous()

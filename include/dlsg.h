@@ -6,7 +6,11 @@
  * on `stream` (a hipStream_t passed as void*) and returns 0 or a negative DLSG_E* code.  All tensors are dense
  * fp32 row-major unless a leading dimension is given; ids are int64.
  *
- * Host-side bindings: d-lsg-video-caption_amd/dlsg_amd/hip.py (ctypes).  See INTEGRATION.md.
+ * Host-side bindings: d-lsg-video-caption_amd/dlsg_amd/hip.py (ctypes).  It does not repeat this file: dlsg_amd/abi.py reads it
+ * when the package is imported and builds every argument struct, every prototype and the DLSG_* constants from the text below.
+ * So this header stays in the subset of C that module knows, and it refuses anything else by line number: integer #defines;
+ * `typedef struct { ... } dlsg_x;` whose members are fixed-width scalars, pointers, earlier structs by value and arrays of these;
+ * prototypes that return int or int64_t.  See INTEGRATION.md.
  */
 #ifndef DLSG_H
 #define DLSG_H
@@ -32,12 +36,9 @@ int dlsg_abi_version(void);
 #define DLSG_ELAUNCH (-2) /* the HIP runtime refused the launch / an RCCL call failed */
 #define DLSG_EALIGN (-3)  /* a pointer or leading dimension misses the alignment the vector loads need */
 #define DLSG_ENOCOMM (-4) /* librccl could not be loaded or the communicator handle is invalid */
-/* sizeof() of the i-th argument struct below (0 gemm_args, 1 rowln_args, 2 rowln_bwd_args, 3 o2v_args, 4 decatt_args,
- * 5 decatt_bwd_args, 6 lstm_pw_args, 7 lstm_pw_bwd_args, 8 dec_mid_args, 9 dec_tail_args, 10 dec_mid_bwd_args, 11 decatt_cache_grads_args,
- * 12 o2v_bwd_args, 13 latent_psl_args, 14 sa_core_args, 15 beam_select_args,
- * 16 gather_multi_args, 17 sa_core_bwd_args, 18 latent_psl_bwd_args, 19 bilstm_args, 20 bilstm_bwd_args, 21 colsum_desc,
- * 22 lstm_seq_args, 23 cln_args, 24 crit_sa_args, 25 crit_pattn_args, 26 crit_tsum_args, 27 crit_score_args, 28 crit_colsum_desc,
- * 29 crit_reduce_desc): lets a binding verify its struct layout without a GPU. */
+/* sizeof() of the argument struct with index `which`, -1 for an index no struct has: lets a binding verify its struct layout
+ * without a GPU.  The indices are in the order the structs were added, not the order of this file; the switch in
+ * csrc/attention.hip is the list (a new struct gets the next index there). */
 int dlsg_struct_size(int which);
 
 /* ---------------------------------------------------------------- GEMM (fp32-in / fp32-acc MFMA 32x32x2)
@@ -46,12 +47,15 @@ int dlsg_struct_size(int which);
  *   sublayer.py:66-68,80, AttentionShare K/V/Q/out sublayer.py:29-31,41, LSTMCell layer.py:571,593,
  *   word_restore layer.py:600.
  * C_g[b] (M x N, ldc) = alpha * opA(A_g[b]) . opB(B_g[b])  (+ bias[n]) (+ C) (tanh)   for every group g, batch b
- *   mode 0 "NT": A[m*lda+k], B[n*ldb+k]      (y = x W^T, Linear forward)
- *   mode 1 "NN": A[m*lda+k], B[k*ldb+n]      (dx = dy W)
- *   mode 2 "TN": A[k*lda+m], B[k*ldb+n]      (dW = dy^T x)
+ *   mode DLSG_GEMM_NT: A[m*lda+k], B[n*ldb+k]      (y = x W^T, Linear forward)
+ *   mode DLSG_GEMM_NN: A[m*lda+k], B[k*ldb+n]      (dx = dy W)
+ *   mode DLSG_GEMM_TN: A[k*lda+m], B[k*ldb+n]      (dW = dy^T x)
  * Groups share M, N, mode and flags but have their own operands, K and output: a K-split or a sum of several
  * (activation, weight) segments is expressed as groups writing separate slabs that the consumer kernel sums.
  */
+#define DLSG_GEMM_NT 0 /* dlsg_gemm_args.mode */
+#define DLSG_GEMM_NN 1
+#define DLSG_GEMM_TN 2
 #define DLSG_GEMM_MAXG 16
 #define DLSG_GEMM_ACCUM 1 /* C += result */
 #define DLSG_GEMM_BIAS 2  /* + bias[n]   */

@@ -8,7 +8,7 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, os.path.join(ROOT, 'd-lsg-video-caption_amd'))
 import torch  # noqa: E402
-from dlsg_amd import hip  # noqa: E402
+from dlsg_amd import abi, hip  # noqa: E402
 
 ops = hip.HipOps()
 L, H = 26, 512
@@ -27,7 +27,7 @@ for n in (192, 64):
         err = torch.zeros(1, dtype=torch.int32, device='cuda')
 
         def run(level, hprev=True, bias=True):
-            a = hip.LstmSeqArgs()
+            a = abi.dlsg_lstm_seq_args()
             for k, v in t.items():
                 setattr(a, k, hip._p(v))
             if not hprev:

@@ -11,7 +11,8 @@ sys.path.insert(0, os.path.join(ROOT, 'd-lsg-video-caption_amd'))
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 import ctypes as C  # noqa: E402
-from dlsg_amd.hip import HipOps, O2VArgs, _p  # noqa: E402
+from dlsg_amd import abi  # noqa: E402
+from dlsg_amd.hip import HipOps, _p  # noqa: E402
 
 ops = HipOps()
 B = int(sys.argv[1]) if len(sys.argv) > 1 else 256
@@ -22,7 +23,7 @@ g, b_ = torch.ones(H, device='cuda'), torch.zeros(H, device='cuda')
 z = torch.empty(B * T, H, device='cuda'); ml = torch.empty(B * T, 2, device='cuda')
 st = torch.empty(B * NO, 2, device='cuda'); S = torch.empty(B, NO, T, device='cuda')
 ws = torch.zeros(B * (T * H + 64), dtype=torch.float32, device='cuda')
-a = O2VArgs()
+a = abi.dlsg_o2v_args()
 a.y, a.v, a.g_obj, a.b_obj, a.z, a.ml, a.ostats, a.S = _p(y), _p(v), _p(g), _p(b_), _p(z), _p(ml), _p(st), _p(S)
 a.ws, a.ws_bytes = _p(ws), ws.numel() * 4
 a.B, a.T, a.NO, a.H, a.nsplit, a.scale, a.eps = B, T, NO, H, 1, 1 / math.sqrt(2048), 1e-5
