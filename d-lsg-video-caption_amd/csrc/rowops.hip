@@ -855,8 +855,11 @@ __device__ __forceinline__ void wave_argmax(float& v, int& i) {
 // One row of the search: the K best classes of a V-wide logit row and the row's log-sum-exp, ONE wave.  The row is read twice
 // (maximum + each lane's own K best in the first pass, the exponential sum in the second -- same summation order as a plain
 // strided loop, so the log-probs are bit-identical to the previous 2 + K pass form), then K merge rounds over the lanes' heads.
-template <int K>
-__device__ __forceinline__ void beam_row_topk(const float* x, int V, int lane, float& lse, float (&outv)[K], int (&outi)[K]) {
+// BAN (dlsg_beam_select_hist): the classes in ban[0..nban) count as -inf.  The list is looked at only for an element that
+// would enter the lane's K best; the row's maximum and exponential sum stay those of the whole row.
+template <int K, bool BAN = false>
+__device__ __forceinline__ void beam_row_topk(const float* x, int V, int lane, float& lse, float (&outv)[K], int (&outi)[K],
+                                              const int* ban = nullptr, int nban = 0) {
     float tv[K];
     int ti[K];
 #pragma unroll
@@ -867,6 +870,10 @@ __device__ __forceinline__ void beam_row_topk(const float* x, int V, int lane, f
         int ci = j;
         m = fmaxf(m, cv);
         if (beam_better(cv, ci, tv[K - 1], ti[K - 1])) {
+            if constexpr (BAN) {
+                for (int q = 0; q < nban; ++q) cv = ban[q] == ci ? -INFINITY : cv;
+                if (!beam_better(cv, ci, tv[K - 1], ti[K - 1])) continue;
+            }
 #pragma unroll
             for (int q = 0; q < K; ++q) {                       // one bubble pass keeps tv sorted
                 const bool up = beam_better(cv, ci, tv[q], ti[q]);
@@ -950,6 +957,116 @@ __global__ __launch_bounds__(64 * K) void beam_select_kernel(const dlsg_beam_sel
             n_end += cls == a.end;
         }
         if (lane == 0 && a.ended_count) atomicAdd(a.ended_count, n_end);
+    }
+}
+
+// The step with a token history that travels with the beams, a repeated-n-gram ban and a minimum length.  hist_in / hist_out
+// (B*k, L) int64, ping-pong: new beam c gets its parent's row with hist[t] = pred and `end` at every position after t (step 0
+// writes whole rows, so the search fills its own buffers).  Each live beam's wave lists the classes it may not choose in LDS:
+// with g = no_repeat_ngram, every h[i + g - 1] whose g - 1 predecessors equal the last g - 1 tokens of the history, and
+// `end` while t < min_len.  g = 0 and min_len = 0 give the bits of beam_select_kernel.
+constexpr int BEAM_MAXL = 64;
+template <int K>
+__global__ __launch_bounds__(64 * K) void beam_select_hist_kernel(const dlsg_beam_select_args a, const int64_t* __restrict__ hist_in,
+                                                                    int64_t* __restrict__ hist_out, int L, int t, int g, int min_len) {
+    __shared__ float cand_lp[K * K];
+    __shared__ int cand_cls[K * K];
+    __shared__ int hist[K][BEAM_MAXL];
+    __shared__ int ban[K][BEAM_MAXL + 1];
+    __shared__ int nban[K];
+    const int b = blockIdx.x, k = K, V = a.V;
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const int nbeam = a.first ? 1 : k;
+    const int64_t row = (int64_t)b * k + w;
+    const bool ended = !a.first && a.last[row] == a.end;
+    const bool ngram = g > 0 && t >= g;                      // (never at step 0)
+    if (ngram) hist[w][lane] = lane < t ? (int)hist_in[row * L + lane] : -1;
+    __syncthreads();
+    if (w < nbeam && !ended) {
+        int n = 0;
+        if (ngram) {                                         // lane i: the g-gram that starts at i ends in a class to ban if its
+            bool hit = lane <= t - g;                        // first g - 1 tokens are the last g - 1 of the history
+            for (int j = 0; hit && j < g - 1; ++j) hit = hist[w][lane + j] == hist[w][t - g + 1 + j];
+            const unsigned long long m = __ballot(hit);
+            if (hit) ban[w][__popcll(m & ((1ull << lane) - 1ull))] = hist[w][lane + g - 1];
+            n = __popcll(m);
+        }
+        if (lane == 0) {
+            if (t < min_len) ban[w][n++] = a.end;
+            nban[w] = n;
+        }
+    }
+    __syncthreads();
+    if (w < nbeam) {
+        const float* x = a.logits + row * a.ld;
+        const float base = a.first ? 0.f : a.last_lp[row];
+        if (ended) {
+            if (lane < k) {
+                cand_lp[w * k + lane] = lane == 0 ? base : -INFINITY;
+                cand_cls[w * k + lane] = lane == 0 ? a.end : (lane - 1 < a.end ? lane - 1 : lane);
+            }
+        } else {
+            float lse, bv[K];
+            int bi[K];
+            beam_row_topk<K, true>(x, V, lane, lse, bv, bi, ban[w], nban[w]);
+            if (lane == 0) {
+#pragma unroll
+                for (int c = 0; c < K; ++c) {
+                    cand_lp[w * k + c] = (bv[c] - lse) + base;
+                    cand_cls[w * k + c] = bi[c];
+                }
+            }
+        }
+    }
+    __syncthreads();
+    if (w == 0) {
+        const int n = nbeam * k;
+        float v = lane < n ? cand_lp[lane] : -INFINITY;
+        int idx = lane < n ? lane : 0x7fffffff;
+        int n_end = 0;
+        for (int c = 0; c < k; ++c) {
+            float bv = v;
+            int bi = idx;
+            wave_argmax(bv, bi);
+            if (lane == bi) v = -INFINITY, idx = 0x7fffffff;
+            if (bi == 0x7fffffff) bi = c < n ? c : 0;
+            const int cls = cand_cls[bi];
+            const int64_t o = (int64_t)b * k + c;
+            if (lane == 0) {
+                a.pred[o] = cls;
+                a.new_lp[o] = bv;
+                a.back[o] = bi / k;
+                a.rows[o] = (int64_t)b * k + bi / k;
+            }
+            if (lane < L)
+                hist_out[o * L + lane] = lane < t ? hist_in[((int64_t)b * k + bi / k) * L + lane] : (lane == t ? (int64_t)cls : (int64_t)a.end);
+            n_end += cls == a.end;
+        }
+        if (lane == 0 && a.ended_count) atomicAdd(a.ended_count, n_end);
+    }
+}
+
+// The n best of each clip's k finished beams, by score = lp / len^alpha (double, stored as float), descending, ties to the lower
+// beam: one wave per clip.  len = tokens up to and including the first `end` of the beam's history row, L without one.
+__global__ __launch_bounds__(64) void beam_finalize_kernel(const int64_t* __restrict__ hist, const float* __restrict__ lp, int k, int L,
+                                                           int64_t end, double alpha, int n, int64_t* __restrict__ ids,
+                                                           float* __restrict__ scores, int64_t* __restrict__ lens) {
+    const int b = blockIdx.x, lane = threadIdx.x;
+    float sc[BEAM_MAXK];
+    int len[BEAM_MAXK];
+    for (int c = 0; c < k; ++c) {
+        const int64_t row = (int64_t)b * k + c;
+        const unsigned long long m = __ballot(lane < L && hist[row * L + lane] == end);
+        len[c] = m ? __ffsll((long long)m) : L;
+        sc[c] = (float)((double)lp[row] / pow((double)len[c], alpha));
+    }
+    for (int c = 0; c < k; ++c) {
+        int rank = 0;
+        for (int d = 0; d < k; ++d) rank += d != c && beam_better(sc[d], d, sc[c], c);
+        if (rank >= n) continue;
+        const int64_t o = (int64_t)b * n + rank;
+        if (lane < L) ids[o * L + lane] = hist[((int64_t)b * k + c) * L + lane];
+        if (lane == 0) { scores[o] = sc[c]; lens[o] = len[c]; }
     }
 }
 
@@ -1306,6 +1423,32 @@ extern "C" int dlsg_beam_select(const dlsg_beam_select_args* a, void* stream) {
         case 7: hipLaunchKernelGGL(beam_select_kernel<7>, dim3(a->B), dim3(448), 0, ST(stream), *a); break;
         default: hipLaunchKernelGGL(beam_select_kernel<8>, dim3(a->B), dim3(512), 0, ST(stream), *a); break;
     }
+    DLSG_CHECK_LAUNCH();
+    return DLSG_OK;
+}
+#define BEAM_HIST_CASE(KK) \
+    case KK: hipLaunchKernelGGL(beam_select_hist_kernel<KK>, dim3(a->B), dim3(64 * KK), 0, ST(stream), *a, hist_in, hist_out, L, t, \
+                                no_repeat_ngram, min_len); break;
+extern "C" int dlsg_beam_select_hist(const dlsg_beam_select_args* a, const int64_t* hist_in, int64_t* hist_out, int L, int t,
+                                     int no_repeat_ngram, int min_len, void* stream) {
+    if (!a || a->k < 1 || a->k > BEAM_MAXK || a->V < a->k) return DLSG_EINVAL;
+    if (!hist_out || L < 1 || L > BEAM_MAXL || t < 0 || t >= L || no_repeat_ngram < 0 || min_len < 0) return DLSG_EINVAL;
+    if ((a->first != 0) != (t == 0) || (t > 0 && (!hist_in || hist_in == hist_out))) return DLSG_EINVAL;
+    if (a->B == 0) return DLSG_OK;
+    switch (a->k) {
+        BEAM_HIST_CASE(1) BEAM_HIST_CASE(2) BEAM_HIST_CASE(3) BEAM_HIST_CASE(4)
+        BEAM_HIST_CASE(5) BEAM_HIST_CASE(6) BEAM_HIST_CASE(7) BEAM_HIST_CASE(8)
+    }
+    DLSG_CHECK_LAUNCH();
+    return DLSG_OK;
+}
+#undef BEAM_HIST_CASE
+extern "C" int dlsg_beam_finalize(const int64_t* hist, const float* lp, int B, int k, int L, int64_t end, double alpha, int n,
+                                  int64_t* ids, float* scores, int64_t* lens, void* stream) {
+    if (!hist || !lp || !ids || !scores || !lens || B < 0 || k < 1 || k > BEAM_MAXK || L < 1 || L > BEAM_MAXL || n < 1 || n > k)
+        return DLSG_EINVAL;
+    if (B == 0) return DLSG_OK;
+    hipLaunchKernelGGL(beam_finalize_kernel, dim3(B), dim3(64), 0, ST(stream), hist, lp, k, L, end, alpha, n, ids, scores, lens);
     DLSG_CHECK_LAUNCH();
     return DLSG_OK;
 }

@@ -7,6 +7,10 @@ back-pointer: K', V' stay one block per clip that its k beams read (dlsg_dec_mid
 are expanded once; only the four LSTM states are reordered (one gather launch, ping-pong slots).  Candidate selection -- log-softmax, top-k over the
 vocabulary per beam, top-k over the k*k continuations, back-pointers -- is one HIP launch per step (`beam_select`);
 the host does not synchronise inside the loop except for the early-exit test every 4th step.
+
+`beam_nbest` is the search beyond the reference: all k hypotheses with their scores, length normalisation, repeated-n-gram
+blocking and a minimum length, with no host synchronisation at all (`beam_select_hist` carries every beam's tokens along, so
+there is no back-trace; `beam_finalize` ranks the beams).
 """
 import torch
 
@@ -29,10 +33,15 @@ def beam_device(model, visual_feats, region_feats, early_exit=True):
     """Everything of the search that runs on the device.  early_exit=False: no host synchronisation at all (all L steps
     are launched; beam_finish cuts the result to the step the reference would have stopped at) -- this form is what
     BeamGraph captures into a hipGraph.  Returns the tensors beam_finish needs."""
+    mems, sv, seed, extras = _encode(model, visual_feats, region_feats)
+    return beam_search_from(model, mems, sv, seed, early_exit, extras)
+
+
+def _encode(model, visual_feats, region_feats):
+    """the encoder of the model's class: the attended memories, the saved tensors, the seed and CapGnnModel's proposals"""
     model.flatten_parameters_()
-    ops, dec = model.ops, model.decoder
+    ops = model.ops
     model._gemm_policy(False)
-    k = dec.beam_size
     seed = model.next_seed()
     sv = {}
     frames = visual_feats.contiguous().float()
@@ -50,7 +59,7 @@ def beam_device(model, visual_feats, region_feats, early_exit=True):
         enc = enc.view(B0, T, -1)
         mems, sv['dec_gsrc'] = [enc], [enc]
     extras = (sv['dec_gsrc'][0], sv['dec_gsrc'][-1]) if hasattr(model, '_encode') else None
-    return beam_search_from(model, mems, sv, seed, early_exit, extras)
+    return mems, sv, seed, extras
 
 
 @torch.no_grad()
@@ -152,3 +161,80 @@ def beam_finish(model, preds, backs, lps, ended, done, B, k, R, L, extras):
     if extras is not None:
         return out, extras[0], extras[1], []
     return out, 0, 0, 0
+
+
+MAX_BEAM, MAX_WORDS = 8, 64          # limits of dlsg_beam_select_hist / dlsg_beam_finalize
+
+
+def check_nbest_options(k, L, n_best=None, length_penalty=0.0, no_repeat_ngram=0, min_len=0):
+    """ValueError for what `beam_nbest` cannot run; returns n"""
+    n = k if n_best is None else n_best
+    if not 1 <= k <= MAX_BEAM:
+        raise ValueError('beam size %d: the n-best search takes 1 to %d beams' % (k, MAX_BEAM))
+    if L > MAX_WORDS:
+        raise ValueError('max_words %d: the n-best search keeps at most %d tokens per beam' % (L, MAX_WORDS))
+    if not 1 <= n <= k:
+        raise ValueError('n_best %d outside 1 .. beam size %d' % (n, k))
+    if no_repeat_ngram < 0 or min_len < 0:
+        raise ValueError('no_repeat_ngram (%d) and min_len (%d) must not be negative' % (no_repeat_ngram, min_len))
+    if min_len >= L:
+        raise ValueError('min_len %d leaves no room for <end> in max_words %d' % (min_len, L))
+    return n
+
+
+@torch.no_grad()
+def beam_nbest(model, visual_feats, region_feats, n_best=None, length_penalty=0.0, no_repeat_ngram=0, min_len=0, beam_size=None):
+    """The n best of the k beams of every clip: (ids (B, n, L) int64, padded with <end>; scores (B, n) float32 =
+    log-prob / len^length_penalty, descending; lens (B, n) int64 = tokens up to and including the first <end>, else L), device
+    tensors.  no_repeat_ngram = g: no caption repeats a g-gram; min_len: no <end> before that many words.  A banned word takes
+    log-prob -inf, the others are not renormalised.  All L steps are launched and nothing is read back: once every beam of a clip
+    has ended a step only appends <end> at log-prob 0, so with the options off the rows are the reference's beams, end-padded.
+    beam_size: the number of beams, default the decoder's.  Because nothing is read back, the persistent BiLSTM's time-out word
+    is not looked at here: call `model.ops.check_persistent()` where the ids are copied to the host (`scoring.gather_results`
+    does)."""
+    dec = model.decoder
+    k, L = dec.beam_size if beam_size is None else beam_size, dec.max_words
+    n = check_nbest_options(k, L, n_best, length_penalty, no_repeat_ngram, min_len)
+    mems, sv, seed, _ = _encode(model, visual_feats, region_feats)
+    ops = model.ops
+    frames = mems[0]
+    s = E.dec_prepare(ops, dec, mems, sv, False, seed)
+    B, V = frames.shape[0], dec.vocab_size
+    end = dec.vocab('<end>')
+    if k > V:
+        raise ValueError('Target vocab size (%d) too small relative to per_node_beam_size (%d)' % (V, k))
+    s['kv_div'] = k
+    s['gq'] = _expand_rows(s['gq'], k)
+    R = B * k
+    E.dec_alloc(dec, s, frames, R, L)
+    dev = frames.device
+    state_keys = ['LHP', 'QH', 'QC', 'LC']                         # two slots per step, as in beam_search_from
+    big = {key: torch.zeros(2 * L + 2, R, s[key].shape[2], dtype=torch.float32, device=dev) for key in state_keys}
+    Emb = dec.word_embed.weight
+    preds = torch.empty(2, R, dtype=torch.int64, device=dev)       # ping-pong: the history keeps the tokens
+    hist = torch.empty(2, R, L, dtype=torch.int64, device=dev)     # filled by step 0
+    back = torch.empty(R, dtype=torch.int64, device=dev)
+    rows = torch.empty(R, dtype=torch.int64, device=dev)
+    lps = torch.zeros(2, R, dtype=torch.float32, device=dev)
+    words = torch.full((R,), dec.vocab('<start>'), dtype=torch.int64, device=dev)
+    for t in range(L):
+        if t:
+            ops.gather_rows_multi([big[key][2 * t - 1] for key in state_keys], rows, [big[key][2 * t] for key in state_keys])
+        for key in state_keys:
+            s[key] = big[key][t:]
+        ops.embed_fwd(Emb, words, s['WE'][t])
+        E.dec_step(ops, dec, s, t, frames, False, seed, R)
+        E.dec_logits(ops, dec, s, t, t + 1)
+        ops.beam_select_hist(s['LOGITS'][t], words, lps[t % 2], preds[t % 2], lps[(t + 1) % 2], back, rows, k, end,
+                             hist[t % 2], hist[(t + 1) % 2], t, no_repeat_ngram, min_len)
+        words = preds[t % 2]
+    ids = torch.empty(B, n, L, dtype=torch.int64, device=dev)
+    scores = torch.empty(B, n, dtype=torch.float32, device=dev)
+    lens = torch.empty(B, n, dtype=torch.int64, device=dev)
+    ops.beam_finalize(hist[L % 2], lps[L % 2], k, end, float(length_penalty), ids, scores, lens)
+    return ids, scores, lens
+
+
+def beam_search(model, visual_feats, region_feats, beam_size=None, **options):
+    """`beam_nbest` with `beam_size` beams (default: the decoder's own, which is not changed)"""
+    return beam_nbest(model, visual_feats, region_feats, beam_size=beam_size, **options)

@@ -513,6 +513,34 @@ class HipOps(object):
         a.B, a.k, a.V, a.end, a.first = R // k, k, V, end, int(first)
         self._check(self.lib.dlsg_beam_select(C.byref(a), self._stream()), 'dlsg_beam_select')
 
+    def beam_select_hist(self, logits, last, last_lp, pred, new_lp, back, rows, k, end, hist_in, hist_out, t, no_repeat_ngram=0,
+                         min_len=0, ended_count=None):
+        """`beam_select` at step t (t == 0 is the first step) with the beams' token history: hist_out[c] = hist_in[parent of c]
+        with hist[t] = pred and `end` behind it ((B*k, L) int64, two buffers), a repeated-n-gram ban and a minimum length (see
+        include/dlsg.h)."""
+        a = abi.dlsg_beam_select_args()
+        R, V = logits.shape
+        L = hist_out.shape[1]
+        for h in (hist_in, hist_out):
+            assert h.dtype == torch.int64 and h.is_contiguous() and h.shape == (R, L), (h.dtype, h.shape)
+        a.logits, a.ld = _p(logits), logits.stride(0)
+        a.last, a.last_lp = _p(last), _p(last_lp)
+        a.pred, a.new_lp, a.back, a.rows, a.ended_count = _p(pred), _p(new_lp), _p(back), _p(rows), _p(ended_count)
+        a.B, a.k, a.V, a.end, a.first = R // k, k, V, end, int(t == 0)
+        self._check(self.lib.dlsg_beam_select_hist(C.byref(a), _p(hist_in), _p(hist_out), L, int(t), int(no_repeat_ngram), int(min_len),
+                                                   self._stream()), 'dlsg_beam_select_hist')
+
+    def beam_finalize(self, hist, lp, k, end, alpha, ids, scores, lens):
+        """the n = ids.shape[1] best of each clip's k beams by lp / len^alpha: ids (B, n, L), scores (B, n), lens (B, n)."""
+        R, L = hist.shape
+        B, n = R // k, ids.shape[1]
+        assert hist.dtype == torch.int64 and hist.is_contiguous() and lp.dtype == torch.float32 and lp.is_contiguous() and lp.numel() == R
+        assert ids.dtype == torch.int64 and ids.is_contiguous() and ids.shape == (B, n, L)
+        assert scores.dtype == torch.float32 and scores.is_contiguous() and scores.shape == (B, n)
+        assert lens.dtype == torch.int64 and lens.is_contiguous() and lens.shape == (B, n)
+        self._check(self.lib.dlsg_beam_finalize(_p(hist), _p(lp), B, k, L, i64(end), C.c_double(alpha), n, _p(ids), _p(scores), _p(lens),
+                                                self._stream()), 'dlsg_beam_finalize')
+
     def gather_rows_multi(self, srcs, rows, dsts):
         """dsts[i][r] = srcs[i][rows[r]] for up to 4 dense (R, n_i) arrays in one launch."""
         a = abi.dlsg_gather_multi_args()

@@ -172,6 +172,16 @@ class _HipModel(_ArenaModule):
     def sample(self, visual_feats, region_feats, n=1, temperature=1.0, seed=None):
         raise NotImplementedError('sampled decoding (self-critical training) is implemented for CapGnnModel only')
 
+    def beam_search(self, visual_feats, region_feats, beam_size=None, n_best=None, length_penalty=0.0, no_repeat_ngram=0, min_len=0):
+        """The n_best (default: all) of `beam_size` (default: the decoder's, at most 8) beams per clip, entirely on the device:
+        (ids (B, n, L) int64 padded with <end>, scores (B, n) float32 = log-prob / len^length_penalty in descending order, lens
+        (B, n) int64 counting the <end>).  no_repeat_ngram = g > 0: no caption repeats a g-gram; min_len: at least that many words
+        before <end>.  With the options off, row 0 is `model(frames, regions, None)` padded with <end> (`beam.beam_nbest`).
+        Nothing synchronises with the host, so call `model.ops.check_persistent()` where the ids are read back."""
+        from .beam import beam_search
+        return beam_search(self, visual_feats, region_feats, beam_size, n_best=n_best, length_penalty=length_penalty,
+                           no_repeat_ngram=no_repeat_ngram, min_len=min_len)
+
     def _draw_coins(self, L, infer, tf_ratio):
         # reference draws one coin per step only when not inferring (layer.py:432)
         if infer:
@@ -687,6 +697,37 @@ class BeamGraph(object):
             self.regions.copy_(regions, non_blocking=True)
         self.graph.replay()
         return beam_finish(self.model, *self.state)
+
+
+class NBestBeamGraph(object):
+    """hipGraph-captured `model.beam_search(frames, regions, **options)` for one batch shape: encoder, all max_words steps with
+    the beams' token history, and the ranking.  A replay returns (ids, scores, lens) -- static buffers, valid until the next
+    replay -- and synchronises nothing (call `model.ops.check_persistent()` where the ids are read back)."""
+
+    def __init__(self, model, frames, regions, **options):
+        self.model = model
+        model.flatten_parameters_()
+        dev = frames.device
+        self.frames, self.regions = frames.clone(), regions.clone()
+        side = _capture_stream(dev)
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side), torch.no_grad():
+            model.beam_search(self.frames, self.regions, **options)                              # warm-up
+            side.synchronize()
+            self.graph = torch.cuda.CUDAGraph()
+            self.graph.capture_begin(capture_error_mode='thread_local')
+            self.out = model.beam_search(self.frames, self.regions, **options)
+            self.graph.capture_end()
+        torch.cuda.current_stream().wait_stream(side)
+
+    @torch.no_grad()
+    def __call__(self, frames, regions):
+        if frames.data_ptr() != self.frames.data_ptr():
+            self.frames.copy_(frames, non_blocking=True)
+        if regions.data_ptr() != self.regions.data_ptr():
+            self.regions.copy_(regions, non_blocking=True)
+        self.graph.replay()
+        return self.out
 
 
 # ================================================================================================ fast training path

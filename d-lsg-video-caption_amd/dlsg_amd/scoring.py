@@ -363,14 +363,19 @@ def convert_prediction(prediction):
     return {str(k): [{u'video_id': str(k), u'caption': v}] for k, v in prediction.items()}
 
 
-def gather_results(net, eval_loader):
-    """evaluate.py:62-78 / 101-117: greedy or beam inference over the eval loader -> OrderedDict video id -> sentence"""
+def gather_results(net, eval_loader, decode=None):
+    """evaluate.py:62-78 / 101-117: greedy or beam inference over the eval loader -> OrderedDict video id -> sentence.
+    `decode`: a dict of `beam_search` options (beam_size, length_penalty, no_repeat_ngram, min_len); the captions are then the
+    best beam of that search."""
     import torch
     result = collections.OrderedDict()
     dec = (net.module if hasattr(net, 'module') else net).decoder
     with torch.no_grad():
         for frames, regions, spatials, video_ids in eval_loader:
-            outputs = net(frames, regions, None)[0]
+            if decode is None:
+                outputs = net(frames, regions, None)[0]
+            else:
+                outputs = (net.module if hasattr(net, 'module') else net).beam_search(frames, regions, **dict(decode, n_best=1))[0][:, 0]
             ids = outputs.cpu()                                    # host synchronisation: the time-out word is final too
             chk = getattr(getattr(net.module if hasattr(net, 'module') else net, 'ops', None), 'check_persistent', None)
             if chk is not None:
@@ -396,12 +401,12 @@ def merge_rank_results(result, process_group=None):
     return merged
 
 
-def evaluate(net, eval_loader, reference, process_group=None, gather=True):
+def evaluate(net, eval_loader, reference, process_group=None, gather=True, decode=None):
     """evaluate.py:56-98 -> (scores, result).  `reference`: dict from convert_data_to_coco_scorer_format.  Inside an
     initialised process group (several GPUs, each with its own partition of the clips in `eval_loader`) the ranks' results are
     merged first (`evaluate_multi_gpu` of evaluate.py:120-134 on the gathered dict, run_gun.py:268-281), so the scores cover
-    the whole test set on every rank; gather=False scores this rank's partition only."""
-    result = gather_results(net, eval_loader)
+    the whole test set on every rank; gather=False scores this rank's partition only.  `decode`: see gather_results."""
+    result = gather_results(net, eval_loader, decode)
     if gather:
         result = merge_rank_results(result, process_group)
     pred = convert_prediction(result)

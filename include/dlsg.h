@@ -716,6 +716,21 @@ typedef struct {
     int32_t B, k, V, end, first, pad_;
 } dlsg_beam_select_args;
 int dlsg_beam_select(const dlsg_beam_select_args* a, void* stream);
+/* dlsg_beam_select at step t (first != 0 exactly when t == 0) with a token history that travels with the beams and two bans.
+ * hist_in / hist_out (B*k, L) int64 rows, two buffers that do not overlap, used ping-pong, L <= 64: new beam c gets its parent's row of
+ * hist_in with hist[t] = pred and `end` at every position after t (step 0 reads no hist_in and writes whole rows), so after the
+ * last step a row is the end-padded caption of its beam.  no_repeat_ngram = g >= 1: a live beam with history h may not choose
+ * class c if an i <= t - g exists with h[i .. i+g-2] == h[t-g+1 .. t-1] and h[i+g-1] == c.  min_len: `end` is banned at steps
+ * t < min_len.  A banned class has log-prob -inf; the log-sum-exp stays that of the whole row; a beam that has ended offers
+ * `end` at log-prob 0 whatever the bans.  g = 0, min_len = 0: pred, new_lp, back, rows, ended_count are the bits of
+ * dlsg_beam_select. */
+int dlsg_beam_select_hist(const dlsg_beam_select_args* a, const int64_t* hist_in, int64_t* hist_out, int L, int t,
+                          int no_repeat_ngram, int min_len, void* stream);
+/* After the last step: the n <= k best beams of every clip by score = lp / len^alpha (computed in double, stored as float),
+ * descending, ties to the lower beam.  hist (B*k, L) the final history, lp (B*k) the final log-probs; len = tokens up to and
+ * including the first `end`, L without one.  Out: ids (B, n, L) int64, scores (B, n), lens (B, n) int64.  One wave per clip. */
+int dlsg_beam_finalize(const int64_t* hist, const float* lp, int B, int k, int L, int64_t end, double alpha, int n,
+                       int64_t* ids, float* scores, int64_t* lens, void* stream);
 /* dst_i[r,:] = src_i[rows[r],:] (dense rows of n[i] floats) for count <= 4 arrays in one launch */
 typedef struct {
     const float* src[4]; float* dst[4]; int32_t n[4];
