@@ -1085,9 +1085,16 @@ __global__ void gather_rows_multi_kernel(const dlsg_gather_multi_args a) {
 }
 
 // ------------------------------------------------------------------------------------------------ Adam
+// CLIP: the gradient is scaled by the clip record's coefficient and, with clipv > 0, clamped to +-clipv (dlsg_adam_clipped); the
+// CLIP = false instantiation is dlsg_adam's arithmetic, untouched
+template <bool CLIP>
 __device__ __forceinline__ void adam_one(float& p, float g, float& m, float& v, float lr_bc1, float b1, float b2, float eps,
-                                         float bc2s, float gscale) {
-    const float gi = g * gscale;
+                                         float bc2s, float gscale, float coef, float clipv) {
+    float gi = g * gscale;
+    if (CLIP) {
+        gi *= coef;                                        // coef == 1.0f: exact, dlsg_adam's bits
+        if (clipv > 0.f) gi = fminf(fmaxf(gi, -clipv), clipv);
+    }
     m = b1 * m + (1.f - b1) * gi;
     v = b2 * v + (1.f - b2) * gi * gi;
     const float denom = sqrtf(v) / bc2s + eps;
@@ -1096,12 +1103,17 @@ __device__ __forceinline__ void adam_one(float& p, float g, float& m, float& v, 
 // NTM: bit 0 non-temporal loads of m, v, g; bit 1 non-temporal stores of m, v; bit 2 / 3 the same for the load / store of p.
 // 28 B of traffic per parameter: 16-byte accesses over the aligned body (the four arrays share one index, so one alignment),
 // scalar head and tail (a trainable range may start at any parameter boundary)
-template <int NTM>
+template <int NTM, bool CLIP>
 __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                                                    float* __restrict__ v, int64_t n, float lr, float b1, float b2, float eps,
                                                    float bc1, float bc2s, float gscale, const float* __restrict__ hyper,
-                                                   const int32_t* __restrict__ guard) {
+                                                   const int32_t* __restrict__ guard, const float* __restrict__ record, float clipv) {
     if (guard && *guard != 0) return;      // a persistent kernel reported a time-out in this step: its gradients are invalid
+    float coef = 1.f;
+    if (CLIP && record) {
+        if (record[DLSG_CLIP_NONFINITE] != 0.f) return;    // the step's gradient holds an inf or a NaN: p, m and v keep their bits
+        coef = record[DLSG_CLIP_COEF];
+    }
     if (hyper) { lr = hyper[0]; bc1 = 1.f; bc2s = hyper[1]; }
     const float lr_bc1 = lr / bc1;
     const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, nth = (int64_t)gridDim.x * blockDim.x;
@@ -1111,7 +1123,7 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const 
     int64_t head = same ? (int64_t)((16 - (reinterpret_cast<uintptr_t>(p) & 15)) & 15) / 4 : n;
     if (head > n) head = n;
     const int64_t nv = (n - head) / 4;                     // float4 elements of the aligned body
-    for (int64_t i = tid; i < head; i += nth) adam_one(p[i], g[i], m[i], v[i], lr_bc1, b1, b2, eps, bc2s, gscale);
+    for (int64_t i = tid; i < head; i += nth) adam_one<CLIP>(p[i], g[i], m[i], v[i], lr_bc1, b1, b2, eps, bc2s, gscale, coef, clipv);
     f32x4* p4 = reinterpret_cast<f32x4*>(p + head);
     const f32x4* g4 = reinterpret_cast<const f32x4*>(g + head);
     f32x4* m4 = reinterpret_cast<f32x4*>(m + head);
@@ -1124,14 +1136,67 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const 
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
             float pe = pp[e], me = mm[e], ve = vv[e];
-            adam_one(pe, gg[e], me, ve, lr_bc1, b1, b2, eps, bc2s, gscale);
+            adam_one<CLIP>(pe, gg[e], me, ve, lr_bc1, b1, b2, eps, bc2s, gscale, coef, clipv);
             pp[e] = pe; mm[e] = me; vv[e] = ve;
         }
         if (NTM & 2) { __builtin_nontemporal_store(mm, m4 + i); __builtin_nontemporal_store(vv, v4 + i); }
         else { m4[i] = mm; v4[i] = vv; }
         if (NTM & 8) __builtin_nontemporal_store(pp, p4 + i); else p4[i] = pp;
     }
-    for (int64_t i = head + 4 * nv + tid; i < n; i += nth) adam_one(p[i], g[i], m[i], v[i], lr_bc1, b1, b2, eps, bc2s, gscale);
+    for (int64_t i = head + 4 * nv + tid; i < n; i += nth) adam_one<CLIP>(p[i], g[i], m[i], v[i], lr_bc1, b1, b2, eps, bc2s, gscale, coef, clipv);
+}
+
+// ------------------------------------------------------------------------------------------------ gradient clipping
+// Wave- and block-wide float64 sums in a fixed order (no atomics): the same input gives the same bits on every launch.
+__device__ __forceinline__ double wave_sum_f64(double v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+    return v;
+}
+// blockDim.x == 256; `red` = 4 doubles of LDS; the result is valid in thread 0
+__device__ __forceinline__ double block256_sum_f64(double v, double* red) {
+    v = wave_sum_f64(v);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return (red[0] + red[1]) + (red[2] + red[3]);
+}
+// slots[blockIdx.x] = this workgroup's share of sum g[i]^2 over g[0..n), squared and added in float64 (the square of a float is
+// exact there).  Grid = DLSG_GRAD_SUMSQ_SLOTS workgroups whatever n is; a workgroup without elements writes 0.  Ordinary loads:
+// the Adam launch behind it reads the same bytes.  16-byte loads over the aligned body, scalar head and tail, as adam_kernel.
+__global__ __launch_bounds__(256) void grad_sumsq_kernel(const float* __restrict__ g, int64_t n, double* __restrict__ slots) {
+    __shared__ double red[4];
+    const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, nth = (int64_t)gridDim.x * blockDim.x;
+    int64_t head = (int64_t)((16 - (reinterpret_cast<uintptr_t>(g) & 15)) & 15) / 4;
+    if (head > n) head = n;
+    const int64_t nv = (n - head) / 4;
+    double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
+    for (int64_t i = tid; i < head; i += nth) { const double x = g[i]; a0 += x * x; }
+    const f32x4* g4 = reinterpret_cast<const f32x4*>(g + head);
+#pragma unroll 4
+    for (int64_t i = tid; i < nv; i += nth) {
+        const f32x4 gg = g4[i];
+        const double x0 = gg[0], x1 = gg[1], x2 = gg[2], x3 = gg[3];
+        a0 += x0 * x0; a1 += x1 * x1; a2 += x2 * x2; a3 += x3 * x3;
+    }
+    for (int64_t i = head + 4 * nv + tid; i < n; i += nth) { const double x = g[i]; a0 += x * x; }
+    const double s = block256_sum_f64((a0 + a1) + (a2 + a3), red);
+    if (threadIdx.x == 0) slots[blockIdx.x] = s;
+}
+// One workgroup: the sum of `count` partials in a fixed order -> record {norm, coef, nonfinite, 0}; see include/dlsg.h
+__global__ __launch_bounds__(256) void clip_coef_kernel(const double* __restrict__ slots, int count, float gscale, float max_norm,
+                                                       float* __restrict__ record, int64_t* __restrict__ skipped) {
+    __shared__ double red[4];
+    double a = 0.0;
+    for (int i = threadIdx.x; i < count; i += 256) a += slots[i];
+    const double s = block256_sum_f64(a, red);
+    if (threadIdx.x != 0) return;
+    const float norm = (float)((double)gscale * sqrt(s));
+    const bool bad = !(fabsf(norm) <= 3.402823466e+38f);   // inf or NaN (a sum that overflows the float norm counts as non-finite)
+    record[DLSG_CLIP_NORM] = norm;
+    record[DLSG_CLIP_COEF] = bad ? 0.f : fminf(1.f, max_norm / (norm + 1e-6f));
+    record[DLSG_CLIP_NONFINITE] = bad ? 1.f : 0.f;
+    record[3] = 0.f;
+    if (bad && skipped) *skipped += 1;
 }
 
 inline int grid_for(int64_t total, int threads = 256, int cap = 4096) {
@@ -1467,8 +1532,36 @@ extern "C" int dlsg_adam(float* p, const float* g, float* m, float* v, int64_t n
     // moments and gradients are read once per step and the moments written once: non-temporal on those streams (mask 3), default
     // policy on the parameters, which the next forward reads.  Measured per launch under rocprofv3 on two boxes: 502 -> 424 us and
     // 421 -> 391 us; every other combination of the four streams within 391-426 us on the second box
-    hipLaunchKernelGGL(adam_kernel<3>, dim3(grid_for((n + 3) / 4, 256, 8192)), dim3(256), 0, ST(stream), p, g, m, v, n, lr, b1, b2, eps, bc1,
-                       bc2s, grad_scale, hyper, guard);
+    hipLaunchKernelGGL((adam_kernel<3, false>), dim3(grid_for((n + 3) / 4, 256, 8192)), dim3(256), 0, ST(stream), p, g, m, v, n, lr, b1, b2,
+                       eps, bc1, bc2s, grad_scale, hyper, guard, (const float*)nullptr, 0.f);
+    DLSG_CHECK_LAUNCH();
+    return DLSG_OK;
+}
+extern "C" int dlsg_grad_sumsq(const float* g, int64_t n, double* slots, void* stream) {
+    if (n < 0 || (!g && n > 0) || !slots) return DLSG_EINVAL;
+    if (reinterpret_cast<uintptr_t>(g) & 3) return DLSG_EALIGN;
+    // (n == 0 launches too: the slots are written, never pre-zeroed by the caller)
+    hipLaunchKernelGGL(grad_sumsq_kernel, dim3(DLSG_GRAD_SUMSQ_SLOTS), dim3(256), 0, ST(stream), g, n, slots);
+    DLSG_CHECK_LAUNCH();
+    return DLSG_OK;
+}
+extern "C" int dlsg_clip_coef(const double* slots, int count, float grad_scale, float max_norm, float* record, int64_t* skipped,
+                              void* stream) {
+    if (!slots || count < 1 || !record || !(max_norm >= 0.f)) return DLSG_EINVAL;
+    hipLaunchKernelGGL(clip_coef_kernel, dim3(1), dim3(256), 0, ST(stream), slots, count, grad_scale, max_norm, record, skipped);
+    DLSG_CHECK_LAUNCH();
+    return DLSG_OK;
+}
+extern "C" int dlsg_adam_clipped(float* p, const float* g, float* m, float* v, int64_t n, float lr, float b1, float b2, float eps,
+                                 int step, float grad_scale, const float* hyper, const int32_t* guard, const float* record,
+                                 float clip_value, void* stream) {
+    if (!(clip_value >= 0.f)) return DLSG_EINVAL;
+    if (n == 0) return DLSG_OK;
+    const float bc1 = 1.f - powf(b1, (float)step);
+    const float bc2s = sqrtf(1.f - powf(b2, (float)step));
+    // the same launch shape and cache policy as dlsg_adam: this is the last reader of g in the step
+    hipLaunchKernelGGL((adam_kernel<3, true>), dim3(grid_for((n + 3) / 4, 256, 8192)), dim3(256), 0, ST(stream), p, g, m, v, n, lr, b1, b2,
+                       eps, bc1, bc2s, grad_scale, hyper, guard, record, clip_value);
     DLSG_CHECK_LAUNCH();
     return DLSG_OK;
 }

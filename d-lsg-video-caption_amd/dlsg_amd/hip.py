@@ -28,6 +28,8 @@ F_ACCUM, F_BIAS, F_TANH = _D['DLSG_GEMM_ACCUM'], _D['DLSG_GEMM_BIAS'], _D['DLSG_
 F_FORCE64, F_FORCE128, F_TILE256, F_BF16X3 = (_D['DLSG_GEMM_' + n] for n in ('FORCE64', 'FORCE128', 'TILE256', 'BF16X3'))
 F_SK, F_NOSK, F_SK_BM128, F_SK_BM256, F_SK_BN128, F_SK_NOXMAP = (_D['DLSG_GEMM_' + n] for n in (
     'SK', 'NOSK', 'SK_BM128', 'SK_BM256', 'SK_BN128', 'SK_NOXMAP'))
+GRAD_SUMSQ_SLOTS = _D['DLSG_GRAD_SUMSQ_SLOTS']   # float64 partials one dlsg_grad_sumsq launch writes
+CLIP_NORM, CLIP_COEF, CLIP_NONFINITE, CLIP_RECORD_FLOATS = (_D['DLSG_CLIP_' + n] for n in ('NORM', 'COEF', 'NONFINITE', 'RECORD_FLOATS'))
 F_SK_GIVEAWAY = _D['DLSG_GEMM_SK_GIVEAWAY']   # test hook (include/dlsg.h): the split tiles are finished by their last contributor alone
 
 i64, u32, u64, f32 = C.c_int64, C.c_uint32, C.c_uint64, C.c_float
@@ -1378,3 +1380,28 @@ class HipOps(object):
         updates nothing; `check_persistent()` then reports it."""
         self._check(self.lib.dlsg_adam(_p(p), _p(g), _p(m), _p(v), i64(p.numel()), f32(lr), f32(b1), f32(b2), f32(eps),
                                        int(step), f32(grad_scale), _p(hyper), _p(self._persist_word(p.device)), self._stream()), 'adam')
+
+    # ------------------------------------------------------------------ gradient clipping (include/dlsg.h)
+    def grad_sumsq(self, g, slots):
+        """slots (float64, GRAD_SUMSQ_SLOTS) <- the partial sums of g^2 over the 1-d float32 view g, one per workgroup; every slot
+        is written (zeros where a workgroup had nothing), none needs clearing first"""
+        assert g.dtype == torch.float32 and g.dim() == 1 and (g.numel() <= 1 or g.stride(0) == 1), (g.dtype, g.shape)
+        assert slots.dtype == torch.float64 and slots.is_contiguous() and slots.numel() == GRAD_SUMSQ_SLOTS, (slots.dtype, slots.shape)
+        self._check(self.lib.dlsg_grad_sumsq(_p(g), i64(g.numel()), _p(slots), self._stream()), 'grad_sumsq')
+
+    def clip_coef(self, slots, grad_scale, max_norm, record, skipped=None):
+        """record (float32, CLIP_RECORD_FLOATS) <- {norm = grad_scale * sqrt(sum of slots), coef = min(1, max_norm / (norm + 1e-6)),
+        nonfinite}; a non-finite norm gives coef 0 and adds one to skipped (int64, 1 element).  max_norm = inf clips nothing."""
+        assert slots.dtype == torch.float64 and slots.is_contiguous() and 1 <= slots.numel() < 2 ** 31
+        assert record.dtype == torch.float32 and record.is_contiguous() and record.numel() == CLIP_RECORD_FLOATS
+        assert skipped is None or (skipped.dtype == torch.int64 and skipped.numel() == 1)
+        self._check(self.lib.dlsg_clip_coef(_p(slots), int(slots.numel()), f32(grad_scale), f32(max_norm), _p(record), _p(skipped),
+                                            self._stream()), 'clip_coef')
+
+    def adam_clipped(self, p, g, m, v, lr, b1, b2, eps, step, grad_scale=1.0, hyper=None, record=None, clip_value=0.0):
+        """`adam` on (g * grad_scale) * record[CLIP_COEF], clamped to +-clip_value when that is > 0; a record whose nonfinite word is
+        set leaves p, m and v as they are (as the time-out word does)"""
+        assert record is None or (record.dtype == torch.float32 and record.is_contiguous() and record.numel() == CLIP_RECORD_FLOATS)
+        self._check(self.lib.dlsg_adam_clipped(_p(p), _p(g), _p(m), _p(v), i64(p.numel()), f32(lr), f32(b1), f32(b2), f32(eps),
+                                               int(step), f32(grad_scale), _p(hyper), _p(self._persist_word(p.device)), _p(record),
+                                               f32(clip_value), self._stream()), 'adam_clipped')

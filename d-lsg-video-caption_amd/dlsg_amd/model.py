@@ -14,6 +14,7 @@ import random
 import torch
 import torch.nn as nn
 
+from . import abi
 from . import engine as E
 from .modules import CapGnnEncoder, Decoder, EncoderVisual
 
@@ -756,7 +757,8 @@ class Trainer(object):
     memory: inputs (static buffers), the dropout seed, the scheduled-sampling coins, the Adam bias corrections."""
 
     def __init__(self, model, lr=1.6e-4, betas=(0.5, 0.9), eps=1e-8, process_group=None, world_size=1, use_graphs=False,
-                 device_coins=None, graph_fallback=False, comm='auto', check_every=100, rehearse_ranks=0):
+                 device_coins=None, graph_fallback=False, comm='auto', check_every=100, rehearse_ranks=0, max_grad_norm=None,
+                 clip_grad_value=None):
         """comm: how the gradient buckets are summed over ranks.
           'rccl'  -- librccl through the C ABI (dlsg_allreduce_bucket) on a side stream forked by an event: the collectives
                      are part of the captured step, so one iteration is ONE hipGraph replay and a bucket's all-reduce runs
@@ -768,8 +770,29 @@ class Trainer(object):
           multi-rank kernel choices of `_use_multi_rank_schedule`, weight gradients flushed at every bucket, every bucket handed
           to the communicator (world 1: the all-reduce is the identity, Adam's 1 / world stays 1) -- so that this schedule can be
           checked against the oracle and timed where only one device exists (tests/test_gpu_bench_parity.py, bench.py's
-          `dp_schedule_world1`).  `rehearse_cotenant` adds the chip-sharing a real all-reduce brings."""
+          `dp_schedule_world1`).  `rehearse_cotenant` adds the chip-sharing a real all-reduce brings.
+        max_grad_norm: clip the gradient to this global 2-norm before Adam (torch.nn.utils.clip_grad_norm_), on the device and as
+          part of the step -- captured with it, no host read.  The norm is that of the gradient Adam applies: over the trainable
+          ranges, after the all-reduce, of the mean over the ranks; every rank reduces the same bits in the same order, so all
+          ranks clip -- or skip -- alike without a collective of their own.  float('inf') clips nothing but still reports and skips.
+        clip_grad_value: clamp every element of that gradient to +-value instead (clip_grad_value_).  At most one of the two.
+          With either set, `last_grad_norm` is a 0-d device view of the last step's norm (float() reads it, and synchronises) and a
+          step whose gradient holds an inf or a NaN updates nothing -- weights and both moments keep their bits -- and adds one
+          to the device counter `skipped_steps`.  `t` advances on a skipped step all the same: the bias corrections are sent
+          from the host before the outcome exists, so the step after a skipped one uses corrections one step further on.
+          With both None the step issues exactly the launches it issued before these options existed."""
         assert comm in ('auto', 'rccl', 'torch'), comm
+        if max_grad_norm is not None and clip_grad_value is not None:
+            raise ValueError('max_grad_norm and clip_grad_value exclude each other: set at most one')
+        if max_grad_norm is not None and not float(max_grad_norm) >= 0.0:
+            raise ValueError('max_grad_norm must be >= 0, not %r' % (max_grad_norm,))
+        if clip_grad_value is not None and not (0.0 < float(clip_grad_value) < float('inf')):
+            raise ValueError('clip_grad_value must be a positive finite number, not %r' % (clip_grad_value,))
+        self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
+        self.clip_grad_value = None if clip_grad_value is None else float(clip_grad_value)
+        self._clip = max_grad_norm is not None or clip_grad_value is not None
+        self._clip_slots = self._clip_rec = self._skipped = None
+        self.last_grad_norm = self.skipped_steps = None
         self.comm = comm
         # every `check_every` steps the persistent kernels' time-out word is read back (one host synchronisation): a launch that
         # was not co-resident (GPU shared with another process) raises here; meanwhile dlsg_adam's guard kept the weights intact
@@ -872,6 +895,21 @@ class Trainer(object):
         # maximal runs of trainable parameters: Adam and the all-reduces cover exactly these (torch.optim skips parameters
         # without a gradient; DDP does not reduce them)
         self._train_ranges = self._minus_frozen(0, model._flat.numel())
+        if self._clip:
+            # scratch of the clip launches, allocated here and never inside a capture: one block of float64 partials per trainable
+            # range (written in full by every dlsg_grad_sumsq launch), the record dlsg_clip_coef writes, the skipped-step counter
+            dev = model._flat.device
+            slots = abi.defines['DLSG_GRAD_SUMSQ_SLOTS'] * max(1, len(self._train_ranges))
+            if self._clip_slots is None or self._clip_slots.numel() != slots or self._clip_slots.device != dev:
+                self._clip_slots = torch.zeros(slots, dtype=torch.float64, device=dev)
+            if self._clip_rec is None or self._clip_rec.device != dev:
+                self._clip_rec = torch.zeros(abi.defines['DLSG_CLIP_RECORD_FLOATS'], dtype=torch.float32, device=dev)
+                old = self._skipped
+                self._skipped = torch.zeros(1, dtype=torch.int64, device=dev)
+                if old is not None:
+                    self._skipped.copy_(old)
+                self.last_grad_norm = self._clip_rec[abi.defines['DLSG_CLIP_NORM']]
+                self.skipped_steps = self._skipped[0]
 
     def _minus_frozen(self, lo, hi):
         out, cur = [], lo
@@ -893,9 +931,26 @@ class Trainer(object):
         if self._arena is not model._flat or frozen != self._frozen:
             self._bind()
 
+    def _clip_grads(self):
+        """the clip launches, between the join of the collectives and the update: the sum of squares of every trainable range of
+        the (all-reduced) gradient arena, then the record {norm, coefficient, non-finite} that `_adam` hands to dlsg_adam_clipped"""
+        if not self._clip:
+            return
+        model, ops = self.model, self.model.ops
+        n = abi.defines['DLSG_GRAD_SUMSQ_SLOTS']
+        for i, (lo, hi) in enumerate(self._train_ranges):
+            ops.grad_sumsq(model._gflat[lo:hi], self._clip_slots[i * n:(i + 1) * n])
+        ops.clip_coef(self._clip_slots, 1.0 / self.world_size, float('inf') if self.max_grad_norm is None else self.max_grad_norm,
+                      self._clip_rec, self._skipped)
+
     def _adam(self, step, hyper=None, ranges=None):
         model, ops = self.model, self.model.ops
         for lo, hi in (self._train_ranges if ranges is None else ranges):
+            if self._clip:
+                ops.adam_clipped(model._flat[lo:hi], model._gflat[lo:hi], self.m[lo:hi], self.v[lo:hi], self.lr, self.betas[0],
+                                 self.betas[1], self.eps, step, 1.0 / self.world_size, hyper=hyper, record=self._clip_rec,
+                                 clip_value=self.clip_grad_value or 0.0)
+                continue
             ops.adam(model._flat[lo:hi], model._gflat[lo:hi], self.m[lo:hi], self.v[lo:hi], self.lr, self.betas[0],
                      self.betas[1], self.eps, step, 1.0 / self.world_size, hyper=hyper)
 
@@ -1188,7 +1243,15 @@ class Trainer(object):
         for w in self._works:
             w.wait()
         self._join_comm()
-        self._adam(self.t)
+        if not self._clip:
+            self._adam(self.t)
+            return loss
+        # a clipping trainer's eager step (a batch of another shape than the captured one, or use_graphs=False) reads the bias
+        # corrections from device words the host computed, as the captured step does: one arithmetic for both, so the two forms
+        # of a step give the same bits (dlsg_adam's own float powf / sqrtf differ from them in the last place)
+        hyper = _h2d(self._hyper(), torch.float32, captions.device)
+        self._clip_grads()
+        self._adam(self.t, hyper=hyper)
         return loss
 
     # ------------------------------------------------------------------ hipGraph path
@@ -1266,6 +1329,7 @@ class Trainer(object):
                     # side stream's collectives; with host-issued collectives it follows their waits
                     self._reduce_guard()
                     self._join_comm()
+                    self._clip_grads()
                     self._adam(1, hyper=st['hyper'])
                 cur[0].capture_end()
                 graphs.append((cur[0], None))
@@ -1406,6 +1470,7 @@ class Trainer(object):
                 w.wait()
             # same arithmetic as the captured Adam launch (bias corrections read from the device word the host just wrote),
             # so a segmented step is bit-identical to the single-graph step
+            self._clip_grads()
             self._adam(self.t, hyper=st['hyper'])
         # the loss lives in the graphs' static memory: hand out a copy, so losses kept across steps do not alias
         return self._loss.clone()

@@ -74,7 +74,7 @@ class SCSTTrainer(object):
     @torch.no_grad()
     def step(self, frames, regions, vids):
         """One SCST step on clips `vids` (B ids of the reward's corpus).  Returns {'loss' (device scalar), 'reward_mean',
-        'baseline_mean', 'mean_len'}.
+        'baseline_mean', 'mean_len'}, and 'grad_norm' (0-d device tensor) when the Trainer clips (`max_grad_norm=` / `clip_grad_value=`).
         Host reward (an object with `scores` only, e.g. `scoring.CiderD`): the one host synchronisation is the copy of the sampled
         words to the host, where the reward, the baseline and the advantages are computed; the three statistics are floats.
         Device reward (an object with `scores_device`, e.g. `scoring.DeviceCiderD`): the sampled rows -- and for the greedy
@@ -103,8 +103,15 @@ class SCSTTrainer(object):
         adv = (r - b).astype(np.float32)
         fx, rx = self._expanded_inputs(frames, regions)
         loss = self.trainer.step(fx, rx, ids, lens, 1.0, max_len=L, seed=seed, seq_weights=_h2d(adv, torch.float32, ids.device))
-        return {'loss': loss, 'reward_mean': float(r.mean()), 'baseline_mean': float(b.mean()),
-                'mean_len': float(host[:, L].double().mean())}
+        return self._with_grad_norm({'loss': loss, 'reward_mean': float(r.mean()), 'baseline_mean': float(b.mean()),
+                                     'mean_len': float(host[:, L].double().mean())})
+
+    def _with_grad_norm(self, stats):
+        """with gradient clipping on (Trainer's max_grad_norm / clip_grad_value): 'grad_norm', a 0-d device tensor, joins the stats"""
+        norm = self.trainer.last_grad_norm
+        if norm is not None:
+            stats['grad_norm'] = norm.clone()
+        return stats
 
     def _device_reward_step(self, frames, regions, vids, seed, ids, lens, greedy):
         model, reward = self.model, self.reward
@@ -120,4 +127,4 @@ class SCSTTrainer(object):
         model.ops.scst_advantage(r, lens, g, n, adv, stats)
         fx, rx = self._expanded_inputs(frames, regions)
         loss = self.trainer.step(fx, rx, ids, lens, 1.0, max_len=L, seed=seed, seq_weights=adv)
-        return {'loss': loss, 'reward_mean': stats[0], 'baseline_mean': stats[1], 'mean_len': stats[2]}
+        return self._with_grad_norm({'loss': loss, 'reward_mean': stats[0], 'baseline_mean': stats[1], 'mean_len': stats[2]})

@@ -744,6 +744,33 @@ int dlsg_adam(float* p, const float* g, float* m, float* v, int64_t n, float lr,
  * replayed with a new step count.  guard (optional, device): the launch updates nothing when *guard != 0 -- the `err` word of the
  * persistent recurrent kernels (dlsg_bilstm_*, dlsg_lstm_seq): a step whose hand-off timed out has invalid gradients. */
 
+/* ---------------------------------------------------------------- gradient clipping by global norm, on the device
+ * torch.nn.utils.clip_grad_norm_ / clip_grad_value_ between the backward and the update, as three launches that can be captured
+ * with the step (no host read of the norm): dlsg_grad_sumsq per trainable range of the gradient arena, dlsg_clip_coef once,
+ * dlsg_adam_clipped per range.  No atomics anywhere: the same gradient bits give the same record bits on every launch, every
+ * graph replay and every rank of a data-parallel job (which reduce the same all-reduced sum), so no collective is needed.
+ *
+ * dlsg_grad_sumsq: slots[w] = workgroup w's share of sum g[i]^2 over g[0..n), w < DLSG_GRAD_SUMSQ_SLOTS; every element is squared
+ *   and accumulated in float64 (the square of a float is exact there), each workgroup reduces in a fixed order, a workgroup
+ *   without elements writes 0 -- the caller never zeroes the slots.  The grid does not depend on n.  g may start at any float
+ *   (16-byte loads over the aligned body, scalar head and tail); one launch per range, each into its own block of slots.
+ * dlsg_clip_coef: one workgroup sums slots[0..count) in a fixed order and writes record[0..DLSG_CLIP_RECORD_FLOATS):
+ *   [DLSG_CLIP_NORM]      (float) (grad_scale * sqrt(sum)): the norm of the averaged gradient
+ *   [DLSG_CLIP_COEF]      min(1, max_norm / (norm + 1e-6))  (clip_grad_norm_'s formula); max_norm = +inf: 1, nothing is clipped
+ *   [DLSG_CLIP_NONFINITE] 1.0 when the norm is inf or NaN, else 0.0; then coef = 0 and *skipped (optional, device) goes up by one.
+ * dlsg_adam_clipped: dlsg_adam on gi = (g * grad_scale) * record[DLSG_CLIP_COEF], then clamped to +-clip_value when clip_value > 0.
+ *   record (optional, device): with record[DLSG_CLIP_NONFINITE] != 0 the launch updates nothing, exactly as under `guard`.
+ *   A record with coef 1.0 (or none) and clip_value 0 gives dlsg_adam's bits. */
+#define DLSG_GRAD_SUMSQ_SLOTS 1024
+#define DLSG_CLIP_NORM 0
+#define DLSG_CLIP_COEF 1
+#define DLSG_CLIP_NONFINITE 2
+#define DLSG_CLIP_RECORD_FLOATS 4
+int dlsg_grad_sumsq(const float* g, int64_t n, double* slots, void* stream);
+int dlsg_clip_coef(const double* slots, int count, float grad_scale, float max_norm, float* record, int64_t* skipped, void* stream);
+int dlsg_adam_clipped(float* p, const float* g, float* m, float* v, int64_t n, float lr, float b1, float b2, float eps, int step,
+                      float grad_scale, const float* hyper, const int32_t* guard, const float* record, float clip_value, void* stream);
+
 
 /* ---------------------------------------------------------------- persistent BiLSTM recurrence (csrc/bilstm.hip)
  * Replaces the time loop of `nn.LSTM(H, H, bidirectional=True, batch_first=True)` in EncoderVisual (models/layer.py:26,52)
