@@ -424,7 +424,7 @@ class StreamedFeatures(_Features):
                     df, dr = tf.to(self.device, non_blocking=True), tr.to(self.device, non_blocking=True)
                     ev = torch.cuda.Event()
                     ev.record(side)
-                torch.cuda.current_stream().wait_stream(side)
+                torch.cuda.current_stream().wait_event(ev)
                 df.record_stream(torch.cuda.current_stream()); dr.record_stream(torch.cuda.current_stream())
                 if pending is not None:                     # the previous batch's copy has certainly been issued before this one
                     pending[1].synchronize()

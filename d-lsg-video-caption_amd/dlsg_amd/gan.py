@@ -24,7 +24,8 @@ import torch
 import torch.nn as nn
 
 from .critic import CriticEngine, C as WIDTH, PW as PSL_WIDTH
-from .model import _ArenaModule, _ALIGN, _capture_stream, _copy_h2d
+from .graphs import capture, capture_segments, stage
+from .model import _ArenaModule, _ALIGN, _copy_h2d
 from .modules import LatentPSL, SelfAttention
 
 
@@ -338,22 +339,18 @@ class GanTrainer(object):
 
     def _capture_critic(self, st):
         eng = self.D.engine
-        side = _capture_stream(st['logits'].device)
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
-            eng.proposals(st['ws'], st['obj'], st['mot'], st['alpha'], st['smask'])       # warm-up on the capture stream
+
+        def warmup():
+            eng.proposals(st['ws'], st['obj'], st['mot'], st['alpha'], st['smask'])
             eng.update_gradients(st['ws'], st['captions'], st['logits'], st['eps'], st['seed'])
-            side.synchronize()
-            pool = torch.cuda.graph_pool_handle()
-            gP, gA, gB = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
-            with torch.cuda.graph(gP, pool=pool, stream=side, capture_error_mode='thread_local'):
-                eng.proposals(st['ws'], st['obj'], st['mot'], st['alpha'], st['smask'])
-            with torch.cuda.graph(gA, pool=pool, stream=side, capture_error_mode='thread_local'):
-                st['stats'] = eng.update_gradients(st['ws'], st['captions'], st['logits'], st['eps'], st['seed'])
-            with torch.cuda.graph(gB, pool=pool, stream=side, capture_error_mode='thread_local'):
-                self._adam_D(hyper=st['hyper'])
-        torch.cuda.current_stream().wait_stream(side)
-        st['graphs'] = (gP, gA, gB)
+
+        def body(cut):
+            eng.proposals(st['ws'], st['obj'], st['mot'], st['alpha'], st['smask'])
+            cut('proposals')
+            st['stats'] = eng.update_gradients(st['ws'], st['captions'], st['logits'], st['eps'], st['seed'])
+            cut('gradients')
+            self._adam_D(hyper=st['hyper'])
+        st['graphs'] = tuple(g for g, _ in capture_segments(st['logits'].device, body, warmup)[0])
 
     def train_disc(self, captions, logits_tm, obj, mot, smask, alpha, alias=False, as_tensor=False):
         """run_gun.py:339-381: num_D critic updates.  logits_tm (L,B,V): the generator's logits, time-major as its decoder writes
@@ -369,7 +366,7 @@ class GanTrainer(object):
             st = self._critic_static(captions, logits_tm, obj, mot, smask, alpha, alias)
             for k_, src in (('captions', captions), ('smask', smask)) + \
                     (() if alias else (('logits', logits_tm), ('obj', obj), ('mot', mot), ('alpha', alpha))):
-                st[k_].copy_(src, non_blocking=True)
+                stage(st[k_], src)
             if st['graphs'] is None:
                 self._capture_critic(st)
             st['graphs'][0].replay()
@@ -434,20 +431,11 @@ class GanTrainer(object):
         st['smask'].copy_(smask, non_blocking=True)
         _copy_h2d(st['seed'], [eng.next_seed()])
         if st['graph'] is None:
-            side = _capture_stream(dev)
-            side.wait_stream(torch.cuda.current_stream())
-
             def run():
                 eng.proposals(st['ws'], st['obj'], st['mot'], st['alpha'], st['smask'])
                 st['score'] = eng.score(st['ws'], st['logits'], st['seed'])
                 st['dhf'] = eng.score_backward(st['ws'], st['logits'], st['ws'].d_outG, st['seed'], None, params=False)
-            with torch.cuda.stream(side):
-                run()
-                side.synchronize()
-                st['graph'] = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(st['graph'], stream=side, capture_error_mode='thread_local'):
-                    run()
-            torch.cuda.current_stream().wait_stream(side)
+            st['graph'] = capture(dev, run)[0]
         st['graph'].replay()
 
         def finish(scale):

@@ -1,0 +1,173 @@
+"""hipGraph capture and replay, in one place: entering and leaving the process's capture stream, the eager warm-up, capturing one
+graph or a chain of segments, dropping a capture whose body raised, staging inputs into the static buffers a graph reads --
+and the captured forms of inference built on it (GreedyGraph, SampleGraph, BeamGraph, NBestBeamGraph).  The Trainer
+(model.py), the GanTrainer (gan.py) and the SCSTTrainer (scst.py) capture through `capture` / `capture_segments`."""
+import torch
+
+
+def stage(dst, src):
+    """src into the static buffer `dst` a captured graph reads -- unless the caller filled that very buffer in place (a producer
+    that writes a graph's inputs directly, `Trainer.static_inputs`): then there is nothing to copy"""
+    if src.data_ptr() != dst.data_ptr():
+        dst.copy_(src, non_blocking=True)
+
+
+def capture_segments(dev, body, warmup):
+    """Capture `body(cut)` on the device's capture stream as a chain of graphs that share one memory pool (a tensor allocated in
+    one segment stays valid for the next): `cut(key, between=None)` ends the running segment under `key`, runs `between()` outside
+    any capture and begins the next segment; the last one ends with the body, under the key None.  Returns ([(graph, key), ...] in
+    replay order, the body's return value).
+    `warmup()` runs first, eagerly, on the same stream: it warms the allocator and that stream's stream-K workspace
+    (hip.HipOps._gemm_workspace), which must never be allocated inside a capture, and makes the one-time kernel attribute calls.
+    If the body raises, the capture in progress is ended, the partial graphs are dropped and the exception propagates."""
+    from .hip import HipOps
+    side = HipOps.capture_stream(dev)
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        warmup()
+        side.synchronize()
+        pool, done, cur = torch.cuda.graph_pool_handle(), [], []
+
+        def begin():
+            cur.append(torch.cuda.CUDAGraph())
+            # thread-local capture mode: calls made by other threads (e.g. the RCCL watchdog) cannot invalidate the capture
+            cur[0].capture_begin(pool=pool, capture_error_mode='thread_local')
+
+        def end(key=None):
+            cur[0].capture_end()
+            done.append((cur.pop(), key))
+
+        def cut(key, between=None):
+            end(key)
+            if between is not None:
+                between()
+            begin()
+        try:
+            begin()
+            out = body(cut)
+            end()
+        except BaseException:
+            # leave no stream in capture mode behind: every capture of the process runs on this one, and a later synchronize
+            # would raise on top of the real error
+            if cur:
+                try:
+                    cur[0].capture_end()
+                except Exception:
+                    pass
+            raise
+    torch.cuda.current_stream().wait_stream(side)
+    return done, out
+
+
+def capture(dev, body, warmup=None):
+    """Capture `body()` as one graph (see capture_segments; the warm-up defaults to the body itself).  Returns (graph, the body's
+    return value): what the body returned are static buffers the replays write."""
+    graphs, out = capture_segments(dev, lambda cut: body(), warmup or body)
+    return graphs[0][0], out
+
+
+def expand_rows(x, n):
+    """x.repeat_interleave(n, 0) as one copy (row b*n + i = x[b]): no host synchronisation, so it may be captured"""
+    if n == 1:
+        return x
+    return x.unsqueeze(1).expand(x.shape[0], n, *x.shape[1:]).reshape(x.shape[0] * n, *x.shape[1:])
+
+
+class _InferenceGraph(object):
+    """A no-grad pass of `model` over (frames, regions), captured once for a batch shape and replayed: a subclass says what to
+    run (`_run`, on the static inputs self.frames / self.regions; its return value becomes self.out).  A captured graph holds raw
+    addresses into the model's parameter arena and the model's train / eval mode at construction: `valid_for` tells whether it
+    still fits, and a replay after the model re-packed its parameters (load_encoder, load_state_dict into a copy, .to()) raises
+    instead of computing from the old arena."""
+
+    def __init__(self, model, frames, regions):
+        model.flatten_parameters_()
+        self.model, self.arena, self.training = model, model._flat, model.training
+        self.frames, self.regions = frames.clone(), regions.clone()
+        with torch.no_grad():
+            self.graph, self.out = capture(frames.device, self._run)
+
+    def valid_for(self, frames, regions):
+        """this graph may be replayed on these inputs: same shapes, the arena it was captured on, the same train / eval mode"""
+        return self.frames.shape == frames.shape and self.regions.shape == regions.shape and \
+            self.arena is self.model._flat and self.training == self.model.training
+
+    def _stage(self, frames, regions):
+        if self.arena is not self.model._flat:
+            raise RuntimeError('%s: the model re-packed its parameter arena after this graph was captured (flatten_parameters_ after '
+                               'load_encoder / load_state_dict / .to()); the graph holds addresses into the old arena -- build a '
+                               'new one' % type(self).__name__)
+        stage(self.frames, frames)
+        stage(self.regions, regions)
+
+    @torch.no_grad()
+    def __call__(self, frames, regions):
+        self._stage(frames, regions)
+        self.graph.replay()
+        return self.out
+
+
+class GreedyGraph(_InferenceGraph):
+    """hipGraph-captured greedy inference (BASELINE configs[4]: 'hipGraph-captured decode step'): encoder + the 26
+    decode steps (argmax and embedding gather stay on device) are captured once for a batch shape and replayed; the
+    ids are identical to the eager `model(frames, regions, None)` path with beam_size 1."""
+
+    def _run(self):
+        L = self.model.decoder.max_words
+        sv = {}
+        self.model._engine_forward(self.frames, self.regions, None, L, [False] * L, False, 0, sv)
+        return sv['dec']['IDS'][1:].t().contiguous()
+
+
+class SampleGraph(_InferenceGraph):
+    """hipGraph-captured `CapGnnModel.sample`: the n-fold expansion of the batch, the encoder on B*n rows and the sampled decode
+    steps, captured once for a batch shape (and for the model's train / eval mode at construction) and replayed.  The seed is
+    read from a device word, so every replay draws fresh samples; a replay with seed s gives the bits of
+    `model.sample(frames, regions, n, temperature, seed=s)`.  Outputs are static buffers, valid until the next replay."""
+
+    def __init__(self, model, frames, regions, n=1, temperature=1.0):
+        self.n, self.temperature = n, temperature
+        self.seed = torch.zeros(1, dtype=torch.int64, device=frames.device)
+        super().__init__(model, frames, regions)
+
+    def _run(self):
+        n = self.n
+        s = self.model._sample_forward(expand_rows(self.frames, n), expand_rows(self.regions, n), self.model.decoder.max_words,
+                                       self.training, self.seed, self.temperature, {})
+        return s['IDS'][1:].t().contiguous(), s['LOGP'].t().contiguous(), s['LENS']
+
+    @torch.no_grad()
+    def __call__(self, frames, regions, seed):
+        from .hip import copy_to_device
+        self._stage(frames, regions)
+        copy_to_device(self.seed, [int(seed)])
+        self.graph.replay()
+        return self.out
+
+
+class BeamGraph(_InferenceGraph):
+    """hipGraph-captured beam search (BASELINE configs[4]): encoder + all max_words beam steps (decode step, `beam_select`,
+    state reorder) captured once for a batch shape; a replay has no host synchronisation, the early stop of the reference is
+    applied afterwards (`beam.beam_finish`).  Ids are identical to `model(frames, regions, None)` with the same beam size."""
+
+    def _run(self):
+        from .beam import beam_device
+        return beam_device(self.model, self.frames, self.regions, early_exit=False)
+
+    @torch.no_grad()
+    def __call__(self, frames, regions):
+        from .beam import beam_finish
+        return beam_finish(self.model, *super().__call__(frames, regions))
+
+
+class NBestBeamGraph(_InferenceGraph):
+    """hipGraph-captured `model.beam_search(frames, regions, **options)` for one batch shape: encoder, all max_words steps with
+    the beams' token history, and the ranking.  A replay returns (ids, scores, lens) -- static buffers, valid until the next
+    replay -- and synchronises nothing (call `model.ops.check_persistent()` where the ids are read back)."""
+
+    def __init__(self, model, frames, regions, **options):
+        self.options = options
+        super().__init__(model, frames, regions)
+
+    def _run(self):
+        return self.model.beam_search(self.frames, self.regions, **self.options)

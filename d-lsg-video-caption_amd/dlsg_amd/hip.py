@@ -178,9 +178,10 @@ class HipOps(object):
 
     @classmethod
     def capture_stream(cls, dev):
-        """the side stream every hipGraph capture of this process runs on (Trainer, GanTrainer, GreedyGraph, BeamGraph): captures
-        are sequential and replays go to the caller's current stream, so one stream -- and one stream-K workspace, warmed by the
-        eager pass each capture site runs first -- serves them all"""
+        """the side stream every hipGraph capture of this process runs on -- graphs.capture_segments takes it for all seven capture
+        sites: the Trainer's step, the GanTrainer's critic update and generator term, GreedyGraph, SampleGraph, BeamGraph and
+        NBestBeamGraph.  Captures are sequential and replays go to the caller's current stream, so one stream -- and one stream-K
+        workspace, warmed by the eager pass that precedes every capture -- serves them all"""
         dev = torch.device(dev)
         idx = dev.index if dev.index is not None else torch.cuda.current_device()
         st = cls._capture_streams.get(idx)

@@ -16,6 +16,7 @@ import torch.nn as nn
 
 from . import abi
 from . import engine as E
+from .graphs import capture_segments, stage, expand_rows, GreedyGraph, SampleGraph, BeamGraph, NBestBeamGraph  # noqa: F401
 from .modules import CapGnnEncoder, Decoder, EncoderVisual
 
 _ALIGN = 64  # floats: every parameter starts 256-B aligned inside the arena (vector loads need 16 B)
@@ -579,158 +580,6 @@ def _copy_h2d(dst, values):
     copy_to_device(dst, values)
 
 
-def _capture_stream(dev):
-    """the one side stream per device all hipGraph captures of this process run on (hip.HipOps.capture_stream)"""
-    from .hip import HipOps
-    return HipOps.capture_stream(dev)
-
-
-class GreedyGraph(object):
-    """hipGraph-captured greedy inference (BASELINE configs[4]: 'hipGraph-captured decode step'): encoder + the 26
-    decode steps (argmax and embedding gather stay on device) are captured once for a batch shape and replayed; the
-    ids are identical to the eager `model(frames, regions, None)` path with beam_size 1."""
-
-    def __init__(self, model, frames, regions):
-        self.model = model
-        model.flatten_parameters_()
-        dev = frames.device
-        self.frames, self.regions = frames.clone(), regions.clone()
-        L = model.decoder.max_words
-        side = _capture_stream(dev)
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side), torch.no_grad():
-            model._engine_forward(self.frames, self.regions, None, L, [False] * L, False, 0, {})     # warm-up
-            side.synchronize()
-            self.graph = torch.cuda.CUDAGraph()
-            self.graph.capture_begin(capture_error_mode='thread_local')
-            sv = {}
-            model._engine_forward(self.frames, self.regions, None, L, [False] * L, False, 0, sv)
-            self.ids = sv['dec']['IDS'][1:].t().contiguous()
-            self.graph.capture_end()
-        torch.cuda.current_stream().wait_stream(side)
-
-    @torch.no_grad()
-    def __call__(self, frames, regions):
-        if frames.data_ptr() != self.frames.data_ptr():
-            self.frames.copy_(frames, non_blocking=True)
-        if regions.data_ptr() != self.regions.data_ptr():
-            self.regions.copy_(regions, non_blocking=True)
-        self.graph.replay()
-        return self.ids
-
-
-def expand_rows(x, n):
-    """x.repeat_interleave(n, 0) as one copy (row b*n + i = x[b]): no host synchronisation, so it may be captured"""
-    if n == 1:
-        return x
-    return x.unsqueeze(1).expand(x.shape[0], n, *x.shape[1:]).reshape(x.shape[0] * n, *x.shape[1:])
-
-
-class SampleGraph(object):
-    """hipGraph-captured `CapGnnModel.sample`: the n-fold expansion of the batch, the encoder on B*n rows and the sampled decode
-    steps, captured once for a batch shape (and for the model's train / eval mode at construction) and replayed.  The seed is
-    read from a device word, so every replay draws fresh samples; a replay with seed s gives the bits of
-    `model.sample(frames, regions, n, temperature, seed=s)`.  Outputs are static buffers, valid until the next replay."""
-
-    def __init__(self, model, frames, regions, n=1, temperature=1.0):
-        self.model, self.n, self.temperature = model, n, temperature
-        model.flatten_parameters_()
-        self.arena = model._flat
-        self.training = model.training
-        dev = frames.device
-        self.frames, self.regions = frames.clone(), regions.clone()
-        self.seed = torch.zeros(1, dtype=torch.int64, device=dev)
-        L = model.decoder.max_words
-        side = _capture_stream(dev)
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side), torch.no_grad():
-            def run():
-                s = model._sample_forward(expand_rows(self.frames, n), expand_rows(self.regions, n), L, self.training, self.seed,
-                                          temperature, {})
-                return s['IDS'][1:].t().contiguous(), s['LOGP'].t().contiguous(), s['LENS']
-            run()                                                                                      # warm-up
-            side.synchronize()
-            self.graph = torch.cuda.CUDAGraph()
-            self.graph.capture_begin(capture_error_mode='thread_local')
-            self.ids, self.logp, self.lens = run()
-            self.graph.capture_end()
-        torch.cuda.current_stream().wait_stream(side)
-
-    @torch.no_grad()
-    def __call__(self, frames, regions, seed):
-        if frames.data_ptr() != self.frames.data_ptr():
-            self.frames.copy_(frames, non_blocking=True)
-        if regions.data_ptr() != self.regions.data_ptr():
-            self.regions.copy_(regions, non_blocking=True)
-        _copy_h2d(self.seed, [int(seed)])
-        self.graph.replay()
-        return self.ids, self.logp, self.lens
-
-
-class BeamGraph(object):
-    """hipGraph-captured beam search (BASELINE configs[4]): encoder + all max_words beam steps (decode step, `beam_select`,
-    state reorder) captured once for a batch shape; a replay has no host synchronisation, the early stop of the reference is
-    applied afterwards (`beam.beam_finish`).  Ids are identical to `model(frames, regions, None)` with the same beam size."""
-
-    def __init__(self, model, frames, regions):
-        from .beam import beam_device
-        self.model = model
-        model.flatten_parameters_()
-        dev = frames.device
-        self.frames, self.regions = frames.clone(), regions.clone()
-        side = _capture_stream(dev)
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side), torch.no_grad():
-            beam_device(model, self.frames, self.regions, early_exit=False)                       # warm-up
-            side.synchronize()
-            self.graph = torch.cuda.CUDAGraph()
-            self.graph.capture_begin(capture_error_mode='thread_local')
-            self.state = beam_device(model, self.frames, self.regions, early_exit=False)
-            self.graph.capture_end()
-        torch.cuda.current_stream().wait_stream(side)
-
-    @torch.no_grad()
-    def __call__(self, frames, regions):
-        from .beam import beam_finish
-        if frames.data_ptr() != self.frames.data_ptr():
-            self.frames.copy_(frames, non_blocking=True)
-        if regions.data_ptr() != self.regions.data_ptr():
-            self.regions.copy_(regions, non_blocking=True)
-        self.graph.replay()
-        return beam_finish(self.model, *self.state)
-
-
-class NBestBeamGraph(object):
-    """hipGraph-captured `model.beam_search(frames, regions, **options)` for one batch shape: encoder, all max_words steps with
-    the beams' token history, and the ranking.  A replay returns (ids, scores, lens) -- static buffers, valid until the next
-    replay -- and synchronises nothing (call `model.ops.check_persistent()` where the ids are read back)."""
-
-    def __init__(self, model, frames, regions, **options):
-        self.model = model
-        model.flatten_parameters_()
-        dev = frames.device
-        self.frames, self.regions = frames.clone(), regions.clone()
-        side = _capture_stream(dev)
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side), torch.no_grad():
-            model.beam_search(self.frames, self.regions, **options)                              # warm-up
-            side.synchronize()
-            self.graph = torch.cuda.CUDAGraph()
-            self.graph.capture_begin(capture_error_mode='thread_local')
-            self.out = model.beam_search(self.frames, self.regions, **options)
-            self.graph.capture_end()
-        torch.cuda.current_stream().wait_stream(side)
-
-    @torch.no_grad()
-    def __call__(self, frames, regions):
-        if frames.data_ptr() != self.frames.data_ptr():
-            self.frames.copy_(frames, non_blocking=True)
-        if regions.data_ptr() != self.regions.data_ptr():
-            self.regions.copy_(regions, non_blocking=True)
-        self.graph.replay()
-        return self.out
-
-
 # ================================================================================================ fast training path
 def ss_epsilon(epoch, ss_factor=20):
     """scheduled-sampling probability, run_gun.py:136"""
@@ -1031,7 +880,9 @@ class Trainer(object):
         dev = self.model._flat.device
         side = self._side_stream()
         t = torch.full((4096,), float(rank), dtype=torch.float32, device=dev)
-        side.wait_stream(torch.cuda.current_stream())
+        ev = torch.cuda.Event()
+        ev.record()
+        side.wait_event(ev)
         self._rccl.allreduce([t], side)
         side.synchronize()
         want = self.world_size * (self.world_size - 1) / 2.0
@@ -1271,16 +1122,13 @@ class Trainer(object):
         st['coins'].fill_(1)
         st['seed'] = st['scalars'][Lp:Lp + 2].view(torch.int64)
         st['hyper'] = st['scalars'][Lp + 2:Lp + 4].view(torch.float32)
-        side = _capture_stream(dev)
-        side.wait_stream(torch.cuda.current_stream())
-        graphs = []
         mode = self._comm_mode()
         # host-issued collectives need the capture cut at every bucket; RCCL's own launches are captured with the step
         cuts = mode == 'torch' or self.force_graph_cuts
         if mode == 'rccl':
             self._rccl_comm()              # communicator setup (a collective itself) outside any capture
-        with torch.cuda.stream(side):
-            # eager warm-up on the capture stream (allocator warm, one-time kernel attribute calls)
+
+        def warmup():
             # (with RCCL the warm-up also runs the collectives once: channel buffers are set up before the capture;
             #  nothing is updated: Adam is not part of the schedule)
             self._schedule(st['frames'], st['regions'], st['captions'], st['lens'], None, st['seed'], st['coins'],
@@ -1288,63 +1136,46 @@ class Trainer(object):
             if mode == 'rccl':
                 self._reduce_guard()
             self._join_comm()
-            side.synchronize()
             if self._comm_stream is not None:
                 self._comm_stream.synchronize()
-            pool = torch.cuda.graph_pool_handle()
-            # thread-local capture mode: calls made by other threads (e.g. the RCCL watchdog) cannot invalidate the capture
-            cur = [torch.cuda.CUDAGraph()]
-            cur[0].capture_begin(pool=pool, capture_error_mode='thread_local')
-            try:
-                def hard_cut(key, between=None):
-                    cur[0].capture_end()
-                    graphs.append((cur[0], key))
-                    if between is not None:
-                        between()
-                    cur[0] = torch.cuda.CUDAGraph()
-                    cur[0].capture_begin(pool=pool, capture_error_mode='thread_local')
 
-                def cut(key):
-                    if mode != 'torch':
-                        self._allreduce(key)               # captured: fork to the side stream (collective and / or Adam)
-                        if cuts:
-                            self._join_comm()              # a capture segment must end with its forks joined
-                    if cuts:
-                        hard_cut(key if mode == 'torch' else None)
-
-                def placeholder(logits, sv):
-                    # the graphs end here and resume after the caller's term: what it will read (logits, saved state, the
-                    # loss) lives in the graphs' pool, what it returns is copied into st['extra'] before the next replay
-                    # (allocated BETWEEN the two captures: inside one, its zero fill would be replayed over the copy)
-                    def alloc():
-                        st['extra'] = torch.zeros_like(logits)
-                    hard_cut('hook', alloc)
-                    self._hook_sv = (logits, sv)
-                    return st['extra']
-
-                loss = self._schedule(st['frames'], st['regions'], st['captions'], st['lens'], None, st['seed'], st['coins'], cut,
-                                      placeholder if hook else None, st['weights'])
+        def body(hard_cut):
+            def cut(key):
                 if mode != 'torch':
-                    # no host-issued collective between backward and update: Adam is part of the graph, behind the join of the
-                    # side stream's collectives; with host-issued collectives it follows their waits
-                    self._reduce_guard()
-                    self._join_comm()
-                    self._clip_grads()
-                    self._adam(1, hyper=st['hyper'])
-                cur[0].capture_end()
-                graphs.append((cur[0], None))
-            except BaseException:
-                # leave no stream in capture mode behind (a later synchronize would raise on top of the real error) and
-                # drop the partial graphs
-                try:
-                    cur[0].capture_end()
-                except Exception:
-                    pass
-                graphs.clear()
-                self._graphs = None
-                self._comm_pending = False
-                raise
-        torch.cuda.current_stream().wait_stream(side)
+                    self._allreduce(key)               # captured: fork to the side stream (collective and / or Adam)
+                    if cuts:
+                        self._join_comm()              # a capture segment must end with its forks joined
+                if cuts:
+                    hard_cut(key if mode == 'torch' else None)
+
+            def placeholder(logits, sv):
+                # the graphs end here and resume after the caller's term: what it will read (logits, saved state, the
+                # loss) lives in the graphs' pool, what it returns is copied into st['extra'] before the next replay
+                # (allocated BETWEEN the two captures: inside one, its zero fill would be replayed over the copy)
+                def alloc():
+                    st['extra'] = torch.zeros_like(logits)
+                hard_cut('hook', alloc)
+                self._hook_sv = (logits, sv)
+                return st['extra']
+
+            loss = self._schedule(st['frames'], st['regions'], st['captions'], st['lens'], None, st['seed'], st['coins'], cut,
+                                  placeholder if hook else None, st['weights'])
+            if mode != 'torch':
+                # no host-issued collective between backward and update: Adam is part of the graph, behind the join of the
+                # side stream's collectives; with host-issued collectives it follows their waits
+                self._reduce_guard()
+                self._join_comm()
+                self._clip_grads()
+                self._adam(1, hyper=st['hyper'])
+            return loss
+
+        try:
+            graphs, loss = capture_segments(dev, body, warmup)
+        except BaseException:
+            # (the capture is ended and its partial graphs are dropped by now: what is left is this trainer's own state)
+            self._graphs = None
+            self._comm_pending = False
+            raise
         self._graphs, self._loss = graphs, loss
         self._adam_in_graph = mode != 'torch'
 
@@ -1382,8 +1213,7 @@ class Trainer(object):
         coins = model._draw_coins(captions.shape[1], False, tf_ratio)
         seed = model.next_seed()
         for k, src in (('frames', frames), ('regions', regions), ('captions', captions)):
-            if src.data_ptr() != st[k].data_ptr():
-                st[k].copy_(src, non_blocking=True)
+            stage(st[k], src)
         self._send_scalars(coins, seed, None)
         self._graphs[0][0].replay()
         logits_tm, sv = self._hook_sv
@@ -1449,8 +1279,7 @@ class Trainer(object):
             return self._eager_step(frames, regions, captions, cap_lens, coins, seed, counted=True, extra_dlogits=extra_dlogits,
                                     seq_weights=seq_weights)
         for k, src in (('frames', frames), ('regions', regions), ('captions', captions), ('lens', cap_lens)):
-            if src.data_ptr() != st[k].data_ptr():
-                st[k].copy_(src, non_blocking=True)
+            stage(st[k], src)
         if weighted:
             st['weights'].copy_(seq_weights, non_blocking=True)
         self._send_scalars(coins, seed, self._hyper())

@@ -11,7 +11,8 @@ on-policy up to the tiling of the vocabulary product.
 import numpy as np
 import torch
 
-from .model import Trainer, GreedyGraph, SampleGraph, expand_rows, _h2d
+from .graphs import GreedyGraph, SampleGraph, expand_rows
+from .model import Trainer, _h2d
 
 
 class SCSTTrainer(object):
@@ -33,15 +34,14 @@ class SCSTTrainer(object):
         self._sampler = self._greedy = None
 
     def _graph_ok(self, g, frames, regions):
-        return g is not None and g.frames.shape == frames.shape and g.regions.shape == regions.shape and \
-            g.arena is self.model._flat
+        return g is not None and g.valid_for(frames, regions)
 
     def _sample(self, frames, regions, seed):
         model = self.model
         if not self.trainer.use_graphs:
             return model.sample(frames, regions, n=self.n, temperature=self.temperature, seed=seed)
         model.flatten_parameters_()
-        if not self._graph_ok(self._sampler, frames, regions) or self._sampler.training != model.training:
+        if not self._graph_ok(self._sampler, frames, regions):
             self._sampler = SampleGraph(model, frames, regions, self.n, self.temperature)
         return self._sampler(frames, regions, seed)
 
@@ -52,7 +52,6 @@ class SCSTTrainer(object):
         if self.trainer.use_graphs:
             if not self._graph_ok(self._greedy, frames, regions):
                 self._greedy = GreedyGraph(model, frames, regions)
-                self._greedy.arena = model._flat
             return self._greedy(frames, regions)
         L = model.decoder.max_words
         sv = {}
