@@ -1,6 +1,8 @@
 // Row-wise / pointwise kernels of the D-LSG hot path (gfx950): tanh+LayerNorm(+PE)(+dropout) forward/backward,
 // strided softmax, LSTM cell pointwise, embedding gather/scatter, argmax, ragged cross entropy, Adam.
 // All are HBM/L2-bound streaming kernels: one pass over the row held in registers, float4 where aligned.
+#include <type_traits>
+
 #include "common.hpp"
 #include "dlsg.h"
 
@@ -472,6 +474,53 @@ __global__ void mean_rows_bwd_kernel(const float* __restrict__ dout, int64_t ldd
         float* d = dx + ((int64_t)b * P + p) * H + h;
         *d = accum ? *d + g : g;
     }
+}
+
+// y[b*n + i, :] = x[b, :], i < n: the encoder's proposals of B clips fanned out to the B*n caption rows the decoder runs on.
+// A workgroup owns one 256-wide piece of one clip row, reads it once and writes it n times (16-byte accesses when VEC).
+template <bool VEC>
+__global__ __launch_bounds__(256) void rows_repeat_kernel(const float* __restrict__ x, float* __restrict__ y, int n, int64_t row,
+                                                          int pieces) {
+    const int64_t b = blockIdx.x / pieces;
+    const int piece = blockIdx.x - (int)b * pieces;
+    if constexpr (VEC) {
+        const int64_t row4 = row >> 2;
+        const int64_t j = (int64_t)piece * 256 + threadIdx.x;
+        if (j >= row4) return;
+        const f32x4 v = reinterpret_cast<const f32x4*>(x + b * row)[j];
+        for (int i = 0; i < n; ++i) reinterpret_cast<f32x4*>(y + (b * n + i) * row)[j] = v;
+    } else {
+        const int64_t j = (int64_t)piece * 256 + threadIdx.x;
+        if (j >= row) return;
+        const float v = x[b * row + j];
+        for (int i = 0; i < n; ++i) y[(b * n + i) * row + j] = v;
+    }
+}
+
+// dx[b, p, h] (+)= sum_{i < n} (dmem[b*n + i, p, h] + dg[b*n + i, h] / P): the gradients of a clip's n caption rows folded back
+// onto the clip, with the backward of the proposals' mean (mean_rows_bwd) in the same pass.  One thread per output element (per
+// four when VEC), the n rows added in the order i = 0 .. n-1: no atomics, the same bits on every launch.
+template <bool VEC>
+__global__ __launch_bounds__(256) void clip_fold_kernel(const float* __restrict__ dmem, const float* __restrict__ dg, int64_t lddg,
+                                                        float* __restrict__ dx, int64_t total, int n, int P, int H, int accum) {
+    constexpr int W = VEC ? 4 : 1;
+    typedef typename std::conditional<VEC, f32x4, float>::type vec_t;
+    const int64_t e = ((int64_t)blockIdx.x * 256 + threadIdx.x) * W;      // first output element of this thread
+    if (e >= total) return;
+    const int64_t PH = (int64_t)P * H;
+    const int64_t b = e / PH, ph = e - b * PH;
+    const int h = (int)(ph % H);
+    const float fP = (float)P;
+    const float* m = dmem + b * n * PH + ph;
+    const float* g = dg ? dg + b * n * lddg + h : nullptr;
+    vec_t s;
+    for (int i = 0; i < n; ++i) {
+        vec_t t = *reinterpret_cast<const vec_t*>(m + i * PH);
+        if (g) t += *reinterpret_cast<const vec_t*>(g + i * lddg) / fP;
+        s = i ? s + t : t;
+    }
+    vec_t* d = reinterpret_cast<vec_t*>(dx + e);
+    *d = accum ? *d + s : s;
 }
 
 __global__ void embed_fwd_kernel(const float* __restrict__ E, const int64_t* __restrict__ ids, float* __restrict__ out,
@@ -1367,6 +1416,33 @@ extern "C" int dlsg_mean_rows_fwd(const float* x, float* out, int64_t ldo, int B
 extern "C" int dlsg_mean_rows_bwd(const float* dout, int64_t lddo, float* dx, int B, int P, int H, int accum, void* stream) {
     if (B == 0) return DLSG_OK;
     hipLaunchKernelGGL(mean_rows_bwd_kernel, dim3((H + 255) / 256, B), dim3(256), 0, ST(stream), dout, lddo, dx, P, H, accum);
+    DLSG_CHECK_LAUNCH();
+    return DLSG_OK;
+}
+extern "C" int dlsg_rows_repeat(const float* x, float* y, int B, int n, int64_t row, void* stream) {
+    if (B < 0 || n < 1 || row < 0) return DLSG_EINVAL;
+    if (B == 0 || row == 0) return DLSG_OK;
+    if (!x || !y) return DLSG_EINVAL;
+    const bool vec = row % 4 == 0 && ((uintptr_t)x | (uintptr_t)y) % 16 == 0;
+    const int64_t pieces = ((vec ? row >> 2 : row) + 255) / 256;
+    if (pieces * B > 0x7fffffff) return DLSG_EINVAL;
+    const dim3 grid((unsigned)(pieces * B));
+    if (vec) hipLaunchKernelGGL(rows_repeat_kernel<true>, grid, dim3(256), 0, ST(stream), x, y, n, row, (int)pieces);
+    else hipLaunchKernelGGL(rows_repeat_kernel<false>, grid, dim3(256), 0, ST(stream), x, y, n, row, (int)pieces);
+    DLSG_CHECK_LAUNCH();
+    return DLSG_OK;
+}
+extern "C" int dlsg_clip_fold(const float* dmem, const float* dg, int64_t lddg, float* dx, int B, int n, int P, int H, int accum,
+                              void* stream) {
+    if (B < 0 || n < 1 || P < 1 || H < 1 || (dg && lddg < H)) return DLSG_EINVAL;
+    if (B == 0) return DLSG_OK;
+    if (!dmem || !dx) return DLSG_EINVAL;
+    const int64_t total = (int64_t)B * P * H;
+    const bool vec = H % 4 == 0 && ((uintptr_t)dmem | (uintptr_t)dx) % 16 == 0 && (!dg || (lddg % 4 == 0 && (uintptr_t)dg % 16 == 0));
+    const int64_t blocks = ((vec ? total >> 2 : total) + 255) / 256;
+    if (blocks > 0x7fffffff) return DLSG_EINVAL;
+    if (vec) hipLaunchKernelGGL(clip_fold_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, ST(stream), dmem, dg, lddg, dx, total, n, P, H, accum);
+    else hipLaunchKernelGGL(clip_fold_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, ST(stream), dmem, dg, lddg, dx, total, n, P, H, accum);
     DLSG_CHECK_LAUNCH();
     return DLSG_OK;
 }

@@ -463,9 +463,15 @@ class TrainLoader(object):
     """get_train_loader (utils/data.py:115-131): yields (frames, regions, None, captions, pos_tags, cap_lens, video_ids), the
     tuple run_gun.py:147 unpacks (`spatials` is read by the reference and never used; it is not loaded here).
     frames / regions are device tensors, regions already cut to num_obj; captions / pos_tags are (B, max_words) int64 on the
-    device; cap_lens / video_ids are tuples of ints ordered like the batch rows (video id descending, utils/data.py:90)."""
+    device; cap_lens / video_ids are tuples of ints ordered like the batch rows (video id descending, utils/data.py:90).
 
-    def __init__(self, captions, features, batch_size, world_size=1, rank=0, shuffle=True, seed=None, drop_last=False):
+    captions_per_clip = n > 1: an item is a clip, not a sentence (`Trainer.step(..., seq_per_clip=n)`).  Each epoch permutes the
+    distinct video ids (same seed rules), draws n of each clip's sentences without replacement -- a clip with fewer cycles
+    through its own in the drawn order -- and yields frames / regions of B clips in descending id, captions / pos_tags /
+    cap_lens of B*n rows with clip b's in rows b*n .. b*n+n-1, and B video ids.  batch_size and len() count clips."""
+
+    def __init__(self, captions, features, batch_size, world_size=1, rank=0, shuffle=True, seed=None, drop_last=False,
+                 captions_per_clip=1):
         """seed None (the default, = the reference): one process shuffles as `DataLoader(shuffle=True)` does -- every pass over
         the data draws two words from torch's global generator (the DataLoader iterator's base seed, then the RandomSampler's
         seed: torch/utils/data/dataloader.py, sampler.py), so after the same `torch.manual_seed` (train_debug.py:34-36) the
@@ -475,6 +481,16 @@ class TrainLoader(object):
         self.features, self.batch_size = features, batch_size
         self.world, self.rank, self.shuffle, self.seed, self.drop_last = world_size, rank, shuffle, seed, drop_last
         self.epoch = 0
+        self.n = int(captions_per_clip)
+        if self.n < 1:
+            raise ValueError('captions_per_clip must be >= 1, not %r' % (captions_per_clip,))
+        if self.n > 1:
+            # the clips in ascending id and the rows of each clip's sentences, in corpus order
+            by = {}
+            for i, v in enumerate(self.caps.video_ids):
+                by.setdefault(v, []).append(i)
+            self._clips = sorted(by)
+            self._sentences = [by[v] for v in self._clips]
         if isinstance(features, StreamedFeatures) and world_size > STREAMED_MAX_RANKS_PER_HOST:
             # measured (tools/loader_bench.py): one process streams 3.9-6.6 k clips/s (16-27 GB/s of host reads + H2D), at or
             # below what ONE GPU's train step consumes; N ranks on one host would need N times that out of the same DRAM / PCIe
@@ -487,14 +503,28 @@ class TrainLoader(object):
     def set_epoch(self, epoch):
         self.epoch = epoch
 
+    def _items(self):
+        return len(self.caps) if self.n == 1 else len(self._clips)
+
+    def _draw(self, clip, base):
+        """n sentence rows of clip number `clip`: a permutation of its sentences seeded by (base, video id) -- the draw does not
+        depend on the batch size or on which rank holds the clip -- cut to n, or repeated up to n"""
+        rows = self._sentences[clip]
+        g = torch.Generator()
+        g.manual_seed((base * 1000003 + self._clips[clip]) & 0x7FFFFFFFFFFFFFFF)
+        order = torch.randperm(len(rows), generator=g).tolist()
+        return [rows[order[j % len(order)]] for j in range(self.n)]
+
     def _batches(self):
-        n = len(self.caps)
+        n = self._items()
+        base = (self.seed or 0) + self.epoch
         if self.world > 1:
             idx = distributed_indices(n, self.world, self.rank, self.epoch, True, self.seed or 0)
         elif self.shuffle and self.seed is None:        # single process: DataLoader(shuffle=True) on torch's global generator
             torch.empty((), dtype=torch.int64).random_()                       # the iterator's base seed (drawn, unused here)
             g = torch.Generator()
-            g.manual_seed(int(torch.empty((), dtype=torch.int64).random_().item()))
+            base = int(torch.empty((), dtype=torch.int64).random_().item())
+            g.manual_seed(base)
             idx = torch.randperm(n, generator=g).tolist()
         else:
             idx = distributed_indices(n, 1, 0, self.epoch, self.shuffle, self.seed or 0)
@@ -503,12 +533,16 @@ class TrainLoader(object):
             b = idx[s:s + self.batch_size]
             if self.drop_last and len(b) < self.batch_size:
                 break
+            if self.n > 1:
+                b = sorted(b, reverse=True)             # clip numbers ascend with the video id
+                out.append(([self._clips[c] for c in b], [r for c in b for r in self._draw(c, base)]))
+                continue
             b = sorted(b, key=lambda i: self.caps.video_ids[i], reverse=True)      # stable, like list.sort in the collate
             out.append(b)
         return out
 
     def __len__(self):
-        n = len(self.caps) if self.world <= 1 else int(math.ceil(len(self.caps) / self.world))
+        n = self._items() if self.world <= 1 else int(math.ceil(self._items() / self.world))
         return n // self.batch_size if self.drop_last else int(math.ceil(n / self.batch_size))
 
     def __iter__(self):
@@ -516,10 +550,20 @@ class TrainLoader(object):
         dev = self.features.device
         caps = self.caps
 
-        def pack(b, f, r):
+        def pack(b, f, r, vids=None):
             ib = torch.as_tensor(b, dtype=torch.int64)
             return (f, r, None, _h2d(caps.captions[ib], torch.int64, dev), _h2d(caps.pos_tags[ib], torch.int64, dev),
-                    tuple(caps.lengths[i] for i in b), tuple(caps.video_ids[i] for i in b))
+                    tuple(caps.lengths[i] for i in b), tuple(caps.video_ids[i] for i in b) if vids is None else tuple(vids))
+        if self.n > 1:
+            # a batch is (its clips' video ids, the B*n caption rows)
+            if isinstance(self.features, StreamedFeatures):
+                for (vids, rows), (_, f, r) in zip(batches, self.features.prefetch([v for v, _ in batches])):
+                    yield pack(rows, f, r, vids)
+            else:
+                for vids, rows in batches:
+                    f, r = self.features.batch(vids)
+                    yield pack(rows, f, r, vids)
+            return
         if isinstance(self.features, StreamedFeatures):
             vids = [[caps.video_ids[i] for i in b] for b in batches]
             for b, (_, f, r) in zip(batches, self.features.prefetch(vids)):

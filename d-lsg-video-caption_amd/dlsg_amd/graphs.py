@@ -123,15 +123,21 @@ class SampleGraph(_InferenceGraph):
     """hipGraph-captured `CapGnnModel.sample`: the n-fold expansion of the batch, the encoder on B*n rows and the sampled decode
     steps, captured once for a batch shape (and for the model's train / eval mode at construction) and replayed.  The seed is
     read from a device word, so every replay draws fresh samples; a replay with seed s gives the bits of
-    `model.sample(frames, regions, n, temperature, seed=s)`.  Outputs are static buffers, valid until the next replay."""
+    `model.sample(frames, regions, n, temperature, seed=s)`.  Outputs are static buffers, valid until the next replay.
+    share_encoder=True captures `model.sample(..., share_encoder=True)` instead: the encoder on the B clips, their proposals
+    fanned out in-graph (`rows_repeat`), the sampled decode steps on B*n rows; a replay with seed s gives that call's bits."""
 
-    def __init__(self, model, frames, regions, n=1, temperature=1.0):
-        self.n, self.temperature = n, temperature
+    def __init__(self, model, frames, regions, n=1, temperature=1.0, share_encoder=False):
+        self.n, self.temperature, self.share_encoder = n, temperature, bool(share_encoder)
         self.seed = torch.zeros(1, dtype=torch.int64, device=frames.device)
         super().__init__(model, frames, regions)
 
     def _run(self):
         n = self.n
+        if self.share_encoder:
+            s = self.model._sample_forward(self.frames, self.regions, self.model.decoder.max_words, self.training, self.seed,
+                                           self.temperature, {}, n=n, share_encoder=True)
+            return s['IDS'][1:].t().contiguous(), s['LOGP'].t().contiguous(), s['LENS']
         s = self.model._sample_forward(expand_rows(self.frames, n), expand_rows(self.regions, n), self.model.decoder.max_words,
                                        self.training, self.seed, self.temperature, {})
         return s['IDS'][1:].t().contiguous(), s['LOGP'].t().contiguous(), s['LENS']

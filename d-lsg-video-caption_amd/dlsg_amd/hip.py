@@ -977,6 +977,20 @@ class HipOps(object):
         self._check(self.lib.dlsg_mean_rows_bwd(_p(dout), i64(dout.stride(0)), _p(dx), B, P, H, int(accum), self._stream()),
                     'mean_rows_bwd')
 
+    def rows_repeat(self, x, y, n):
+        """y[b*n + i] = x[b], i < n (x (B, ...) and y (B*n, ...) contiguous float32): x.repeat_interleave(n, 0) as one launch"""
+        B = x.shape[0]
+        assert x.is_contiguous() and y.is_contiguous() and y.shape[0] == B * n and y.shape[1:] == x.shape[1:], (x.shape, y.shape, n)
+        self._check(self.lib.dlsg_rows_repeat(_p(x), _p(y), B, int(n), i64(x.numel() // max(B, 1)), self._stream()), 'rows_repeat')
+
+    def clip_fold(self, dmem, dg, dx, n, accum=False):
+        """dx[b,p,h] (+)= sum_{i<n} (dmem[b*n + i, p, h] + dg[b*n + i, h] / P); dg None, or (B*n, H) with any row stride"""
+        B, P, H = dx.shape
+        assert dmem.is_contiguous() and dx.is_contiguous() and dmem.shape == (B * n, P, H), (dmem.shape, dx.shape, n)
+        assert dg is None or (dg.shape == (B * n, H) and dg.stride(1) == 1), (dg.shape, dg.stride())
+        self._check(self.lib.dlsg_clip_fold(_p(dmem), _p(dg) if dg is not None else None, i64(dg.stride(0) if dg is not None else 0),
+                                            _p(dx), B, int(n), P, H, int(accum), self._stream()), 'clip_fold')
+
     def embed_fwd(self, E, ids, out, p=0.0, seed=0, site=0, row0=0):
         rows, W = out.shape
         sd, sp = _seed(seed)

@@ -165,13 +165,29 @@ class _HipModel(_ArenaModule):
         return (0x5DEECE66D * self.seed_counter + 0xB) & 0xFFFFFFFFFFFF
 
     # ------------------------------------------------------------------ to be provided by subclasses
-    def _engine_forward(self, frames, regions, captions, L, coins, training, seed, sv):
+    def _engine_forward(self, frames, regions, captions, L, coins, training, seed, sv, seq_per_clip=1):
         raise NotImplementedError
 
-    def _engine_backward(self, sv, dlogits_tm, dobj, dmot, dalpha_tm, training, seed):
+    def _engine_backward(self, sv, dlogits_tm, dobj, dmot, dalpha_tm, training, seed, seq_per_clip=1):
         raise NotImplementedError
 
-    def sample(self, visual_feats, region_feats, n=1, temperature=1.0, seed=None):
+    @staticmethod
+    def _check_seq_per_clip(seq_per_clip, clips, captions):
+        """seq_per_clip = n >= 1 captions per clip: `captions` (None at inference) must have n rows per clip"""
+        n = int(seq_per_clip)
+        if n < 1:
+            raise ValueError('seq_per_clip must be >= 1, not %r' % (seq_per_clip,))
+        if captions is not None and captions.shape[0] != n * clips:
+            raise ValueError('%d caption rows for %d clips with seq_per_clip = %d: expected %d (rows b*n .. b*n+n-1 belong to clip b)'
+                             % (captions.shape[0], clips, n, n * clips))
+        return n
+
+    def _only_one_seq_per_clip(self, seq_per_clip):
+        if int(seq_per_clip) != 1:
+            raise ValueError('seq_per_clip > 1 (several captions per clip on one encoder pass) is implemented for CapGnnModel '
+                             'only, not for %s' % type(self).__name__)
+
+    def sample(self, visual_feats, region_feats, n=1, temperature=1.0, seed=None, share_encoder=False):
         raise NotImplementedError('sampled decoding (self-critical training) is implemented for CapGnnModel only')
 
     def beam_search(self, visual_feats, region_feats, beam_size=None, n_best=None, length_penalty=0.0, no_repeat_ngram=0, min_len=0):
@@ -193,11 +209,13 @@ class _HipModel(_ArenaModule):
 
 class _ModelFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, model, frames, regions, captions, L, coins, seed, *params):
+    def forward(ctx, model, frames, regions, captions, L, coins, seed, seq_per_clip, *params):
         sv = {}
         training = model.training
-        outs = model._engine_forward(frames, regions, captions, L, coins, training, seed, sv)
-        ctx.model, ctx.sv, ctx.seed, ctx.training = model, sv, seed, training
+        # (keyword only when set: the default form calls the engine exactly as before)
+        kw = {'seq_per_clip': seq_per_clip} if seq_per_clip != 1 else {}
+        outs = model._engine_forward(frames, regions, captions, L, coins, training, seed, sv, **kw)
+        ctx.model, ctx.sv, ctx.seed, ctx.training, ctx.kw = model, sv, seed, training, kw
         ctx.nparams = len(params)
         return outs
 
@@ -211,18 +229,26 @@ class _ModelFn(torch.autograd.Function):
         if dalpha is not None and dalpha.numel() > 0:
             da_tm = torch.empty(L, Bn, dalpha.shape[-1], dtype=torch.float32, device=dlogits.device)
             ops.permute_tb(dalpha.contiguous(), da_tm)
-        model._engine_backward(ctx.sv, dl_tm, dobj, dmot, da_tm, ctx.training, ctx.seed)
+        model._engine_backward(ctx.sv, dl_tm, dobj, dmot, da_tm, ctx.training, ctx.seed, **ctx.kw)
         G = model.grad_views()
         grads = []
         for name, p in model.named_parameters():
             grads.append(G[name].clone() if (name not in model.unused_parameters and p.requires_grad) else None)
         ctx.sv = None
-        return (None,) * 7 + tuple(grads)
+        return (None,) * 8 + tuple(grads)
 
 
 class CapGnnModel(_HipModel):
     """models/model.py:25-43.  forward(visual_feats, region_feats, caption, max_words=None,
-    teacher_forcing_ratio=1.0) -> (outputs, obj_proposals, motion_proposals, alpha_all)."""
+    teacher_forcing_ratio=1.0, seq_per_clip=1) -> (outputs, obj_proposals, motion_proposals, alpha_all).
+
+    seq_per_clip = n > 1: `caption` holds n captions for each of the B clips (rows b*n .. b*n+n-1 belong to clip b, the layout
+    `sample` returns).  The encoder runs once on the B clips, its proposals are fanned out to the B*n caption rows
+    (`rows_repeat`) and the decoder runs on those; the backward folds the caption rows' gradients back onto the clips
+    (`clip_fold`) before the encoder's backward, which runs on B rows.  outputs and alpha_all have B*n rows, the proposals B.
+    Dropout: the encoder's masks are keyed by the clip row 0..B-1, so the n captions of a clip see the same encoder masks;
+    decoder and word dropout stay keyed by the B*n caption rows.  Under one seed these are the masks of
+    `sample(..., share_encoder=True)`, not those of a pass over the clips repeated n times."""
 
     @property
     def unused_parameters(self):
@@ -288,8 +314,22 @@ class CapGnnModel(_HipModel):
                                             (enc.motion_encoder, 'encoder.motion_encoder', E.SITE_PSL_MOT)], regions, sv, training, seed)
         return obj, mot
 
-    def _engine_forward(self, frames, regions, captions, L, coins, training, seed, sv, dev_coins=None, outputs=True):
+    def _fan_out(self, obj, mot, n, sv):
+        """the proposals of B clips -> the B*n caption rows of the decoder (row b*n + i = clip b); sv keeps the B-row tensors"""
+        sv['enc_out'] = [obj, mot]
+        if n == 1:
+            return obj, mot
         ops = self.ops
+        out = []
+        for x in (obj, mot):
+            y = torch.empty((x.shape[0] * n,) + tuple(x.shape[1:]), dtype=torch.float32, device=x.device)
+            ops.rows_repeat(x, y, n)
+            out.append(y)
+        return out
+
+    def _engine_forward(self, frames, regions, captions, L, coins, training, seed, sv, dev_coins=None, outputs=True, seq_per_clip=1):
+        ops = self.ops
+        n = self._check_seq_per_clip(seq_per_clip, frames.shape[0], captions)
         self._gemm_policy(False)
         if getattr(ops, 'colsum_defer', None) is not None:
             ops.colsum_defer = None         # (a backward that raised half-way must not leave the collector armed)
@@ -297,11 +337,13 @@ class CapGnnModel(_HipModel):
         regions = regions.contiguous().float()
         obj, mot = self._encode(frames, regions, training, seed, sv)
         sv['frames'], sv['regions'] = frames, regions
-        sv['dec_gsrc'] = [obj, mot]
-        s = E.dec_fwd(ops, self.decoder, [obj, mot], sv, captions, L, coins, training, seed, dev_coins)
+        # seq_per_clip = n > 1: the encoder ran on the B clips, the decoder runs on their B*n caption rows
+        mems = self._fan_out(obj, mot, n, sv)
+        sv['dec_gsrc'] = list(mems)
+        s = E.dec_fwd(ops, self.decoder, list(mems), sv, captions, L, coins, training, seed, dev_coins)
         if not outputs:            # fused trainer: the loss reads the time-major logits in place
             return None
-        B = frames.shape[0]
+        B = frames.shape[0] * n
         V = self.decoder.vocab_size
         logits = torch.empty(B, L, V, dtype=torch.float32, device=frames.device)
         ops.permute_tb(s['LOGITS'], logits)
@@ -309,8 +351,9 @@ class CapGnnModel(_HipModel):
         ops.permute_tb(s['ALPHA'], alpha)
         return logits, obj, mot, alpha
 
-    def _engine_backward(self, sv, dlogits_tm, dobj, dmot, dalpha_tm, training, seed, on_bucket=None):
+    def _engine_backward(self, sv, dlogits_tm, dobj, dmot, dalpha_tm, training, seed, on_bucket=None, seq_per_clip=1):
         ops, enc = self.ops, self.encoder
+        n = int(seq_per_clip)
         self._gemm_policy(True)
         G = self._G
         ops.fill(self._gflat, 0.0)
@@ -337,8 +380,18 @@ class CapGnnModel(_HipModel):
                 on_bucket(key)
         bucket('decoder')
         dob, dmo = dmems
-        ops.mean_rows_bwd(dgfeat[:, :H], dob, accum=True)
-        ops.mean_rows_bwd(dgfeat[:, H:], dmo, accum=True)
+        if n == 1:
+            ops.mean_rows_bwd(dgfeat[:, :H], dob, accum=True)
+            ops.mean_rows_bwd(dgfeat[:, H:], dmo, accum=True)
+        else:
+            # the decoder's backward ran on the B*n caption rows: one pass per stream folds a clip's n rows -- proposals'
+            # gradient and the backward of their mean -- onto the clip, in a fixed order; the encoder's backward runs on B rows
+            folded = []
+            for i, dm in enumerate(dmems):
+                dx = torch.empty((B,) + tuple(dm.shape[1:]), dtype=torch.float32, device=dm.device)
+                ops.clip_fold(dm, dgfeat[:, i * H:(i + 1) * H], dx, n)
+                folded.append(dx)
+            dob, dmo = folded
         if dobj is not None:
             ops.copy2d(dobj.reshape(-1, H), dob.view(-1, H), accum=True)
         if dmot is not None:
@@ -377,8 +430,10 @@ class CapGnnModel(_HipModel):
         if on_bucket:
             on_bucket(('encoder.motion_encoder', 'encoder.obj_encoder'))
 
-    def _sample_forward(self, frames, regions, L, training, seed, temperature, sv):
-        """encoder + sampled decoding (engine.dec_sample) -> the decoder state (IDS, LOGP, LENS)"""
+    def _sample_forward(self, frames, regions, L, training, seed, temperature, sv, n=1, share_encoder=False):
+        """encoder + sampled decoding (engine.dec_sample) -> the decoder state (IDS, LOGP, LENS).  share_encoder: frames / regions
+        are the B clips, the encoder runs on them once and the decoding on their B*n fanned-out rows; else the caller has
+        repeated the clips and n is not used"""
         ops = self.ops
         self._gemm_policy(False)
         if getattr(ops, 'colsum_defer', None) is not None:
@@ -387,15 +442,19 @@ class CapGnnModel(_HipModel):
         regions = regions.contiguous().float()
         obj, mot = self._encode(frames, regions, training, seed, sv)
         sv['frames'], sv['regions'] = frames, regions
-        sv['dec_gsrc'] = [obj, mot]
-        return E.dec_sample(ops, self.decoder, [obj, mot], sv, L, training, seed, temperature)
+        mems = self._fan_out(obj, mot, n if share_encoder else 1, sv)
+        sv['dec_gsrc'] = list(mems)
+        return E.dec_sample(ops, self.decoder, list(mems), sv, L, training, seed, temperature)
 
     # ------------------------------------------------------------------ public forward
-    def forward(self, visual_feats, region_feats, caption, max_words=None, teacher_forcing_ratio=1.0):
+    def forward(self, visual_feats, region_feats, caption, max_words=None, teacher_forcing_ratio=1.0, seq_per_clip=1):
+        n = self._check_seq_per_clip(seq_per_clip, visual_feats.shape[0], caption)
         self.flatten_parameters_()
         dec = self.decoder
         infer = caption is None
         L = dec.max_words if max_words is None else max_words
+        if infer and n != 1:
+            raise ValueError('seq_per_clip > 1 needs captions; for several decoded captions per clip use sample() or beam_search()')
         if infer and dec.beam_size != 1:
             from .beam import beam_infer
             return beam_infer(self, visual_feats, region_feats)
@@ -407,25 +466,35 @@ class CapGnnModel(_HipModel):
                 self._engine_forward(visual_feats, region_feats, None, L, coins, False, seed, sv)
             ids = sv['dec']['IDS'][1:].t().contiguous()
             return ids, sv['dec_gsrc'][0], sv['dec_gsrc'][1], []
+        kw = {'seq_per_clip': n} if n != 1 else {}
         params = [p for _, p in self.named_parameters()]
         needs_grad = torch.is_grad_enabled() and any(p.requires_grad for p in params)
         if not needs_grad:
             with torch.no_grad():
-                return self._engine_forward(visual_feats, region_feats, caption, L, coins, self.training, seed, {})
-        return _ModelFn.apply(self, visual_feats, region_feats, caption, L, coins, seed, *params)
+                return self._engine_forward(visual_feats, region_feats, caption, L, coins, self.training, seed, {}, **kw)
+        return _ModelFn.apply(self, visual_feats, region_feats, caption, L, coins, seed, n, *params)
 
     @torch.no_grad()
-    def sample(self, visual_feats, region_feats, n=1, temperature=1.0, seed=None):
+    def sample(self, visual_feats, region_feats, n=1, temperature=1.0, seed=None, share_encoder=False):
         """Draw n captions per clip from softmax(logits / temperature) (self-critical training; temperature 0 is greedy).
         Returns (ids (B*n, L) int64, logp (B*n, L) float32 log-probabilities of the drawn words, lens (B*n,) int64: first
         <end> position + 1, else L); clip b's samples are rows b*n .. b*n + n - 1.  The clips are repeated n times before the
         encoder (it runs on B*n rows, with their own dropout rows).  Dropout follows `self.training`.  seed None draws the next
         seed of the model's sequence; a given seed reproduces the draw -- and the dropout masks of a train step on the same
-        rows with that seed, so the sampled words are on-policy for it."""
+        rows with that seed, so the sampled words are on-policy for it.
+        share_encoder=True: the encoder runs once, on the B clips, and only the sampled decoding runs on B*n rows (the proposals
+        are fanned out with `rows_repeat`).  The encoder's dropout masks are then keyed by the clip row 0..B-1 -- the n samples
+        of a clip share them -- while decoder and word dropout stay keyed by the B*n caption rows: these are the masks of a train
+        pass `forward(..., seq_per_clip=n)` / `Trainer.step(..., seq_per_clip=n)` with the same seed, so the draw is on-policy for
+        that pass; they are not the masks of the unshared draw, which is why sharing is opt-in."""
         self.flatten_parameters_()
         if seed is None:
             seed = self.next_seed()
         sv = {}
+        if share_encoder:
+            s = self._sample_forward(visual_feats, region_feats, self.decoder.max_words, self.training, seed, temperature, sv,
+                                     n=int(n), share_encoder=True)
+            return s['IDS'][1:].t().contiguous(), s['LOGP'].t().contiguous(), s['LENS']
         s = self._sample_forward(expand_rows(visual_feats, n), expand_rows(region_feats, n), self.decoder.max_words, self.training,
                                  seed, temperature, sv)
         return s['IDS'][1:].t().contiguous(), s['LOGP'].t().contiguous(), s['LENS']
@@ -445,7 +514,8 @@ class CapBaseline1(_HipModel):
     def update_beam_size(self, beam_size):
         self.decoder.update_beam_size(beam_size)
 
-    def _engine_forward(self, frames, regions, captions, L, coins, training, seed, sv, dev_coins=None, outputs=True):
+    def _engine_forward(self, frames, regions, captions, L, coins, training, seed, sv, dev_coins=None, outputs=True, seq_per_clip=1):
+        self._only_one_seq_per_clip(seq_per_clip)
         ops = self.ops
         self._gemm_policy(False)
         frames = frames.contiguous().float()
@@ -474,7 +544,8 @@ class CapBaseline1(_HipModel):
         if on_bucket:
             on_bucket(('decoder', 'encoder'))
 
-    def forward(self, visual_feats, region_feats, caption, max_words=None, teacher_forcing_ratio=1.0):
+    def forward(self, visual_feats, region_feats, caption, max_words=None, teacher_forcing_ratio=1.0, seq_per_clip=1):
+        self._only_one_seq_per_clip(seq_per_clip)
         self.flatten_parameters_()
         dec = self.decoder
         infer = caption is None
@@ -493,7 +564,7 @@ class CapBaseline1(_HipModel):
         if not (torch.is_grad_enabled() and any(p.requires_grad for p in params)):
             with torch.no_grad():
                 return self._engine_forward(visual_feats, region_feats, caption, L, coins, self.training, seed, {})[0], 0, 0, 0
-        out = _ModelFn.apply(self, visual_feats, region_feats, caption, L, coins, seed, *params)
+        out = _ModelFn.apply(self, visual_feats, region_feats, caption, L, coins, seed, 1, *params)
         return out[0], 0, 0, 0
 
 
@@ -537,7 +608,8 @@ class CapBaselineModel(_HipModel):
                         E.SITE_PSL_MOT, self.fused_o2v)
         return mot.view(B, T, -1)
 
-    def _engine_forward(self, frames, regions, captions, L, coins, training, seed, sv, dev_coins=None, outputs=True):
+    def _engine_forward(self, frames, regions, captions, L, coins, training, seed, sv, dev_coins=None, outputs=True, seq_per_clip=1):
+        self._only_one_seq_per_clip(seq_per_clip)
         ops = self.ops
         self._gemm_policy(False)
         frames = frames.contiguous().float()
@@ -669,6 +741,7 @@ class Trainer(object):
         self._contact_checked = False
         self._hook_mode, self._hook_sv = False, None
         self._weighted_mode = False     # the captured graphs weight the CrossEntropy per caption (step(seq_weights=...))
+        self._spc_mode = 1              # captions per clip of the captured graphs (step(seq_per_clip=...))
         self.m = self.v = None
         if world_size > 1 or self.rehearse_ranks > 1:
             assert world_size == 1 or not self.rehearse_ranks, 'rehearse_ranks is for one-rank runs'
@@ -1015,14 +1088,18 @@ class Trainer(object):
             self._rccl = None
 
     # ------------------------------------------------------------------ one step, as a schedule
-    def _schedule(self, frames, regions, captions, cap_lens, coins, seed, dev_coins, on_bucket, extra_dlogits=None, seq_weights=None):
+    def _schedule(self, frames, regions, captions, cap_lens, coins, seed, dev_coins, on_bucket, extra_dlogits=None, seq_weights=None,
+                  seq_per_clip=1):
         model, ops = self.model, self.model.ops
         L = captions.shape[1]
         sv = {}
         training = model.training
+        # seq_per_clip = n > 1: frames / regions hold B clips, captions / cap_lens / seq_weights their B*n caption rows (the keyword
+        # is passed only then: the default form calls the engine exactly as before)
+        kw = {'seq_per_clip': seq_per_clip} if seq_per_clip != 1 else {}
         # a bucket handed to a reduction (or closing a graph segment) must be complete: deferred weight gradients go out there
         model._flush_at_buckets = self._comm_mode() != 'none' or self.force_graph_cuts
-        model._engine_forward(frames, regions, captions, L, coins, training, seed, sv, dev_coins, outputs=False)
+        model._engine_forward(frames, regions, captions, L, coins, training, seed, sv, dev_coins, outputs=False, **kw)
         s = sv['dec']
         Bn = captions.shape[0]
         dl = torch.empty_like(s['LOGITS'])
@@ -1039,7 +1116,7 @@ class Trainer(object):
             g = extra_dlogits(s['LOGITS'], sv)
             V = dl.shape[-1]
             ops.copy2d(g.contiguous().view(-1, V), dl.view(-1, V), accum=True)
-        model._engine_backward(sv, dl, None, None, None, training, seed, on_bucket=on_bucket)
+        model._engine_backward(sv, dl, None, None, None, training, seed, on_bucket=on_bucket, **kw)
         return loss
 
     def _hyper(self):
@@ -1047,7 +1124,8 @@ class Trainer(object):
         return [self.lr / (1.0 - b1 ** self.t), math.sqrt(1.0 - b2 ** self.t)]
 
     @torch.no_grad()
-    def step(self, frames, regions, captions, cap_lens, tf_ratio, max_len=26, extra_dlogits=None, seed=None, seq_weights=None):
+    def step(self, frames, regions, captions, cap_lens, tf_ratio, max_len=26, extra_dlogits=None, seed=None, seq_weights=None,
+             seq_per_clip=1):
         """One optimisation step.  Returns the (device) scalar loss of this rank's shard.
         extra_dlogits: optional callable (logits (L,B,V) time-major, saved-state dict) -> (L,B,V) gradient of an additional
         loss on the logits, added to the CrossEntropy's before the backward.  With use_graphs the captured step is cut at
@@ -1056,8 +1134,14 @@ class Trainer(object):
         seed: the dropout seed of the step (None: the model's next one) -- a self-critical step passes the seed its samples were
         drawn with, so that the masks are those of the sampling pass.
         seq_weights: optional (B,) per-caption weights of the CrossEntropy (`ce_ragged_weighted`; the advantages of self-critical
-        training); with use_graphs that form of the step is captured on its own, the weights read from a static device buffer."""
+        training); with use_graphs that form of the step is captured on its own, the weights read from a static device buffer.
+        seq_per_clip = n > 1 (CapGnnModel): frames / regions hold B clips and captions / cap_lens / seq_weights their B*n caption
+        rows, clip b's in rows b*n .. b*n+n-1.  The encoder and its backward run once per clip (`CapGnnModel.forward`), the loss
+        is the same ragged CrossEntropy over all B*n captions, and the gradient arena, buckets, clipping and Adam are those of
+        any step.  Encoder dropout is keyed by the clip row, decoder and word dropout by the caption row.  With use_graphs the
+        captured step is for one n and one pair of row counts; other batches run kernel by kernel."""
         model, ops = self.model, self.model.ops
+        n_seq = model._check_seq_per_clip(seq_per_clip, frames.shape[0], captions)
         self._check_binding()
         captions = captions[:, :max_len].contiguous()
         if not (torch.is_tensor(cap_lens) and cap_lens.device == captions.device and cap_lens.dtype == torch.int64):
@@ -1071,17 +1155,19 @@ class Trainer(object):
         if weighted and not (torch.is_tensor(seq_weights) and seq_weights.device == captions.device
                              and seq_weights.dtype == torch.float32):
             seq_weights = _h2d(seq_weights, torch.float32, captions.device)
-        if self.use_graphs and (self._graphs is None or (self._hook_mode == hook and self._weighted_mode == weighted)):
-            loss = self._step_graphs(frames, regions, captions, cap_lens, coins, seed, extra_dlogits, seq_weights)
+        if self.use_graphs and (self._graphs is None or (self._hook_mode == hook and self._weighted_mode == weighted
+                                                         and self._spc_mode == n_seq)):
+            loss = self._step_graphs(frames, regions, captions, cap_lens, coins, seed, extra_dlogits, seq_weights, n_seq)
         else:
             # (a trainer's graphs are captured for one form of the step; the other forms run kernel by kernel)
             loss = self._eager_step(frames, regions, captions, cap_lens, coins, seed, counted=True, extra_dlogits=extra_dlogits,
-                                    seq_weights=seq_weights)
+                                    seq_weights=seq_weights, seq_per_clip=n_seq)
         if self.check_every and self.t % self.check_every == 0:
             self.check()
         return loss
 
-    def _eager_step(self, frames, regions, captions, cap_lens, coins, seed, counted=False, extra_dlogits=None, seq_weights=None):
+    def _eager_step(self, frames, regions, captions, cap_lens, coins, seed, counted=False, extra_dlogits=None, seq_weights=None,
+                    seq_per_clip=1):
         model, ops = self.model, self.model.ops
         if not counted:
             self.t += 1
@@ -1089,7 +1175,8 @@ class Trainer(object):
         if self.device_coins:
             dev_coins = _h2d([int(c) for c in coins], torch.int32, captions.device)
         self._works = []
-        loss = self._schedule(frames, regions, captions, cap_lens, coins, seed, dev_coins, self._allreduce, extra_dlogits, seq_weights)
+        loss = self._schedule(frames, regions, captions, cap_lens, coins, seed, dev_coins, self._allreduce, extra_dlogits, seq_weights,
+                              seq_per_clip)
         self._reduce_guard()
         for w in self._works:
             w.wait()
@@ -1106,11 +1193,12 @@ class Trainer(object):
         return loss
 
     # ------------------------------------------------------------------ hipGraph path
-    def _capture(self, frames, regions, captions, cap_lens, hook=False, weighted=False):
+    def _capture(self, frames, regions, captions, cap_lens, hook=False, weighted=False, seq_per_clip=1):
         dev = frames.device
         L = captions.shape[1]
         self._hook_mode, self._hook_sv = hook, None
         self._weighted_mode = weighted
+        self._spc_mode = seq_per_clip
         st = self._static = dict(frames=frames.clone(), regions=regions.clone(), captions=captions.clone(),
                                  lens=cap_lens.clone())
         st['weights'] = torch.ones(captions.shape[0], dtype=torch.float32, device=dev) if weighted else None
@@ -1132,7 +1220,7 @@ class Trainer(object):
             # (with RCCL the warm-up also runs the collectives once: channel buffers are set up before the capture;
             #  nothing is updated: Adam is not part of the schedule)
             self._schedule(st['frames'], st['regions'], st['captions'], st['lens'], None, st['seed'], st['coins'],
-                           self._allreduce if mode == 'rccl' else None, seq_weights=st['weights'])
+                           self._allreduce if mode == 'rccl' else None, seq_weights=st['weights'], seq_per_clip=seq_per_clip)
             if mode == 'rccl':
                 self._reduce_guard()
             self._join_comm()
@@ -1159,7 +1247,7 @@ class Trainer(object):
                 return st['extra']
 
             loss = self._schedule(st['frames'], st['regions'], st['captions'], st['lens'], None, st['seed'], st['coins'], cut,
-                                  placeholder if hook else None, st['weights'])
+                                  placeholder if hook else None, st['weights'], seq_per_clip)
             if mode != 'torch':
                 # no host-issued collective between backward and update: Adam is part of the graph, behind the join of the
                 # side stream's collectives; with host-issued collectives it follows their waits
@@ -1179,13 +1267,13 @@ class Trainer(object):
         self._graphs, self._loss = graphs, loss
         self._adam_in_graph = mode != 'torch'
 
-    def _capture_agreed(self, frames, regions, captions, cap_lens, hook, weighted=False):
+    def _capture_agreed(self, frames, regions, captions, cap_lens, hook, weighted=False, seq_per_clip=1):
         """`_capture`, and with several ranks the agreement on its outcome: returns None when EVERY rank captured, else the error
         (this rank's own, or a stand-in when only another rank failed) after dropping this rank's graphs -- so that all ranks take
         the same fallback together"""
         err = None
         try:
-            self._capture(frames, regions, captions, cap_lens, hook, weighted)
+            self._capture(frames, regions, captions, cap_lens, hook, weighted, seq_per_clip)
         except Exception as e:            # (any failure votes: an AssertionError on one rank must not leave the others in the vote)
             err = e
         if self.world_size > 1:
@@ -1196,13 +1284,15 @@ class Trainer(object):
         return err
 
     @torch.no_grad()
-    def forward_only(self, frames, regions, captions, tf_ratio, max_len=26, time_major=False):
+    def forward_only(self, frames, regions, captions, tf_ratio, max_len=26, time_major=False, seq_per_clip=1):
         """The no-grad generator forward of the GAN iteration (run_gun.py:167) from the captured step's FIRST graph (forward +
         CrossEntropy): same coin / dropout-seed draws as `model(frames, regions, captions, max_len, tf_ratio)`, returns
         (logits (B,L,V), obj, mot, alpha (B,L,2P)) as views of the graphs' static buffers -- valid until the next replay --
-        or None when this trainer has no cut graphs for that batch shape (the caller then calls the model)."""
+        or None when this trainer has no cut graphs for that batch shape (the caller then calls the model).
+        seq_per_clip = n: as in `step` -- B clips, B*n caption rows; logits and alpha have B*n rows, obj and mot B, as the model
+        returns them; None unless the graphs were captured for that n."""
         if not (self.use_graphs and self._graphs is not None and self._hook_mode and self._hook_sv is not None
-                and self.model.training):
+                and self.model.training and self._spc_mode == int(seq_per_clip)):
             return None
         st = self._static
         captions = captions[:, :max_len].contiguous()
@@ -1218,7 +1308,8 @@ class Trainer(object):
         self._graphs[0][0].replay()
         logits_tm, sv = self._hook_sv
         # time_major: the logits as the decoder wrote them, (L,B,V) -- what the critic's schedule reads (gan.GanTrainer)
-        return (logits_tm if time_major else logits_tm.transpose(0, 1)), sv['dec_gsrc'][0], sv['dec_gsrc'][1], \
+        enc_out = sv['enc_out'] if self._spc_mode != 1 else sv['dec_gsrc']      # (the B-row proposals, as the model returns them)
+        return (logits_tm if time_major else logits_tm.transpose(0, 1)), enc_out[0], enc_out[1], \
             sv['dec']['ALPHA'].transpose(0, 1)
 
     def _send_scalars(self, coins, seed, hyper):
@@ -1239,7 +1330,7 @@ class Trainer(object):
 
     def static_inputs(self):
         """The captured graphs read their batch from these device buffers: (frames, regions, captions, cap_lens), or None
-        before the first replayed step.  A producer that fills them in place (the HBM-resident feature store gathers a batch
+        before the first replayed step (captured with seq_per_clip = n: frames / regions of B rows, captions / cap_lens of B*n).  A producer that fills them in place (the HBM-resident feature store gathers a batch
         straight into them, `ResidentFeatures.batch(ids, out=...)`) and then passes the very same tensors to `step` saves the
         device-to-device staging copy of the batch (258 MB per step at batch 64, MSVD-shaped)."""
         if self._graphs is None:
@@ -1247,12 +1338,12 @@ class Trainer(object):
         st = self._static
         return st['frames'], st['regions'], st['captions'], st['lens']
 
-    def _step_graphs(self, frames, regions, captions, cap_lens, coins, seed, extra_dlogits=None, seq_weights=None):
+    def _step_graphs(self, frames, regions, captions, cap_lens, coins, seed, extra_dlogits=None, seq_weights=None, seq_per_clip=1):
         model, ops = self.model, self.model.ops
         hook = extra_dlogits is not None
         weighted = seq_weights is not None
         if self._graphs is None:
-            err = self._capture_agreed(frames, regions, captions, cap_lens, hook, weighted)
+            err = self._capture_agreed(frames, regions, captions, cap_lens, hook, weighted, seq_per_clip)
             if err is not None and self.graph_fallback and self._comm_mode() == 'rccl' and self.world_size > 1:
                 # the in-graph RCCL capture was refused somewhere: EVERY rank retries the segmented form (torch.distributed
                 # collectives issued by the host between graph segments) -- a rank replaying graphs that hold private-communicator
@@ -1262,7 +1353,7 @@ class Trainer(object):
                               'torch.distributed collectives between graph segments' % (type(err).__name__, err))
                 torch.cuda.synchronize()
                 self.comm = 'torch'
-                err = self._capture_agreed(frames, regions, captions, cap_lens, hook, weighted)
+                err = self._capture_agreed(frames, regions, captions, cap_lens, hook, weighted, seq_per_clip)
             if err is not None:
                 if not self.graph_fallback:
                     raise err
@@ -1272,12 +1363,13 @@ class Trainer(object):
                 torch.cuda.synchronize()
                 self.use_graphs, self._graphs = False, None
                 return self._eager_step(frames, regions, captions, cap_lens, coins, seed, counted=True, extra_dlogits=extra_dlogits,
-                                        seq_weights=seq_weights)
+                                        seq_weights=seq_weights, seq_per_clip=seq_per_clip)
         st = self._static
         if (frames.shape, regions.shape, captions.shape) != (st['frames'].shape, st['regions'].shape, st['captions'].shape):
-            # a batch of another shape (the short last batch of an epoch): the captured graphs are for one shape only
+            # a batch of another shape (the short last batch of an epoch; other clip or caption row counts): the captured graphs
+            # are for one shape only
             return self._eager_step(frames, regions, captions, cap_lens, coins, seed, counted=True, extra_dlogits=extra_dlogits,
-                                    seq_weights=seq_weights)
+                                    seq_weights=seq_weights, seq_per_clip=seq_per_clip)
         for k, src in (('frames', frames), ('regions', regions), ('captions', captions), ('lens', cap_lens)):
             stage(st[k], src)
         if weighted:

@@ -21,15 +21,21 @@ class SCSTTrainer(object):
     the GPU (see `step`).
     baseline: 'mean' -- the leave-one-out mean of the clip's other n - 1 rewards (needs n_samples >= 2); 'greedy' -- the reward
     of the clip's eval-mode greedy caption.  The remaining keywords go to the owned `Trainer` (lr, use_graphs, data parallel,
-    ...), whose Adam state, gradient buckets and graphs the step reuses."""
+    ...), whose Adam state, gradient buckets and graphs the step reuses.
+    share_encoder=True: the n samples and the train pass run the encoder once per clip -- `sample(..., share_encoder=True)`,
+    then `Trainer.step(frames, regions, ids, lens, ..., seq_per_clip=n)` on the B clips and their B*n sampled captions -- instead
+    of on the clips repeated n times.  The encoder's dropout masks are then shared by a clip's n samples (keyed by the clip
+    row), in the sampling pass and in the train pass alike, so the step stays on-policy; the masks differ from those of the
+    unshared step, which is why it is opt-in."""
 
-    def __init__(self, model, reward, n_samples=5, baseline='mean', temperature=1.0, **trainer_kwargs):
+    def __init__(self, model, reward, n_samples=5, baseline='mean', temperature=1.0, share_encoder=False, **trainer_kwargs):
         if baseline not in ('mean', 'greedy'):
             raise ValueError("baseline must be 'mean' or 'greedy', not %r" % (baseline,))
         if baseline == 'mean' and n_samples < 2:
             raise ValueError("the 'mean' baseline needs n_samples >= 2 (leave-one-out over the clip's samples)")
         self.model, self.reward = model, reward
         self.n, self.baseline, self.temperature = int(n_samples), baseline, float(temperature)
+        self.share_encoder = bool(share_encoder)
         self.trainer = Trainer(model, **trainer_kwargs)
         self._sampler = self._greedy = None
 
@@ -39,10 +45,15 @@ class SCSTTrainer(object):
     def _sample(self, frames, regions, seed):
         model = self.model
         if not self.trainer.use_graphs:
+            if self.share_encoder:
+                return model.sample(frames, regions, n=self.n, temperature=self.temperature, seed=seed, share_encoder=True)
             return model.sample(frames, regions, n=self.n, temperature=self.temperature, seed=seed)
         model.flatten_parameters_()
         if not self._graph_ok(self._sampler, frames, regions):
-            self._sampler = SampleGraph(model, frames, regions, self.n, self.temperature)
+            if self.share_encoder:
+                self._sampler = SampleGraph(model, frames, regions, self.n, self.temperature, share_encoder=True)
+            else:
+                self._sampler = SampleGraph(model, frames, regions, self.n, self.temperature)
         return self._sampler(frames, regions, seed)
 
     def _greedy_ids(self, frames, regions):
@@ -100,10 +111,17 @@ class SCSTTrainer(object):
             R = r.reshape(B, n)
             b = ((R.sum(1, keepdims=True) - R) / (n - 1)).reshape(-1)
         adv = (r - b).astype(np.float32)
-        fx, rx = self._expanded_inputs(frames, regions)
-        loss = self.trainer.step(fx, rx, ids, lens, 1.0, max_len=L, seed=seed, seq_weights=_h2d(adv, torch.float32, ids.device))
+        loss = self._train_step(frames, regions, ids, lens, L, seed, _h2d(adv, torch.float32, ids.device))
         return self._with_grad_norm({'loss': loss, 'reward_mean': float(r.mean()), 'baseline_mean': float(b.mean()),
                                      'mean_len': float(host[:, L].double().mean())})
+
+    def _train_step(self, frames, regions, ids, lens, L, seed, adv):
+        """the policy-gradient step on the sampled words: on the clips repeated n times, or (share_encoder) on the B clips with
+        their B*n captions"""
+        if self.share_encoder:
+            return self.trainer.step(frames, regions, ids, lens, 1.0, max_len=L, seed=seed, seq_weights=adv, seq_per_clip=self.n)
+        fx, rx = self._expanded_inputs(frames, regions)
+        return self.trainer.step(fx, rx, ids, lens, 1.0, max_len=L, seed=seed, seq_weights=adv)
 
     def _with_grad_norm(self, stats):
         """with gradient clipping on (Trainer's max_grad_norm / clip_grad_value): 'grad_norm', a 0-d device tensor, joins the stats"""
@@ -124,6 +142,5 @@ class SCSTTrainer(object):
         adv = torch.empty(B * n, dtype=torch.float32, device=ids.device)
         stats = torch.empty(3, dtype=torch.float64, device=ids.device)
         model.ops.scst_advantage(r, lens, g, n, adv, stats)
-        fx, rx = self._expanded_inputs(frames, regions)
-        loss = self.trainer.step(fx, rx, ids, lens, 1.0, max_len=L, seed=seed, seq_weights=adv)
+        loss = self._train_step(frames, regions, ids, lens, L, seed, adv)
         return self._with_grad_norm({'loss': loss, 'reward_mean': stats[0], 'baseline_mean': stats[1], 'mean_len': stats[2]})

@@ -456,6 +456,14 @@ int dlsg_lstm_pw_bwd_n(const dlsg_lstm_pw_bwd_args* a, int count, void* stream);
  * mean over P proposals (layer.py:407-410): out[b, off + h] = mean_p x[b,p,h]; and its backward (accumulating) */
 int dlsg_mean_rows_fwd(const float* x, float* out, int64_t ldo, int B, int P, int H, void* stream);
 int dlsg_mean_rows_bwd(const float* dout, int64_t lddo, float* dx, int B, int P, int H, int accum, void* stream);
+/* several captions per clip on one encoder pass: y[b*n + i, :] = x[b, :] for i < n (x: B contiguous rows of `row` floats, y: B*n);
+ * 16-byte accesses when row % 4 == 0 and both bases are 16-byte aligned, else a scalar path */
+int dlsg_rows_repeat(const float* x, float* y, int B, int n, int64_t row, void* stream);
+/* and the fold of the caption rows' gradients back onto the clip, with the backward of the proposals' mean in the same pass:
+ * dx[b,p,h] (+)= sum_{i<n} (dmem[b*n + i, p, h] + dg[(b*n + i)*lddg + h] / P), added in the order i = 0..n-1 by one thread per
+ * output element (no atomics: bit-reproducible).  dmem (B*n,P,H) and dx (B,P,H) contiguous; dg optional (NULL: no mean term),
+ * B*n rows of H floats with row stride lddg >= H; accum != 0 adds to dx. */
+int dlsg_clip_fold(const float* dmem, const float* dg, int64_t lddg, float* dx, int B, int n, int P, int H, int accum, void* stream);
 /* embedding gather + dropout (layer.py:421-422,438-439): out[r, :] = drop(E[ids[r], :]); the dropout mask of
  * element (r, j) is keyed by (row0 + r) * W + j so a slice of a larger call reproduces the same mask. */
 int dlsg_embed_fwd(const float* E, const int64_t* ids, float* out, int64_t ldo, int rows, int W, float p, uint64_t seed,

@@ -7,7 +7,11 @@
   * `device_reward` -- the same with the reward on the GPU (`scoring.DeviceCiderD`, vocabulary 1000): `cider_kernel_ms` (HIP
     events around `dlsg_cider_d` on the 320 rows), `advantage_kernel_ms` (`dlsg_scst_advantage`), `scst_step_ms` and its split
     (`reward_ms`: the CIDEr-D and advantage launches, no host transfer), and the scores' largest difference to the host scorer.
+  * `share` -- one more line: the device-reward step with the encoder run once per clip (`SCSTTrainer(share_encoder=True)`:
+    shared sampling, `Trainer.step(seq_per_clip=n)`) against the unshared step, both timed in the same process in alternating
+    rounds, each with its sample / reward / train split.
 usage: python3 tools/scst_bench.py [steps=10] [batch=64] [n=5]
+       python3 tools/scst_bench.py share [steps=10] [batch=64] [n=5] [rounds=2]
        python3 tools/scst_bench.py kernels      (rocprofv3 --kernel-trace --stats target: eager greedy and sampled decodes)
        python3 tools/scst_bench.py reward-kernels   (rocprofv3 target: 20 launches each of dlsg_cider_d and dlsg_scst_advantage)"""
 import json
@@ -139,6 +143,59 @@ def device_leg(net, vocab, frames, regions, refs, steps, B, n):
             'last_step': {k: float(v) for k, v in out.items()}}
 
 
+def step_leg(net, dc, frames, regions, steps, B, share):
+    """ms per device-reward SCST step (graph replays), and its split measured on further steps with a synchronisation around
+    each part"""
+    n = share['n']
+    tr = SC.SCSTTrainer(net, dc, n_samples=n, use_graphs=True, share_encoder=share['on'])
+    vb = [str(b) for b in range(B)]
+    for _ in range(2):
+        tr.step(frames, regions, vb)                   # captures
+    step_ms = timed(lambda: tr.step(frames, regions, vb), steps)
+    parts = {'sample': 0.0, 'reward': 0.0, 'train': 0.0}
+    inner_scores, inner_adv = dc.scores_device, net.ops.scst_advantage
+
+    def clock(key, fn):
+        def f(*a, **k):
+            torch.cuda.synchronize()
+            t = time.perf_counter()
+            out = fn(*a, **k)
+            torch.cuda.synchronize()
+            parts[key] += time.perf_counter() - t
+            return out
+        return f
+    tr._sample = clock('sample', tr._sample)
+    dc.scores_device = clock('reward', inner_scores)
+    net.ops.scst_advantage = clock('reward', inner_adv)
+    tr.trainer.step = clock('train', tr.trainer.step)
+    try:
+        for _ in range(steps):
+            tr.step(frames, regions, vb)
+        torch.cuda.synchronize()
+    finally:
+        del net.ops.scst_advantage
+        del dc.scores_device
+    tr.trainer.check()
+    return {'scst_step_ms': round(step_ms, 2), 'parts_ms': {k: round(v / steps * 1e3, 2) for k, v in parts.items()}}
+
+
+def share_main(steps=10, B=64, n=5, rounds=2):
+    net, vocab, frames, regions, refs = setup(B)
+    dc = dlsg_amd.DeviceCiderD(refs, vocab)
+    legs = []
+    for r in range(rounds):
+        for on in (False, True):
+            leg = step_leg(net, dc, frames, regions, steps, B, {'n': n, 'on': on})
+            leg.update(round=r, share_encoder=on)
+            legs.append(leg)
+    best = {on: min(x['scst_step_ms'] for x in legs if x['share_encoder'] == on) for on in (False, True)}
+    print(json.dumps({
+        'what': 'SCST step with the device reward at the MSVD shape, batch %d x %d samples, vocabulary 1000, train mode, hipGraph '
+                'replays: encoder on the %d repeated rows (share_encoder False) against once per clip (True)' % (B, n, B * n),
+        'legs': legs, 'best_unshared_ms': best[False], 'best_shared_ms': best[True],
+        'saved_ms': round(best[False] - best[True], 2), 'steps': steps}))
+
+
 def main(steps=10, B=64, n=5):
     net, vocab, frames, regions, refs = setup(B)
     rows = B * n
@@ -205,5 +262,7 @@ if __name__ == '__main__':
         kernels()
     elif len(sys.argv) > 1 and sys.argv[1] == 'reward-kernels':
         reward_kernels()
+    elif len(sys.argv) > 1 and sys.argv[1] == 'share':
+        share_main(*[int(x) for x in sys.argv[2:6]])
     else:
         main(*[int(x) for x in sys.argv[1:4]])
