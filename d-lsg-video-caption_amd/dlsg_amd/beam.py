@@ -15,11 +15,7 @@ there is no back-trace; `beam_finalize` ranks the beams).
 import torch
 
 from . import engine as E
-
-
-def _expand_rows(t, k):
-    B = t.shape[0]
-    return t.unsqueeze(1).expand(B, k, *t.shape[1:]).reshape(B * k, *t.shape[1:]).contiguous()
+from .graphs import expand_rows
 
 
 @torch.no_grad()
@@ -38,28 +34,49 @@ def beam_device(model, visual_feats, region_feats, early_exit=True):
 
 
 def _encode(model, visual_feats, region_feats):
-    """the encoder of the model's class: the attended memories, the saved tensors, the seed and CapGnnModel's proposals"""
+    """the encoder of the model's class: the attended memories, the saved tensors, the seed and the proposals forward() returns"""
     model.flatten_parameters_()
-    ops = model.ops
-    model._gemm_policy(False)
     seed = model.next_seed()
     sv = {}
-    frames = visual_feats.contiguous().float()
-    # ---- encoder + step-invariant decoder work on B rows
-    if hasattr(model, '_encode'):
-        regions = region_feats.contiguous().float()
-        obj, mot = model._encode(frames, regions, False, seed, sv)
-        mems, sv['dec_gsrc'] = [obj, mot], [obj, mot]
-    elif hasattr(model, '_motion_nodes'):
-        mot = model._motion_nodes(frames, region_feats.contiguous().float(), False, seed, sv)
-        mems, sv['dec_gsrc'] = [mot], [mot]
-    else:
-        B0, T, F = frames.shape
-        enc = E.encvis_fwd(ops, model.encoder, 'encoder', frames.view(B0 * T, F), B0, T, sv, False, seed)
-        enc = enc.view(B0, T, -1)
-        mems, sv['dec_gsrc'] = [enc], [enc]
-    extras = (sv['dec_gsrc'][0], sv['dec_gsrc'][-1]) if hasattr(model, '_encode') else None
-    return mems, sv, seed, extras
+    props, mems = model._encoder_pass(visual_feats, region_feats, False, seed, sv)
+    return mems, sv, seed, props
+
+
+def _beam_setup(model, mems, sv, seed, k):
+    """What the two searches share: the step-invariant decoder work on the B clips, the state of their R = B*k beams, and
+    `advance(t, words, rows)` -- step t of all beams on `words`, for t > 0 after the reorder of the state by the back-pointer rows
+    `rows` of step t-1 -- which returns the step's logits (R, V).  -> (advance, B, R, L)"""
+    ops, dec = model.ops, model.decoder
+    frames = mems[0]                                   # (reference tensor for device / dtype of the scratch arrays)
+    s = E.dec_prepare(ops, dec, mems, sv, False, seed)
+    B, V, L = frames.shape[0], dec.vocab_size, dec.max_words
+    if k > V:
+        raise ValueError('Target vocab size (%d) too small relative to per_node_beam_size (%d)' % (V, k))
+    # ---- K', V' stay one block per CLIP: the k beams of a clip are consecutive rows and read their clip's block (kv_div) -- no
+    # expanded (B*k)-row copies (82 MB at 128 x 5 rows).  Measured: the word step is not faster for it (20.0 ms per batch either
+    # way: the fused step kernel is bound by its per-row chain, the expanded copies were Infinity-Cache resident); it saves the
+    # memory and the one-time copies.  Only the small global-feature gate term is expanded to B*k rows
+    s['kv_div'] = k
+    s['gq'] = expand_rows(s['gq'], k)
+    R = B * k
+    E.dec_alloc(dec, s, frames, R, L)
+    # recurrent state: two physical slots per step.  Step t reads slot 2t and writes slot 2t+1; the reorder by
+    # back-pointer gathers slot 2t+1 into slot 2t+2, so nothing is gathered in place and nothing is copied back.
+    state_keys = ['LHP', 'QH', 'QC', 'LC']
+    big = {key: torch.zeros(2 * L + 2, R, s[key].shape[2], dtype=torch.float32, device=frames.device) for key in state_keys}
+    Emb = dec.word_embed.weight
+
+    def advance(t, words, rows):
+        if t:
+            # state of step t: slot 2t <- slot 2t-1, rows reordered by the parents chosen at step t-1
+            ops.gather_rows_multi([big[key][2 * t - 1] for key in state_keys], rows, [big[key][2 * t] for key in state_keys])
+        for key in state_keys:
+            s[key] = big[key][t:]                                  # index t -> slot 2t, index t+1 -> slot 2t+1
+        ops.embed_fwd(Emb, words, s['WE'][t])                      # beam_step applies no word dropout (layer.py:537)
+        E.dec_step(ops, dec, s, t, frames, False, seed, R)
+        E.dec_logits(ops, dec, s, t, t + 1)
+        return s['LOGITS'][t]
+    return advance, B, R, L
 
 
 @torch.no_grad()
@@ -70,59 +87,30 @@ def beam_search_from(model, mems, sv, seed, early_exit=True, extras=None):
     (layer.py:404-405)."""
     ops, dec = model.ops, model.decoder
     k = dec.beam_size
-    frames = mems[0]                                   # (reference tensor for device / dtype of the scratch arrays)
-    s = E.dec_prepare(ops, dec, mems, sv, False, seed)
-    B = frames.shape[0]
-    V = dec.vocab_size
-    L = dec.max_words
+    advance, B, R, L = _beam_setup(model, mems, sv, seed, k)
     end = dec.vocab('<end>')
-    if k > V:
-        raise ValueError('Target vocab size (%d) too small relative to per_node_beam_size (%d)' % (V, k))
-    # ---- K', V' stay one block per CLIP: the k beams of a clip are consecutive rows and read their clip's block (kv_div) -- no
-    # expanded (B*k)-row copies (82 MB at 128 x 5 rows).  Measured: the word step is not faster for it (20.0 ms per batch either
-    # way: the fused step kernel is bound by its per-row chain, the expanded copies were Infinity-Cache resident); it saves the
-    # memory and the one-time copies.  Only the small global-feature gate term is expanded to B*k rows
-    s['kv_div'] = k
-    s['gq'] = _expand_rows(s['gq'], k)
-    R = B * k
-    E.dec_alloc(dec, s, frames, R, L)
-    dev = frames.device
-    # recurrent state: two physical slots per step.  Step t reads slot 2t and writes slot 2t+1; the reorder by
-    # back-pointer gathers slot 2t+1 into slot 2t+2, so nothing is gathered in place and nothing is copied back.
-    state_keys = ['LHP', 'QH', 'QC', 'LC']
-    big = {key: torch.zeros(2 * L + 2, R, s[key].shape[2], dtype=torch.float32, device=dev) for key in state_keys}
-    Emb = dec.word_embed.weight
+    dev = mems[0].device
     preds = torch.empty(L, R, dtype=torch.int64, device=dev)       # chosen classes per step, (B,k) flattened
     backs = torch.zeros(L, R, dtype=torch.int64, device=dev)
     rows = torch.empty(R, dtype=torch.int64, device=dev)
     lps = torch.zeros(2, R, dtype=torch.float32, device=dev)       # running log-probs, ping-pong
     ended = torch.zeros(L, dtype=torch.int32, device=dev)          # number of <end> among the classes chosen at step t
     start = torch.full((R,), dec.vocab('<start>'), dtype=torch.int64, device=dev)
-
-    def step(t, words):
-        for key in state_keys:
-            s[key] = big[key][t:]                                  # index t -> slot 2t, index t+1 -> slot 2t+1
-        ops.embed_fwd(Emb, words, s['WE'][t])                      # beam_step applies no word dropout (layer.py:537)
-        E.dec_step(ops, dec, s, t, frames, False, seed, R)
-        E.dec_logits(ops, dec, s, t, t + 1)
-
     # the reference tests `all beams ended` on the host before every step (allennlp_beamsearch.py:168); here the count of
     # <end> tokens is kept on the device and read every CHECK steps, and the result is cut to the step the reference
     # would have stopped at (steps after that only append <end> at log-prob 0 and change nothing before them)
     CHECK = 4
-    step(0, start)
-    ops.beam_select(s['LOGITS'][0], start, lps[0], preds[0], lps[1], backs[0], rows, k, end, first=True, ended_count=ended[0:1])
+    logits = advance(0, start, rows)
+    ops.beam_select(logits, start, lps[0], preds[0], lps[1], backs[0], rows, k, end, first=True, ended_count=ended[0:1])
     done = 1
     for t in range(1, L):
         if early_exit and t % CHECK == 0:
             cnt = ended[:t].tolist()
             if any(c == R for c in cnt):
                 break
-        # state of step t: slot 2t <- slot 2t-1, rows reordered by the parents chosen at step t-1
-        ops.gather_rows_multi([big[key][2 * t - 1] for key in state_keys], rows, [big[key][2 * t] for key in state_keys])
-        step(t, preds[t - 1])
+        logits = advance(t, preds[t - 1], rows)
         cur, nxt = lps[t % 2], lps[(t + 1) % 2]
-        ops.beam_select(s['LOGITS'][t], preds[t - 1], cur, preds[t], nxt, backs[t], rows, k, end, ended_count=ended[t:t + 1])
+        ops.beam_select(logits, preds[t - 1], cur, preds[t], nxt, backs[t], rows, k, end, ended_count=ended[t:t + 1])
         done = t + 1
     return preds, backs, lps, ended, done, B, k, R, L, extras
 
@@ -158,9 +146,7 @@ def beam_finish(model, preds, backs, lps, ended, done, B, k, R, L, extras):
     best = last_lp.topk(1)[1].squeeze(1)                          # layer.py:456-460
     # (one gather: indexing clip by clip reads best[i] back to the host B times -- 128 synchronisations per batch)
     out = all_preds.gather(1, best.view(B, 1, 1).expand(B, 1, all_preds.shape[2])).squeeze(1)
-    if extras is not None:
-        return out, extras[0], extras[1], []
-    return out, 0, 0, 0
+    return model._public(out, extras, [])
 
 
 MAX_BEAM, MAX_WORDS = 8, 64          # limits of dlsg_beam_select_hist / dlsg_beam_finalize
@@ -197,20 +183,9 @@ def beam_nbest(model, visual_feats, region_feats, n_best=None, length_penalty=0.
     n = check_nbest_options(k, L, n_best, length_penalty, no_repeat_ngram, min_len)
     mems, sv, seed, _ = _encode(model, visual_feats, region_feats)
     ops = model.ops
-    frames = mems[0]
-    s = E.dec_prepare(ops, dec, mems, sv, False, seed)
-    B, V = frames.shape[0], dec.vocab_size
+    advance, B, R, _ = _beam_setup(model, mems, sv, seed, k)
     end = dec.vocab('<end>')
-    if k > V:
-        raise ValueError('Target vocab size (%d) too small relative to per_node_beam_size (%d)' % (V, k))
-    s['kv_div'] = k
-    s['gq'] = _expand_rows(s['gq'], k)
-    R = B * k
-    E.dec_alloc(dec, s, frames, R, L)
-    dev = frames.device
-    state_keys = ['LHP', 'QH', 'QC', 'LC']                         # two slots per step, as in beam_search_from
-    big = {key: torch.zeros(2 * L + 2, R, s[key].shape[2], dtype=torch.float32, device=dev) for key in state_keys}
-    Emb = dec.word_embed.weight
+    dev = mems[0].device
     preds = torch.empty(2, R, dtype=torch.int64, device=dev)       # ping-pong: the history keeps the tokens
     hist = torch.empty(2, R, L, dtype=torch.int64, device=dev)     # filled by step 0
     back = torch.empty(R, dtype=torch.int64, device=dev)
@@ -218,15 +193,9 @@ def beam_nbest(model, visual_feats, region_feats, n_best=None, length_penalty=0.
     lps = torch.zeros(2, R, dtype=torch.float32, device=dev)
     words = torch.full((R,), dec.vocab('<start>'), dtype=torch.int64, device=dev)
     for t in range(L):
-        if t:
-            ops.gather_rows_multi([big[key][2 * t - 1] for key in state_keys], rows, [big[key][2 * t] for key in state_keys])
-        for key in state_keys:
-            s[key] = big[key][t:]
-        ops.embed_fwd(Emb, words, s['WE'][t])
-        E.dec_step(ops, dec, s, t, frames, False, seed, R)
-        E.dec_logits(ops, dec, s, t, t + 1)
-        ops.beam_select_hist(s['LOGITS'][t], words, lps[t % 2], preds[t % 2], lps[(t + 1) % 2], back, rows, k, end,
-                             hist[t % 2], hist[(t + 1) % 2], t, no_repeat_ngram, min_len)
+        logits = advance(t, words, rows)
+        ops.beam_select_hist(logits, words, lps[t % 2], preds[t % 2], lps[(t + 1) % 2], back, rows, k, end, hist[t % 2],
+                             hist[(t + 1) % 2], t, no_repeat_ngram, min_len)
         words = preds[t % 2]
     ids = torch.empty(B, n, L, dtype=torch.int64, device=dev)
     scores = torch.empty(B, n, dtype=torch.float32, device=dev)

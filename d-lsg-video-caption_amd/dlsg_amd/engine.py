@@ -1036,21 +1036,25 @@ def dec_alloc(dec, s, ref, B, L):
     s['LOGITS'] = _empty(ref, L, B, V)
 
 
+def dec_begin(ops, dec, mems, sv, L, training, seed):
+    """What every word loop starts with: the step-invariant work, the state arrays, <start> in slot 0 and the word-dropout rate
+    (kept as s['pw'] for the backward).  -> (s, mems[0], its rows, the embedding matrix, s['IDS'], the rate)"""
+    s = dec_prepare(ops, dec, mems, sv, training, seed)
+    ref = mems[0]
+    B = ref.shape[0]
+    dec_alloc(dec, s, ref, B, L)
+    s['IDS'][0].fill_(dec.vocab('<start>'))
+    s['pw'] = dec.p_drop if training else 0.0
+    return s, ref, B, dec.word_embed.weight, s['IDS'], s['pw']
+
+
 def dec_fwd(ops, dec, mems, sv, captions, L, coins, training, seed, dev_coins=None):
     """Decoder.forward, training / greedy branch (models/layer.py:394-447).
     coins[i] True -> step i feeds captions[:, i] to step i+1, else the argmax of its own logits.
     captions None -> greedy inference (all coins False).  Returns the decoder state dict.
     dev_coins: optional int32 device array of the same coins; then the word choice happens on device
     (`select_embed`) and the launch sequence no longer depends on the coin pattern (hipGraph capture)."""
-    s = dec_prepare(ops, dec, mems, sv, training, seed)
-    ref = mems[0]
-    B = ref.shape[0]
-    dec_alloc(dec, s, ref, B, L)
-    E = dec.word_embed.weight
-    pw = dec.p_drop if training else 0.0
-    ids = s['IDS']
-    ids[0].fill_(dec.vocab('<start>'))
-    s['pw'] = pw
+    s, ref, B, E, ids, pw = dec_begin(ops, dec, mems, sv, L, training, seed)
     if dev_coins is not None:
         ops.embed_fwd(E, ids[0], s['WE'][0], p=pw, seed=seed, site=SITE_WORD, row0=0)
         pre = captions is not None and L > 1
@@ -1104,15 +1108,7 @@ def dec_sample(ops, dec, mems, sv, L, training, seed, temperature):
     words), LOGP (L, B) their log-probabilities and LENS (B,): first <end> position + 1, else L.  The word-dropout rows are those
     of dec_fwd, so a teacher-forced pass over the sampled words with the same seed sees the same masks.  No host
     synchronisation: capturable, the seed may be a device word."""
-    s = dec_prepare(ops, dec, mems, sv, training, seed)
-    ref = mems[0]
-    B = ref.shape[0]
-    dec_alloc(dec, s, ref, B, L)
-    E = dec.word_embed.weight
-    pw = dec.p_drop if training else 0.0
-    ids = s['IDS']
-    ids[0].fill_(dec.vocab('<start>'))
-    s['pw'] = pw
+    s, ref, B, E, ids, pw = dec_begin(ops, dec, mems, sv, L, training, seed)
     s['LOGP'] = _empty(ref, L, B)
     s['LENS'] = torch.full((B,), L, dtype=torch.int64, device=ref.device)
     end = dec.vocab('<end>')
@@ -1123,6 +1119,16 @@ def dec_sample(ops, dec, mems, sv, L, training, seed, temperature):
         ops.sample_embed(s['LOGITS'][t], E, ids[t + 1], s['WE'][t + 1], s['LOGP'][t], s['LENS'], t, end, temperature=temperature,
                          p=pw, seed=seed, site=SITE_WORD, site_sample=SITE_SAMPLE, row0=(t + 1) * B)
     return s
+
+
+def dec_outputs(ops, s, alpha=True):
+    """the word loop's time-major logits (L, B, V) and attention weights as the batch-major tensors a caller of forward() gets;
+    alpha=False: no copy of the weights, an empty tensor in their place (the one-attention models do not return them)"""
+    def batch_major(x):
+        y = _empty(x, x.shape[1], x.shape[0], x.shape[2])
+        ops.permute_tb(x, y)
+        return y
+    return batch_major(s['LOGITS']), batch_major(s['ALPHA']) if alpha else torch.empty(0, device=s['ALPHA'].device)
 
 
 def dec_bwd(ops, dec, sv, G, dlogits_tm, seed, training, dalpha_tm=None):

@@ -113,10 +113,7 @@ class GreedyGraph(_InferenceGraph):
     ids are identical to the eager `model(frames, regions, None)` path with beam_size 1."""
 
     def _run(self):
-        L = self.model.decoder.max_words
-        sv = {}
-        self.model._engine_forward(self.frames, self.regions, None, L, [False] * L, False, 0, sv)
-        return sv['dec']['IDS'][1:].t().contiguous()
+        return self.model._greedy_ids(self.frames, self.regions, 0)[0]
 
 
 class SampleGraph(_InferenceGraph):
@@ -133,14 +130,7 @@ class SampleGraph(_InferenceGraph):
         super().__init__(model, frames, regions)
 
     def _run(self):
-        n = self.n
-        if self.share_encoder:
-            s = self.model._sample_forward(self.frames, self.regions, self.model.decoder.max_words, self.training, self.seed,
-                                           self.temperature, {}, n=n, share_encoder=True)
-            return s['IDS'][1:].t().contiguous(), s['LOGP'].t().contiguous(), s['LENS']
-        s = self.model._sample_forward(expand_rows(self.frames, n), expand_rows(self.regions, n), self.model.decoder.max_words,
-                                       self.training, self.seed, self.temperature, {})
-        return s['IDS'][1:].t().contiguous(), s['LOGP'].t().contiguous(), s['LENS']
+        return self.model.sample(self.frames, self.regions, self.n, self.temperature, self.seed, self.share_encoder)
 
     @torch.no_grad()
     def __call__(self, frames, regions, seed):

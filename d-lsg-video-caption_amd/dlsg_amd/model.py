@@ -165,16 +165,27 @@ class _HipModel(_ArenaModule):
         return (0x5DEECE66D * self.seed_counter + 0xB) & 0xFFFFFFFFFFFF
 
     # ------------------------------------------------------------------ to be provided by subclasses
-    def _engine_forward(self, frames, regions, captions, L, coins, training, seed, sv, seq_per_clip=1):
+    seq_per_clip_ok = False            # several captions per clip on one encoder pass: CapGnnModel
+
+    def _memories(self, frames, regions, training, seed, sv):
+        """the class's encoder on B clips -> the list of (B, P, H) tensors its decoder attends over, one per attention stream:
+        their row means form the global feature, and `_public` hands the first and the last back as obj / mot proposals"""
         raise NotImplementedError
 
-    def _engine_backward(self, sv, dlogits_tm, dobj, dmot, dalpha_tm, training, seed, seq_per_clip=1):
+    def _engine_backward(self, sv, dlogits_tm, dobj, dmot, dalpha_tm, training, seed, on_bucket=None, seq_per_clip=1):
         raise NotImplementedError
 
-    @staticmethod
-    def _check_seq_per_clip(seq_per_clip, clips, captions):
+    def _public(self, x, proposals, alpha):
+        """what forward() returns for the logits or ids x (models/model.py:94-107: the frames-only variants return no proposals)"""
+        return x, 0, 0, 0
+
+    # ------------------------------------------------------------------ engine schedules shared by the classes
+    def _check_seq_per_clip(self, seq_per_clip, clips, captions):
         """seq_per_clip = n >= 1 captions per clip: `captions` (None at inference) must have n rows per clip"""
         n = int(seq_per_clip)
+        if n != 1 and not self.seq_per_clip_ok:
+            raise ValueError('seq_per_clip > 1 (several captions per clip on one encoder pass) is implemented for CapGnnModel '
+                             'only, not for %s' % type(self).__name__)
         if n < 1:
             raise ValueError('seq_per_clip must be >= 1, not %r' % (seq_per_clip,))
         if captions is not None and captions.shape[0] != n * clips:
@@ -182,10 +193,68 @@ class _HipModel(_ArenaModule):
                              % (captions.shape[0], clips, n, n * clips))
         return n
 
-    def _only_one_seq_per_clip(self, seq_per_clip):
-        if int(seq_per_clip) != 1:
-            raise ValueError('seq_per_clip > 1 (several captions per clip on one encoder pass) is implemented for CapGnnModel '
-                             'only, not for %s' % type(self).__name__)
+    def _encoder_pass(self, frames, regions, training, seed, sv, n=1):
+        """What every forward pass begins with: the forward GEMM policy, the class's encoder on the B clips, and its memories fanned
+        out to the B*n rows the decoder runs on (row b*n + i = clip b; sv keeps the B-row tensors).
+        -> (the memories of the B clips, of the B*n rows)"""
+        ops = self.ops
+        self._gemm_policy(False)
+        if getattr(ops, 'colsum_defer', None) is not None:
+            ops.colsum_defer = None         # (a backward that raised half-way must not leave the collector armed)
+        frames = frames.contiguous().float()
+        regions = regions.contiguous().float()
+        props = self._memories(frames, regions, training, seed, sv)
+        sv['frames'], sv['regions'], sv['enc_out'] = frames, regions, props
+        mems = props
+        if n != 1:
+            # seq_per_clip = n > 1: the encoder ran on the B clips, the decoder runs on their B*n caption rows
+            mems = [torch.empty((x.shape[0] * n,) + tuple(x.shape[1:]), dtype=torch.float32, device=x.device) for x in props]
+            for x, y in zip(props, mems):
+                ops.rows_repeat(x, y, n)
+        sv['dec_gsrc'] = list(mems)
+        return props, mems
+
+    def _engine_forward(self, frames, regions, captions, L, coins, training, seed, sv, dev_coins=None, outputs=True, seq_per_clip=1):
+        n = self._check_seq_per_clip(seq_per_clip, frames.shape[0], captions)
+        props, mems = self._encoder_pass(frames, regions, training, seed, sv, n)
+        s = E.dec_fwd(self.ops, self.decoder, list(mems), sv, captions, L, coins, training, seed, dev_coins)
+        if not outputs:            # fused trainer: the loss reads the time-major logits in place
+            return None
+        logits, alpha = E.dec_outputs(self.ops, s, alpha=self.decoder.multi_modal)
+        return logits, props[0], props[-1], alpha
+
+    @torch.no_grad()
+    def _greedy_ids(self, frames, regions, seed, L=None):
+        """eval-mode greedy decoding (no dropout, so the seed is immaterial) -> (ids (B, L), the encoder's memories)"""
+        L = self.decoder.max_words if L is None else L
+        sv = {}
+        self._engine_forward(frames, regions, None, L, [False] * L, False, seed, sv)
+        return sv['dec']['IDS'][1:].t().contiguous(), sv['enc_out']
+
+    # ------------------------------------------------------------------ public forward
+    def forward(self, visual_feats, region_feats, caption, max_words=None, teacher_forcing_ratio=1.0, seq_per_clip=1):
+        n = self._check_seq_per_clip(seq_per_clip, visual_feats.shape[0], caption)
+        self.flatten_parameters_()
+        dec = self.decoder
+        infer = caption is None
+        L = dec.max_words if max_words is None else max_words
+        if infer and n != 1:
+            raise ValueError('seq_per_clip > 1 needs captions; for several decoded captions per clip use sample() or beam_search()')
+        if infer and dec.beam_size != 1:
+            from .beam import beam_infer
+            return beam_infer(self, visual_feats, region_feats)
+        coins = self._draw_coins(L, infer, teacher_forcing_ratio)
+        seed = self.next_seed()
+        if infer:
+            ids, props = self._greedy_ids(visual_feats, region_feats, seed, L)
+            return self._public(ids, props, [])
+        params = [p for _, p in self.named_parameters()]
+        if torch.is_grad_enabled() and any(p.requires_grad for p in params):
+            out = _ModelFn.apply(self, visual_feats, region_feats, caption, L, coins, seed, n, *params)
+        else:
+            with torch.no_grad():
+                out = self._engine_forward(visual_feats, region_feats, caption, L, coins, self.training, seed, {}, seq_per_clip=n)
+        return self._public(out[0], out[1:3], out[3])
 
     def sample(self, visual_feats, region_feats, n=1, temperature=1.0, seed=None, share_encoder=False):
         raise NotImplementedError('sampled decoding (self-critical training) is implemented for CapGnnModel only')
@@ -212,10 +281,8 @@ class _ModelFn(torch.autograd.Function):
     def forward(ctx, model, frames, regions, captions, L, coins, seed, seq_per_clip, *params):
         sv = {}
         training = model.training
-        # (keyword only when set: the default form calls the engine exactly as before)
-        kw = {'seq_per_clip': seq_per_clip} if seq_per_clip != 1 else {}
-        outs = model._engine_forward(frames, regions, captions, L, coins, training, seed, sv, **kw)
-        ctx.model, ctx.sv, ctx.seed, ctx.training, ctx.kw = model, sv, seed, training, kw
+        outs = model._engine_forward(frames, regions, captions, L, coins, training, seed, sv, seq_per_clip=seq_per_clip)
+        ctx.model, ctx.sv, ctx.seed, ctx.training, ctx.seq_per_clip = model, sv, seed, training, seq_per_clip
         ctx.nparams = len(params)
         return outs
 
@@ -229,7 +296,7 @@ class _ModelFn(torch.autograd.Function):
         if dalpha is not None and dalpha.numel() > 0:
             da_tm = torch.empty(L, Bn, dalpha.shape[-1], dtype=torch.float32, device=dlogits.device)
             ops.permute_tb(dalpha.contiguous(), da_tm)
-        model._engine_backward(ctx.sv, dl_tm, dobj, dmot, da_tm, ctx.training, ctx.seed, **ctx.kw)
+        model._engine_backward(ctx.sv, dl_tm, dobj, dmot, da_tm, ctx.training, ctx.seed, seq_per_clip=ctx.seq_per_clip)
         G = model.grad_views()
         grads = []
         for name, p in model.named_parameters():
@@ -261,6 +328,8 @@ class CapGnnModel(_HipModel):
             for e in ('obj_encoder', 'motion_encoder'):
                 names += ['encoder.%s.obj_visual_norm.1.weight' % e, 'encoder.%s.obj_visual_norm.1.bias' % e]
         return frozenset(names)
+
+    seq_per_clip_ok = True
 
     def __init__(self, args, vocab):
         super().__init__()
@@ -314,42 +383,11 @@ class CapGnnModel(_HipModel):
                                             (enc.motion_encoder, 'encoder.motion_encoder', E.SITE_PSL_MOT)], regions, sv, training, seed)
         return obj, mot
 
-    def _fan_out(self, obj, mot, n, sv):
-        """the proposals of B clips -> the B*n caption rows of the decoder (row b*n + i = clip b); sv keeps the B-row tensors"""
-        sv['enc_out'] = [obj, mot]
-        if n == 1:
-            return obj, mot
-        ops = self.ops
-        out = []
-        for x in (obj, mot):
-            y = torch.empty((x.shape[0] * n,) + tuple(x.shape[1:]), dtype=torch.float32, device=x.device)
-            ops.rows_repeat(x, y, n)
-            out.append(y)
-        return out
+    def _memories(self, frames, regions, training, seed, sv):
+        return list(self._encode(frames, regions, training, seed, sv))
 
-    def _engine_forward(self, frames, regions, captions, L, coins, training, seed, sv, dev_coins=None, outputs=True, seq_per_clip=1):
-        ops = self.ops
-        n = self._check_seq_per_clip(seq_per_clip, frames.shape[0], captions)
-        self._gemm_policy(False)
-        if getattr(ops, 'colsum_defer', None) is not None:
-            ops.colsum_defer = None         # (a backward that raised half-way must not leave the collector armed)
-        frames = frames.contiguous().float()
-        regions = regions.contiguous().float()
-        obj, mot = self._encode(frames, regions, training, seed, sv)
-        sv['frames'], sv['regions'] = frames, regions
-        # seq_per_clip = n > 1: the encoder ran on the B clips, the decoder runs on their B*n caption rows
-        mems = self._fan_out(obj, mot, n, sv)
-        sv['dec_gsrc'] = list(mems)
-        s = E.dec_fwd(ops, self.decoder, list(mems), sv, captions, L, coins, training, seed, dev_coins)
-        if not outputs:            # fused trainer: the loss reads the time-major logits in place
-            return None
-        B = frames.shape[0] * n
-        V = self.decoder.vocab_size
-        logits = torch.empty(B, L, V, dtype=torch.float32, device=frames.device)
-        ops.permute_tb(s['LOGITS'], logits)
-        alpha = torch.empty(B, L, s['ALPHA'].shape[-1], dtype=torch.float32, device=frames.device)
-        ops.permute_tb(s['ALPHA'], alpha)
-        return logits, obj, mot, alpha
+    def _public(self, x, proposals, alpha):
+        return x, proposals[0], proposals[-1], alpha
 
     def _engine_backward(self, sv, dlogits_tm, dobj, dmot, dalpha_tm, training, seed, on_bucket=None, seq_per_clip=1):
         ops, enc = self.ops, self.encoder
@@ -430,50 +468,6 @@ class CapGnnModel(_HipModel):
         if on_bucket:
             on_bucket(('encoder.motion_encoder', 'encoder.obj_encoder'))
 
-    def _sample_forward(self, frames, regions, L, training, seed, temperature, sv, n=1, share_encoder=False):
-        """encoder + sampled decoding (engine.dec_sample) -> the decoder state (IDS, LOGP, LENS).  share_encoder: frames / regions
-        are the B clips, the encoder runs on them once and the decoding on their B*n fanned-out rows; else the caller has
-        repeated the clips and n is not used"""
-        ops = self.ops
-        self._gemm_policy(False)
-        if getattr(ops, 'colsum_defer', None) is not None:
-            ops.colsum_defer = None
-        frames = frames.contiguous().float()
-        regions = regions.contiguous().float()
-        obj, mot = self._encode(frames, regions, training, seed, sv)
-        sv['frames'], sv['regions'] = frames, regions
-        mems = self._fan_out(obj, mot, n if share_encoder else 1, sv)
-        sv['dec_gsrc'] = list(mems)
-        return E.dec_sample(ops, self.decoder, list(mems), sv, L, training, seed, temperature)
-
-    # ------------------------------------------------------------------ public forward
-    def forward(self, visual_feats, region_feats, caption, max_words=None, teacher_forcing_ratio=1.0, seq_per_clip=1):
-        n = self._check_seq_per_clip(seq_per_clip, visual_feats.shape[0], caption)
-        self.flatten_parameters_()
-        dec = self.decoder
-        infer = caption is None
-        L = dec.max_words if max_words is None else max_words
-        if infer and n != 1:
-            raise ValueError('seq_per_clip > 1 needs captions; for several decoded captions per clip use sample() or beam_search()')
-        if infer and dec.beam_size != 1:
-            from .beam import beam_infer
-            return beam_infer(self, visual_feats, region_feats)
-        coins = self._draw_coins(L, infer, teacher_forcing_ratio)
-        seed = self.next_seed()
-        if infer:
-            sv = {}
-            with torch.no_grad():
-                self._engine_forward(visual_feats, region_feats, None, L, coins, False, seed, sv)
-            ids = sv['dec']['IDS'][1:].t().contiguous()
-            return ids, sv['dec_gsrc'][0], sv['dec_gsrc'][1], []
-        kw = {'seq_per_clip': n} if n != 1 else {}
-        params = [p for _, p in self.named_parameters()]
-        needs_grad = torch.is_grad_enabled() and any(p.requires_grad for p in params)
-        if not needs_grad:
-            with torch.no_grad():
-                return self._engine_forward(visual_feats, region_feats, caption, L, coins, self.training, seed, {}, **kw)
-        return _ModelFn.apply(self, visual_feats, region_feats, caption, L, coins, seed, n, *params)
-
     @torch.no_grad()
     def sample(self, visual_feats, region_feats, n=1, temperature=1.0, seed=None, share_encoder=False):
         """Draw n captions per clip from softmax(logits / temperature) (self-critical training; temperature 0 is greedy).
@@ -490,13 +484,11 @@ class CapGnnModel(_HipModel):
         self.flatten_parameters_()
         if seed is None:
             seed = self.next_seed()
+        if not share_encoder:           # the clips repeated n times, then the shared form with one row per clip
+            visual_feats, region_feats, n = expand_rows(visual_feats, n), expand_rows(region_feats, n), 1
         sv = {}
-        if share_encoder:
-            s = self._sample_forward(visual_feats, region_feats, self.decoder.max_words, self.training, seed, temperature, sv,
-                                     n=int(n), share_encoder=True)
-            return s['IDS'][1:].t().contiguous(), s['LOGP'].t().contiguous(), s['LENS']
-        s = self._sample_forward(expand_rows(visual_feats, n), expand_rows(region_feats, n), self.decoder.max_words, self.training,
-                                 seed, temperature, sv)
+        _, mems = self._encoder_pass(visual_feats, region_feats, self.training, seed, sv, int(n))
+        s = E.dec_sample(self.ops, self.decoder, list(mems), sv, self.decoder.max_words, self.training, seed, temperature)
         return s['IDS'][1:].t().contiguous(), s['LOGP'].t().contiguous(), s['LENS']
 
 
@@ -514,23 +506,12 @@ class CapBaseline1(_HipModel):
     def update_beam_size(self, beam_size):
         self.decoder.update_beam_size(beam_size)
 
-    def _engine_forward(self, frames, regions, captions, L, coins, training, seed, sv, dev_coins=None, outputs=True, seq_per_clip=1):
-        self._only_one_seq_per_clip(seq_per_clip)
-        ops = self.ops
-        self._gemm_policy(False)
-        frames = frames.contiguous().float()
+    def _memories(self, frames, regions, training, seed, sv):
         B, T, F = frames.shape
-        H = self.decoder.visual_hidden_size
-        enc = E.encvis_fwd(ops, self.encoder, 'encoder', frames.view(B * T, F), B, T, sv, training, seed).view(B, T, H)
-        sv['frames'] = frames
-        sv['dec_gsrc'] = [enc]
-        s = E.dec_fwd(ops, self.decoder, [enc], sv, captions, L, coins, training, seed, dev_coins)
-        V = self.decoder.vocab_size
-        logits = torch.empty(B, L, V, dtype=torch.float32, device=frames.device)
-        ops.permute_tb(s['LOGITS'], logits)
-        return logits, enc, enc, torch.empty(0, device=frames.device)
+        enc = E.encvis_fwd(self.ops, self.encoder, 'encoder', frames.view(B * T, F), B, T, sv, training, seed)
+        return [enc.view(B, T, -1)]
 
-    def _engine_backward(self, sv, dlogits_tm, dobj, dmot, dalpha_tm, training, seed, on_bucket=None):
+    def _engine_backward(self, sv, dlogits_tm, dobj, dmot, dalpha_tm, training, seed, on_bucket=None, seq_per_clip=1):
         ops = self.ops
         self._gemm_policy(True)
         G = self._G
@@ -543,29 +524,6 @@ class CapBaseline1(_HipModel):
         E.encvis_bwd(ops, self.encoder, 'encoder', frames.view(B * T, F), B, T, sv, G, denc.view(B * T, -1), training, seed)
         if on_bucket:
             on_bucket(('decoder', 'encoder'))
-
-    def forward(self, visual_feats, region_feats, caption, max_words=None, teacher_forcing_ratio=1.0, seq_per_clip=1):
-        self._only_one_seq_per_clip(seq_per_clip)
-        self.flatten_parameters_()
-        dec = self.decoder
-        infer = caption is None
-        L = dec.max_words if max_words is None else max_words
-        if infer and dec.beam_size != 1:
-            from .beam import beam_infer
-            return beam_infer(self, visual_feats, region_feats)
-        coins = self._draw_coins(L, infer, teacher_forcing_ratio)
-        seed = self.next_seed()
-        if infer:
-            sv = {}
-            with torch.no_grad():
-                self._engine_forward(visual_feats, region_feats, None, L, coins, False, seed, sv)
-            return sv['dec']['IDS'][1:].t().contiguous(), 0, 0, 0
-        params = [p for _, p in self.named_parameters()]
-        if not (torch.is_grad_enabled() and any(p.requires_grad for p in params)):
-            with torch.no_grad():
-                return self._engine_forward(visual_feats, region_feats, caption, L, coins, self.training, seed, {})[0], 0, 0, 0
-        out = _ModelFn.apply(self, visual_feats, region_feats, caption, L, coins, seed, 1, *params)
-        return out[0], 0, 0, 0
 
 
 class CapBaselineModel(_HipModel):
@@ -599,31 +557,16 @@ class CapBaselineModel(_HipModel):
     def update_beam_size(self, beam_size):
         self.decoder.update_beam_size(beam_size)
 
-    def _motion_nodes(self, frames, regions, training, seed, sv):
+    def _memories(self, frames, regions, training, seed, sv):
         ops, enc = self.ops, self.encoder
         B, T, F = frames.shape
         f2 = frames.view(B * T, F)
         mot_in = E.encvis_fwd(ops, enc.motion_pre_encoder, 'encoder.motion_pre_encoder', f2, B, T, sv, training, seed)
         mot = E.tun_fwd(ops, enc.motion_encoder, 'encoder.motion_encoder', mot_in, regions, sv, training, seed,
                         E.SITE_PSL_MOT, self.fused_o2v)
-        return mot.view(B, T, -1)
+        return [mot.view(B, T, -1)]
 
-    def _engine_forward(self, frames, regions, captions, L, coins, training, seed, sv, dev_coins=None, outputs=True, seq_per_clip=1):
-        self._only_one_seq_per_clip(seq_per_clip)
-        ops = self.ops
-        self._gemm_policy(False)
-        frames = frames.contiguous().float()
-        regions = regions.contiguous().float()
-        mot = self._motion_nodes(frames, regions, training, seed, sv)
-        sv['frames'], sv['regions'] = frames, regions
-        sv['dec_gsrc'] = [mot]
-        s = E.dec_fwd(ops, self.decoder, [mot], sv, captions, L, coins, training, seed, dev_coins)
-        B = frames.shape[0]
-        logits = torch.empty(B, L, self.decoder.vocab_size, dtype=torch.float32, device=frames.device)
-        ops.permute_tb(s['LOGITS'], logits)
-        return logits, mot, mot, torch.empty(0, device=frames.device)
-
-    def _engine_backward(self, sv, dlogits_tm, dobj, dmot, dalpha_tm, training, seed, on_bucket=None):
+    def _engine_backward(self, sv, dlogits_tm, dobj, dmot, dalpha_tm, training, seed, on_bucket=None, seq_per_clip=1):
         ops, enc = self.ops, self.encoder
         self._gemm_policy(True)
         G = self._G
@@ -638,8 +581,6 @@ class CapBaselineModel(_HipModel):
                      training, seed)
         if on_bucket:
             on_bucket(('decoder', 'linear_baseline', 'encoder.obj_encoder', 'encoder.motion_pre_encoder', 'encoder.motion_encoder'))
-
-    forward = CapBaseline1.forward
 
 
 def _h2d(values, dtype, device):
@@ -1094,12 +1035,10 @@ class Trainer(object):
         L = captions.shape[1]
         sv = {}
         training = model.training
-        # seq_per_clip = n > 1: frames / regions hold B clips, captions / cap_lens / seq_weights their B*n caption rows (the keyword
-        # is passed only then: the default form calls the engine exactly as before)
-        kw = {'seq_per_clip': seq_per_clip} if seq_per_clip != 1 else {}
+        # seq_per_clip = n > 1: frames / regions hold B clips, captions / cap_lens / seq_weights their B*n caption rows
         # a bucket handed to a reduction (or closing a graph segment) must be complete: deferred weight gradients go out there
         model._flush_at_buckets = self._comm_mode() != 'none' or self.force_graph_cuts
-        model._engine_forward(frames, regions, captions, L, coins, training, seed, sv, dev_coins, outputs=False, **kw)
+        model._engine_forward(frames, regions, captions, L, coins, training, seed, sv, dev_coins, outputs=False, seq_per_clip=seq_per_clip)
         s = sv['dec']
         Bn = captions.shape[0]
         dl = torch.empty_like(s['LOGITS'])
@@ -1116,7 +1055,7 @@ class Trainer(object):
             g = extra_dlogits(s['LOGITS'], sv)
             V = dl.shape[-1]
             ops.copy2d(g.contiguous().view(-1, V), dl.view(-1, V), accum=True)
-        model._engine_backward(sv, dl, None, None, None, training, seed, on_bucket=on_bucket, **kw)
+        model._engine_backward(sv, dl, None, None, None, training, seed, on_bucket=on_bucket, seq_per_clip=seq_per_clip)
         return loss
 
     def _hyper(self):

@@ -208,17 +208,13 @@ class Decoder(nn.Module):
         if infer and self.beam_size != 1:
             # layer.py:449-460 (the search always runs self.max_words steps: BeamSearch(max_steps=max_words) is built in __init__)
             from .beam import beam_search_from, beam_finish
-            return beam_finish(model, *beam_search_from(model, mems, sv, model.next_seed(), early_exit=True))[0], []
+            return beam_finish(model, *beam_search_from(model, mems, sv, model.next_seed(), early_exit=True, extras=mems))[0], []
         coins = model._draw_coins(L, infer, teacher_forcing_ratio)
         with torch.no_grad():
             s = E.dec_fwd(ops, self, mems, sv, captions, L, coins, self.training and not infer, model.next_seed())
             if infer:
                 return s['IDS'][1:].t().contiguous(), []
-            B = feats1.shape[0]
-            logits = torch.empty(B, L, self.vocab_size, dtype=torch.float32, device=feats1.device)
-            ops.permute_tb(s['LOGITS'], logits)
-            alpha = torch.empty(B, L, s['ALPHA'].shape[-1], dtype=torch.float32, device=feats1.device)
-            ops.permute_tb(s['ALPHA'], alpha)
+            logits, alpha = E.dec_outputs(ops, s)
         return logits, [alpha[:, i].unsqueeze(2) for i in range(L)]
 
     def decode_tokens(self, tokens):

@@ -45,15 +45,10 @@ class SCSTTrainer(object):
     def _sample(self, frames, regions, seed):
         model = self.model
         if not self.trainer.use_graphs:
-            if self.share_encoder:
-                return model.sample(frames, regions, n=self.n, temperature=self.temperature, seed=seed, share_encoder=True)
-            return model.sample(frames, regions, n=self.n, temperature=self.temperature, seed=seed)
+            return model.sample(frames, regions, self.n, self.temperature, seed, self.share_encoder)
         model.flatten_parameters_()
         if not self._graph_ok(self._sampler, frames, regions):
-            if self.share_encoder:
-                self._sampler = SampleGraph(model, frames, regions, self.n, self.temperature, share_encoder=True)
-            else:
-                self._sampler = SampleGraph(model, frames, regions, self.n, self.temperature)
+            self._sampler = SampleGraph(model, frames, regions, self.n, self.temperature, self.share_encoder)
         return self._sampler(frames, regions, seed)
 
     def _greedy_ids(self, frames, regions):
@@ -64,10 +59,7 @@ class SCSTTrainer(object):
             if not self._graph_ok(self._greedy, frames, regions):
                 self._greedy = GreedyGraph(model, frames, regions)
             return self._greedy(frames, regions)
-        L = model.decoder.max_words
-        sv = {}
-        model._engine_forward(frames, regions, None, L, [False] * L, False, 0, sv)
-        return sv['dec']['IDS'][1:].t().contiguous()
+        return model._greedy_ids(frames, regions, 0)[0]
 
     def _expanded_inputs(self, frames, regions):
         """the batch repeated n times, written straight into the Trainer's static graph inputs when they have that shape"""
