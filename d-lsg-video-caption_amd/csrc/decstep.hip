@@ -9,6 +9,7 @@
 //   dec_tail: language LSTM cell pointwise (+dropout) -> tanh(LayerNorm) for the vocab projection
 // Arithmetic is the same as lstm_pw_fwd / rowln_fwd / decatt_fwd (rowops.hip, attention.hip), element for element.
 #include "common.hpp"
+#include "persist.hpp"
 #include "dlsg.h"
 
 using namespace dlsg;
@@ -18,6 +19,17 @@ namespace {
 constexpr int DT = 1024;         // threads per row: one workgroup has to hide the whole chain's memory latency itself
 constexpr int MAXW = 2048;       // max Q / H / D
 constexpr int MAXP = 72;        // attended rows per stream: proposals, or the frame nodes of the baseline decoders (PositionalEncoding max_len, sublayer.py:87)
+// The EARLY instantiations of dec_mid_fwd / dec_mid_bwd request every load whose address depends on nothing the kernel computes
+// before their first phase, into registers, and use it where the other instantiation loads it: the phases of the chain no
+// longer begin with a round trip to memory.  The registers are free only while a workgroup has its CU to itself (a 1024-thread
+// workgroup may hold 128 VGPRs per thread), so the entry points take EARLY when there are no more rows than CUs.  Guards are
+// clamped addresses, not branches: every early load is issued by every lane, and a clamped lane never uses its value.
+constexpr int PF = 8;            // rows of the thread's own V' (forward) / K' (backward) column block held in registers; rows beyond stay loads
+constexpr int ROWREG = 16;       // registers for the head of the wave's first K' (forward) / V' (backward) row: 1024 columns at V = 4
+
+// a.field[s] of a kernel-argument array.  With a per-thread s the compiler fetches the element from the argument segment with
+// a vector load, one more round trip in front of the load through it; the EARLY instantiations select between the two instead.
+#define PICK(f, s) (EARLY ? ((s) ? (f)[1] : (f)[0]) : (f)[s])
 
 template <int V> struct Vec;
 template <> struct Vec<4> { using T = float4; };
@@ -124,7 +136,7 @@ __device__ __forceinline__ void ln_stats(const float* v, int n, float eps, float
     rstd = rsqrtf(block_sum(q, red) / n + eps);
 }
 
-template <int V>
+template <int V, bool EARLY>
 __global__ __launch_bounds__(DT) void dec_mid_fwd_kernel(const dlsg_dec_mid_args a) {
     __shared__ __attribute__((aligned(16))) float gb[4 * MAXW];   // activated gates; later tanh(context) of both streams
     __shared__ __attribute__((aligned(16))) float hb[MAXW];       // h
@@ -136,6 +148,33 @@ __global__ __launch_bounds__(DT) void dec_mid_fwd_kernel(const dlsg_dec_mid_args
     const int Q = a.Q, H = a.H, P = a.P, ns = a.nstream;
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     const uint64_t seed = a.seed + (a.seed_ptr ? *a.seed_ptr : 0ull);
+    constexpr int IQ = MAXW / DT, IC = 2 * MAXW / DT, KCH = ROWREG / V;
+    float lqg[IQ], lqb[IQ], lcg[IC], lcb[IC], kr[KCH][V], vr[PF][V];      // EARLY only
+    if constexpr (EARLY) {
+#pragma unroll
+        for (int i = 0; i < IQ; ++i) {
+            const int j = min(threadIdx.x + i * DT, Q - 1);
+            lqg[i] = a.lnq_g[j]; lqb[i] = a.lnq_b[j];
+        }
+#pragma unroll
+        for (int i = 0; i < IC; ++i) {
+            const int it = min(threadIdx.x + i * DT, ns * H - 1), s = it >= H, j = it - s * H;
+            lcg[i] = PICK(a.lnc_g, s)[j]; lcb[i] = PICK(a.lnc_b, s)[j];
+        }
+        {   // the head of the K' row of the wave's first score dot
+            const int d = min(w, ns * P - 1), s = d >= P, p = d - s * P;
+            const float* kp = PICK(a.Kp, s) + ((int64_t)bk * P + p) * Q;
+#pragma unroll
+            for (int c = 0; c < KCH; ++c) vload<V>(kr[c], kp + min((lane + 64 * c) * V, Q - V));
+        }
+        {   // the first PF rows of the thread's V' columns
+            const int it = threadIdx.x * V < ns * H ? threadIdx.x * V : 0, s = it >= H, j = it - s * H;
+            const float* vp = PICK(a.Vp, s) + (int64_t)bk * P * H + j;
+#pragma unroll
+            for (int p = 0; p < PF; ++p) vload<V>(vr[p], vp + (int64_t)min(p, P - 1) * H);
+        }
+        __builtin_amdgcn_sched_barrier(0);      // the scheduler must not sink these loads below the cell, next to their uses
+    }
 
     cell_row<V>(b, Q, a.slabs, a.nslab, a.slab_stride, a.addend, a.ldadd, a.b_ih, a.b_hh, a.c_prev, a.c, a.h, a.gates, 0.f, 0,
                 seed, gb, hb);
@@ -143,20 +182,37 @@ __global__ __launch_bounds__(DT) void dec_mid_fwd_kernel(const dlsg_dec_mid_args
     float mean, rstd;
     ln_stats(hb, Q, a.eps, red, mean, rstd);
     if (threadIdx.x == 0) { a.st_q[2 * b] = mean; a.st_q[2 * b + 1] = rstd; }
-    for (int j = threadIdx.x; j < Q; j += DT) {
-        float v = (hb[j] - mean) * rstd * a.lnq_g[j] + a.lnq_b[j];
+    auto query = [&](int j, float g, float bt) {
+        float v = (hb[j] - mean) * rstd * g + bt;
         if (a.p_q > 0.f) v *= drop_scale(seed, a.site_q, (uint64_t)b * Q + j, a.p_q);
         a.qcur[(int64_t)b * Q + j] = v;
         qb[j] = v;
+    };
+    if constexpr (EARLY) {
+#pragma unroll
+        for (int i = 0; i < IQ; ++i)
+            if (threadIdx.x + i * DT < Q) query(threadIdx.x + i * DT, lqg[i], lqb[i]);
+    } else {
+        for (int j = threadIdx.x; j < Q; j += DT) query(j, a.lnq_g[j], a.lnq_b[j]);
     }
     __syncthreads();
     // ---- attention scores of every stream: score_p = K'[b,p,:] . q * scale  (one wave per dot)
     for (int d = w; d < ns * P; d += DT / 64) {
         const int s = d / P, p = d % P;
-        const float* kp = a.Kp[s] + ((int64_t)bk * P + p) * Q;
+        const float* kp = PICK(a.Kp, s) + ((int64_t)bk * P + p) * Q;
         float acc = 0.f;
+        int j = lane * V;
+        if constexpr (EARLY) {
+            if (d == w) {
+#pragma unroll
+                for (int c = 0; c < KCH; ++c, j += 64 * V)
+                    if (j < Q)
+#pragma unroll
+                        for (int e = 0; e < V; ++e) acc += kr[c][e] * qb[j + e];
+            }
+        }
 #pragma unroll 4
-        for (int j = lane * V; j < Q; j += 64 * V) {
+        for (; j < Q; j += 64 * V) {
             float kv[V];
             vload<V>(kv, kp + j);
 #pragma unroll
@@ -181,11 +237,30 @@ __global__ __launch_bounds__(DT) void dec_mid_fwd_kernel(const dlsg_dec_mid_args
     float* cb = gb;
     for (int it = threadIdx.x * V; it < ns * H; it += DT * V) {
         const int s = it / H, j = it % H;
-        const float* vp = a.Vp[s] + (int64_t)bk * P * H + j;
+        const float* vp = PICK(a.Vp, s) + (int64_t)bk * P * H + j;
         float acc[V], t[4][V];
 #pragma unroll
         for (int e = 0; e < V; ++e) acc[e] = 0.f;
         int p = 0;
+        if constexpr (EARLY) {
+            if (it == threadIdx.x * V) {
+#pragma unroll
+                for (int g = 0; g < PF; g += 4)       // whole groups of four rows, then single rows: as the loops below take them
+                    if (g + 4 <= P) {
+#pragma unroll
+                        for (int u = 0; u < 4; ++u)
+#pragma unroll
+                            for (int e = 0; e < V; ++e) acc[e] += wt[s * MAXP + g + u] * vr[g + u][e];
+                        p = g + 4;
+                    }
+#pragma unroll
+                for (int r = 0; r < PF; ++r)
+                    if (r >= p && r < P)
+#pragma unroll
+                        for (int e = 0; e < V; ++e) acc[e] += wt[s * MAXP + r] * vr[r][e];
+                p = max(p, min(P, PF));
+            }
+        }
         for (; p + 4 <= P; p += 4) {
 #pragma unroll
             for (int u = 0; u < 4; ++u) vload<V>(t[u], vp + (int64_t)(p + u) * H);
@@ -199,7 +274,7 @@ __global__ __launch_bounds__(DT) void dec_mid_fwd_kernel(const dlsg_dec_mid_args
 #pragma unroll
             for (int e = 0; e < V; ++e) acc[e] += wt[s * MAXP + p] * t[0][e];
         }
-        vstore<V>(a.cpre[s] + (int64_t)b * H + j, acc);
+        vstore<V>(PICK(a.cpre, s) + (int64_t)b * H + j, acc);
 #pragma unroll
         for (int e = 0; e < V; ++e) acc[e] = tanhf(acc[e]);
         vstore<V>(cb + s * MAXW + j, acc);
@@ -221,11 +296,18 @@ __global__ __launch_bounds__(DT) void dec_mid_fwd_kernel(const dlsg_dec_mid_args
         a.st_c[0][2 * b] = m0; a.st_c[0][2 * b + 1] = r0;
         if (ns > 1) { a.st_c[1][2 * b] = m1; a.st_c[1][2 * b + 1] = r1; }
     }
-    for (int it = threadIdx.x; it < ns * H; it += DT) {
+    auto output = [&](int it, float g, float bt) {
         const int s = it / H, j = it % H;
-        float v = (cb[s * MAXW + j] - (s ? m1 : m0)) * (s ? r1 : r0) * a.lnc_g[s][j] + a.lnc_b[s][j];
-        if (a.p_att[s] > 0.f) v *= drop_scale(seed, a.site_att[s], (uint64_t)b * H + j, a.p_att[s]);
-        a.ctx[s][(int64_t)b * H + j] = v;
+        float v = (cb[s * MAXW + j] - (s ? m1 : m0)) * (s ? r1 : r0) * g + bt;
+        if (PICK(a.p_att, s) > 0.f) v *= drop_scale(seed, PICK(a.site_att, s), (uint64_t)b * H + j, PICK(a.p_att, s));
+        PICK(a.ctx, s)[(int64_t)b * H + j] = v;
+    };
+    if constexpr (EARLY) {
+#pragma unroll
+        for (int i = 0; i < IC; ++i)
+            if (threadIdx.x + i * DT < ns * H) output(threadIdx.x + i * DT, lcg[i], lcb[i]);
+    } else {
+        for (int it = threadIdx.x; it < ns * H; it += DT) output(it, a.lnc_g[it / H][it % H], a.lnc_b[it / H][it % H]);
     }
 }
 
@@ -339,14 +421,14 @@ __device__ __forceinline__ void block_sumN(float (&v)[N], float* red) {   // red
 
 // Backward of dec_mid_fwd_kernel for one batch row.  LDS holds the summed input gradient, d(pre-tanh context) of
 // both streams and the per-stream dq partials; LayerNorm temporaries live in registers across the reductions.
-template <int V>
+template <int V, bool EARLY>
 __global__ __launch_bounds__(DT) void dec_mid_bwd_kernel(const dlsg_dec_mid_bwd_args a) {
     __shared__ __attribute__((aligned(16))) float dxb[3 * MAXW];   // [d ctx_0 | d ctx_1 | d q_cur] (dense: ns*H + Q)
     __shared__ __attribute__((aligned(16))) float dcp[2 * MAXW];   // d(pre-tanh context), stream s at s*MAXW
     __shared__ __attribute__((aligned(16))) float dqb[2 * MAXW];   // dq contribution of stream s at s*MAXW
     __shared__ float dwb[2 * MAXP], dsb[2 * MAXP], wb[2 * MAXP];
     __shared__ float red[64];
-    constexpr int IC = 2 * MAXW / DT, IQ = MAXW / DT;
+    constexpr int IC = 2 * MAXW / DT, IQ = MAXW / DT, VCH = ROWREG / V;
     const int b = blockIdx.x;
     const int Q = a.Q, H = a.H, D = a.D, P = a.P, ns = a.nstream;
     const int NX = ns * H + Q, WT = NX + D;
@@ -359,7 +441,7 @@ __global__ __launch_bounds__(DT) void dec_mid_bwd_kernel(const dlsg_dec_mid_bwd_
     for (int i = 0; i < IC; ++i) {
         const int it = threadIdx.x + i * DT;
         yv[i] = 0.f;
-        if (it < ns * H) { const int s = it / H, j = it % H; yv[i] = a.cpre[s][(int64_t)b * H + j]; }
+        if (it < ns * H) { const int s = it / H, j = it % H; yv[i] = PICK(a.cpre, s)[(int64_t)b * H + j]; }
     }
 #pragma unroll
     for (int i = 0; i < IQ; ++i) {
@@ -380,9 +462,36 @@ __global__ __launch_bounds__(DT) void dec_mid_bwd_kernel(const dlsg_dec_mid_bwd_
             }
         }
     }
+    float al = 0.f;
     if (threadIdx.x < ns * P) {
-        const int s = threadIdx.x / P, p = threadIdx.x % P;
-        wb[s * MAXP + p] = a.alpha[(int64_t)b * ns * P + threadIdx.x];
+        al = a.alpha[(int64_t)b * ns * P + threadIdx.x];
+        if constexpr (!EARLY) wb[(threadIdx.x / P) * MAXP + threadIdx.x % P] = al;
+    }
+    float stc[2][2], stq[2], lcg[IC], lqg[IQ], gt[IQ][4], cv[IQ], cpv[IQ], dcv[IQ], vrow[VCH][V], kr[PF][V];      // EARLY only
+    if constexpr (EARLY) {
+#pragma unroll
+        for (int s = 0; s < 2; ++s) {
+            const float* st = PICK(a.st_c, min(s, ns - 1)) + 2 * b;
+            stc[s][0] = st[0]; stc[s][1] = st[1];
+        }
+#pragma unroll
+        for (int i = 0; i < IC; ++i) {
+            const int it = min(threadIdx.x + i * DT, ns * H - 1), s = it >= H, j = it - s * H;
+            lcg[i] = PICK(a.lnc_g, s)[j];
+        }
+        {   // the head of the V' row of the wave's first dot
+            const int d = min(w, ns * P - 1), s = d >= P, p = d - s * P;
+            const float* vp = PICK(a.Vp, s) + ((int64_t)b * P + p) * H;
+#pragma unroll
+            for (int c = 0; c < VCH; ++c) vload<V>(vrow[c], vp + min((lane + 64 * c) * V, H - V));
+        }
+        {   // the first PF rows of the thread's K' columns
+            const int it = threadIdx.x * V < ns * Q ? threadIdx.x * V : 0, s = it >= Q, j = it - s * Q;
+            const float* kp = PICK(a.Kp, s) + (int64_t)b * P * Q + j;
+#pragma unroll
+            for (int r = 0; r < PF; ++r) vload<V>(kr[r], kp + (int64_t)min(r, P - 1) * Q);
+        }
+        __builtin_amdgcn_sched_barrier(0);      // the scheduler must not sink these loads below the slab sum, next to their uses
     }
     // ---- sum the slabs of the language cell's input-gradient GEMM
     const int ncol = a.write_rec ? WT : NX;
@@ -414,6 +523,8 @@ __global__ __launch_bounds__(DT) void dec_mid_bwd_kernel(const dlsg_dec_mid_bwd_
         if (col < NX) vstore<V>(dxb + col, acc);
         else vstore<V>(a.dlh_rec + (int64_t)b * D + (col - NX), acc);
     }
+    if constexpr (EARLY)
+        if (threadIdx.x < ns * P) wb[(threadIdx.x / P) * MAXP + threadIdx.x % P] = al;
     __syncthreads();
     // ---- output_layer LayerNorm backward of both streams (x = tanh(cpre))
     float xh[IC], gx[IC];
@@ -426,14 +537,15 @@ __global__ __launch_bounds__(DT) void dec_mid_bwd_kernel(const dlsg_dec_mid_bwd_
             const int s = it / H, j = it % H;
             const float y = tanhf(yv[i]);
             yv[i] = y;
-            const float mean = a.st_c[s][2 * b], rstd = a.st_c[s][2 * b + 1];
+            const float mean = EARLY ? (s ? stc[1][0] : stc[0][0]) : PICK(a.st_c, s)[2 * b];
+            const float rstd = EARLY ? (s ? stc[1][1] : stc[0][1]) : PICK(a.st_c, s)[2 * b + 1];
             xh[i] = (y - mean) * rstd;
             float g = dxb[it];
-            if (a.p_att[s] > 0.f) g *= drop_scale(seed, a.site_att[s], (uint64_t)b * H + j, a.p_att[s]);
-            float* pc = a.part_c[s] + (int64_t)b * 2 * H;
+            if (PICK(a.p_att, s) > 0.f) g *= drop_scale(seed, PICK(a.site_att, s), (uint64_t)b * H + j, PICK(a.p_att, s));
+            float* pc = PICK(a.part_c, s) + (int64_t)b * 2 * H;
             pc[j] = g * xh[i];
             pc[H + j] = g;
-            gx[i] = g * a.lnc_g[s][j];
+            gx[i] = g * (EARLY ? lcg[i] : PICK(a.lnc_g, s)[j]);
             if (s == 0) { sums[0] += gx[i]; sums[1] += gx[i] * xh[i]; }
             else { sums[2] += gx[i]; sums[3] += gx[i] * xh[i]; }
         }
@@ -444,21 +556,46 @@ __global__ __launch_bounds__(DT) void dec_mid_bwd_kernel(const dlsg_dec_mid_bwd_
         const int it = threadIdx.x + i * DT;
         if (it < ns * H) {
             const int s = it / H, j = it % H;
-            const float rstd = a.st_c[s][2 * b + 1];
+            const float rstd = EARLY ? (s ? stc[1][1] : stc[0][1]) : PICK(a.st_c, s)[2 * b + 1];
             const float m1 = sums[2 * s] / H, m2 = sums[2 * s + 1] / H;
             const float d = rstd * (gx[i] - m1 - xh[i] * m2) * (1.f - yv[i] * yv[i]);
             dcp[s * MAXW + j] = d;
-            a.dcpre[s][(int64_t)b * H + j] = d;
+            PICK(a.dcpre, s)[(int64_t)b * H + j] = d;
         }
+    }
+    if constexpr (EARLY) {
+        // the operands of the query LayerNorm backward and of the cell backward, used three phases on: requested here, where the
+        // output LayerNorm backward's registers are free again (with them in the prologue the kernel does not fit 128 VGPRs)
+#pragma unroll
+        for (int i = 0; i < IQ; ++i) {
+            const int j = min(threadIdx.x + i * DT, Q - 1);
+            const int64_t o = (int64_t)b * Q + j;
+            lqg[i] = a.lnq_g[j];
+#pragma unroll
+            for (int g = 0; g < 4; ++g) gt[i][g] = a.gates[(int64_t)b * 4 * Q + g * Q + j];
+            cv[i] = a.c[o]; cpv[i] = a.c_prev ? a.c_prev[o] : 0.f; dcv[i] = a.dc[o];
+        }
+        stq[0] = a.st_q[2 * b]; stq[1] = a.st_q[2 * b + 1];
+        __builtin_amdgcn_sched_barrier(0);
     }
     __syncthreads();
     // ---- attention backward: dw_p = V'[b,p,:] . dcpre (+ dalpha), softmax backward, dq
     for (int d = w; d < ns * P; d += DT / 64) {
         const int s = d / P, p = d % P;
-        const float* vp = a.Vp[s] + ((int64_t)b * P + p) * H;
+        const float* vp = PICK(a.Vp, s) + ((int64_t)b * P + p) * H;
         float acc = 0.f;
+        int j = lane * V;
+        if constexpr (EARLY) {
+            if (d == w) {
+#pragma unroll
+                for (int c = 0; c < VCH; ++c, j += 64 * V)
+                    if (j < H)
+#pragma unroll
+                        for (int e = 0; e < V; ++e) acc += vrow[c][e] * dcp[s * MAXW + j + e];
+            }
+        }
 #pragma unroll 4
-        for (int j = lane * V; j < H; j += 64 * V) {
+        for (; j < H; j += 64 * V) {
             float vv[V];
             vload<V>(vv, vp + j);
 #pragma unroll
@@ -479,11 +616,30 @@ __global__ __launch_bounds__(DT) void dec_mid_bwd_kernel(const dlsg_dec_mid_bwd_
     __syncthreads();
     for (int it = threadIdx.x * V; it < ns * Q; it += DT * V) {
         const int s = it / Q, j = it % Q;
-        const float* kp = a.Kp[s] + (int64_t)b * P * Q + j;
+        const float* kp = PICK(a.Kp, s) + (int64_t)b * P * Q + j;
         float acc[V], t[4][V];
 #pragma unroll
         for (int e = 0; e < V; ++e) acc[e] = 0.f;
         int p = 0;
+        if constexpr (EARLY) {
+            if (it == threadIdx.x * V) {
+#pragma unroll
+                for (int g = 0; g < PF; g += 4)       // whole groups of four rows, then single rows: as the loops below take them
+                    if (g + 4 <= P) {
+#pragma unroll
+                        for (int u = 0; u < 4; ++u)
+#pragma unroll
+                            for (int e = 0; e < V; ++e) acc[e] += dsb[s * MAXP + g + u] * kr[g + u][e];
+                        p = g + 4;
+                    }
+#pragma unroll
+                for (int r = 0; r < PF; ++r)
+                    if (r >= p && r < P)
+#pragma unroll
+                        for (int e = 0; e < V; ++e) acc[e] += dsb[s * MAXP + r] * kr[r][e];
+                p = max(p, min(P, PF));
+            }
+        }
         for (; p + 4 <= P; p += 4) {
 #pragma unroll
             for (int u = 0; u < 4; ++u) vload<V>(t[u], kp + (int64_t)(p + u) * Q);
@@ -503,7 +659,7 @@ __global__ __launch_bounds__(DT) void dec_mid_bwd_kernel(const dlsg_dec_mid_bwd_
     // ---- query_lstm_layernorm backward + recurrent part + query cell backward
     float gq[IQ], xhq[IQ];
     float s2[2] = {0.f, 0.f};
-    const float meanq = a.st_q[2 * b], rstdq = a.st_q[2 * b + 1];
+    const float meanq = EARLY ? stq[0] : a.st_q[2 * b], rstdq = EARLY ? stq[1] : a.st_q[2 * b + 1];
 #pragma unroll
     for (int i = 0; i < IQ; ++i) {
         const int j = threadIdx.x + i * DT;
@@ -516,7 +672,7 @@ __global__ __launch_bounds__(DT) void dec_mid_bwd_kernel(const dlsg_dec_mid_bwd_
             float* pq = a.part_q + (int64_t)b * 2 * Q;
             pq[j] = g * xhq[i];
             pq[Q + j] = g;
-            gq[i] = g * a.lnq_g[j];
+            gq[i] = g * (EARLY ? lqg[i] : a.lnq_g[j]);
             s2[0] += gq[i]; s2[1] += gq[i] * xhq[i];
         }
     }
@@ -528,11 +684,12 @@ __global__ __launch_bounds__(DT) void dec_mid_bwd_kernel(const dlsg_dec_mid_bwd_
         if (j < Q) {
             const float dh = rstdq * (gq[i] - m1 - xhq[i] * m2) + rec[i];
             const float* gp = a.gates + (int64_t)b * 4 * Q;
-            const float ig = gp[j], fg = gp[Q + j], gg = gp[2 * Q + j], og = gp[3 * Q + j];
-            const float c = a.c[(int64_t)b * Q + j];
-            const float cp = a.c_prev ? a.c_prev[(int64_t)b * Q + j] : 0.f;
+            const float ig = EARLY ? gt[i][0] : gp[j], fg = EARLY ? gt[i][1] : gp[Q + j], gg = EARLY ? gt[i][2] : gp[2 * Q + j],
+                        og = EARLY ? gt[i][3] : gp[3 * Q + j];
+            const float c = EARLY ? cv[i] : a.c[(int64_t)b * Q + j];
+            const float cp = EARLY ? cpv[i] : (a.c_prev ? a.c_prev[(int64_t)b * Q + j] : 0.f);
             const float tc = tanhf(c);
-            const float dc = dh * og * (1.f - tc * tc) + a.dc[(int64_t)b * Q + j];
+            const float dc = dh * og * (1.f - tc * tc) + (EARLY ? dcv[i] : a.dc[(int64_t)b * Q + j]);
             float* dgp = a.dgates + (int64_t)b * 4 * Q;
             dgp[j] = dc * gg * ig * (1.f - ig);
             dgp[Q + j] = dc * cp * fg * (1.f - fg);
@@ -579,18 +736,24 @@ __global__ __launch_bounds__(256) void decatt_cache_grads_kernel(const dlsg_deca
 }
 
 bool vec_ok(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+// sched field of the dec_mid args: 1 / 2 name the instantiation; 0 takes the early loads when every row's workgroup gets a CU
+// of its own.  Arguments and device only: a captured graph and the eager path choose alike.
+bool early_loads(int sched, int B) { return sched == 2 || (sched == 0 && B <= persist::device_cus()); }
 
 }  // namespace
 
 extern "C" int dlsg_dec_mid_fwd(const dlsg_dec_mid_args* a, void* stream) {
-    if (!a || a->Q < 1 || a->Q > MAXW || a->H < 1 || a->H > MAXW || a->P < 1 || a->P > MAXP || a->nstream < 1 || a->nstream > 2)
+    if (!a || a->Q < 1 || a->Q > MAXW || a->H < 1 || a->H > MAXW || a->P < 1 || a->P > MAXP || a->nstream < 1 || a->nstream > 2 ||
+        a->sched < 0 || a->sched > 2)
         return DLSG_EINVAL;
     if (a->B == 0) return DLSG_OK;
     bool v4 = a->Q % 4 == 0 && a->H % 4 == 0 && a->slab_stride % 4 == 0 && a->ldadd % 4 == 0 && vec_ok(a->slabs) &&
               vec_ok(a->addend) && vec_ok(a->b_ih) && vec_ok(a->b_hh) && vec_ok(a->gates);
     for (int s = 0; s < a->nstream; ++s) v4 = v4 && vec_ok(a->Kp[s]) && vec_ok(a->Vp[s]) && vec_ok(a->cpre[s]);
-    hipLaunchKernelGGL(v4 ? dec_mid_fwd_kernel<4> : dec_mid_fwd_kernel<1>, dim3(a->B), dim3(DT), 0,
-                       reinterpret_cast<hipStream_t>(stream), *a);
+    const bool early = early_loads(a->sched, a->B);
+    hipLaunchKernelGGL(v4 ? (early ? dec_mid_fwd_kernel<4, true> : dec_mid_fwd_kernel<4, false>)
+                          : (early ? dec_mid_fwd_kernel<1, true> : dec_mid_fwd_kernel<1, false>),
+                       dim3(a->B), dim3(DT), 0, reinterpret_cast<hipStream_t>(stream), *a);
     DLSG_CHECK_LAUNCH();
     return DLSG_OK;
 }
@@ -607,13 +770,15 @@ extern "C" int dlsg_dec_tail_fwd(const dlsg_dec_tail_args* a, void* stream) {
 }
 extern "C" int dlsg_dec_mid_bwd(const dlsg_dec_mid_bwd_args* a, void* stream) {
     if (!a || a->Q < 1 || a->Q > MAXW || a->H < 1 || a->H > MAXW || a->D < 0 || a->P < 1 || a->P > MAXP || a->nstream < 1 ||
-        a->nstream > 2)
+        a->nstream > 2 || a->sched < 0 || a->sched > 2)
         return DLSG_EINVAL;
     if (a->B == 0) return DLSG_OK;
     bool v4 = a->Q % 4 == 0 && a->H % 4 == 0 && a->D % 4 == 0 && a->slab_stride % 4 == 0 && vec_ok(a->slabs) && vec_ok(a->dlh_rec);
     for (int s = 0; s < a->nstream; ++s) v4 = v4 && vec_ok(a->Kp[s]) && vec_ok(a->Vp[s]);
-    hipLaunchKernelGGL(v4 ? dec_mid_bwd_kernel<4> : dec_mid_bwd_kernel<1>, dim3(a->B), dim3(DT), 0,
-                       reinterpret_cast<hipStream_t>(stream), *a);
+    const bool early = early_loads(a->sched, a->B);
+    hipLaunchKernelGGL(v4 ? (early ? dec_mid_bwd_kernel<4, true> : dec_mid_bwd_kernel<4, false>)
+                          : (early ? dec_mid_bwd_kernel<1, true> : dec_mid_bwd_kernel<1, false>),
+                       dim3(a->B), dim3(DT), 0, reinterpret_cast<hipStream_t>(stream), *a);
     DLSG_CHECK_LAUNCH();
     return DLSG_OK;
 }

@@ -663,12 +663,13 @@ class HipOps(object):
 
     # ------------------------------------------------------------------ fused decoder step
     def dec_mid_fwd(self, slabs, addend, b_ih, b_hh, c_prev, c, h, gates, lnq, qcur, st_q, p_q, site_q, Kp, Vp, lnc, cpre,
-                    ctx, st_c, alpha, p_att, site_att, scale, seed=0, eps=1e-5, kv_div=1):
+                    ctx, st_c, alpha, p_att, site_att, scale, seed=0, eps=1e-5, kv_div=1, sched=0):
         """query cell pointwise -> LN(+dropout) -> attention over Kp/Vp (per stream) -> tanh -> LN(+dropout); one launch.
         lnq = (gamma, beta); lnc = [(gamma, beta)] per stream.  kv_div = k > 1: Kp / Vp hold one block per k consecutive rows
-        (beam search: the k beams of a clip share their clip's K', V')."""
+        (beam search: the k beams of a clip share their clip's K', V').  sched: 0 the library's choice, 1 loads where they are
+        used, 2 loads requested up front (include/dlsg.h); the outputs are bit-identical."""
         a = abi.dlsg_dec_mid_args()
-        a.kv_div = kv_div
+        a.kv_div, a.sched = kv_div, sched
         assert Kp[0].size(0) * max(1, kv_div) == c.size(0), (Kp[0].shape, c.shape, kv_div)
         a.slabs, a.nslab, a.slab_stride = _p(slabs), slabs.size(0), slabs.stride(0)
         a.addend, a.ldadd = _p(addend), (addend.stride(0) if addend is not None else 0)
@@ -724,10 +725,11 @@ class HipOps(object):
         self._check(self.lib.dlsg_dec_tail_fwd(C.byref(a), self._stream()), 'dlsg_dec_tail_fwd')
 
     def dec_mid_bwd(self, slabs, dlh_rec, cpre, st_c, lnc_g, part_c, dcpre, p_att, site_att, Kp, Vp, alpha, dalpha, ds, qh,
-                    st_q, lnq_g, part_q, p_q, site_q, rec_slabs, gates, c, c_prev, dc, dgates, scale, seed=0):
+                    st_q, lnq_g, part_q, p_q, site_q, rec_slabs, gates, c, c_prev, dc, dgates, scale, seed=0, sched=0):
         """backward of dec_mid_fwd for one word step (see include/dlsg.h).  slabs (S,B,ns*H+Q+D); dlh_rec (B,D) or None;
-        rec_slabs (S',B,Q) view of the query cell's input-gradient slabs of step t+1, or None."""
+        rec_slabs (S',B,Q) view of the query cell's input-gradient slabs of step t+1, or None.  sched as in dec_mid_fwd."""
         a = abi.dlsg_dec_mid_bwd_args()
+        a.sched = sched
         ns = len(Kp)
         B, Q = c.shape
         H, P = Vp[0].size(2), Kp[0].size(1)

@@ -345,6 +345,10 @@ typedef struct {
                                                     then hold one block per CLIP -- the beams share the lines in L2 instead of
                                                     each streaming its own expanded copy */
     uint64_t seed; const uint64_t* seed_ptr;
+    int32_t sched;                               /* 0: the library's choice (early loads when B <= the device's CUs, so that the
+                                                    workgroup has its CU's registers to itself); 1: loads requested where they
+                                                    are used; 2: every load whose address depends on nothing the kernel computes
+                                                    requested up front into registers.  Same arithmetic, bit-identical outputs */
 } dlsg_dec_mid_args;
 int dlsg_dec_mid_fwd(const dlsg_dec_mid_args* a, void* stream);
 /* language LSTM cell pointwise (+dropout on h) -> tanh(lang_lstm_layernorm(h)) for the vocab projection. */
@@ -399,6 +403,7 @@ typedef struct {
     int32_t B, Q, H, D, P, nstream;
     float scale; float pad2_;
     uint64_t seed; const uint64_t* seed_ptr;
+    int32_t sched;                       /* as dlsg_dec_mid_args.sched */
 } dlsg_dec_mid_bwd_args;
 int dlsg_dec_mid_bwd(const dlsg_dec_mid_bwd_args* a, void* stream);
 /* dK'[s][b,p,:] = sum_t ds[t,b,s*P+p] * q_cur[t,b,:],  dV'[s][b,p,:] = sum_t alpha[t,b,s*P+p] * dcpre[s][t,b,:]
