@@ -1,0 +1,294 @@
+// Filtered sampled word step (gfx950): dlsg_sample_embed with a repeated-n-gram ban, a minimum length, top-k and nucleus (top-p)
+// truncation in front of the Gumbel-max draw.  One workgroup of 256 per row holds the row's tempered logits in LDS and finds the
+// two thresholds without sorting: a descent over an order-preserving uint32 image of the float, two bits per round, each
+// round one pass over the candidates still undecided and one fixed-order block reduction (an integer count for top-k, a float
+// mass for top-p).  No atomics anywhere: two launches, or an eager launch and a graph replay, give the same bits.
+#include <math.h>
+#include <mutex>
+
+#include "common.hpp"
+#include "dlsg.h"
+
+using namespace dlsg;
+
+namespace {
+
+constexpr int SF_THREADS = 256;
+constexpr int SF_MAXL = 64;             // history positions: lane i of wave 0 holds word i
+
+// u < v as floats  <=>  ord_key(u) < ord_key(v) as unsigned, for everything but NaN (staging turns NaN into -inf, -0 into +0)
+__device__ __forceinline__ uint32_t ord_key(float z) {
+    const uint32_t u = __float_as_uint(z);
+    return u ^ ((u >> 31) ? 0xFFFFFFFFu : 0x80000000u);
+}
+
+__device__ __forceinline__ int wave_sum_i32(int v) {
+    v += __builtin_amdgcn_update_dpp(0, v, 0xB1, 0xF, 0xF, true);
+    v += __builtin_amdgcn_update_dpp(0, v, 0x4E, 0xF, 0xF, true);
+    v += __builtin_amdgcn_update_dpp(0, v, 0x141, 0xF, 0xF, true);
+    v += __builtin_amdgcn_update_dpp(0, v, 0x140, 0xF, 0xF, true);
+    return __builtin_amdgcn_readlane(v, 0) + __builtin_amdgcn_readlane(v, 16) + __builtin_amdgcn_readlane(v, 32) +
+           __builtin_amdgcn_readlane(v, 48);
+}
+
+// Block sums of NF floats and NI ints at once with ONE barrier: the waves' partial sums go to red[par], the next call uses the
+// other half, so a wave may start writing the round after next only after a barrier every reader of this round has passed.
+// The four wave sums are added in a fixed order; every thread gets the same bits.
+struct Red {
+    float f[2][3][4];
+    int i[2][4][4];
+};
+template <int NF, int NI>
+__device__ __forceinline__ void block_sum(float (&f)[3], int (&n)[4], Red& red, int& par) {
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+#pragma unroll
+    for (int q = 0; q < NF; ++q) f[q] = wave_sum_dpp(f[q]);
+#pragma unroll
+    for (int q = 0; q < NI; ++q) n[q] = wave_sum_i32(n[q]);
+    if (lane == 0) {
+#pragma unroll
+        for (int q = 0; q < NF; ++q) red.f[par][q][w] = f[q];
+#pragma unroll
+        for (int q = 0; q < NI; ++q) red.i[par][q][w] = n[q];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int q = 0; q < NF; ++q) f[q] = (red.f[par][q][0] + red.f[par][q][1]) + (red.f[par][q][2] + red.f[par][q][3]);
+#pragma unroll
+    for (int q = 0; q < NI; ++q) n[q] = (red.i[par][q][0] + red.i[par][q][1]) + (red.i[par][q][2] + red.i[par][q][3]);
+    par ^= 1;
+}
+
+// The threshold search.  A thread owns the candidates zs[tid + 256 i], i < cnt (its private list: nobody else touches those
+// slots, so it compacts them in place without a barrier).  The answer lies in [T, upper); a round splits that interval in four
+// (two bits of the image), every thread counts (MASS: sums exp(z - m) of) its candidates at or above the three inner bounds on
+// top of `acc`, what it has already seen above `upper`, one block reduction decides the quarter, and the next round drops the
+// candidates that fell out of the interval on either side.  The lists shrink about fourfold per round, so all rounds together
+// read little more than the row once.  Ends early when the interval holds no candidate (nothing left to decide), or, counting,
+// when a bound has exactly k candidates at or above it (the set is then the top k with every tie at the k-th).
+//   counting: the largest T with count{key >= T} >= k, or a smaller bound with the same set {key >= T};
+//   MASS:     the same for mass{key >= T} >= target.  The order of the additions is fixed by (V, the row's values): the same
+//             bits on every launch.
+template <bool MASS>
+__device__ __forceinline__ uint32_t descend(float* zs, int& cnt, float m, int k, float target, Red& red, int& par) {
+    const int tid = threadIdx.x;
+    uint32_t T = 0;
+    uint64_t upper = 1ull << 32;
+    float accf = 0.f;
+    int acci = 0;
+    for (int b = 30; b >= 0; b -= 2) {
+        const uint32_t c1 = T | (1u << b), c2 = T | (2u << b), c3 = T | (3u << b);
+        float f[3] = {0.f, 0.f, 0.f};
+        int n[4] = {0, 0, 0, 0};
+        int w = 0;
+        for (int i = 0; i < cnt; ++i) {
+            const float z = zs[tid + SF_THREADS * i];
+            const uint32_t key = ord_key(z);
+            if (key < T) continue;
+            if ((uint64_t)key >= upper) {
+                if constexpr (MASS) accf += __expf(z - m);
+                else ++acci;
+                continue;
+            }
+            zs[tid + SF_THREADS * w++] = z;                  // (w <= i: a slot already read)
+            if constexpr (MASS) {
+                const float e = __expf(z - m);
+                f[0] += key >= c1 ? e : 0.f; f[1] += key >= c2 ? e : 0.f; f[2] += key >= c3 ? e : 0.f;
+            } else {
+                n[1] += key >= c1; n[2] += key >= c2; n[3] += key >= c3;
+            }
+        }
+        cnt = w;
+        n[0] = w;                                            // candidates inside the interval this round split
+        int pick;
+        if constexpr (MASS) {
+            f[0] += accf; f[1] += accf; f[2] += accf;
+            block_sum<3, 1>(f, n, red, par);
+            pick = f[2] >= target ? 3 : f[1] >= target ? 2 : f[0] >= target ? 1 : 0;
+        } else {
+            n[1] += acci; n[2] += acci; n[3] += acci;
+            block_sum<0, 4>(f, n, red, par);
+            pick = n[3] >= k ? 3 : n[2] >= k ? 2 : n[1] >= k ? 1 : 0;
+        }
+        T |= (uint32_t)pick << b;
+        upper = (uint64_t)T + (1ull << b);
+        if (n[0] == 0) break;
+        if (!MASS && pick > 0 && n[pick] == k) break;
+    }
+    return T;
+}
+
+// (m, s) of an online log-sum-exp merged with (om, os), as in sample_embed_kernel
+__device__ __forceinline__ void lse_merge(float& m, float& s, float om, float os) {
+    const float nm = fmaxf(m, om);
+    s = (m == -INFINITY ? 0.f : s * __expf(m - nm)) + (om == -INFINITY ? 0.f : os * __expf(om - nm));
+    m = nm;
+}
+
+// hist: the row's earlier words, time-major: word i of row r at hist[i * hist_stride + r], i < t.
+__global__ __launch_bounds__(SF_THREADS) void sample_filter_embed_kernel(
+    const float* __restrict__ logits, int64_t ld, int V, float tau, const float* __restrict__ E, int64_t* __restrict__ ids_out,
+    float* __restrict__ out, int64_t ldo, int W, float* __restrict__ logp, int64_t* __restrict__ lens, int t, int64_t end_id, float p,
+    uint64_t seed, uint32_t site_word, uint32_t site_sample, int64_t row0, const uint64_t* seed_ptr, int top_k, float top_p,
+    int min_len, int g, const int64_t* hist, int64_t hist_stride, int32_t* __restrict__ kept) {
+    extern __shared__ float zs[];                            // V floats: the threads' candidate lists (descend)
+    __shared__ Red red;
+    __shared__ int hs[SF_MAXL], ban[SF_MAXL + 1], nban_s;
+    __shared__ float bv[4], bm[4], bs[4];
+    __shared__ int bi[4], bn[4];
+    __shared__ int64_t chosen;
+    if (seed_ptr) seed += *seed_ptr;
+    const int r = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const float* x = logits + (int64_t)r * ld;
+    const bool gumbel = tau > 0.f;
+    const float sc = gumbel ? 1.f / tau : 1.f;
+    int par = 0;
+
+    // ---- the classes this row may not choose (the rule of beam_select_hist_kernel on the row's own words)
+    const bool ngram = g > 0 && t >= g;
+    if (ngram && tid < SF_MAXL) hs[tid] = tid < t ? (int)hist[(int64_t)tid * hist_stride + r] : -1;
+    __syncthreads();
+    if (w == 0) {
+        int n = 0;
+        if (ngram) {                                         // lane i: the g-gram that starts at i ends in a class to ban if its
+            bool hit = lane <= t - g;                        // first g - 1 words are the last g - 1 of the history
+            for (int j = 0; hit && j < g - 1; ++j) hit = hs[lane + j] == hs[t - g + 1 + j];
+            const unsigned long long mk = __ballot(hit);
+            if (hit) ban[__popcll(mk & ((1ull << lane) - 1ull))] = hs[lane + g - 1];
+            n = __popcll(mk);
+        }
+        if (lane == 0) {
+            if (t < min_len) ban[n++] = (int)end_id;
+            nban_s = n;
+        }
+    }
+    __syncthreads();
+    const int nban = nban_s;
+
+    // ---- thresholds.  A word is kept iff it is alive (finite, not banned) and ord_key(z) >= T.
+    // alive(j, z): z_j = x_j / tau (+ 0: -0 becomes +0, so equal values have equal images), false for NaN, -inf and banned words
+    auto alive = [&](int j, float& z) {
+        z = x[j] * sc + 0.f;
+        bool dead = !(z > -INFINITY);
+        for (int b = 0; b < nban; ++b) dead |= ban[b] == j;
+        return !dead;
+    };
+    uint32_t T = 0;
+    if (gumbel && (top_k > 0 || top_p < 1.f)) {
+        // stage the alive words as this thread's candidate list; the row's maximum and the number of alive words
+        float m = -INFINITY;
+        int cnt = 0;
+        for (int j = tid; j < V; j += SF_THREADS) {
+            float z;
+            if (!alive(j, z)) continue;
+            zs[tid + SF_THREADS * cnt++] = z;
+            m = fmaxf(m, z);
+        }
+        float f[3] = {0.f, 0.f, 0.f};
+        int n[4] = {cnt, 0, 0, 0};
+        m = wave_max(m);
+        if (lane == 0) red.f[par][1][w] = m;
+        block_sum<0, 1>(f, n, red, par);                     // (its barrier publishes the maxima too)
+        m = fmaxf(fmaxf(red.f[par ^ 1][1][0], red.f[par ^ 1][1][1]), fmaxf(red.f[par ^ 1][1][2], red.f[par ^ 1][1][3]));
+        const int nfin = n[0];
+        bool restage = false;
+        if (top_k > 0 && top_k < nfin) {
+            T = descend<false>(zs, cnt, m, top_k, 0.f, red, par);
+            restage = true;                                  // the search consumed the lists
+        }
+        if (top_p < 1.f && nfin > 0) {
+            const uint32_t Tk = T;
+            if (restage) {                                   // what top-k kept, from the row again (it is in L2)
+                cnt = 0;
+                for (int j = tid; j < V; j += SF_THREADS) {
+                    float z;
+                    if (alive(j, z) && ord_key(z) >= Tk) zs[tid + SF_THREADS * cnt++] = z;
+                }
+            }
+            f[0] = 0.f;
+            for (int i = 0; i < cnt; ++i) f[0] += __expf(zs[tid + SF_THREADS * i] - m);
+            block_sum<1, 0>(f, n, red, par);
+            T = descend<true>(zs, cnt, m, 0, top_p * f[0], red, par);
+            T = T > Tk ? T : Tk;
+        }
+    }
+
+    // ---- the draw over the kept set, with sample_embed_kernel's noise and its online log-sum-exp
+    const uint64_t key0 = (uint64_t)(row0 + r) * (uint64_t)V;
+    float best = -INFINITY, m = -INFINITY, s = 0.f;
+    int idx = 0x7fffffff, nk = 0;
+    for (int j = tid; j < V; j += SF_THREADS) {
+        float zl;
+        if (!alive(j, zl) || ord_key(zl) < T) continue;
+        ++nk;
+        // the arithmetic below is sample_embed_kernel's, statement for statement: whatever the compiler contracts there it
+        // contracts here, and the two kernels agree to the bit
+        const float z = x[j] * sc;
+        float key = z;
+        if (gumbel) {
+            const uint32_t hi = counter_hash(seed, site_sample, key0 + j) >> 8;
+            const float e = hi < (1u << 23) ? -logf(((float)hi + 0.5f) * (1.0f / 16777216.0f))
+                                            : -log1pf(-((float)(0xFFFFFFu - hi) + 0.5f) * (1.0f / 16777216.0f));
+            key = z - logf(e);
+        }
+        if (key > best || (key == best && j < idx)) { best = key; idx = j; }
+        if (z > m) { s = s * __expf(m - z) + 1.f; m = z; }
+        else s += __expf(z - m);
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const float ov = __shfl_xor(best, o, 64);
+        const int oi = __shfl_xor(idx, o, 64);
+        if (ov > best || (ov == best && oi < idx)) { best = ov; idx = oi; }
+        const float om = __shfl_xor(m, o, 64), os = __shfl_xor(s, o, 64);
+        lse_merge(m, s, om, os);
+    }
+    nk = wave_sum_i32(nk);
+    if (lane == 0) { bv[w] = best; bi[w] = idx; bm[w] = m; bs[w] = s; bn[w] = nk; }
+    __syncthreads();
+    if (tid == 0) {
+        for (int k = 1; k < 4; ++k) {
+            if (bv[k] > best || (bv[k] == best && bi[k] < idx)) { best = bv[k]; idx = bi[k]; }
+            lse_merge(m, s, bm[k], bs[k]);
+        }
+        const int64_t id = idx == 0x7fffffff ? 0 : idx;      // nothing to keep: word 0, as sample_embed_kernel
+        chosen = id;
+        ids_out[r] = id;
+        const int nkept = (bn[0] + bn[1]) + (bn[2] + bn[3]);
+        logp[r] = nkept == 1 ? 0.f : x[id] * sc - m - logf(s);   // one word left: probability 1, whatever x * sc rounds to
+        if (kept) kept[r] = nkept;
+        if (id == end_id && lens[r] > t) lens[r] = t + 1;
+    }
+    __syncthreads();
+    const int64_t id = chosen;
+    for (int j = tid; j < W; j += SF_THREADS) {
+        float v = E[id * W + j];
+        if (p > 0.f) v *= drop_scale(seed, site_word, (uint64_t)(row0 + r) * W + j, p);
+        out[(int64_t)r * ldo + j] = v;
+    }
+}
+
+}  // namespace
+
+extern "C" int dlsg_sample_filter_embed(const float* logits, int64_t ld, int V, float temperature, const float* E, int64_t* ids_out,
+                                        float* out, int64_t ldo, int W, float* logp, int64_t* lens, int t, int64_t end_id, int rows,
+                                        float p, uint64_t seed, uint32_t site_word, uint32_t site_sample, int64_t row0,
+                                        const uint64_t* seed_ptr, int top_k, float top_p, int min_len, int no_repeat_ngram,
+                                        const int64_t* hist, int64_t hist_stride, int32_t* kept, void* stream) {
+    if (rows == 0) return DLSG_OK;
+    if (V < 1 || V > DLSG_SAMPLE_FILTER_MAXV || W < 0 || !(temperature >= 0.f) || top_k < 0 || !(top_p > 0.f && top_p <= 1.f) ||
+        min_len < 0 || no_repeat_ngram < 0 || t < 0 || t >= SF_MAXL || (no_repeat_ngram > 0 && t > 0 && (!hist || hist_stride < rows)))
+        return DLSG_EINVAL;
+    static std::once_flag once;
+    static hipError_t attr_rc = hipSuccess;
+    std::call_once(once, [] {
+        attr_rc = hipFuncSetAttribute(reinterpret_cast<const void*>(&sample_filter_embed_kernel),
+                                      hipFuncAttributeMaxDynamicSharedMemorySize, DLSG_SAMPLE_FILTER_MAXV * 4);
+    });
+    if (attr_rc != hipSuccess) return DLSG_ELAUNCH;
+    hipLaunchKernelGGL(sample_filter_embed_kernel, dim3(rows), dim3(SF_THREADS), (size_t)V * 4, reinterpret_cast<hipStream_t>(stream),
+                       logits, ld, V, temperature, E, ids_out, out, ldo, W, logp, lens, t, end_id, p, seed, site_word, site_sample,
+                       row0, seed_ptr, top_k, top_p, min_len, no_repeat_ngram, hist, hist_stride, kept);
+    DLSG_CHECK_LAUNCH();
+    return DLSG_OK;
+}

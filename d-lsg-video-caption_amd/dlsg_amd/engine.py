@@ -21,7 +21,7 @@ import math
 
 import torch
 
-from .hip import GEMM_NT, GEMM_NN, GEMM_TN, F_ACCUM, F_TANH, F_BF16X3, F_FORCE128
+from .hip import GEMM_NT, GEMM_NN, GEMM_TN, F_ACCUM, F_TANH, F_BF16X3, F_FORCE128, SAMPLE_FILTER_MAXV
 
 V_SK = 7        # include/dlsg.h DLSG_GEMM_V_SK: the persistent stream-K kernel
 
@@ -31,6 +31,7 @@ SITE_PSL_OBJ, SITE_PSL_MOT, SITE_LSTM, SITE_PE, SITE_SA, SITE_WORD, SITE_QUERY, 
 STEP_SITE = 64
 # Gumbel noise of sampled decoding (hip.sample_embed): keyed like a dropout mask, on a site no mask uses
 SITE_SAMPLE = 11
+SAMPLE_FILTER_MAXL = 64          # words of history hip.sample_filter_embed looks at (one per lane)
 
 
 def _empty(ref, *shape, dtype=torch.float32):
@@ -1102,20 +1103,50 @@ def dec_fwd(ops, dec, mems, sv, captions, L, coins, training, seed, dev_coins=No
     return s
 
 
-def dec_sample(ops, dec, mems, sv, L, training, seed, temperature):
+def check_sample_options(L, top_k=0, top_p=1.0, min_len=0, no_repeat_ngram=0, vocab_size=None):
+    """the sampling controls of `sample` / SampleGraph / dec_sample; True when at least one is on (ValueError for a bad one)"""
+    if top_k < 0 or int(top_k) != top_k:
+        raise ValueError('top_k (%r) must be an integer >= 0 (0: off)' % (top_k,))
+    if not 0.0 < top_p <= 1.0:
+        raise ValueError('top_p (%r) must be in (0, 1] (1: off)' % (top_p,))
+    if not 0 <= min_len <= L:
+        raise ValueError('min_len (%r) must be in [0, max_words = %d]' % (min_len, L))
+    if no_repeat_ngram < 0:
+        raise ValueError('no_repeat_ngram (%r) must not be negative' % (no_repeat_ngram,))
+    on = top_k > 0 or top_p < 1.0 or min_len > 0 or no_repeat_ngram > 0
+    if on and L > SAMPLE_FILTER_MAXL:
+        raise ValueError('filtered sampling keeps at most %d words of history, max_words is %d' % (SAMPLE_FILTER_MAXL, L))
+    if on and vocab_size is not None and vocab_size > SAMPLE_FILTER_MAXV:
+        raise ValueError('filtered sampling holds a row of logits in LDS: vocabulary %d > %d' % (vocab_size, SAMPLE_FILTER_MAXV))
+    return on
+
+
+def dec_sample(ops, dec, mems, sv, L, training, seed, temperature, top_k=0, top_p=1.0, min_len=0, no_repeat_ngram=0):
     """Sampled decoding for self-critical training: step t feeds a word drawn from softmax(logits_t / temperature) to step t+1
     (`sample_embed`, Gumbel noise keyed by (seed, SITE_SAMPLE, row); temperature 0 is greedy).  Fills IDS (slots 1..L: the
     words), LOGP (L, B) their log-probabilities and LENS (B,): first <end> position + 1, else L.  The word-dropout rows are those
     of dec_fwd, so a teacher-forced pass over the sampled words with the same seed sees the same masks.  No host
-    synchronisation: capturable, the seed may be a device word."""
+    synchronisation: capturable, the seed may be a device word.
+    With one of the controls on (top_k, top_p, min_len, no_repeat_ngram) the step draws with `sample_filter_embed` instead --
+    from what the bans, top-k and the nucleus leave, LOGP under that truncated distribution -- and KEPT (L, B) int32 holds the
+    number of words each draw chose from.  With all of them off the launches are the ones above."""
+    filtered = check_sample_options(L, top_k, top_p, min_len, no_repeat_ngram, dec.vocab_size)
     s, ref, B, E, ids, pw = dec_begin(ops, dec, mems, sv, L, training, seed)
     s['LOGP'] = _empty(ref, L, B)
     s['LENS'] = torch.full((B,), L, dtype=torch.int64, device=ref.device)
+    if filtered:
+        s['KEPT'] = torch.empty(L, B, dtype=torch.int32, device=ref.device)
     end = dec.vocab('<end>')
     ops.embed_fwd(E, ids[0], s['WE'][0], p=pw, seed=seed, site=SITE_WORD, row0=0)
     for t in range(L):
         dec_step(ops, dec, s, t, ref, training, seed, B)
         dec_logits(ops, dec, s, t, t + 1)
+        if filtered:
+            ops.sample_filter_embed(s['LOGITS'][t], E, ids[t + 1], s['WE'][t + 1], s['LOGP'][t], s['LENS'], t, end,
+                                    temperature=temperature, p=pw, seed=seed, site=SITE_WORD, site_sample=SITE_SAMPLE,
+                                    row0=(t + 1) * B, top_k=top_k, top_p=top_p, min_len=min_len, no_repeat_ngram=no_repeat_ngram,
+                                    hist=ids[1:], kept=s['KEPT'][t])
+            continue
         ops.sample_embed(s['LOGITS'][t], E, ids[t + 1], s['WE'][t + 1], s['LOGP'][t], s['LENS'], t, end, temperature=temperature,
                          p=pw, seed=seed, site=SITE_WORD, site_sample=SITE_SAMPLE, row0=(t + 1) * B)
     return s

@@ -122,15 +122,18 @@ class SampleGraph(_InferenceGraph):
     read from a device word, so every replay draws fresh samples; a replay with seed s gives the bits of
     `model.sample(frames, regions, n, temperature, seed=s)`.  Outputs are static buffers, valid until the next replay.
     share_encoder=True captures `model.sample(..., share_encoder=True)` instead: the encoder on the B clips, their proposals
-    fanned out in-graph (`rows_repeat`), the sampled decode steps on B*n rows; a replay with seed s gives that call's bits."""
+    fanned out in-graph (`rows_repeat`), the sampled decode steps on B*n rows; a replay with seed s gives that call's bits.
+    top_k, top_p, min_len, no_repeat_ngram, return_kept: the sampling controls of `CapGnnModel.sample`, fixed at capture."""
 
-    def __init__(self, model, frames, regions, n=1, temperature=1.0, share_encoder=False):
+    def __init__(self, model, frames, regions, n=1, temperature=1.0, share_encoder=False, top_k=0, top_p=1.0, min_len=0,
+                 no_repeat_ngram=0, return_kept=False):
         self.n, self.temperature, self.share_encoder = n, temperature, bool(share_encoder)
+        self.options = dict(top_k=top_k, top_p=top_p, min_len=min_len, no_repeat_ngram=no_repeat_ngram, return_kept=return_kept)
         self.seed = torch.zeros(1, dtype=torch.int64, device=frames.device)
         super().__init__(model, frames, regions)
 
     def _run(self):
-        return self.model.sample(self.frames, self.regions, self.n, self.temperature, self.seed, self.share_encoder)
+        return self.model.sample(self.frames, self.regions, self.n, self.temperature, self.seed, self.share_encoder, **self.options)
 
     @torch.no_grad()
     def __call__(self, frames, regions, seed):

@@ -23,6 +23,7 @@ LIB_PATH = os.path.join(_HERE, 'libdlsg_hip.so')
 _D = abi.defines
 ABI_VERSION = _D['DLSG_ABI_VERSION']
 MAXG = _D['DLSG_GEMM_MAXG']
+SAMPLE_FILTER_MAXV = _D['DLSG_SAMPLE_FILTER_MAXV']
 GEMM_NT, GEMM_NN, GEMM_TN = _D['DLSG_GEMM_NT'], _D['DLSG_GEMM_NN'], _D['DLSG_GEMM_TN']
 F_ACCUM, F_BIAS, F_TANH = _D['DLSG_GEMM_ACCUM'], _D['DLSG_GEMM_BIAS'], _D['DLSG_GEMM_TANH']
 F_FORCE64, F_FORCE128, F_TILE256, F_BF16X3 = (_D['DLSG_GEMM_' + n] for n in ('FORCE64', 'FORCE128', 'TILE256', 'BF16X3'))
@@ -1030,6 +1031,29 @@ class HipOps(object):
         self._check(self.lib.dlsg_sample_embed(_p(logits), i64(logits.stride(0)), V, f32(temperature), _p(E), _p(ids_out), _p(out),
                                                i64(out.stride(0)), out.shape[1], _p(logp), _p(lens), int(t), i64(end_id), rows, f32(p),
                                                u64(sd), u32(site), u32(site_sample), i64(row0), sp, self._stream()), 'sample_embed')
+
+    def sample_filter_embed(self, logits, E, ids_out, out, logp, lens, t, end_id, temperature=1.0, p=0.0, seed=0, site=0, site_sample=0,
+                            row0=0, top_k=0, top_p=1.0, min_len=0, no_repeat_ngram=0, hist=None, kept=None):
+        """`sample_embed` on the truncated distribution: <end> banned while t < min_len, the classes that would repeat a
+        no_repeat_ngram-gram of the row's history banned (hist: (>= t, rows) int64 time-major, the rows' earlier words), then
+        top_k and top_p; the noise of a word is `sample_embed`'s.  logp is the log-probability under the truncated
+        distribution, kept (rows,) int32 or None the number of words kept (include/dlsg.h)."""
+        rows, V = logits.shape
+        if V > SAMPLE_FILTER_MAXV:
+            raise ValueError('sample_filter_embed holds a row of logits in LDS: vocabulary %d > %d' % (V, SAMPLE_FILTER_MAXV))
+        assert E.shape[0] >= V and E.is_contiguous() and ids_out.numel() == rows and logp.numel() == rows and lens.numel() == rows
+        assert ids_out.dtype == torch.int64 and lens.dtype == torch.int64 and out.shape == (rows, E.shape[1])
+        assert kept is None or (kept.dtype == torch.int32 and kept.numel() == rows and kept.is_contiguous())
+        if no_repeat_ngram > 0 and t > 0:
+            assert hist is not None and hist.dtype == torch.int64 and hist.shape[0] >= t and hist.shape[1] == rows and \
+                hist.stride(1) == 1, 'hist: the rows\' earlier words, (>= t, rows) int64'
+        sd, sp = _seed(seed)
+        self._check(self.lib.dlsg_sample_filter_embed(
+            _p(logits), i64(logits.stride(0)), V, f32(temperature), _p(E), _p(ids_out), _p(out), i64(out.stride(0)), out.shape[1],
+            _p(logp), _p(lens), int(t), i64(end_id), rows, f32(p), u64(sd), u32(site), u32(site_sample), i64(row0), sp, int(top_k),
+            f32(top_p), int(min_len), int(no_repeat_ngram), _p(hist) if hist is not None else None,
+            i64(hist.stride(0) if hist is not None else 0), _p(kept) if kept is not None else None, self._stream()),
+            'sample_filter_embed')
 
     def copy2d(self, src, dst, accum=False):
         rows, n = src.shape

@@ -256,7 +256,8 @@ class _HipModel(_ArenaModule):
                 out = self._engine_forward(visual_feats, region_feats, caption, L, coins, self.training, seed, {}, seq_per_clip=n)
         return self._public(out[0], out[1:3], out[3])
 
-    def sample(self, visual_feats, region_feats, n=1, temperature=1.0, seed=None, share_encoder=False):
+    def sample(self, visual_feats, region_feats, n=1, temperature=1.0, seed=None, share_encoder=False, top_k=0, top_p=1.0,
+               min_len=0, no_repeat_ngram=0, return_kept=False):
         raise NotImplementedError('sampled decoding (self-critical training) is implemented for CapGnnModel only')
 
     def beam_search(self, visual_feats, region_feats, beam_size=None, n_best=None, length_penalty=0.0, no_repeat_ngram=0, min_len=0):
@@ -469,7 +470,8 @@ class CapGnnModel(_HipModel):
             on_bucket(('encoder.motion_encoder', 'encoder.obj_encoder'))
 
     @torch.no_grad()
-    def sample(self, visual_feats, region_feats, n=1, temperature=1.0, seed=None, share_encoder=False):
+    def sample(self, visual_feats, region_feats, n=1, temperature=1.0, seed=None, share_encoder=False, top_k=0, top_p=1.0,
+               min_len=0, no_repeat_ngram=0, return_kept=False):
         """Draw n captions per clip from softmax(logits / temperature) (self-critical training; temperature 0 is greedy).
         Returns (ids (B*n, L) int64, logp (B*n, L) float32 log-probabilities of the drawn words, lens (B*n,) int64: first
         <end> position + 1, else L); clip b's samples are rows b*n .. b*n + n - 1.  The clips are repeated n times before the
@@ -480,7 +482,16 @@ class CapGnnModel(_HipModel):
         are fanned out with `rows_repeat`).  The encoder's dropout masks are then keyed by the clip row 0..B-1 -- the n samples
         of a clip share them -- while decoder and word dropout stay keyed by the B*n caption rows: these are the masks of a train
         pass `forward(..., seq_per_clip=n)` / `Trainer.step(..., seq_per_clip=n)` with the same seed, so the draw is on-policy for
-        that pass; they are not the masks of the unshared draw, which is why sharing is opt-in."""
+        that pass; they are not the masks of the unshared draw, which is why sharing is opt-in.
+        Sampling controls, applied in this order at every word (`dlsg_sample_filter_embed`): min_len -- no <end> before that many
+        words; no_repeat_ngram = g > 0 -- no caption repeats a g-gram; top_k > 0 -- only the k likeliest words (ties at the k-th
+        kept); top_p < 1 -- of those, the smallest set of likeliest words whose probability reaches top_p.  logp is then the
+        log-probability under the truncated, renormalised distribution.  A word's Gumbel noise does not depend on the controls.
+        return_kept=True adds a fourth value, (B*n, L) int32: how many words each draw chose from (needs a control on)."""
+        L = self.decoder.max_words
+        filtered = E.check_sample_options(L, top_k, top_p, min_len, no_repeat_ngram, self.decoder.vocab_size)
+        if return_kept and not filtered:
+            raise ValueError('return_kept needs one of top_k, top_p, min_len, no_repeat_ngram switched on')
         self.flatten_parameters_()
         if seed is None:
             seed = self.next_seed()
@@ -488,8 +499,10 @@ class CapGnnModel(_HipModel):
             visual_feats, region_feats, n = expand_rows(visual_feats, n), expand_rows(region_feats, n), 1
         sv = {}
         _, mems = self._encoder_pass(visual_feats, region_feats, self.training, seed, sv, int(n))
-        s = E.dec_sample(self.ops, self.decoder, list(mems), sv, self.decoder.max_words, self.training, seed, temperature)
-        return s['IDS'][1:].t().contiguous(), s['LOGP'].t().contiguous(), s['LENS']
+        s = E.dec_sample(self.ops, self.decoder, list(mems), sv, L, self.training, seed, temperature, top_k=top_k, top_p=top_p,
+                         min_len=min_len, no_repeat_ngram=no_repeat_ngram)
+        out = s['IDS'][1:].t().contiguous(), s['LOGP'].t().contiguous(), s['LENS']
+        return out + (s['KEPT'].t().contiguous(),) if return_kept else out
 
 
 class CapBaseline1(_HipModel):

@@ -11,6 +11,7 @@ on-policy up to the tiling of the vocabulary product.
 import numpy as np
 import torch
 
+from .engine import check_sample_options
 from .graphs import GreedyGraph, SampleGraph, expand_rows
 from .model import Trainer, _h2d
 
@@ -26,9 +27,14 @@ class SCSTTrainer(object):
     then `Trainer.step(frames, regions, ids, lens, ..., seq_per_clip=n)` on the B clips and their B*n sampled captions -- instead
     of on the clips repeated n times.  The encoder's dropout masks are then shared by a clip's n samples (keyed by the clip
     row), in the sampling pass and in the train pass alike, so the step stays on-policy; the masks differ from those of the
-    unshared step, which is why it is opt-in."""
+    unshared step, which is why it is opt-in.
+    sample_options: a dict of `CapGnnModel.sample`'s sampling controls (top_k, top_p, min_len, no_repeat_ngram), forwarded to
+    `sample` / `SampleGraph`: the captions are then drawn from the truncated policy (the `train_sample_method = top<k> / top<p>`
+    recipe of the usual captioning toolkits).  The train pass is unchanged: it differentiates the FULL-softmax log-probabilities
+    of the words drawn from the truncated policy -- the usual, biased, estimator.  Without the keyword the step is the plain one."""
 
-    def __init__(self, model, reward, n_samples=5, baseline='mean', temperature=1.0, share_encoder=False, **trainer_kwargs):
+    def __init__(self, model, reward, n_samples=5, baseline='mean', temperature=1.0, share_encoder=False, sample_options=None,
+                 **trainer_kwargs):
         if baseline not in ('mean', 'greedy'):
             raise ValueError("baseline must be 'mean' or 'greedy', not %r" % (baseline,))
         if baseline == 'mean' and n_samples < 2:
@@ -36,6 +42,11 @@ class SCSTTrainer(object):
         self.model, self.reward = model, reward
         self.n, self.baseline, self.temperature = int(n_samples), baseline, float(temperature)
         self.share_encoder = bool(share_encoder)
+        self.sample_options = dict(sample_options or {})
+        unknown = sorted(set(self.sample_options) - {'top_k', 'top_p', 'min_len', 'no_repeat_ngram'})
+        if unknown:
+            raise ValueError('sample_options: unknown keys %s (top_k, top_p, min_len, no_repeat_ngram)' % unknown)
+        check_sample_options(model.decoder.max_words, vocab_size=model.decoder.vocab_size, **self.sample_options)
         self.trainer = Trainer(model, **trainer_kwargs)
         self._sampler = self._greedy = None
 
@@ -45,10 +56,10 @@ class SCSTTrainer(object):
     def _sample(self, frames, regions, seed):
         model = self.model
         if not self.trainer.use_graphs:
-            return model.sample(frames, regions, self.n, self.temperature, seed, self.share_encoder)
+            return model.sample(frames, regions, self.n, self.temperature, seed, self.share_encoder, **self.sample_options)
         model.flatten_parameters_()
         if not self._graph_ok(self._sampler, frames, regions):
-            self._sampler = SampleGraph(model, frames, regions, self.n, self.temperature, self.share_encoder)
+            self._sampler = SampleGraph(model, frames, regions, self.n, self.temperature, self.share_encoder, **self.sample_options)
         return self._sampler(frames, regions, seed)
 
     def _greedy_ids(self, frames, regions):

@@ -495,6 +495,28 @@ int dlsg_argmax(const float* logits, int64_t ld, int64_t* ids, int rows, int V, 
 int dlsg_sample_embed(const float* logits, int64_t ld, int V, float temperature, const float* E, int64_t* ids_out, float* out,
                       int64_t ldo, int W, float* logp, int64_t* lens, int t, int64_t end_id, int rows, float p, uint64_t seed,
                       uint32_t site_word, uint32_t site_sample, int64_t row0, const uint64_t* seed_ptr, void* stream);
+/* dlsg_sample_embed behind logits processors and warpers, in the order of the usual toolkits (processors, then warpers).  For
+ * row r at word step t, z_j = logits[r, j] / temperature:
+ *   1. bans (z_j = -inf): end_id while t < min_len; with g = no_repeat_ngram > 0, every class c for which an i <= t - g exists
+ *      with h[i .. i+g-2] == h[t-g+1 .. t-1] and h[i+g-1] == c (the rule of dlsg_beam_select_hist on the row's own words:
+ *      h[i] = hist[i * hist_stride + r], i < t, time-major ids; hist may be NULL when g == 0).  NaN and -inf logits are never kept;
+ *   2. top_k (0 = off): keep {j : z_j >= v_k}, v_k the k-th largest unbanned value -- ties at v_k are all kept;
+ *   3. top_p in (0, 1] (1 = off), over what top_k kept: theta = the largest value with mass{z_j >= theta} >= top_p * mass(kept
+ *      by top_k) (mass = sum of exp(z_j - max), float32, summed in a fixed order), keep {z_j >= theta}: never empty;
+ *   4. the draw: Gumbel-max over the kept set with the noise of dlsg_sample_embed, keyed (seed, site_sample, (row0 + r) * V + j)
+ *      -- a word's noise does not depend on the filters, and the word drawn is the one dlsg_sample_embed draws from the same row
+ *      with the logits that are not kept set to -inf;
+ *   5. logp[r] = z_id - logsumexp(z over the kept set), the log-probability under the distribution drawn from (exactly 0 when
+ *      one word is kept); kept[r] (may be NULL) = the size of the kept set; lens, out and the word dropout as dlsg_sample_embed.
+ * temperature 0: the first maximum over the unbanned words, top_k and top_p ignored, logp of the untempered softmax over the
+ * unbanned words, kept = their number.  A row with nothing to keep gives word 0 and kept 0.  No atomics and fixed reduction
+ * orders: two launches, or a launch and a graph replay, give the same bits.  One workgroup per row stages the row in LDS:
+ * 1 <= V <= DLSG_SAMPLE_FILTER_MAXV, a larger V returns DLSG_EINVAL (the row is not re-read from memory).  0 <= t < 64. */
+#define DLSG_SAMPLE_FILTER_MAXV 32768
+int dlsg_sample_filter_embed(const float* logits, int64_t ld, int V, float temperature, const float* E, int64_t* ids_out, float* out,
+                             int64_t ldo, int W, float* logp, int64_t* lens, int t, int64_t end_id, int rows, float p, uint64_t seed,
+                             uint32_t site_word, uint32_t site_sample, int64_t row0, const uint64_t* seed_ptr, int top_k, float top_p,
+                             int min_len, int no_repeat_ngram, const int64_t* hist, int64_t hist_stride, int32_t* kept, void* stream);
 /* strided 2-d copy / add: dst[r*ldd + j] (+)= src[r*lds + j] */
 int dlsg_copy2d(const float* src, int64_t lds, float* dst, int64_t ldd, int rows, int n, int accum, void* stream);
 /* elementwise dropout with the stateless mask: y = x * keep(seed, site, r*n+j)/(1-p) */

@@ -10,7 +10,12 @@
   * `share` -- one more line: the device-reward step with the encoder run once per clip (`SCSTTrainer(share_encoder=True)`:
     shared sampling, `Trainer.step(seq_per_clip=n)`) against the unshared step, both timed in the same process in alternating
     rounds, each with its sample / reward / train split.
+  * `filter` -- one more line: a SampleGraph replay with the sampling controls on (top_k 50, top_p 0.9, no_repeat_ngram 3,
+    min_len 4: `dlsg_sample_filter_embed` in the word step) against the plain one, HIP events around the replays, alternating
+    rounds in one process; and the two kernels alone on the same 320 rows of logits (vocabulary 1000 and 10 000), HIP events
+    around 200 back-to-back launches each.
 usage: python3 tools/scst_bench.py [steps=10] [batch=64] [n=5]
+       python3 tools/scst_bench.py filter [steps=20] [batch=64] [n=5] [rounds=3]
        python3 tools/scst_bench.py share [steps=10] [batch=64] [n=5] [rounds=2]
        python3 tools/scst_bench.py kernels      (rocprofv3 --kernel-trace --stats target: eager greedy and sampled decodes)
        python3 tools/scst_bench.py reward-kernels   (rocprofv3 target: 20 launches each of dlsg_cider_d and dlsg_scst_advantage)"""
@@ -196,6 +201,50 @@ def share_main(steps=10, B=64, n=5, rounds=2):
         'saved_ms': round(best[False] - best[True], 2), 'steps': steps}))
 
 
+FILTER_OPTS = dict(top_k=50, top_p=0.9, no_repeat_ngram=3, min_len=4)
+
+
+def filter_main(steps=20, B=64, n=5, rounds=3):
+    from dlsg_amd import engine as E
+    net, vocab, frames, regions, refs = setup(B)
+    graphs = {'plain': dlsg_amd.SampleGraph(net, frames, regions, n=n),
+              'filtered': dlsg_amd.SampleGraph(net, frames, regions, n=n, **FILTER_OPTS)}
+    seeds = iter(range(1, 10 ** 6))
+    legs = {k: [] for k in graphs}
+    for _ in range(rounds):
+        for k, g in graphs.items():
+            legs[k].append(round(event_ms(lambda: g(frames, regions, next(seeds)), steps), 3))
+    lens = graphs['filtered'](frames, regions, 3)[2].double().mean().item()
+    lens0 = graphs['plain'](frames, regions, 3)[2].double().mean().item()
+    # the two kernels alone: 320 rows at word step 6, histories of random words
+    rows, L, W = B * n, net.decoder.max_words, net.decoder.word_embed.weight.shape[1]
+    kern = {}
+    for V in (1000, 10000):
+        g = torch.Generator().manual_seed(V)
+        x = (torch.randn(rows, V, generator=g) * 3).cuda()
+        Em = torch.randn(V, W, generator=g).cuda()
+        hist = torch.randint(4, 40, (L, rows), generator=g).cuda()
+        ids, out = torch.empty(rows, dtype=torch.int64, device='cuda'), torch.empty(rows, W, device='cuda')
+        logp, ln = torch.empty(rows, device='cuda'), torch.full((rows,), L, dtype=torch.int64, device='cuda')
+        kept = torch.empty(rows, dtype=torch.int32, device='cuda')
+        common = dict(temperature=1.0, p=0.5, seed=5, site=E.SITE_WORD, site_sample=E.SITE_SAMPLE, row0=rows)
+
+        def filt(**o):
+            return lambda: net.ops.sample_filter_embed(x, Em, ids, out, logp, ln, 6, 2, hist=hist, kept=kept, **common, **o)
+        kern[V] = {'sample_embed_us': round(event_ms(lambda: net.ops.sample_embed(x, Em, ids, out, logp, ln, 6, 2, **common), 200) * 1e3, 2),
+                   'filter_all_on_us': round(event_ms(filt(**FILTER_OPTS), 200) * 1e3, 2),
+                   'filter_bans_only_us': round(event_ms(filt(no_repeat_ngram=3, min_len=4), 200) * 1e3, 2),
+                   'filter_top_k_only_us': round(event_ms(filt(top_k=50), 200) * 1e3, 2),
+                   'filter_top_p_only_us': round(event_ms(filt(top_p=0.9), 200) * 1e3, 2)}
+    best = {k: min(v) for k, v in legs.items()}
+    print(json.dumps({
+        'what': 'SampleGraph replay at the MSVD shape, batch %d x %d samples, vocabulary 1000, train mode: plain sampling against '
+                '%s; HIP events, %d replays per leg, alternating' % (B, n, FILTER_OPTS, steps),
+        'legs_ms': legs, 'best_plain_ms': best['plain'], 'best_filtered_ms': best['filtered'],
+        'filtered_over_plain': round(best['filtered'] / best['plain'], 4), 'mean_len_plain': lens0, 'mean_len_filtered': lens,
+        'kernels_320_rows': kern}))
+
+
 def main(steps=10, B=64, n=5):
     net, vocab, frames, regions, refs = setup(B)
     rows = B * n
@@ -262,6 +311,8 @@ if __name__ == '__main__':
         kernels()
     elif len(sys.argv) > 1 and sys.argv[1] == 'reward-kernels':
         reward_kernels()
+    elif len(sys.argv) > 1 and sys.argv[1] == 'filter':
+        filter_main(*[int(x) for x in sys.argv[2:6]])
     elif len(sys.argv) > 1 and sys.argv[1] == 'share':
         share_main(*[int(x) for x in sys.argv[2:6]])
     else:
