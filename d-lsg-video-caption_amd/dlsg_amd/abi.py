@@ -17,8 +17,8 @@ import re
 
 HEADER = os.path.normpath(os.path.join(os.path.dirname(os.path.abspath(__file__)), '..', '..', 'include', 'dlsg.h'))
 
-SCALARS = {'int32_t': C.c_int32, 'int64_t': C.c_int64, 'uint32_t': C.c_uint32, 'uint64_t': C.c_uint64, 'float': C.c_float,
-           'int': C.c_int, 'double': C.c_double}
+SCALARS = {'int32_t': C.c_int32, 'int64_t': C.c_int64, 'uint16_t': C.c_uint16, 'uint32_t': C.c_uint32, 'uint64_t': C.c_uint64,
+           'float': C.c_float, 'int': C.c_int, 'double': C.c_double}
 
 # one top-level item of the header, after comments are blanked
 _ITEM = re.compile(r'''\s*(?:

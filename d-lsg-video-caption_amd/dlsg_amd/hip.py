@@ -31,6 +31,7 @@ F_SK, F_NOSK, F_SK_BM128, F_SK_BM256, F_SK_BN128, F_SK_NOXMAP = (_D['DLSG_GEMM_'
     'SK', 'NOSK', 'SK_BM128', 'SK_BM256', 'SK_BN128', 'SK_NOXMAP'))
 GRAD_SUMSQ_SLOTS = _D['DLSG_GRAD_SUMSQ_SLOTS']   # float64 partials one dlsg_grad_sumsq launch writes
 CLIP_NORM, CLIP_COEF, CLIP_NONFINITE, CLIP_RECORD_FLOATS = (_D['DLSG_CLIP_' + n] for n in ('NORM', 'COEF', 'NONFINITE', 'RECORD_FLOATS'))
+METRICS_STAGE = _D['DLSG_METRICS_STAGE']        # reference words dlsg_caption_metrics stages in LDS per pass
 F_SK_GIVEAWAY = _D['DLSG_GEMM_SK_GIVEAWAY']   # test hook (include/dlsg.h): the split tiles are finished by their last contributor alone
 
 i64, u32, u64, f32 = C.c_int64, C.c_uint32, C.c_uint64, C.c_float
@@ -1398,6 +1399,37 @@ class HipOps(object):
         assert out.dtype == torch.float64 and out.is_contiguous() and out.numel() == R
         self._check(self.lib.dlsg_cider_d(_p(ids), i64(ids.stride(0)), R, L, _p(clip_idx), i64(end_id), C.byref(cider_tables(tables)),
                                           _p(out), self._stream()), 'cider_d')
+
+    def caption_metrics(self, ids, clip_idx, end_id, tables, scores=None, stats=None, reward=None, weights=None, base=None):
+        """BLEU-1..4 and ROUGE_L of the words of ids[r] (as in `cider_d`) against the references of clip clip_idx[r] in `tables` (a
+        scoring.DeviceCaptionMetrics).  Outputs, each optional: scores (float64 (R, 5)), stats (int32 (R, 10): correct[4], guess[4],
+        length, closest reference length), reward (float64 (R,)) = weights[0] base + weights[1..4] BLEU-1..4 + weights[5] ROUGE_L
+        with weights a sequence of 6 host floats and base float64 (R,) (needed only when weights[0] != 0)"""
+        R, L = ids.shape
+        assert ids.dtype == torch.int64 and (ids.stride(1) == 1 or L <= 1), (ids.dtype, ids.stride())
+        assert clip_idx.dtype == torch.int32 and clip_idx.is_contiguous() and clip_idx.numel() == R
+        assert scores is None or (scores.dtype == torch.float64 and scores.is_contiguous() and scores.shape == (R, 5))
+        assert stats is None or (stats.dtype == torch.int32 and stats.is_contiguous() and stats.shape == (R, 10))
+        assert reward is None or (reward.dtype == torch.float64 and reward.is_contiguous() and reward.numel() == R)
+        assert base is None or (base.dtype == torch.float64 and base.is_contiguous() and base.numel() == R)
+        assert tables.ref_words.dtype == torch.int16 and tables.clip_off.dtype == tables.ref_off.dtype == torch.int64
+        w = None
+        if reward is not None:
+            assert weights is not None and len(weights) == 6 and (base is not None or float(weights[0]) == 0.0)
+            w = (C.c_double * 6)(*[float(x) for x in weights])
+        self._check(self.lib.dlsg_caption_metrics(_p(ids), i64(ids.stride(0)), R, L, _p(clip_idx), i64(end_id), _p(tables.clip_off),
+                                                  _p(tables.ref_off), _p(tables.ref_words), tables.n_clips, tables.V, w, _p(base),
+                                                  _p(scores), _p(stats), _p(reward), self._stream()), 'caption_metrics')
+
+    def caption_corpus(self, stats, scores, base, out):
+        """out (float64 (6,)) = corpus BLEU-1..4 from the column sums of stats (int32 (R, 10)), the mean of scores[:, 4] (ROUGE_L;
+        scores float64 (R, 5)) and the mean of base (float64 (R,), None: NaN); R >= 1"""
+        R = stats.shape[0]
+        assert stats.dtype == torch.int32 and stats.is_contiguous() and stats.shape == (R, 10)
+        assert scores.dtype == torch.float64 and scores.is_contiguous() and scores.shape == (R, 5)
+        assert base is None or (base.dtype == torch.float64 and base.is_contiguous() and base.numel() == R)
+        assert out.dtype == torch.float64 and out.is_contiguous() and out.numel() == 6
+        self._check(self.lib.dlsg_caption_corpus(_p(stats), _p(scores), _p(base), R, _p(out), self._stream()), 'caption_corpus')
 
     def scst_advantage(self, rewards, lens, greedy, n, adv, stats):
         """adv = (float32) rewards - baseline over B clips x n samples: greedy[b] (float64 (B,)) or, greedy None, the leave-one-out

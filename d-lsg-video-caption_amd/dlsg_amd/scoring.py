@@ -1,6 +1,8 @@
 """caption scoring and the evaluation driver (reference evaluate.py:16-98 and the pure-Python
 metrics of caption-eval/pycocoevalcap: BLEU-1..4, ROUGE_L, CIDEr-D).  CPU-side, off the GPU critical path, except for
-`DeviceCiderD`: the self-critical reward scored on the GPU (`dlsg_cider_d`) against tables built from `CiderD`'s.
+`DeviceCiderD`: the self-critical reward scored on the GPU (`dlsg_cider_d`) against tables built from `CiderD`'s, and for
+`DeviceCaptionMetrics` / `DeviceMixedReward`: sentence BLEU-1..4 and ROUGE_L on the GPU (`dlsg_caption_metrics`) and their
+weighted mix with CIDEr-D as the reward.
 
 Not reproduced: METEOR and the Stanford PTB tokenizer (caption-eval/pycocoevalcap/{meteor,tokenizer}) shell out to Java with
 jars that are not in the reference tree; `tokenize` below is a regular-expression stand-in that lower-cases, splits
@@ -325,6 +327,205 @@ class DeviceCiderD(object):
         import torch
         out = torch.empty(ids.shape[0], dtype=torch.float64, device=ids.device)
         self._ops().cider_d(ids, clip_idx, self.end_id if end_id is None else int(end_id), self, out)
+        return out
+
+
+# ------------------------------------------------------------------------------------------------ BLEU / ROUGE_L on the device
+REF_OOV = 0xFFFF                # a reference word outside the vocabulary in `ref_words`: no id reaches it (V <= 65535)
+METRIC_NAMES = ('bleu1', 'bleu2', 'bleu3', 'bleu4', 'rouge_l')
+WEIGHT_KEYS = ('cider',) + METRIC_NAMES
+
+
+def _check_refs(refs):
+    for v in refs:
+        for r in refs[v]:
+            if not r.split():
+                raise ValueError('clip %r has a reference with no words' % (v,))
+
+
+def _host_metrics(refs, vids, hyps):
+    """(R, 5) float64: the per-id BLEU-1..4 of `bleu` and ROUGE_L of `rouge_l` for hyps[i] against refs[vids[i]]"""
+    memo = {}
+    out = np.empty((len(hyps), 5), dtype=np.float64)
+    for i, (v, h) in enumerate(zip(vids, hyps)):
+        key = (v, h)
+        if key not in memo:
+            gts, res = {0: refs[v]}, {0: [h]}
+            memo[key] = [p[0] for p in bleu(gts, res, 4)[1]] + [rouge_l(gts, res)[1][0]]
+        out[i] = memo[key]
+    return out
+
+
+class DeviceCaptionMetrics(object):
+    """Sentence-level BLEU-1..4 and ROUGE_L of captions given as vocabulary ids, scored on the GPU (`dlsg_caption_metrics`), and
+    the corpus figures of a batch of them (`dlsg_caption_corpus`).  `refs` {vid: [tokenized caption, ...]} as for `CiderD`.  Built
+    once and copied to HBM:
+      * `clip_off` -- clip c (clips in sorted vid order, the order of `DeviceCiderD`: one `index()` serves both) owns references
+        [clip_off[c], clip_off[c + 1]);
+      * `ref_off`, `ref_words` -- reference q owns the words ref_words[ref_off[q] : ref_off[q + 1]], mapped through
+        `vocab.word2idx` (no `<unk>` mapping); a word outside the vocabulary is REF_OOV, which nothing matches, a sampled
+        `<unk>` included.  16 bits a word (stored as int16 bit patterns), hence V <= 65535.
+    `scores_device` gives, to rounding (1e-12), what `scores` -- `bleu`'s and `rouge_l`'s per-id values -- gives for the decoded
+    strings (decode_tokens: the words before the first <end>); an id outside [0, len(vocab)) is a word that matches nothing.
+    The corpus figures of `corpus_device` are `bleu`, `rouge_l` (and the mean of `base`, e.g. CIDEr-D) over the decode_tokens
+    strings and these tokenized references.  `scoring.evaluate` is not built on it: `CaptionScorer` re-tokenizes the hypothesis
+    STRING, which splits a `<unk>` into three tokens, so its figures differ wherever the model emits `<unk>`.
+    `ops`: the kernel binding (None: a `hip.HipOps` made on first use)."""
+
+    def __init__(self, refs, vocab, device='cuda'):
+        import torch
+        V = len(vocab)
+        if V > REF_OOV:
+            raise ValueError('DeviceCaptionMetrics keeps 16 bits per word: a vocabulary of %d words is over the %d limit' % (V, REF_OOV))
+        _check_refs(refs)
+        self.refs, self.vocab, self.device, self.V = refs, vocab, torch.device(device), V
+        self.end_id = vocab('<end>')
+        self.ops = None
+        self.vids = sorted(refs)
+        self.vid_index = {v: i for i, v in enumerate(self.vids)}
+        w2i = vocab.word2idx
+        clip_off, ref_off, words = [0], [0], []
+        for v in self.vids:
+            for r in refs[v]:
+                words.extend(w2i.get(w, REF_OOV) for w in r.split())
+                ref_off.append(len(words))
+            clip_off.append(len(ref_off) - 1)
+
+        def dev(a, dtype):
+            return torch.from_numpy(np.ascontiguousarray(a)).to(dtype).to(self.device)
+        self.clip_off = dev(np.array(clip_off, dtype=np.int64), torch.int64)
+        self.ref_off = dev(np.array(ref_off, dtype=np.int64), torch.int64)
+        self.ref_words = dev(np.array(words, dtype=np.uint16).view(np.int16), torch.int16)     # uint16 bits
+        self.n_clips = len(self.vids)
+
+    index = DeviceCiderD.index
+    _ops = DeviceCiderD._ops
+
+    def scores(self, vids, hyps):
+        """host: (R, 5) float64 BLEU-1..4, ROUGE_L of tokenized strings (`bleu`, `rouge_l`)"""
+        return _host_metrics(self.refs, vids, hyps)
+
+    def _launch(self, ids, clip_idx, end_id, **out):
+        self._ops().caption_metrics(ids, clip_idx, self.end_id if end_id is None else int(end_id), self, **out)
+
+    def scores_device(self, ids, clip_idx, end_id=None):
+        """BLEU-1..4 and ROUGE_L of the id rows ids (int64 (R, L), L <= 64, any row stride) against the references of clips
+        clip_idx (int32 (R,), from `index`) -> float64 (R, 5) on ids' device.  One launch, no host synchronisation."""
+        import torch
+        out = torch.empty(ids.shape[0], 5, dtype=torch.float64, device=ids.device)
+        self._launch(ids, clip_idx, end_id, scores=out)
+        return out
+
+    def stats_device(self, ids, clip_idx, end_id=None):
+        """int32 (R, 10): correct[4], guess[4], hypothesis length, closest reference length -- what corpus BLEU sums"""
+        import torch
+        out = torch.empty(ids.shape[0], 10, dtype=torch.int32, device=ids.device)
+        self._launch(ids, clip_idx, end_id, stats=out)
+        return out
+
+    def corpus_device(self, ids, clip_idx, base=None, end_id=None):
+        """float64 (6,) on the device: corpus Bleu_1..4 and the mean ROUGE_L of the R >= 1 rows, and the mean of `base` (float64
+        (R,), e.g. the rows' CIDEr-D; NaN without it).  Two launches, no host synchronisation."""
+        import torch
+        R = ids.shape[0]
+        scores = torch.empty(R, 5, dtype=torch.float64, device=ids.device)
+        stats = torch.empty(R, 10, dtype=torch.int32, device=ids.device)
+        out = torch.empty(6, dtype=torch.float64, device=ids.device)
+        self._launch(ids, clip_idx, end_id, scores=scores, stats=stats)
+        self._ops().caption_corpus(stats, scores, base, out)
+        return out
+
+
+def _mix_weights(weights):
+    unknown = sorted(set(weights) - set(WEIGHT_KEYS))
+    if unknown:
+        raise ValueError('reward weights: unknown keys %s (%s)' % (unknown, ', '.join(WEIGHT_KEYS)))
+    w = [float(weights.get(k, 0.0)) for k in WEIGHT_KEYS]
+    if not any(x != 0.0 for x in w):
+        raise ValueError('reward weights: every weight is zero')
+    return w
+
+
+def _mix(w, cider_scores, metrics):
+    """w[0] cider + w[1..4] BLEU-1..4 + w[5] ROUGE_L, added in that order, a term with weight 0 left out (the kernel's order)"""
+    acc = np.zeros(len(cider_scores) if metrics is None else len(metrics), dtype=np.float64)
+    if w[0] != 0.0:
+        acc = acc + w[0] * np.asarray(cider_scores, dtype=np.float64)
+    for j in range(5):
+        if w[j + 1] != 0.0:
+            acc = acc + w[j + 1] * metrics[:, j]
+    return acc
+
+
+class MixedReward(object):
+    """A weighted sum of CIDEr-D, BLEU-1..4 and ROUGE_L as the self-critical reward (the cider_reward_weight /
+    bleu_reward_weight recipe of the usual captioning toolkits), on the host: `scores(vids, hyps)` like `CiderD.scores`.
+    `weights`: a dict over 'cider', 'bleu1'..'bleu4', 'rouge_l'; a missing key is 0.  Mind the scales: CIDEr-D is on a x10 scale
+    (a good caption scores several units), BLEU and ROUGE_L lie in [0, 1] -- {'cider': 1, 'bleu4': 1} is all but CIDEr-D alone.
+    A metric with weight 0 is neither tabulated nor computed."""
+
+    def __init__(self, refs, weights, n=4, sigma=6.0):
+        self.w = _mix_weights(weights)
+        self.weights = dict(zip(WEIGHT_KEYS, self.w))
+        _check_refs(refs)
+        self.refs = refs
+        self.cider = CiderD(refs, n, sigma) if self.w[0] != 0.0 else None
+
+    def scores(self, vids, hyps):
+        c = self.cider.scores(vids, hyps) if self.cider is not None else None
+        m = _host_metrics(self.refs, vids, hyps) if any(x != 0.0 for x in self.w[1:]) else None
+        return _mix(self.w, c, m)
+
+    def to_device(self, vocab, device='cuda'):
+        """the same reward with device tables over `vocab`'s ids (`DeviceMixedReward`); the corpus statistics are not recomputed"""
+        return DeviceMixedReward(None, vocab, None, device, _host=self)
+
+
+class DeviceMixedReward(object):
+    """`MixedReward` scored on the GPU for `SCSTTrainer`: `index(vids)` and `scores_device(ids, clip_idx, end_id)` -> float64
+    (R,), which is `dlsg_cider_d` followed by `dlsg_caption_metrics` with the CIDEr-D scores as its `base` -- two launches, no
+    ATen kernel between them, no host synchronisation.  It owns a `DeviceCiderD` (`cider`; None when the 'cider' weight is 0) and
+    a `DeviceCaptionMetrics` (`metrics`; None when only 'cider' is weighted: the CIDEr launch is then the only one, its scores
+    scaled in place when the weight is not 1).
+    `scores(vids, hyps)` is the host `MixedReward`'s.  Scales: CIDEr-D x10, BLEU and ROUGE_L in [0, 1] (see `MixedReward`)."""
+
+    def __init__(self, refs, vocab, weights, device='cuda', _host=None):
+        host = _host if _host is not None else MixedReward(refs, weights)
+        self.host, self.w, self.weights, self.vocab = host, host.w, host.weights, vocab
+        self.end_id = vocab('<end>')
+        self.cider = host.cider.to_device(vocab, device) if host.cider is not None else None
+        self.metrics = DeviceCaptionMetrics(host.refs, vocab, device) if any(x != 0.0 for x in self.w[1:]) else None
+        self.ops = None
+
+    @property
+    def ops(self):
+        return self._ops_
+
+    @ops.setter
+    def ops(self, ops):
+        self._ops_ = ops
+        for part in (self.cider, self.metrics):
+            if part is not None:
+                part.ops = ops
+
+    def scores(self, vids, hyps):
+        """MixedReward.scores: tokenized strings on the host"""
+        return self.host.scores(vids, hyps)
+
+    def index(self, vids):
+        """clip indices of `vids` for `scores_device` (the two tables list the clips in the same order)"""
+        return (self.metrics if self.metrics is not None else self.cider).index(vids)
+
+    def scores_device(self, ids, clip_idx, end_id=None):
+        """the mixed reward of the id rows ids (int64 (R, L), L <= 64) against the references of clips clip_idx -> float64 (R,)"""
+        import torch
+        w = self.w
+        end_id = self.end_id if end_id is None else int(end_id)
+        base = self.cider.scores_device(ids, clip_idx, end_id) if self.cider is not None else None
+        if self.metrics is None:
+            return base if w[0] == 1.0 else base.mul_(w[0])
+        out = torch.empty(ids.shape[0], dtype=torch.float64, device=ids.device)
+        self.metrics._ops().caption_metrics(ids, clip_idx, end_id, self.metrics, reward=out, weights=w, base=base)
         return out
 
 

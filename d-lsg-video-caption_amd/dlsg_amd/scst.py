@@ -19,7 +19,8 @@ from .model import Trainer, _h2d
 class SCSTTrainer(object):
     """reward: an object with `scores(vids, hyps) -> np.ndarray` (a `scoring.CiderD` over the training references), or one that
     also has `index(vids)` and `scores_device(ids, clip_idx, end_id)` (a `scoring.DeviceCiderD`): the reward is then computed on
-    the GPU (see `step`).
+    the GPU (see `step`).  `scoring.MixedReward` / `scoring.DeviceMixedReward` are the two forms of a weighted sum of CIDEr-D,
+    BLEU-1..4 and ROUGE_L.
     baseline: 'mean' -- the leave-one-out mean of the clip's other n - 1 rewards (needs n_samples >= 2); 'greedy' -- the reward
     of the clip's eval-mode greedy caption.  The remaining keywords go to the owned `Trainer` (lr, use_graphs, data parallel,
     ...), whose Adam state, gradient buckets and graphs the step reuses.

@@ -736,6 +736,30 @@ int dlsg_cider_d(const int64_t* ids, int64_t ld, int rows, int L, const int32_t*
  * One workgroup, fixed-order sums.  Without greedy n >= 2. */
 int dlsg_scst_advantage(const double* rewards, const int64_t* lens, const double* greedy, int B, int n, float* adv, double* stats,
                         void* stream);
+/* Sentence-level BLEU-1..4 and ROUGE_L (beta = 1.2) of row r of ids (rows as in dlsg_cider_d: int64, row stride ld, the words
+ * before the first end_id, L <= 64) against the references of clip clip_idx[r], in float64 and in the operation order of
+ * scoring.bleu / scoring.rouge_l.  Reference tables (scoring.DeviceCaptionMetrics): clip c owns references [clip_off[c],
+ * clip_off[c + 1]), reference q the words ref_words[ref_off[q] .. ref_off[q + 1]) -- vocabulary ids, 0xFFFF for a word outside
+ * the vocabulary, which nothing matches; a reference may be longer than 64 words.  An id outside [0, vocab) is a word that
+ * matches no reference word but counts in the length.  Outputs, each optional (NULL):
+ *   scores (rows, 5)  BLEU-1..4 (clipped against the maximum count over the references, brevity penalty against the closest
+ *                     reference length, shorter on ties) and ROUGE_L (best LCS precision and best LCS recall over the references);
+ *                     all 0 for an empty row;
+ *   stats (rows, 10)  correct[4], guess[4], row length, closest reference length: the integers corpus BLEU sums;
+ *   reward (rows)     weights[0] base[r] + weights[1..4] BLEU-1..4 + weights[5] ROUGE_L, added in that order, a term with weight
+ *                     exactly 0 left out.  weights: 6 doubles in HOST memory, read during the call; base: float64 per row (the
+ *                     rows' CIDEr-D of dlsg_cider_d), may be NULL when weights[0] == 0.
+ * A clip index outside [0, n_clips), or a clip without references, gives NaN scores and reward and zero stats.  One workgroup
+ * per row, no atomics, fixed-order reductions (bit-identical on every launch).  References pass through LDS DLSG_METRICS_STAGE
+ * words at a time; a longer single reference is read from global memory.  vocab in 1..65535; rows == 0 launches nothing. */
+#define DLSG_METRICS_STAGE 2048
+int dlsg_caption_metrics(const int64_t* ids, int64_t ld, int rows, int L, const int32_t* clip_idx, int64_t end_id,
+                         const int64_t* clip_off, const int64_t* ref_off, const uint16_t* ref_words, int n_clips, int vocab,
+                         const double* weights, const double* base, double* scores, int32_t* stats, double* reward, void* stream);
+/* Corpus figures of rows scored by dlsg_caption_metrics: out[0..3] = corpus BLEU-1..4 from the column sums of stats (64-bit
+ * integers; the closing loop of scoring.bleu), out[4] = mean of scores[:, 4] (ROUGE_L), out[5] = mean of base (NaN without base).
+ * One workgroup, fixed-order sums.  rows >= 1. */
+int dlsg_caption_corpus(const int32_t* stats, const double* scores, const double* base, int rows, double* out, void* stream);
 int dlsg_log_softmax(const float* logits, float* out, int rows, int V, void* stream);
 /* One beam-search step for every batch item (BeamSearch.search, allennlp_beamsearch.py:140-260, per-node k == k):
  * log-softmax + per-beam top-k over the vocabulary + top-k over the k*k summed candidates, in one launch.

@@ -1,0 +1,478 @@
+"""CPU: BLEU-1..4 / ROUGE_L on the device's tables (`scoring.DeviceCaptionMetrics`), the mixed reward (`scoring.MixedReward`,
+`scoring.DeviceMixedReward`) and its SCST step.  The two kernels (`dlsg_caption_metrics`, `dlsg_caption_corpus`) are emulated in
+numpy, following the kernel's algorithm over the very tables the class builds (`emul_caption_metrics`, `MetricsEmul` below),
+and checked against the host functions `scoring.bleu` / `scoring.rouge_l` and the reference-made fixture
+tests/golden/scoring.json.  The GPU side is tests/test_gpu_caption_metrics.py."""
+import json
+import math
+import random
+
+import numpy as np
+import pytest
+import torch
+
+import dlsg_amd
+from dlsg_amd import scoring as S
+from test_cider_device_host import GOLD, OOV, CiderEmul, _spy, corpus_for, encode, host_words, random_corpus, vocab_of
+from test_scst_host import small_net
+
+HYP_BAD = 0x10000                       # the kernel's code of an id outside [0, V): no 16-bit reference word equals it
+M64 = (1 << 64) - 1
+
+
+def np_tables(tb):
+    return tb.clip_off.cpu().numpy(), tb.ref_off.cpu().numpy(), tb.ref_words.cpu().numpy().view(np.uint16).astype(np.int64)
+
+
+def lcs_bits(hyp, ref):
+    """the kernel's bit-parallel LCS: bit i of V is cleared where the LCS grows at hypothesis word i; 64-bit, carry dropped"""
+    V = M64
+    for w in ref:
+        M = sum(1 << i for i, h in enumerate(hyp) if h == w)
+        U = V & M
+        V = ((V + U) & M64) | (V & ~M & M64)
+    return bin(~V & ((1 << len(hyp)) - 1)).count('1')
+
+
+def emul_caption_metrics(tb, ids, clip_idx, end_id, weights=None, base=None):
+    """numpy restatement of caption_metrics_kernel (csrc/metrics.hip) -> (scores (R, 5), stats (R, 10), reward (R,) or None).
+    Per order k the row's n-grams at every position, kept at their first position with their count, one holding an id outside
+    [0, V) dropped; per reference a window slides over its words and counts the windows equal to each kept n-gram, the clip is
+    the maximum over the references; the closest reference length, shorter on ties; per reference the bit-parallel LCS against
+    the row, best precision and best recall apart; then the float64 arithmetic of scoring.bleu / scoring.rouge_l."""
+    clip_off, ref_off, words = np_tables(tb)
+    ids = ids.cpu().numpy()
+    clip_idx = clip_idx.cpu().numpy()
+    R, L = ids.shape
+    assert L <= 64
+    scores = np.empty((R, 5), dtype=np.float64)
+    stats = np.zeros((R, 10), dtype=np.int32)
+    reward = np.empty(R, dtype=np.float64) if weights is not None else None
+    small, tiny = 1e-9, 1e-15
+    for r in range(R):
+        c = int(clip_idx[r])
+        if not 0 <= c < tb.n_clips or clip_off[c + 1] <= clip_off[c]:
+            scores[r] = float('nan')
+            if reward is not None:
+                reward[r] = float('nan')
+            continue
+        refs = [words[ref_off[q]:ref_off[q + 1]].tolist() for q in range(int(clip_off[c]), int(clip_off[c + 1]))]
+        row = ids[r]
+        hits = np.nonzero(row == end_id)[0]
+        ln = int(hits[0]) if len(hits) else L
+        code = [HYP_BAD if (x < 0 or x >= tb.V) else int(x) for x in row[:ln]]
+        correct, guess = [0] * 4, [0] * 4
+        for k in range(4):
+            g = guess[k] = max(0, ln - k)
+            grams = [tuple(code[i:i + k + 1]) for i in range(g)]
+            for i in range(g):
+                if HYP_BAD in grams[i] or grams.index(grams[i]) != i:
+                    continue
+                tf = grams.count(grams[i])
+                clip = max(sum(1 for j in range(k, len(ref)) if tuple(ref[j - k:j + 1]) == grams[i]) for ref in refs)
+                correct[k] += min(tf, clip)
+        best = min((abs(len(ref) - ln), len(ref)) for ref in refs)[1]
+        stats[r] = correct + guess + [ln, best]
+        b, ratio = 1.0, (ln + tiny) / (best + small)
+        for k in range(4):
+            b *= (correct[k] + tiny) / (guess[k] + small)
+            s = b ** (1.0 / (k + 1))
+            scores[r, k] = s * math.exp(1 - 1 / ratio) if ratio < 1 else s
+        p = q = 0.0
+        for ref in refs:
+            if ln > 0 and len(ref) > 0:
+                l = lcs_bits(code, ref)
+                p, q = max(p, l / float(ln)), max(q, l / float(len(ref)))
+        scores[r, 4] = (1 + 1.2 ** 2) * p * q / (q + 1.2 ** 2 * p) if p and q else 0.0
+        if reward is not None:
+            acc = 0.0
+            if weights[0] != 0.0:
+                acc += weights[0] * float(base[r])
+            for j in range(5):
+                if weights[j + 1] != 0.0:
+                    acc += weights[j + 1] * scores[r, j]
+            reward[r] = acc
+    return scores, stats, reward
+
+
+def emul_caption_corpus(stats, scores, base):
+    """caption_corpus_kernel: the closing loop of scoring.bleu over the column sums, the mean ROUGE_L, the mean base"""
+    t = stats.astype(np.int64).sum(0)
+    small, tiny = 1e-9, 1e-15
+    out = np.empty(6, dtype=np.float64)
+    b, ratio = 1.0, (t[8] + tiny) / (t[9] + small)
+    for k in range(4):
+        b *= (t[k] + tiny) / (t[4 + k] + small)
+        s = b ** (1.0 / (k + 1))
+        out[k] = s * math.exp(1 - 1 / ratio) if ratio < 1 else s
+    out[4] = scores[:, 4].mean()
+    out[5] = base.mean() if base is not None else float('nan')
+    return out
+
+
+class MetricsEmul(CiderEmul):
+    """CiderEmul + the two caption-metric kernels (the signatures of HipOps.caption_metrics / caption_corpus)"""
+
+    def caption_metrics(self, ids, clip_idx, end_id, tables, scores=None, stats=None, reward=None, weights=None, base=None):
+        assert ids.dtype == torch.int64 and clip_idx.dtype == torch.int32 and tables.ref_words.dtype == torch.int16
+        assert reward is None or (weights is not None and len(weights) == 6 and (base is not None or weights[0] == 0.0))
+        sc, st, rw = emul_caption_metrics(tables, ids, clip_idx, end_id, weights if reward is not None else None,
+                                          None if base is None else base.numpy())
+        if scores is not None:
+            assert scores.dtype == torch.float64 and scores.shape == (ids.shape[0], 5)
+            scores.copy_(torch.from_numpy(sc))
+        if stats is not None:
+            assert stats.dtype == torch.int32 and stats.shape == (ids.shape[0], 10)
+            stats.copy_(torch.from_numpy(st))
+        if reward is not None:
+            assert reward.dtype == torch.float64 and reward.shape == (ids.shape[0],)
+            reward.copy_(torch.from_numpy(rw))
+
+    def caption_corpus(self, stats, scores, base, out):
+        assert stats.dtype == torch.int32 and scores.dtype == torch.float64 and out.dtype == torch.float64 and out.numel() == 6
+        out.copy_(torch.from_numpy(emul_caption_corpus(stats.numpy(), scores.numpy(), None if base is None else base.numpy())))
+
+
+def emul_metrics(refs, vocab):
+    dm = S.DeviceCaptionMetrics(refs, vocab, device='cpu')
+    dm.ops = MetricsEmul()
+    return dm
+
+
+def host_stats(refs, hyp):
+    """correct[4], guess[4], length, closest reference length of one hypothesis string, as scoring.bleu counts them"""
+    h = hyp.split()
+    rs = [r.split() for r in refs]
+    hc = S._ngrams(h, 4)
+    mx = {}
+    for r in rs:
+        for g, c in S._ngrams(r, 4).items():
+            mx[g] = max(mx.get(g, 0), c)
+    correct = [0] * 4
+    for g, c in hc.items():
+        correct[len(g) - 1] += min(c, mx.get(g, 0))
+    return correct + [max(0, len(h) - k) for k in range(4)] + [len(h), min((abs(len(r) - len(h)), len(r)) for r in rs)[1]]
+
+
+def host_corpus(refs, vids, hyps):
+    """corpus Bleu_1..4 and ROUGE_L of scoring.bleu / scoring.rouge_l with one id per row"""
+    gts = {'%06d' % i: refs[v] for i, v in enumerate(vids)}
+    res = {'%06d' % i: [h] for i, h in enumerate(hyps)}
+    return list(S.bleu(gts, res, 4)[0]) + [S.rouge_l(gts, res)[0]]
+
+
+def check_rows(dm, vids, rows, rtol=1e-12, atol=1e-12, device=None):
+    """device (or, on the CPU, emulated) scores, statistics and corpus figures of id rows against the host functions over
+    their decoded strings -> (scores, stats, hypothesis strings)"""
+    ids = torch.tensor(rows, dtype=torch.int64, device=device)
+    cidx = dm.index(vids)
+    got = dm.scores_device(ids, cidx).cpu().numpy()
+    stats = dm.stats_device(ids, cidx).cpu().numpy()
+    hyps = [host_words(dm.vocab, r, dm.end_id) for r in rows]
+    want = dm.scores(vids, hyps)
+    assert got.shape == want.shape == (len(rows), 5)
+    err = np.abs(got - want)
+    assert np.allclose(got, want, rtol=rtol, atol=atol), (err.max(), np.unravel_index(err.argmax(), err.shape))
+    want_stats = np.array([host_stats(dm.refs[v], h) for v, h in zip(vids, hyps)], dtype=np.int32)
+    assert np.array_equal(stats, want_stats), np.nonzero((stats != want_stats).any(1))[0][:5]
+    base = torch.arange(len(rows), dtype=torch.float64, device=device) * 0.25
+    corpus = dm.corpus_device(ids, cidx, base).cpu().numpy()
+    assert np.allclose(corpus[:5], host_corpus(dm.refs, vids, hyps), rtol=rtol, atol=atol), corpus
+    assert abs(corpus[5] - 0.25 * (len(rows) - 1) / 2) <= 1e-12
+    return got, stats, hyps
+
+
+# ------------------------------------------------------------------------------------------------ the golden cases
+def golden_vocabs(case):
+    """(full, partial): every word of the case; the hypothesis words of two clips and every third reference word"""
+    gts, res = case['gts'], case['res']
+    vids = sorted(gts)
+    ref_words = sorted(set(w for v in vids for c in gts[v] for w in c.split()))
+    all_hyp = sorted(set(w for v in vids for w in res[v][0].split()))
+    two_hyp = sorted(set(w for v in vids[:2] for w in res[v][0].split()))
+    return vocab_of(ref_words + [w for w in all_hyp if w not in ref_words]), vocab_of(two_hyp + [w for w in ref_words[::3] if w not in two_hyp])
+
+
+def check_golden_case(case, make, device=None):
+    gts, res = case['gts'], case['res']
+    vids = sorted(gts)
+    full, part = golden_vocabs(case)
+    for vocab in (full, part):
+        dm = make(gts, vocab)
+        got, stats, hyps = check_rows(dm, vids, [encode(vocab, res[v][0], 26) for v in vids], device=device)
+        whole = [i for i, v in enumerate(vids) if all(w in vocab.word2idx for w in res[v][0].split())]
+        assert len(whole) >= 2
+        want = np.array(case['bleu_per'] + [case['rouge_per']]).T            # bleu_per is [order][clip]
+        assert np.allclose(got[whole], want[whole], rtol=0, atol=1e-9)
+        if vocab is full:
+            assert len(whole) == len(vids)
+            ids = torch.tensor([encode(vocab, res[v][0], 26) for v in vids], dtype=torch.int64, device=device)
+            base = torch.tensor(case['cider_per'], dtype=torch.float64, device=device)
+            corpus = dm.corpus_device(ids, dm.index(vids), base).cpu().numpy()
+            assert np.allclose(corpus, case['bleu'] + [case['rouge'], case['cider']], rtol=0, atol=1e-9), corpus
+        else:
+            assert len(set(w for v in vids for c in gts[v] for w in c.split()) - set(vocab.word2idx)) > 0
+
+
+def test_golden_cases_full_and_partial_vocabulary():
+    for case in json.load(open(GOLD)):
+        check_golden_case(case, emul_metrics)
+
+
+# ------------------------------------------------------------------------------------------------ edge rows
+def edge_corpus(L=64):
+    """A random corpus over 14 words (3 of them outside the vocabulary) with clips of 1, 4, 5 and 41 references and one reference
+    of 100 words, and per clip the row kinds of test_random_corpora_and_edge_rows plus: no <end> at L = 64 over 2 distinct
+    words (every mask bit in use, the LCS add carries out of bit 63), a reference itself, a hypothesis of 1..3 words, a word
+    repeated more often than in any reference, and a hypothesis of 6 words between references of 5 and 7.
+    -> (refs, vocab, vids, rows, index of the tie row, index of the first 64-word row)"""
+    rng = random.Random(77)
+    words = ['w%d' % i for i in range(14)]
+    refs = random_corpus(rng, 9, 5, words)
+    refs['c1'] = refs['c1'][:1]
+    refs['c2'] = refs['c2'][:4]
+    refs['c3'] = [' '.join(rng.choice(words) for _ in range(rng.randint(1, 14))) for _ in range(41)]
+    refs['c4'][2] = ' '.join(rng.choice(words[:5]) for _ in range(100))
+    refs['c5'] = ['w0 w1 w2 w3 w4', 'w0 w1 w2 w3 w4 w5 w6']                      # lengths 5 and 7 around a hypothesis of 6
+    refs['c6'][0] = ' '.join(['w1', 'w2'] * 20)
+    vocab = vocab_of(words[:11])                                                  # w11..w13 appear in references only
+    end, unk, pad = vocab('<end>'), vocab('<unk>'), vocab('<pad>')
+    inv = [vocab.word2idx[w] for w in words[:11]]
+    vids, rows = [], []
+    for c in sorted(refs):
+        for kind in range(12):
+            if kind == 0:
+                row = [end] + [rng.choice(inv) for _ in range(L - 1)]                                   # empty hypothesis
+            elif kind == 1:
+                row = [rng.choice(inv), end] + [rng.randrange(len(vocab)) for _ in range(L - 2)]        # one word
+            elif kind == 2:
+                row = [rng.choice(inv[1:3]) for _ in range(L - 1)] + [inv[2]]                           # no <end>, 2 distinct words
+            elif kind == 3:
+                row = [rng.choice(inv + [unk, pad]) for _ in range(9)] + [end] + [0] * (L - 10)
+            elif kind == 4:
+                row = encode(vocab, ' '.join(w for w in refs[c][0].split() if w in vocab.word2idx), L, rng)
+            elif kind == 5:
+                row = encode(vocab, ' '.join(refs[c][-1].split()[:L - 1]), L, rng)                      # a reference, <unk> and all
+            elif kind == 6:
+                row = encode(vocab, ' '.join(refs[c][0].split()[:rng.randint(1, 3)]), L, rng)           # shorter than 4 words
+            elif kind == 7:
+                w = refs[c][0].split()[0]
+                row = encode(vocab, ' '.join([w] * 9 + refs[c][0].split()[:3]), L, rng)                 # clipped repeats
+            else:
+                row = [rng.choice(inv) for _ in range(rng.randint(2, 12))]
+                row = (row + [end] + [rng.randrange(len(vocab)) for _ in range(L)])[:L]
+            assert len(row) == L
+            vids.append(c)
+            rows.append(row)
+    tie = len(rows)
+    vids.append('c5')
+    rows.append(encode(vocab, 'w0 w1 w9 w3 w4 w5', L, rng))
+    return refs, vocab, vids, rows, tie, 2
+
+
+def check_edge_rows(make, device=None):
+    refs, vocab, vids, rows, tie, full = edge_corpus()
+    assert sorted(set(len(r) for r in refs.values())) == [1, 2, 4, 5, 41] and max(len(c.split()) for c in refs['c4']) == 100
+    dm = make(refs, vocab)
+    got, stats, hyps = check_rows(dm, vids, rows, device=device)
+    assert stats[tie, 8] == 6 and stats[tie, 9] == 5                           # 5 and 7 are equally close: the shorter
+    assert stats[full, 8] == 64 and stats[0, 8] == 0 and np.all(got[0] == 0)   # all 64 words; the empty row scores 0
+    assert (stats[:, 8] < 4).any() and (stats[stats[:, 8] == 2][:, 6:8] == 0).all()
+    clipped = [i for i, h in enumerate(hyps) if len(h.split()) >= 12 and len(set(h.split()[:9])) == 1]
+    assert clipped and any(stats[i, 0] < stats[i, 4] for i in clipped)
+    assert (got[:, 1] > 1e-3).sum() > len(rows) // 4 and (got[:, 3] > 1e-3).sum() >= 9 and (got[:, 4] > 0).mean() > 0.5 and (got[:, 4] == 1.0).any()
+    return dm, vids, rows
+
+
+def test_edge_rows_over_a_random_corpus():
+    check_edge_rows(emul_metrics)
+
+
+def test_lcs_bits_is_the_host_lcs():
+    rng = random.Random(3)
+    for _ in range(300):
+        h = [rng.randrange(4) for _ in range(rng.choice([0, 1, 2, 7, 63, 64]))]
+        r = [rng.randrange(5) for _ in range(rng.randint(0, 80))]
+        assert lcs_bits(h, r) == S._lcs(r, h)
+
+
+# ------------------------------------------------------------------------------------------------ vocabulary handling
+def outside_ids_case():
+    rng = random.Random(5)
+    words = ['w%d' % i for i in range(8)]
+    refs = random_corpus(rng, 4, 4, words, 3, 9)
+    vocab = vocab_of(words)
+    V, end = len(vocab), vocab('<end>')
+    inv = [vocab.word2idx[w] for w in words]
+    rows, vids = [], []
+    for c in sorted(refs):
+        for bad in (-1, V, 1 << 40, -(1 << 62)):
+            row = [vocab(w) for w in refs[c][0].split()] + [rng.choice(inv) for _ in range(3)]
+            row[rng.randrange(len(row))] = bad
+            row[rng.randrange(len(row))] = bad
+            rows.append((row + [end] + [bad] * 16)[:16])
+            vids.append(c)
+    rows.append([inv[0], V, end] + [0] * 13)
+    vids.append('c0')
+    return refs, vocab, vids, rows
+
+
+def test_ids_outside_the_vocabulary_match_nothing_and_count_in_the_length():
+    refs, vocab, vids, rows = outside_ids_case()
+    got, stats, hyps = check_rows(emul_metrics(refs, vocab), vids, rows)
+    assert OOV in ' '.join(hyps) and stats[-1, 8] == 2 and stats[-1, 4] == 2 and stats[-1, 0] == (1 if 'w0' in ' '.join(refs['c0']) else 0)
+
+
+def unk_case():
+    refs = {'a': ['a dog runs zebroid fast', 'a dog runs'], 'b': ['the cat sits']}
+    vocab = vocab_of(['a', 'dog', 'runs', 'fast', 'the', 'cat', 'sits'])         # 'zebroid' is not a word of the vocabulary
+    unk = vocab('<unk>')
+    assert vocab('zebroid') == unk and 'zebroid' not in vocab.word2idx
+    rows = [encode(vocab, 'a dog runs', 8), encode(vocab, 'a dog runs <unk> fast', 8)]
+    assert rows[1][3] == unk and rows[1][5] == vocab('<end>')
+    return refs, vocab, ['a', 'a'], rows
+
+
+def test_out_of_vocabulary_reference_word_does_not_match_a_sampled_unk():
+    refs, vocab, vids, rows = unk_case()
+    dm = emul_metrics(refs, vocab)
+    assert np_tables(dm)[2].tolist().count(S.REF_OOV) == 1
+    got, stats, _ = check_rows(dm, vids, rows)
+    cheat = dm.scores(['a'], ['a dog runs zebroid fast'])[0]
+    assert stats[1, 0] == 4 and stats[1, 8] == 5 and got[1, 4] < cheat[4] - 1e-3 and got[1, 0] < cheat[0] - 1e-3
+
+
+# ------------------------------------------------------------------------------------------------ the mixed reward
+MIX = {'cider': 1, 'bleu4': 2, 'rouge_l': 1}
+
+
+def test_mixed_reward_is_the_weighted_sum_in_order():
+    rng = random.Random(8)
+    words = ['w%d' % i for i in range(9)]
+    refs = random_corpus(rng, 5, 3, words, 3, 8)
+    vocab = vocab_of(words[:7])
+    weights = {'cider': 0.5, 'bleu1': 0.25, 'bleu3': 3.0, 'rouge_l': 2.0}
+    host = S.MixedReward(refs, weights)
+    dev = host.to_device(vocab, device='cpu')
+    dev.ops = MetricsEmul()
+    assert dev.host is host and dev.cider.cider is host.cider and dev.cider.ops is dev.ops and dev.metrics.ops is dev.ops
+    vids = [rng.choice(sorted(refs)) for _ in range(12)]
+    rows = [encode(vocab, ' '.join(rng.choice(words) for _ in range(rng.randint(0, 9))), 12, rng) for _ in vids]
+    hyps = [host_words(vocab, r, dev.end_id) for r in rows]
+    got = dev.scores_device(torch.tensor(rows), dev.index(vids)).numpy()
+    want = host.scores(vids, hyps)
+    assert np.allclose(got, want, rtol=1e-12, atol=1e-12) and np.array_equal(want, dev.scores(vids, hyps))
+    c, m = host.cider.scores(vids, hyps), S.DeviceCaptionMetrics(refs, vocab, device='cpu').scores(vids, hyps)
+    assert np.array_equal(want, ((0.5 * c + 0.25 * m[:, 0]) + 3.0 * m[:, 2]) + 2.0 * m[:, 4]) and want.max() > 1
+
+
+@pytest.mark.parametrize('baseline', ['mean', 'greedy'])
+def test_scst_step_on_a_device_mixed_reward_equals_the_host_mixed_reward_step(baseline):
+    res = []
+    for device_reward in (False, True):
+        net, sd, args, vocab, frames, regions, _, _ = small_net()
+        net.set_ops(MetricsEmul())
+        host = S.MixedReward(corpus_for(vocab, 3), MIX)
+        reward = host.to_device(vocab, device='cpu') if device_reward else host
+        if device_reward:
+            reward.ops = net.ops
+        tr = dlsg_amd.SCSTTrainer(net, reward, n_samples=4, baseline=baseline, lr=1e-3)
+        seen = _spy(tr)
+        net.ops.recording = []
+        outs = [tr.step(frames, regions, ['0', '1', '2']) for _ in range(2)]
+        log, net.ops.recording = net.ops.recording, None
+        res.append((outs, seen, net._flat.clone(), log))
+    (oh, sh, fh, lh), (od, sd_, fd, ld) = res
+    for a, b in zip(sh, sd_):
+        assert torch.equal(a[0][2], b[0][2]) and torch.equal(a[0][3], b[0][3])          # the same sampled words and lengths
+        wh, wd = a[1]['seq_weights'], b[1]['seq_weights']
+        assert wd.dtype == torch.float32 and (wh - wd).abs().max().item() <= 1e-6
+        assert wh.abs().max().item() > 0
+    for a, b in zip(oh, od):
+        assert isinstance(a['reward_mean'], float) and torch.is_tensor(b['reward_mean']) and b['reward_mean'].dim() == 0
+        for k in ('reward_mean', 'baseline_mean', 'mean_len'):
+            assert abs(a[k] - float(b[k])) <= 1e-12, k
+        assert abs(float(a['loss']) - float(b['loss'])) <= 1e-6
+    assert (fh - fd).abs().max().item() <= 1e-6
+    # per scored batch (the samples, and the greedy rows for that baseline) one CIDEr-D launch and one metrics launch
+    batches = 2 * (2 if baseline == 'greedy' else 1)
+    assert ld.count('cider_d') == batches and ld.count('caption_metrics') == batches and ld.count('scst_advantage') == 2
+    assert not any(c in ('cider_d', 'caption_metrics', 'caption_corpus') for c in lh)
+    new = ('cider_d', 'caption_metrics', 'scst_advantage')
+    assert [c for c in ld if c not in new] == lh
+
+
+def test_cider_only_mix_issues_the_cider_launch_alone():
+    net, sd, args, vocab, frames, regions, _, _ = small_net()
+    net.set_ops(MetricsEmul())
+    refs = corpus_for(vocab, 3)
+    reward = S.DeviceMixedReward(refs, vocab, {'cider': 1.0, 'bleu2': 0.0}, device='cpu')
+    assert reward.metrics is None
+    reward.ops = net.ops
+    tr = dlsg_amd.SCSTTrainer(net, reward, n_samples=3, lr=1e-3)
+    net.ops.recording = []
+    tr.step(frames, regions, ['0', '1', '2'])
+    log, net.ops.recording = net.ops.recording, None
+    assert log.count('cider_d') == 1 and 'caption_metrics' not in log
+    rows = torch.tensor([encode(vocab, refs['1'][0], 10)])
+    half = S.DeviceMixedReward(refs, vocab, {'cider': 0.5}, device='cpu')
+    half.ops = net.ops
+    assert torch.equal(half.scores_device(rows, half.index(['1'])) * 2, reward.scores_device(rows, reward.index(['1'])))
+    nocider = S.DeviceMixedReward(refs, vocab, {'bleu4': 1.0}, device='cpu')
+    assert nocider.cider is None and nocider.host.cider is None and nocider.index(['2', '0']).tolist() == [2, 0]
+
+
+# ------------------------------------------------------------------------------------------------ tables and refusals
+def test_table_invariants_and_index():
+    rng = random.Random(2)
+    words = ['w%d' % i for i in range(10)]
+    refs = random_corpus(rng, 5, 3, words)
+    refs['c2'] = refs['c2'][:1]
+    vocab = vocab_of(words[:8])
+    dm = S.DeviceCaptionMetrics(refs, vocab, device='cpu')
+    clip_off, ref_off, w = np_tables(dm)
+    assert dm.clip_off.dtype == dm.ref_off.dtype == torch.int64 and dm.ref_words.dtype == torch.int16
+    assert clip_off[0] == 0 and ref_off[0] == 0 and np.all(np.diff(clip_off) >= 1) and np.all(np.diff(ref_off) >= 1)
+    assert clip_off[-1] == len(ref_off) - 1 == sum(len(r) for r in refs.values()) and ref_off[-1] == len(w) and dm.n_clips == 5
+    q = 0
+    for v in sorted(refs):
+        for r in refs[v]:
+            assert w[ref_off[q]:ref_off[q + 1]].tolist() == [vocab.word2idx.get(x, S.REF_OOV) for x in r.split()]
+            q += 1
+    assert S.REF_OOV in w and ((w < len(vocab)) | (w == S.REF_OOV)).all() and vocab('<unk>') not in w
+    dc = S.DeviceCiderD(refs, vocab, device='cpu')
+    assert dm.vids == dc.vids and torch.equal(dm.clip_off, dc.clip_off)              # one index() serves both
+    idx = dm.index(['c3', 'c0', 'c3'])
+    assert idx.dtype == torch.int32 and idx.tolist() == [3, 0, 3] and torch.equal(idx, dc.index(['c3', 'c0', 'c3']))
+    for name in ('DeviceCaptionMetrics', 'MixedReward', 'DeviceMixedReward'):
+        assert getattr(dlsg_amd, name) is getattr(S, name)
+
+
+def test_refusals_and_unscorable_clips():
+    refs = {'a': ['x y z'], 'b': ['z y']}
+    with pytest.raises(ValueError):
+        S.DeviceCaptionMetrics(refs, dlsg_amd.make_vocab(65536), device='cpu')
+    S.DeviceCaptionMetrics(refs, dlsg_amd.make_vocab(65535), device='cpu')
+    vocab = vocab_of(['x', 'y', 'z'])
+    for empty in ('', '   '):
+        with pytest.raises(ValueError):
+            S.DeviceCaptionMetrics({'a': ['x y', empty]}, vocab, device='cpu')
+        with pytest.raises(ValueError):
+            S.MixedReward({'a': ['x y', empty]}, {'bleu1': 1})
+    with pytest.raises(ValueError):
+        S.MixedReward(refs, {'cider': 1, 'meteor': 1})
+    for w in ({}, {'cider': 0, 'bleu4': 0.0}):
+        with pytest.raises(ValueError):
+            S.MixedReward(refs, w)
+        with pytest.raises(ValueError):
+            S.DeviceMixedReward(refs, vocab, w, device='cpu')
+    dm = emul_metrics(refs, vocab)
+    with pytest.raises(KeyError):
+        dm.index(['a', 'c'])
+    with pytest.raises(KeyError):
+        S.DeviceMixedReward(refs, vocab, MIX, device='cpu').index(['c'])
+    # a clip index outside the tables: NaN scores and reward, zero statistics
+    ids = torch.tensor([encode(vocab, 'x y', 6)] * 3)
+    cidx = torch.tensor([0, 2, -1], dtype=torch.int32)
+    sc, st, rw = emul_caption_metrics(dm, ids, cidx, dm.end_id, [0, 0, 0, 0, 1, 1], None)
+    assert np.isfinite(sc[0]).all() and np.isnan(sc[1:]).all() and np.isnan(rw[1:]).all() and not st[1:].any() and st[0].any()

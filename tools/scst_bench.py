@@ -14,7 +14,12 @@
     min_len 4: `dlsg_sample_filter_embed` in the word step) against the plain one, HIP events around the replays, alternating
     rounds in one process; and the two kernels alone on the same 320 rows of logits (vocabulary 1000 and 10 000), HIP events
     around 200 back-to-back launches each.
+  * `mixed` -- one more line: `dlsg_caption_metrics` (BLEU-1..4 + ROUGE_L + the weighted mix) against `dlsg_cider_d` on the same
+    320 sampled-like rows x 20 and x 40 references (vocabulary 10 000, a corpus of 300 clips; HIP events around back-to-back
+    launches replayed from a hipGraph, alternating rounds), and the graph-replayed SCST step with the CIDEr-only device reward against the mixed reward
+    {'cider': 1, 'bleu4': 2, 'rouge_l': 1} (`scoring.DeviceMixedReward`), alternating rounds in one process.
 usage: python3 tools/scst_bench.py [steps=10] [batch=64] [n=5]
+       python3 tools/scst_bench.py mixed [steps=20] [batch=64] [n=5] [rounds=2]
        python3 tools/scst_bench.py filter [steps=20] [batch=64] [n=5] [rounds=3]
        python3 tools/scst_bench.py share [steps=10] [batch=64] [n=5] [rounds=2]
        python3 tools/scst_bench.py kernels      (rocprofv3 --kernel-trace --stats target: eager greedy and sampled decodes)
@@ -201,6 +206,79 @@ def share_main(steps=10, B=64, n=5, rounds=2):
         'saved_ms': round(best[False] - best[True], 2), 'steps': steps}))
 
 
+MIX = {'cider': 1.0, 'bleu4': 2.0, 'rouge_l': 1.0}
+
+
+def metric_kernels(B, n, refs_per_clip, rounds, reps=3000):
+    """HIP-event us per launch of dlsg_cider_d, of dlsg_caption_metrics (scores only) and of the mixed-reward launch, on B*n rows
+    that are references of their clip with a fifth of the words replaced (a heavy-headed vocabulary of 10 000, 300 clips)"""
+    vocab = dlsg_amd.make_vocab(10000)
+    rng = random.Random(refs_per_clip)
+    words = [vocab.idx2word[i] for i in range(4, len(vocab))]
+    pick = lambda: words[min(int(rng.paretovariate(0.8)) - 1, len(words) - 1)]
+    refs = {'v%03d' % c: [' '.join(pick() for _ in range(rng.randint(5, 12))) for _ in range(refs_per_clip)] for c in range(300)}
+    mixed = dlsg_amd.DeviceMixedReward(refs, vocab, MIX)
+    dc, dm = mixed.cider, mixed.metrics
+    vids = [v for v in rng.sample(sorted(refs), B) for _ in range(n)]
+    end, L = vocab('<end>'), 26
+    rows = []
+    for v in vids:
+        ws = [rng.randrange(4, len(vocab)) if rng.random() < 0.2 else vocab(w) for w in rng.choice(refs[v]).split()]
+        rows.append((ws + [end] + [rng.randrange(len(vocab)) for _ in range(L)])[:L])
+    ids = torch.tensor(rows, dtype=torch.int64, device='cuda')
+    cidx = dc.index(vids)
+    base = dc.scores_device(ids, cidx)
+    out5 = torch.empty(B * n, 5, dtype=torch.float64, device='cuda')
+    rew = torch.empty(B * n, dtype=torch.float64, device='cuda')
+    ops = dm._ops()
+    legs = {'cider_d': lambda: ops.cider_d(ids, cidx, end, dc, base),
+            'caption_metrics': lambda: ops.caption_metrics(ids, cidx, end, dm, scores=out5),
+            'caption_metrics_reward': lambda: ops.caption_metrics(ids, cidx, end, dm, reward=rew, weights=mixed.w, base=base)}
+    # a hipGraph of `per` launches per leg, so that the host's launch rate is not what the events see
+    per, graphs = 200, {}
+    side = torch.cuda.Stream()
+    for k, fn in legs.items():
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            fn()                                       # warm-up outside the capture
+        torch.cuda.current_stream().wait_stream(side)
+        graphs[k] = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graphs[k]):
+            for _ in range(per):
+                fn()
+    us = {k: [] for k in legs}
+    for _ in range(rounds):
+        for k in legs:
+            us[k].append(round(event_ms(graphs[k].replay, reps // per) / per * 1e3, 2))
+    hyps = [' '.join(vocab.idx2word[t] for t in r[:r.index(end)]) for r in rows]
+    err = float(np.abs(rew.cpu().numpy() - mixed.scores(vids, hyps)).max())
+    return {'rows': B * n, 'refs_per_clip': refs_per_clip, 'launches_per_leg': reps, 'us': us, 'best_us': {k: min(v) for k, v in us.items()},
+            'max_abs_diff_to_host_reward': err}
+
+
+def mixed_main(steps=20, B=64, n=5, rounds=2):
+    kern = [metric_kernels(B, n, q, rounds) for q in (20, 40)]
+    net, vocab, frames, regions, refs = setup(B)
+    rewards = {'cider_only': dlsg_amd.DeviceCiderD(refs, vocab), 'mixed': dlsg_amd.DeviceMixedReward(refs, vocab, MIX)}
+    vb = [str(b) for b in range(B)]
+    trainers = {}
+    for k, rw in rewards.items():
+        trainers[k] = SC.SCSTTrainer(net, rw, n_samples=n, use_graphs=True)
+        for _ in range(2):
+            trainers[k].step(frames, regions, vb)      # captures
+    legs = {k: [] for k in trainers}
+    for _ in range(rounds):
+        for k, tr in trainers.items():
+            legs[k].append(round(timed(lambda: tr.step(frames, regions, vb), steps), 3))
+            tr.trainer.check()
+    best = {k: min(v) for k, v in legs.items()}
+    print(json.dumps({
+        'what': 'caption-metric kernels against dlsg_cider_d (HIP events, back-to-back launches in a hipGraph) and the graph-replayed SCST step at '
+                'the MSVD shape, batch %d x %d samples, vocabulary 1000, with the CIDEr-only device reward against %s' % (B, n, MIX),
+        'kernels': kern, 'step_legs_ms': legs, 'best_cider_only_ms': best['cider_only'], 'best_mixed_ms': best['mixed'],
+        'mixed_minus_cider_only_ms': round(best['mixed'] - best['cider_only'], 3), 'steps': steps}))
+
+
 FILTER_OPTS = dict(top_k=50, top_p=0.9, no_repeat_ngram=3, min_len=4)
 
 
@@ -313,6 +391,8 @@ if __name__ == '__main__':
         reward_kernels()
     elif len(sys.argv) > 1 and sys.argv[1] == 'filter':
         filter_main(*[int(x) for x in sys.argv[2:6]])
+    elif len(sys.argv) > 1 and sys.argv[1] == 'mixed':
+        mixed_main(*[int(x) for x in sys.argv[2:6]])
     elif len(sys.argv) > 1 and sys.argv[1] == 'share':
         share_main(*[int(x) for x in sys.argv[2:6]])
     else:
