@@ -1095,6 +1095,173 @@ __global__ __launch_bounds__(64 * K) void beam_select_hist_kernel(const dlsg_bea
     }
 }
 
+// The step of an ensemble (dlsg_beam_select_ens): beam_select_hist_kernel, but a live beam's V candidate values are combined from
+// M logit rows, one per member.  Per member the row's log-sum-exp in beam_row_topk's order (strided maximum + wave_max, strided
+// exponential sum + wave_sum), then per class, in member order and float32,
+//   mode 0: c = mx + logf(sum_m expf(v_m - mx)),  v_m = (x_m - lse_m) + logw_m,  mx = max_m v_m   (log of the weighted mean probability)
+//   mode 1: c = sum_m w_m (x_m - lse_m)                                                          (weighted mean log-probability)
+// and the K best unbanned c of the row, by beam_row_topk's insert and merge (restated in the two helpers below, because the
+// existing kernels' code is pinned).  With one member of weight 1 both modes give c = x - lse exactly, so the launch returns
+// what beam_select_hist_kernel returns.  The M pointers, strides and weights travel by value in the argument block.
+struct EnsPack {
+    const float* x[DLSG_ENS_MAX];
+    int64_t ld[DLSG_ENS_MAX];
+    float w[DLSG_ENS_MAX], logw[DLSG_ENS_MAX];
+    int M, mode;
+};
+
+// (cv, ci) into a lane's sorted K best unless it is banned: the loop body of beam_row_topk<K, true>
+template <int K>
+__device__ __forceinline__ void beam_topk_push(float (&tv)[K], int (&ti)[K], float cv, int ci, const int* ban, int nban) {
+    if (!beam_better(cv, ci, tv[K - 1], ti[K - 1])) return;
+    for (int q = 0; q < nban; ++q) cv = ban[q] == ci ? -INFINITY : cv;
+    if (!beam_better(cv, ci, tv[K - 1], ti[K - 1])) return;
+#pragma unroll
+    for (int q = 0; q < K; ++q) {
+        const bool up = beam_better(cv, ci, tv[q], ti[q]);
+        const float nv = up ? tv[q] : cv;
+        const int ni = up ? ti[q] : ci;
+        tv[q] = up ? cv : tv[q];
+        ti[q] = up ? ci : ti[q];
+        cv = nv; ci = ni;
+    }
+}
+// the K best of the wave from the lanes' sorted lists: the merge rounds of beam_row_topk
+template <int K>
+__device__ __forceinline__ void beam_topk_merge(float (&tv)[K], int (&ti)[K], float (&outv)[K], int (&outi)[K]) {
+#pragma unroll
+    for (int c = 0; c < K; ++c) {
+        float bv = tv[0];
+        int bi = ti[0];
+        wave_argmax(bv, bi);
+        outv[c] = bv; outi[c] = bi;
+        if (ti[0] == bi && bi != 0x7fffffff) {
+#pragma unroll
+            for (int q = 0; q + 1 < K; ++q) { tv[q] = tv[q + 1]; ti[q] = ti[q + 1]; }
+            tv[K - 1] = -INFINITY; ti[K - 1] = 0x7fffffff;
+        }
+    }
+}
+
+template <int K>
+__global__ __launch_bounds__(64 * K) void beam_select_ens_kernel(const dlsg_beam_select_args a, const EnsPack e,
+                                                                   const int64_t* __restrict__ hist_in, int64_t* __restrict__ hist_out,
+                                                                   int L, int t, int g, int min_len) {
+    __shared__ float cand_lp[K * K];
+    __shared__ int cand_cls[K * K];
+    __shared__ int hist[K][BEAM_MAXL];
+    __shared__ int ban[K][BEAM_MAXL + 1];
+    __shared__ int nban[K];
+    __shared__ float lse_s[K][DLSG_ENS_MAX];                 // (in LDS: the member loop that fills it is not unrolled)
+    const int b = blockIdx.x, k = K, V = a.V;
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const int nbeam = a.first ? 1 : k;
+    const int64_t row = (int64_t)b * k + w;
+    const bool ended = !a.first && a.last[row] == a.end;
+    const bool ngram = g > 0 && t >= g;
+    if (ngram) hist[w][lane] = lane < t ? (int)hist_in[row * L + lane] : -1;
+    __syncthreads();
+    if (w < nbeam && !ended) {
+        int n = 0;
+        if (ngram) {
+            bool hit = lane <= t - g;
+            for (int j = 0; hit && j < g - 1; ++j) hit = hist[w][lane + j] == hist[w][t - g + 1 + j];
+            const unsigned long long m = __ballot(hit);
+            if (hit) ban[w][__popcll(m & ((1ull << lane) - 1ull))] = hist[w][lane + g - 1];
+            n = __popcll(m);
+        }
+        if (lane == 0) {
+            if (t < min_len) ban[w][n++] = a.end;
+            nban[w] = n;
+        }
+    }
+    __syncthreads();
+    if (w < nbeam) {
+        const float base = a.first ? 0.f : a.last_lp[row];
+        if (ended) {
+            if (lane < k) {
+                cand_lp[w * k + lane] = lane == 0 ? base : -INFINITY;
+                cand_cls[w * k + lane] = lane == 0 ? a.end : (lane - 1 < a.end ? lane - 1 : lane);
+            }
+        } else {
+            for (int m = 0; m < e.M; ++m) {                  // every lane writes the wave's value and reads back its own store
+                const float* x = e.x[m] + row * e.ld[m];
+                float mx = -INFINITY;
+                for (int j = lane; j < V; j += 64) mx = fmaxf(mx, x[j]);
+                mx = dlsg::wave_max(mx);
+                float sum = 0.f;
+                for (int j = lane; j < V; j += 64) sum += expf(x[j] - mx);
+                sum = dlsg::wave_sum(sum);
+                lse_s[w][m] = logf(sum) + mx;
+            }
+            const float* x[DLSG_ENS_MAX];
+            float lse[DLSG_ENS_MAX];
+#pragma unroll
+            for (int m = 0; m < DLSG_ENS_MAX; ++m) {
+                x[m] = m < e.M ? e.x[m] + row * e.ld[m] : nullptr;
+                lse[m] = m < e.M ? lse_s[w][m] : 0.f;
+            }
+            float tv[K], bv[K];
+            int ti[K], bi[K];
+#pragma unroll
+            for (int q = 0; q < K; ++q) { tv[q] = -INFINITY; ti[q] = 0x7fffffff; }
+            for (int j = lane; j < V; j += 64) {
+                float c;
+                if (e.mode == 0) {
+                    float v[DLSG_ENS_MAX], mx = -INFINITY, sum = 0.f;
+#pragma unroll
+                    for (int m = 0; m < DLSG_ENS_MAX; ++m)
+                        if (m < e.M) { v[m] = (x[m][j] - lse[m]) + e.logw[m]; mx = fmaxf(mx, v[m]); }
+#pragma unroll
+                    for (int m = 0; m < DLSG_ENS_MAX; ++m)
+                        if (m < e.M) sum += expf(v[m] - mx);
+                    c = mx == -INFINITY ? -INFINITY : mx + logf(sum);
+                } else {
+                    c = 0.f;
+#pragma unroll
+                    for (int m = 0; m < DLSG_ENS_MAX; ++m)
+                        if (m < e.M) c += e.w[m] * (x[m][j] - lse[m]);
+                }
+                beam_topk_push<K>(tv, ti, c, j, ban[w], nban[w]);
+            }
+            beam_topk_merge<K>(tv, ti, bv, bi);
+            if (lane == 0) {
+#pragma unroll
+                for (int q = 0; q < K; ++q) {
+                    cand_lp[w * k + q] = bv[q] + base;
+                    cand_cls[w * k + q] = bi[q];
+                }
+            }
+        }
+    }
+    __syncthreads();
+    if (w == 0) {
+        const int n = nbeam * k;
+        float v = lane < n ? cand_lp[lane] : -INFINITY;
+        int idx = lane < n ? lane : 0x7fffffff;
+        int n_end = 0;
+        for (int c = 0; c < k; ++c) {
+            float bv = v;
+            int bi = idx;
+            wave_argmax(bv, bi);
+            if (lane == bi) v = -INFINITY, idx = 0x7fffffff;
+            if (bi == 0x7fffffff) bi = c < n ? c : 0;
+            const int cls = cand_cls[bi];
+            const int64_t o = (int64_t)b * k + c;
+            if (lane == 0) {
+                a.pred[o] = cls;
+                a.new_lp[o] = bv;
+                a.back[o] = bi / k;
+                a.rows[o] = (int64_t)b * k + bi / k;
+            }
+            if (lane < L)
+                hist_out[o * L + lane] = lane < t ? hist_in[((int64_t)b * k + bi / k) * L + lane] : (lane == t ? (int64_t)cls : (int64_t)a.end);
+            n_end += cls == a.end;
+        }
+        if (lane == 0 && a.ended_count) atomicAdd(a.ended_count, n_end);
+    }
+}
+
 // The n best of each clip's k finished beams, by score = lp / len^alpha (double, stored as float), descending, ties to the lower
 // beam: one wave per clip.  len = tokens up to and including the first `end` of the beam's history row, L without one.
 __global__ __launch_bounds__(64) void beam_finalize_kernel(const int64_t* __restrict__ hist, const float* __restrict__ lp, int k, int L,
@@ -1584,6 +1751,31 @@ extern "C" int dlsg_beam_select_hist(const dlsg_beam_select_args* a, const int64
     return DLSG_OK;
 }
 #undef BEAM_HIST_CASE
+#define BEAM_ENS_CASE(KK) \
+    case KK: hipLaunchKernelGGL(beam_select_ens_kernel<KK>, dim3(a->B), dim3(64 * KK), 0, ST(stream), *a, e, hist_in, hist_out, L, t, \
+                                no_repeat_ngram, min_len); break;
+extern "C" int dlsg_beam_select_ens(const dlsg_beam_select_args* a, const float* const* logits, const int64_t* ld, const float* w,
+                                    const float* logw, int M, int mode, const int64_t* hist_in, int64_t* hist_out, int L, int t,
+                                    int no_repeat_ngram, int min_len, void* stream) {
+    if (!a || a->k < 1 || a->k > BEAM_MAXK || a->V < a->k) return DLSG_EINVAL;
+    if (!logits || !ld || !w || !logw || M < 1 || M > DLSG_ENS_MAX || (mode != 0 && mode != 1)) return DLSG_EINVAL;
+    if (!hist_out || L < 1 || L > BEAM_MAXL || t < 0 || t >= L || no_repeat_ngram < 0 || min_len < 0) return DLSG_EINVAL;
+    if ((a->first != 0) != (t == 0) || (t > 0 && (!hist_in || hist_in == hist_out))) return DLSG_EINVAL;
+    EnsPack e = {};
+    for (int m = 0; m < M; ++m) {
+        if (!logits[m]) return DLSG_EINVAL;
+        e.x[m] = logits[m]; e.ld[m] = ld[m]; e.w[m] = w[m]; e.logw[m] = logw[m];
+    }
+    e.M = M; e.mode = mode;
+    if (a->B == 0) return DLSG_OK;
+    switch (a->k) {
+        BEAM_ENS_CASE(1) BEAM_ENS_CASE(2) BEAM_ENS_CASE(3) BEAM_ENS_CASE(4)
+        BEAM_ENS_CASE(5) BEAM_ENS_CASE(6) BEAM_ENS_CASE(7) BEAM_ENS_CASE(8)
+    }
+    DLSG_CHECK_LAUNCH();
+    return DLSG_OK;
+}
+#undef BEAM_ENS_CASE
 extern "C" int dlsg_beam_finalize(const int64_t* hist, const float* lp, int B, int k, int L, int64_t end, double alpha, int n,
                                   int64_t* ids, float* scores, int64_t* lens, void* stream) {
     if (!hist || !lp || !ids || !scores || !lens || B < 0 || k < 1 || k > BEAM_MAXK || L < 1 || L > BEAM_MAXL || n < 1 || n > k)

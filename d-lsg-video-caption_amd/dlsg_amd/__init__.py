@@ -6,5 +6,7 @@ from .gan import DiscV2, GanTrainer, GANLambdaHandler, save_checkpoint, load_che
 from .data import H5File, CaptionSet, ResidentFeatures, StreamedFeatures, TrainLoader, EvalLoader, distributed_indices  # noqa: F401
 from .scst import SCSTTrainer  # noqa: F401
 from .beam import beam_search, beam_nbest  # noqa: F401
+from .ensemble import Ensemble  # noqa: F401
+from .graphs import EnsembleBeamGraph  # noqa: F401
 from .scoring import DeviceCaptionMetrics, MixedReward, DeviceMixedReward  # noqa: F401
 from .scoring import CiderD, DeviceCiderD, CaptionScorer, convert_data_to_coco_scorer_format, convert_prediction, evaluate  # noqa: F401

@@ -10,7 +10,8 @@ the host does not synchronise inside the loop except for the early-exit test eve
 
 `beam_nbest` is the search beyond the reference: all k hypotheses with their scores, length normalisation, repeated-n-gram
 blocking and a minimum length, with no host synchronisation at all (`beam_select_hist` carries every beam's tokens along, so
-there is no back-trace; `beam_finalize` ranks the beams).
+there is no back-trace; `beam_finalize` ranks the beams).  `ensemble_nbest` is that search run by several models at once: each
+member steps its own state, `beam_select_ens` combines their logits and chooses the beams (`ensemble.Ensemble`).
 """
 import torch
 
@@ -196,6 +197,43 @@ def beam_nbest(model, visual_feats, region_feats, n_best=None, length_penalty=0.
         logits = advance(t, words, rows)
         ops.beam_select_hist(logits, words, lps[t % 2], preds[t % 2], lps[(t + 1) % 2], back, rows, k, end, hist[t % 2],
                              hist[(t + 1) % 2], t, no_repeat_ngram, min_len)
+        words = preds[t % 2]
+    ids = torch.empty(B, n, L, dtype=torch.int64, device=dev)
+    scores = torch.empty(B, n, dtype=torch.float32, device=dev)
+    lens = torch.empty(B, n, dtype=torch.int64, device=dev)
+    ops.beam_finalize(hist[L % 2], lps[L % 2], k, end, float(length_penalty), ids, scores, lens)
+    return ids, scores, lens
+
+
+@torch.no_grad()
+def ensemble_nbest(models, weights, mode, visual_feats, region_feats, n_best=None, length_penalty=0.0, no_repeat_ngram=0, min_len=0,
+                   beam_size=None):
+    """`beam_nbest` with several models that decode one caption: every member runs its own encoder and its own decode step on the
+    shared words and back-pointer rows (its own state slots; any of the model classes, any hidden sizes), and one
+    `beam_select_ens` launch per step combines the members' logit rows -- mode 0: log of the weighted mean probability, mode 1:
+    weighted mean log-probability -- and chooses the beams.  One set of preds / hist / back / rows / lps; no host synchronisation.
+    The members share vocabulary, max_words and device (`ensemble.Ensemble` checks that); beam_size defaults to the first member's."""
+    dec = models[0].decoder
+    k, L = dec.beam_size if beam_size is None else beam_size, dec.max_words
+    n = check_nbest_options(k, L, n_best, length_penalty, no_repeat_ngram, min_len)
+    steps = []
+    for model in models:
+        mems, sv, seed, _ = _encode(model, visual_feats, region_feats)
+        advance, B, R, _ = _beam_setup(model, mems, sv, seed, k)
+        steps.append(advance)
+    ops = models[0].ops
+    end = dec.vocab('<end>')
+    dev = mems[0].device
+    preds = torch.empty(2, R, dtype=torch.int64, device=dev)
+    hist = torch.empty(2, R, L, dtype=torch.int64, device=dev)
+    back = torch.empty(R, dtype=torch.int64, device=dev)
+    rows = torch.empty(R, dtype=torch.int64, device=dev)
+    lps = torch.zeros(2, R, dtype=torch.float32, device=dev)
+    words = torch.full((R,), dec.vocab('<start>'), dtype=torch.int64, device=dev)
+    for t in range(L):
+        logits = [advance(t, words, rows) for advance in steps]
+        ops.beam_select_ens(logits, weights, mode, words, lps[t % 2], preds[t % 2], lps[(t + 1) % 2], back, rows, k, end, hist[t % 2],
+                            hist[(t + 1) % 2], t, no_repeat_ngram, min_len)
         words = preds[t % 2]
     ids = torch.empty(B, n, L, dtype=torch.int64, device=dev)
     scores = torch.empty(B, n, dtype=torch.float32, device=dev)

@@ -1,6 +1,6 @@
 """hipGraph capture and replay, in one place: entering and leaving the process's capture stream, the eager warm-up, capturing one
 graph or a chain of segments, dropping a capture whose body raised, staging inputs into the static buffers a graph reads --
-and the captured forms of inference built on it (GreedyGraph, SampleGraph, BeamGraph, NBestBeamGraph).  The Trainer
+and the captured forms of inference built on it (GreedyGraph, SampleGraph, BeamGraph, NBestBeamGraph, EnsembleBeamGraph).  The Trainer
 (model.py), the GanTrainer (gan.py) and the SCSTTrainer (scst.py) capture through `capture` / `capture_segments`."""
 import torch
 
@@ -170,3 +170,31 @@ class NBestBeamGraph(_InferenceGraph):
 
     def _run(self):
         return self.model.beam_search(self.frames, self.regions, **self.options)
+
+
+class EnsembleBeamGraph(_InferenceGraph):
+    """hipGraph-captured `ensemble.beam_search(frames, regions, **options)` (ensemble.Ensemble) for one batch shape: every member's
+    encoder and decode steps, one `beam_select_ens` per word, the ranking.  The graph holds addresses into EVERY member's arena and
+    every member's train / eval mode: `valid_for` and the stale-arena error cover all of them.  A replay returns (ids, scores,
+    lens), static buffers, and synchronises nothing."""
+
+    def __init__(self, ensemble, frames, regions, **options):
+        self.ensemble, self.options = ensemble, options
+        for m in ensemble.members:
+            m.flatten_parameters_()
+        self.held = [(m, m._flat, m.training) for m in ensemble.members]
+        super().__init__(ensemble.members[0], frames, regions)
+
+    def _run(self):
+        return self.ensemble.beam_search(self.frames, self.regions, **self.options)
+
+    def valid_for(self, frames, regions):
+        return super().valid_for(frames, regions) and all(a is m._flat and tr == m.training for m, a, tr in self.held)
+
+    def _stage(self, frames, regions):
+        for i, (m, arena, _) in enumerate(self.held):
+            if arena is not m._flat:
+                raise RuntimeError('EnsembleBeamGraph: member %d re-packed its parameter arena after this graph was captured '
+                                   '(flatten_parameters_ after load_encoder / load_state_dict / .to()); the graph holds addresses '
+                                   'into the old arena -- build a new one' % i)
+        super()._stage(frames, regions)

@@ -10,6 +10,7 @@ All methods take torch *views*: 2-d (rows, cols) with unit inner stride and an a
 (batch, rows, cols) for batched GEMMs (the batch stride may be 0 via .expand()).
 """
 import ctypes as C
+import math
 import os
 
 import torch
@@ -31,6 +32,7 @@ F_SK, F_NOSK, F_SK_BM128, F_SK_BM256, F_SK_BN128, F_SK_NOXMAP = (_D['DLSG_GEMM_'
     'SK', 'NOSK', 'SK_BM128', 'SK_BM256', 'SK_BN128', 'SK_NOXMAP'))
 GRAD_SUMSQ_SLOTS = _D['DLSG_GRAD_SUMSQ_SLOTS']   # float64 partials one dlsg_grad_sumsq launch writes
 CLIP_NORM, CLIP_COEF, CLIP_NONFINITE, CLIP_RECORD_FLOATS = (_D['DLSG_CLIP_' + n] for n in ('NORM', 'COEF', 'NONFINITE', 'RECORD_FLOATS'))
+ENS_MAX = _D['DLSG_ENS_MAX']                    # members dlsg_beam_select_ens combines
 METRICS_STAGE = _D['DLSG_METRICS_STAGE']        # reference words dlsg_caption_metrics stages in LDS per pass
 F_SK_GIVEAWAY = _D['DLSG_GEMM_SK_GIVEAWAY']   # test hook (include/dlsg.h): the split tiles are finished by their last contributor alone
 
@@ -97,6 +99,15 @@ def copy_to_device(dst, values, dtype=None):
     if dst.is_cuda and not t.is_cuda:
         t = t.contiguous().pin_memory()
     dst.copy_(t.view(dst.shape), non_blocking=True)
+
+
+def normalised_weights(weights):
+    """the members' weights of `beam_select_ens` as the kernel gets them: w / sum(w) in float64 (a list of Python floats)"""
+    w = [float(x) for x in weights]
+    if not w or not all(math.isfinite(x) and x > 0.0 for x in w):
+        raise ValueError('ensemble weights must be finite and positive, not %r' % (list(weights),))
+    tot = math.fsum(w)
+    return [x / tot for x in w]
 
 
 def _chk2(t):
@@ -534,6 +545,31 @@ class HipOps(object):
         a.B, a.k, a.V, a.end, a.first = R // k, k, V, end, int(t == 0)
         self._check(self.lib.dlsg_beam_select_hist(C.byref(a), _p(hist_in), _p(hist_out), L, int(t), int(no_repeat_ngram), int(min_len),
                                                    self._stream()), 'dlsg_beam_select_hist')
+
+    def beam_select_ens(self, logits_list, weights, mode, last, last_lp, pred, new_lp, back, rows, k, end, hist_in, hist_out, t,
+                        no_repeat_ngram=0, min_len=0, ended_count=None):
+        """`beam_select_hist` for an ensemble: the candidates of beam row r are combined from logits_list[m][r], one (R, V) float32
+        array per member, with `weights` (positive, normalised here in float64) -- mode 0: log of the weighted mean probability,
+        mode 1: weighted mean log-probability (see include/dlsg.h)."""
+        a = abi.dlsg_beam_select_args()
+        M = len(logits_list)
+        R, V = logits_list[0].shape
+        L = hist_out.shape[1]
+        for h in (hist_in, hist_out):
+            assert h.dtype == torch.int64 and h.is_contiguous() and h.shape == (R, L), (h.dtype, h.shape)
+        for x in logits_list:
+            assert x.dtype == torch.float32 and x.shape == (R, V) and x.stride(1) == 1 and x.device == hist_out.device, (x.dtype, x.shape)
+        assert len(weights) == M, (len(weights), M)
+        w = normalised_weights(weights)
+        a.last, a.last_lp = _p(last), _p(last_lp)
+        a.pred, a.new_lp, a.back, a.rows, a.ended_count = _p(pred), _p(new_lp), _p(back), _p(rows), _p(ended_count)
+        a.B, a.k, a.V, a.end, a.first = R // k, k, V, end, int(t == 0)
+        ptrs = (C.c_void_p * M)(*[x.data_ptr() for x in logits_list])
+        lds = (C.c_int64 * M)(*[x.stride(0) for x in logits_list])
+        ws = (C.c_float * M)(*w)
+        logws = (C.c_float * M)(*[math.log(x) for x in w])
+        self._check(self.lib.dlsg_beam_select_ens(C.byref(a), ptrs, lds, ws, logws, M, int(mode), _p(hist_in), _p(hist_out), L, int(t),
+                                                  int(no_repeat_ngram), int(min_len), self._stream()), 'dlsg_beam_select_ens')
 
     def beam_finalize(self, hist, lp, k, end, alpha, ids, scores, lens):
         """the n = ids.shape[1] best of each clip's k beams by lp / len^alpha: ids (B, n, L), scores (B, n), lens (B, n)."""

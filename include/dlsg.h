@@ -785,6 +785,21 @@ int dlsg_beam_select(const dlsg_beam_select_args* a, void* stream);
  * dlsg_beam_select. */
 int dlsg_beam_select_hist(const dlsg_beam_select_args* a, const int64_t* hist_in, int64_t* hist_out, int L, int t,
                           int no_repeat_ngram, int min_len, void* stream);
+/* dlsg_beam_select_hist for an ensemble of M members that decode one caption: a live beam's V candidate values are combined from M
+ * logit rows, logits[m] + r * ld[m] for beam row r (a->logits and a->ld are ignored).  With l_m = x_m - lse_m, lse_m the row's
+ * log-sum-exp in the order dlsg_beam_select_hist takes it, per class, in member order and float32:
+ *   mode 0 ("prob"):     c = mx + logf(sum_m expf(v_m - mx)), v_m = l_m + logw[m], mx = max_m v_m (-inf when mx is): the log of
+ *                        the weighted mean of the members' probabilities;
+ *   mode 1 ("logprob"):  c = sum_m w[m] * l_m, from 0: the weighted mean of their log-probabilities, not renormalised.
+ * The k best unbanned c of the row (larger first, ties to the lower class) are offered at c + last_lp; the bans, ended beams, the
+ * k*k merge, pred / new_lp / back / rows, the history and ended_count are those of dlsg_beam_select_hist.  With M == 1, w = {1},
+ * logw = {0} either mode gives c = x - lse, the value dlsg_beam_select_hist ranks by.  logits, ld, w (normalised to sum 1),
+ * logw = log(w): HOST arrays of M entries, read during the call and passed to the kernel by value (a captured launch keeps them).
+ * EINVAL for M outside 1..DLSG_ENS_MAX, mode outside {0, 1}, k outside 1..8, L > 64.  Each member row is read three times. */
+#define DLSG_ENS_MAX 8
+int dlsg_beam_select_ens(const dlsg_beam_select_args* a, const float* const* logits, const int64_t* ld, const float* w,
+                         const float* logw, int M, int mode, const int64_t* hist_in, int64_t* hist_out, int L, int t,
+                         int no_repeat_ngram, int min_len, void* stream);
 /* After the last step: the n <= k best beams of every clip by score = lp / len^alpha (computed in double, stored as float),
  * descending, ties to the lower beam.  hist (B*k, L) the final history, lp (B*k) the final log-probs; len = tokens up to and
  * including the first `end`, L without one.  Out: ids (B, n, L) int64, scores (B, n), lens (B, n) int64.  One wave per clip. */
