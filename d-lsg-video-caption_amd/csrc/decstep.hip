@@ -8,6 +8,7 @@
 //             -> tanh -> LayerNorm(+dropout)
 //   dec_tail: language LSTM cell pointwise (+dropout) -> tanh(LayerNorm) for the vocab projection
 // Arithmetic is the same as lstm_pw_fwd / rowln_fwd / decatt_fwd (rowops.hip, attention.hip), element for element.
+#include <algorithm>
 #include "common.hpp"
 #include "persist.hpp"
 #include "dlsg.h"
@@ -58,8 +59,9 @@ __device__ __forceinline__ void block_sum2(float& a, float& b, float* red) {
 
 // LSTM cell of one row (gate order i, f, g, o): gate pre-activations = slabs + addend + biases, all loads of a thread
 // independent (V-wide, slabs unrolled by 4) so one round trip covers them; activated gates go to `gb` (LDS, 4N) and
-// `gates`; then c = f*c_prev + i*g, h = o*tanh(c) (* dropout) per unit; h is left in `hb` (LDS).
-template <int V>
+// `gates`; then c = f*c_prev + i*g, h = o*tanh(c) (* dropout) per unit; h is left in `hb` (LDS).  ST = false: the same
+// arithmetic with no store to memory (the workgroups of dec_tail_fwd that only need a row's h again).
+template <int V, bool ST = true>
 __device__ __forceinline__ void cell_row(int b, int N, const float* slabs, int nslab, int64_t slab_stride, const float* addend,
                                          int64_t ldadd, const float* b_ih, const float* b_hh, const float* c_prev, float* c_out,
                                          float* h_out, float* gates, float p, uint32_t site, uint64_t seed, float* gb, float* hb) {
@@ -107,7 +109,7 @@ __device__ __forceinline__ void cell_row(int b, int N, const float* slabs, int n
         const bool is_g = (col / N) == 2;
 #pragma unroll
         for (int e = 0; e < V; ++e) acc[e] = is_g ? tanhf(acc[e]) : sigmoidf_(acc[e]);
-        vstore<V>(gates + (int64_t)b * 4 * N + col, acc);
+        if constexpr (ST) vstore<V>(gates + (int64_t)b * 4 * N + col, acc);
         vstore<V>(gb + col, acc);
     }
     __syncthreads();
@@ -118,9 +120,9 @@ __device__ __forceinline__ void cell_row(int b, int N, const float* slabs, int n
         const float cp = cpv[i];
         const float c = gb[N + j] * cp + gb[j] * gb[2 * N + j];
         float h = gb[3 * N + j] * tanhf(c);
-        c_out[(int64_t)b * N + j] = c;
+        if constexpr (ST) c_out[(int64_t)b * N + j] = c;
         if (p > 0.f) h *= drop_scale(seed, site, (uint64_t)b * N + j, p);
-        h_out[(int64_t)b * N + j] = h;
+        if constexpr (ST) h_out[(int64_t)b * N + j] = h;
         hb[j] = h;
     }
     __syncthreads();
@@ -311,12 +313,24 @@ __global__ __launch_bounds__(DT) void dec_mid_fwd_kernel(const dlsg_dec_mid_args
     }
 }
 
+// One (best logit, first index) pair of a part in the row's workspace, and the row's ticket counter: global address space,
+// agent scope -- the pair goes out as ONE write-through 8-byte store and comes back through loads that pass the CU's L1.
+using gu64 = __attribute__((address_space(1))) unsigned long long;
+using gu32 = __attribute__((address_space(1))) unsigned int;
+constexpr int TAIL_WS_CNT = 2 * DLSG_DEC_TAIL_MAX_SPLIT;      // word of the counter in a row's DLSG_DEC_TAIL_WS_WORDS
+static_assert(TAIL_WS_CNT < DLSG_DEC_TAIL_WS_WORDS, "a workspace row holds the pairs and the counter");
+
+// `split` workgroups per row (dlsg.h), grid (B, split): workgroup part * B + row in dispatch order (x runs fastest), so the B
+// part-0 workgroups -- the only ones with work on a teacher-forced step -- are dispatched first.  The part is the grid's y and
+// not a quotient of x: part 0 then reaches its loads without a division, and without waiting for an argument, in front of them.
 template <int V>
-__global__ __launch_bounds__(DT) void dec_tail_fwd_kernel(const dlsg_dec_tail_args a) {
+__global__ __launch_bounds__(DT) void dec_tail_fwd_kernel(const dlsg_dec_tail_args a, const int split) {
     __shared__ __attribute__((aligned(16))) float gb[4 * MAXW];
     __shared__ __attribute__((aligned(16))) float hb[MAXW];
     __shared__ float red[32];
-    const int b = blockIdx.x;
+    const int part = blockIdx.y, b = blockIdx.x;
+    // (the other parts have nothing to do on a teacher-forced step: the coin is all they touch)
+    if (part > 0 && a.s_coins[a.s_t] != 0) return;
     const int D = a.D;
     const uint64_t seed = a.seed + (a.seed_ptr ? *a.seed_ptr : 0ull);
     constexpr int ND = MAXW / DT;
@@ -326,11 +340,15 @@ __global__ __launch_bounds__(DT) void dec_tail_fwd_kernel(const dlsg_dec_tail_ar
         const int j = threadIdx.x + i * DT;
         lg[i] = j < D ? a.ln_g[j] : 0.f; lb[i] = j < D ? a.ln_b[j] : 0.f;
     }
-    cell_row<V>(b, D, a.slabs, a.nslab, a.slab_stride, nullptr, 0, a.b_ih, a.b_hh, a.c_prev, a.c, a.hd, a.gates, a.p, a.site,
-                seed, gb, hb);
+    if (part == 0)
+        cell_row<V>(b, D, a.slabs, a.nslab, a.slab_stride, nullptr, 0, a.b_ih, a.b_hh, a.c_prev, a.c, a.hd, a.gates, a.p, a.site,
+                    seed, gb, hb);
+    else
+        cell_row<V, false>(b, D, a.slabs, a.nslab, a.slab_stride, nullptr, 0, a.b_ih, a.b_hh, a.c_prev, nullptr, nullptr, nullptr,
+                           a.p, a.site, seed, gb, hb);
     float mean, rstd;
     ln_stats(hb, D, a.eps, red, mean, rstd);
-    if (threadIdx.x == 0) { a.st_l[2 * b] = mean; a.st_l[2 * b + 1] = rstd; }
+    if (threadIdx.x == 0 && part == 0) { a.st_l[2 * b] = mean; a.st_l[2 * b + 1] = rstd; }
     const bool sample = a.s_coins != nullptr && a.s_coins[a.s_t] == 0;        // block-uniform
     float dv[ND];
 #pragma unroll
@@ -339,7 +357,7 @@ __global__ __launch_bounds__(DT) void dec_tail_fwd_kernel(const dlsg_dec_tail_ar
         dv[i] = 0.f;
         if (j >= D) break;
         dv[i] = tanhf((hb[j] - mean) * rstd * lg[i] + lb[i]);
-        a.dout[(int64_t)b * D + j] = dv[i];
+        if (part == 0) a.dout[(int64_t)b * D + j] = dv[i];
     }
     if (!sample) return;
     // ---- the next word is sampled from this row's own logits: project it (dout . s_W^T + s_b), first maximum, embed
@@ -355,30 +373,73 @@ __global__ __launch_bounds__(DT) void dec_tail_fwd_kernel(const dlsg_dec_tail_ar
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     float best = -INFINITY;
     int bidx = 0x7fffffff;
+    // this part's share of the vocabulary: rows [lo, hi), contiguous, possibly empty
+    const int lo = (int)((int64_t)a.s_V * part / split), hi = (int)((int64_t)a.s_V * (part + 1) / split);
     constexpr int CU4 = 4;                        // vocabulary rows per wave and trip: their loads are in flight together
-    for (int v0 = w * CU4; v0 < a.s_V; v0 += (DT / 64) * CU4) {
+    constexpr int NJ = 1024 / (64 * V);           // chunks of 64 * V columns of a row held in registers: the first 1024 columns
+    float wr_[CU4][NJ][V], bq[CU4];
+    // request a trip's rows (and their biases, first: a wait for a later load would wait for the rows as well).  Guards are
+    // clamped addresses: every lane issues every load, a clamped one is never used.
+    auto request = [&](int v0) {
+#pragma unroll
+        for (int u = 0; u < CU4; ++u) bq[u] = a.s_b ? a.s_b[min(v0 + u, hi - 1)] : 0.f;
+#pragma unroll
+        for (int u = 0; u < CU4; ++u) {
+            const float* wr = a.s_W + (int64_t)min(v0 + u, hi - 1) * D;
+#pragma unroll
+            for (int c = 0; c < NJ; ++c) vload<V>(wr_[u][c], wr + min((lane + 64 * c) * V, D - V));
+        }
+    };
+    int v0 = lo + w * CU4;
+    if (v0 < hi) request(v0);
+    for (; v0 < hi; v0 += (DT / 64) * CU4) {
         float acc[CU4];
 #pragma unroll
         for (int u = 0; u < CU4; ++u) {
             acc[u] = 0.f;
-            const int v = min(v0 + u, a.s_V - 1);
-            const float* wr = a.s_W + (int64_t)v * D;
             if (V == 4) {
-                for (int j = 4 * lane; j < D; j += 256) {
-                    const f32x4 x = *reinterpret_cast<const f32x4*>(hb + j);
-                    const f32x4 y = *reinterpret_cast<const f32x4*>(wr + j);
-                    acc[u] += x[0] * y[0] + x[1] * y[1] + x[2] * y[2] + x[3] * y[3];
+#pragma unroll
+                for (int c = 0; c < NJ; ++c) {
+                    const int j = 4 * lane + 256 * c;
+                    if (j < D) {
+                        const f32x4 x = *reinterpret_cast<const f32x4*>(hb + j);
+                        const float (&y)[V] = wr_[u][c];
+                        acc[u] += x[0] * y[0] + x[1] * y[1] + x[2] * y[2] + x[3] * y[3];
+                    }
+                }
+                if (D > 1024) {                   // columns past the registers: loaded here, in the same order
+                    const float* wr = a.s_W + (int64_t)min(v0 + u, hi - 1) * D;
+                    for (int j = 4 * lane + 1024; j < D; j += 256) {
+                        const f32x4 x = *reinterpret_cast<const f32x4*>(hb + j);
+                        const f32x4 y = *reinterpret_cast<const f32x4*>(wr + j);
+                        acc[u] += x[0] * y[0] + x[1] * y[1] + x[2] * y[2] + x[3] * y[3];
+                    }
                 }
             } else {
-                for (int j = lane; j < D; j += 64) acc[u] += hb[j] * wr[j];
+#pragma unroll
+                for (int c = 0; c < NJ; ++c) {
+                    const int j = lane + 64 * c;
+                    if (j < D) acc[u] += hb[j] * wr_[u][c][0];
+                }
+                if (D > 1024) {
+                    const float* wr = a.s_W + (int64_t)min(v0 + u, hi - 1) * D;
+                    for (int j = lane + 1024; j < D; j += 64) acc[u] += hb[j] * wr[j];
+                }
             }
         }
+        float bc[CU4];
+#pragma unroll
+        for (int u = 0; u < CU4; ++u) bc[u] = bq[u];
+        // the next trip's rows are on their way while this trip's four sums are reduced
+        const int vn = v0 + (DT / 64) * CU4;
+        if (vn < hi) request(vn);
+        __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int u = 0; u < CU4; ++u) {
             const int v = v0 + u;
             float s_ = wave_sum(acc[u]);
-            if (a.s_b) s_ += a.s_b[min(v, a.s_V - 1)];
-            if (v < a.s_V && (s_ > best || (s_ == best && v < bidx))) { best = s_; bidx = v; }
+            if (a.s_b) s_ += bc[u];
+            if (v < hi && (s_ > best || (s_ == best && v < bidx))) { best = s_; bidx = v; }
         }
     }
     if (lane == 0) { red[w] = best; s_bi[w] = bidx; }
@@ -386,12 +447,35 @@ __global__ __launch_bounds__(DT) void dec_tail_fwd_kernel(const dlsg_dec_tail_ar
     if (threadIdx.x == 0) {
         for (int k = 1; k < DT / 64; ++k)
             if (red[k] > best || (red[k] == best && s_bi[k] < bidx)) { best = red[k]; bidx = s_bi[k]; }
+        bool last = true;
+        if (split > 1) {
+            // hand the pair over and draw a ticket; whoever draws the last one has every part's pair behind its ticket
+            gu64* pairs = (gu64*)(a.s_ws + (int64_t)b * DLSG_DEC_TAIL_WS_WORDS);
+            gu32* cnt = (gu32*)(a.s_ws + (int64_t)b * DLSG_DEC_TAIL_WS_WORDS + TAIL_WS_CNT);
+            __hip_atomic_store(pairs + part, ((unsigned long long)__float_as_uint(best) << 32) | (unsigned)bidx, __ATOMIC_RELAXED,
+                               __HIP_MEMORY_SCOPE_AGENT);
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            const unsigned ticket = __hip_atomic_fetch_add(cnt, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            last = ticket == (unsigned)(split - 1);
+            if (last) {
+                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");     // (no instruction: the loads stay below the ticket)
+                best = -INFINITY; bidx = 0x7fffffff;
+                for (int k = 0; k < split; ++k) {      // in part order, with the tie rule of the scan: arrival order plays no role
+                    const unsigned long long pr = __hip_atomic_load(pairs + k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    const float pv = __uint_as_float((unsigned)(pr >> 32));
+                    const int pi = (int)(unsigned)pr;
+                    if (pv > best || (pv == best && pi < bidx)) { best = pv; bidx = pi; }
+                }
+                __hip_atomic_store(cnt, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // ready for the next launch
+            }
+        }
         if (bidx == 0x7fffffff) bidx = 0;       // a row without a maximum (all NaN / -inf): word 0, never an out-of-range gather below
-        s_chosen = bidx;
-        a.s_ids[b] = bidx;
+        s_chosen = last ? bidx : -1;
+        if (last) a.s_ids[b] = bidx;
     }
     __syncthreads();
     const int64_t id = s_chosen;
+    if (id < 0) return;                         // another part of this row draws the last ticket
     for (int j = threadIdx.x; j < a.s_Wd; j += DT) {
         float e = a.s_E[id * a.s_Wd + j];
         if (a.s_p > 0.f) e *= drop_scale(seed, a.s_site, (uint64_t)(a.s_row0 + b) * a.s_Wd + j, a.s_p);
@@ -757,14 +841,21 @@ extern "C" int dlsg_dec_mid_fwd(const dlsg_dec_mid_args* a, void* stream) {
     DLSG_CHECK_LAUNCH();
     return DLSG_OK;
 }
+extern "C" int dlsg_dec_tail_split(int32_t B, int32_t cus) {
+    return B < 1 ? 1 : std::max(1, std::min<int>(DLSG_DEC_TAIL_MAX_SPLIT, cus / B));
+}
 extern "C" int dlsg_dec_tail_fwd(const dlsg_dec_tail_args* a, void* stream) {
-    if (!a || a->D < 1 || a->D > MAXW) return DLSG_EINVAL;
+    if (!a || a->D < 1 || a->D > MAXW || a->s_split < 0 || a->s_split > DLSG_DEC_TAIL_MAX_SPLIT) return DLSG_EINVAL;
     if (a->B == 0) return DLSG_OK;
     if (a->s_coins && (!a->s_W || !a->s_E || !a->s_ids || !a->s_we || a->s_V < 1 || a->s_Wd < 1)) return DLSG_EINVAL;
     const bool v4 = a->D % 4 == 0 && a->slab_stride % 4 == 0 && vec_ok(a->slabs) && vec_ok(a->b_ih) && vec_ok(a->b_hh) &&
                     vec_ok(a->gates) && (!a->s_coins || vec_ok(a->s_W));
-    hipLaunchKernelGGL(v4 ? dec_tail_fwd_kernel<4> : dec_tail_fwd_kernel<1>, dim3(a->B), dim3(DT), 0,
-                       reinterpret_cast<hipStream_t>(stream), *a);
+    // the split of a sampled step's vocabulary scan: arguments and device only, so a captured graph and the eager path choose alike
+    int split = 1;
+    if (a->s_ws && a->s_coins && a->c_prev != a->c && (reinterpret_cast<uintptr_t>(a->s_ws) & 7) == 0)
+        split = a->s_split ? a->s_split : dlsg_dec_tail_split(a->B, persist::device_cus());
+    hipLaunchKernelGGL(v4 ? dec_tail_fwd_kernel<4> : dec_tail_fwd_kernel<1>, dim3(a->B, split), dim3(DT), 0,
+                       reinterpret_cast<hipStream_t>(stream), *a, split);
     DLSG_CHECK_LAUNCH();
     return DLSG_OK;
 }

@@ -129,6 +129,7 @@ class HipOps(object):
         self.extra_flags = 0      # OR-ed into every dlsg_gemm call (precision policy: F_BF16X3), set by the model
         self.prof_min_flops = 2e9  # dlsg_gemm calls below this are not bracketed by profile events (tools/pmc_step_target.py: 0)
         self.flop_count = None     # a float: every dlsg_gemm call adds its 2 M N K (bench.py: executed flops of a step)
+        self._tail_ws = {}         # device -> workspace of dec_tail_fwd's split vocabulary scan (_dec_tail_ws)
 
     # ------------------------------------------------------------------ live per-kernel timing (bench.py roofline)
     def _prof_begin(self):
@@ -739,10 +740,27 @@ class HipOps(object):
     def dec_tail_sample_supported(self, V, D):
         return V * D <= self.DEC_TAIL_SAMPLE_MAX_WEIGHTS
 
+    # s_split of every dec_tail_fwd(sample=...) launch: 0 the library's choice (dlsg_dec_tail_split), 1 unsplit, 2 ..
+    # DLSG_DEC_TAIL_MAX_SPLIT forced (tests).  The outputs do not depend on it.
+    dec_tail_split = 0
+
+    def _dec_tail_ws(self, device, B):
+        """the split scan's workspace of `device` (include/dlsg.h: zeroed once, here; every launch leaves it zeroed), one per
+        device and kept.  Allocated and zeroed outside a capture only -- a step's warm-up launches come first -- so a capture
+        that finds none large enough gets None, the unsplit launch."""
+        ws = self._tail_ws.get(device)
+        if ws is None or ws.numel() < B * abi.defines['DLSG_DEC_TAIL_WS_WORDS']:
+            if torch.cuda.is_current_stream_capturing():
+                return None
+            ws = torch.zeros(max(B, 256) * abi.defines['DLSG_DEC_TAIL_WS_WORDS'], dtype=torch.int32, device=device)
+            self._tail_ws[device] = ws
+        return ws
+
     def dec_tail_fwd(self, slabs, b_ih, b_hh, c_prev, c, hd, gates, ln, dout, st_l, p, site, seed=0, eps=1e-5, sample=None):
         """language cell pointwise (+dropout on h) -> tanh(LN(h)); one launch.
         sample: optional dict(coins (int32 device vector), t, W (V,D), b (V) or None, E (V,Wd), ids_out (B) int64, we_out (B,Wd),
-        p, site, row0): the next step's word is sampled inside the launch when coins[t] == 0 (include/dlsg.h)."""
+        p, site, row0): the next step's word is sampled inside the launch when coins[t] == 0 (include/dlsg.h); the vocabulary
+        scan of such a step is split over the workgroups `dec_tail_split` says, on the workspace this object keeps."""
         a = abi.dlsg_dec_tail_args()
         if sample is not None:
             sm = sample
@@ -753,6 +771,7 @@ class HipOps(object):
             a.s_W, a.s_b, a.s_E, a.s_Wd = _p(sm['W']), _p(sm.get('b')), _p(sm['E']), sm['E'].shape[1]
             a.s_site, a.s_ids, a.s_we, a.s_ldwe = sm.get('site', 0), _p(sm['ids_out']), _p(sm['we_out']), sm['we_out'].stride(0)
             a.s_row0, a.s_p = int(sm.get('row0', 0)), float(sm.get('p', 0.0))
+            a.s_ws, a.s_split = _p(self._dec_tail_ws(c.device, c.size(0))), self.dec_tail_split
         a.slabs, a.nslab, a.slab_stride = _p(slabs), slabs.size(0), slabs.stride(0)
         a.b_ih, a.b_hh, a.c_prev, a.c, a.hd, a.gates = _p(b_ih), _p(b_hh), _p(c_prev), _p(c), _p(hd), _p(gates)
         for t in (c, hd, gates, dout):

@@ -373,8 +373,26 @@ typedef struct {
     const float* s_E; int32_t s_Wd; uint32_t s_site;
     int64_t* s_ids; float* s_we; int64_t s_ldwe;
     int64_t s_row0; float s_p; float pad2_;
+    /* optional (s_ws != NULL): the vocabulary scan of a sampled step split over S workgroups per row, grid B x S, still one launch.
+     * Part 0 of a row is the workgroup described above; on a sampled step it scans only the first of S contiguous shares of the
+     * vocabulary.  Parts 1 .. S-1 read the coin first and return on a teacher-forced step; on a sampled step they recompute the
+     * row's dout (same arithmetic, no stores) and scan their share.  Every part leaves its (best logit, first index) in the
+     * row's workspace and draws a ticket from the row's counter; the part that draws the last one takes the maximum of the S
+     * pairs (lower index on equality), writes s_ids / s_we and sets the counter back to 0.  No part waits for another, and
+     * every output has the bits of the unsplit launch.
+     * s_ws: DLSG_DEC_TAIL_WS_WORDS int32 words per row, 8-byte aligned, ZEROED ONCE by the caller when it is allocated and never
+     * again (every sampled launch leaves the counters at 0; a teacher-forced one does not touch them); not shared by two
+     * launches that may run at the same time.  s_split: 0 the library's choice, dlsg_dec_tail_split(B, CUs of the device);
+     * 1 unsplit; 2 .. DLSG_DEC_TAIL_MAX_SPLIT forced (tests).  Unsplit as well when s_ws or s_coins is NULL or c_prev == c
+     * (the other parts would read what part 0 writes).  Zeroed fields: the launch of ABI 7. */
+    int32_t* s_ws; int32_t s_split; int32_t pad3_;
 } dlsg_dec_tail_args;
+#define DLSG_DEC_TAIL_MAX_SPLIT 8
+#define DLSG_DEC_TAIL_WS_WORDS 32 /* per row: MAX_SPLIT 8-byte pairs, the ticket counter, padding to one 128-byte line */
 int dlsg_dec_tail_fwd(const dlsg_dec_tail_args* a, void* stream);
+/* host only, no launch: the split dlsg_dec_tail_fwd chooses for s_split = 0 on a device of `cus` compute units --
+ * min(DLSG_DEC_TAIL_MAX_SPLIT, cus / B), at least 1: the parts of all rows fit the device together. */
+int dlsg_dec_tail_split(int32_t B, int32_t cus);
 /* Backward of dlsg_dec_mid_fwd for one word step, one workgroup per batch row.  Consumes the slabs of the language
  * cell's input-gradient GEMM directly (their sum is [d ctx_0 | d ctx_1 | d q_cur | d lang_h(recurrent)]), runs the
  * output_layer LayerNorm backward of each stream, the attention backward (score / softmax / context), the
