@@ -1,7 +1,12 @@
 """Ensemble decoding: several trained models -- seeds of one configuration, CapGnnModel beside a baseline, the checkpoints a GAN run
 and an SCST run leave behind -- decode one caption per clip in ONE beam search.  Every member runs its own encoder and decode
 step; `dlsg_beam_select_ens` combines their logit rows on the device at every word (`beam.ensemble_nbest`), so the search has the
-launches of the members' searches plus nothing that touches the host.  An ensemble decodes; it does not train."""
+launches of the members' searches plus nothing that touches the host.  An ensemble decodes, and it teaches: `teacher_logits`
+gives a `Trainer(teacher=...)` the members' teacher-forced rows, which `dlsg_ce_ragged_soft` combines by the same rule into the
+word distribution a student is distilled towards; its own members it does not train."""
+import torch
+
+from .graphs import expand_rows
 from .hip import ENS_MAX, normalised_weights
 
 MODES = {'prob': 0, 'logprob': 1}
@@ -52,6 +57,31 @@ class Ensemble(object):
     def greedy(self, visual_feats, region_feats):
         """(B, L) ids, <end>-padded: the search with one beam"""
         return self.beam_search(visual_feats, region_feats, beam_size=1, n_best=1)[0][:, 0]
+
+    @torch.no_grad()
+    def teacher_logits(self, frames, regions, captions, max_words=None, seq_per_clip=1):
+        """The members' logits on `captions`, teacher-forced at every position and without dropout whatever a member's `.training`
+        says (the flag is not touched): a list of M time-major (L, B*n, V) float32 tensors, row (t, b) what member m predicts for
+        word t of caption b after its words 0..t-1.  L = captions.shape[1], cut to max_words when that is set.  seq_per_clip = n:
+        frames / regions hold B clips, captions their B*n rows; a CapGnnModel member runs its encoder once per clip, the baseline
+        models get the clip rows repeated.  Nothing is read back; the launches may be captured."""
+        n = int(seq_per_clip)
+        if n < 1 or captions.shape[0] != n * frames.shape[0]:
+            raise ValueError('%d caption rows for %d clips with seq_per_clip = %r' % (captions.shape[0], frames.shape[0], seq_per_clip))
+        if max_words is not None:
+            captions = captions[:, :max_words]
+        captions = captions.contiguous()
+        L = captions.shape[1]
+        out = []
+        for m in self.members:
+            m.flatten_parameters_()
+            sv = {}
+            if n == 1 or m.seq_per_clip_ok:
+                m._engine_forward(frames, regions, captions, L, [True] * L, False, 0, sv, outputs=False, seq_per_clip=n)
+            else:
+                m._engine_forward(expand_rows(frames, n), expand_rows(regions, n), captions, L, [True] * L, False, 0, sv, outputs=False)
+            out.append(sv['dec']['LOGITS'])
+        return out
 
     def __call__(self, visual_feats, region_feats, captions=None):
         """inference as `model(frames, regions, None)` returns it: (ids (B, L) of the best beam at the first member's beam size,

@@ -1445,6 +1445,43 @@ class HipOps(object):
         self._check(self.lib.dlsg_ce_ragged_weighted(_p(logits), _p(targets), _p(lens), _p(weights), _p(dlogits), _p(row_loss), _p(loss),
                                                      B, L, V, int(time_major), self._stream()), 'ce_ragged_weighted')
 
+    def ce_ragged_soft(self, logits, targets, lens, dlogits, row_loss, loss, time_major, smoothing=0.0, weights=None, teachers=(),
+                       teacher_weights=None, mode=0, alpha=0.0):
+        """ce_ragged against the soft target row (1 - alpha) * ((1 - smoothing) * onehot + smoothing / V) + alpha * q, q the word
+        distribution of `teachers` -- a sequence of float32 logits arrays of the shape and row order of `logits` (rows may be
+        strided), combined with `teacher_weights` (positive, default uniform, normalised here in float64) by `mode` 0 (weighted mean
+        probability) or 1 (weighted geometric mean, renormalised); see include/dlsg.h.  weights: optional (B,) float32 per caption.
+        row_loss: scratch of 3 * B * L floats; loss: 3 floats {mixed loss, NLL of the targets, CrossEntropy against q}."""
+        if time_major:
+            L, B, V = logits.shape
+        else:
+            B, L, V = logits.shape
+        M = len(teachers)
+        assert logits.dtype == dlogits.dtype == torch.float32 and logits.is_contiguous() and dlogits.is_contiguous()
+        assert dlogits.shape == logits.shape, (dlogits.shape, logits.shape)
+        assert targets.dtype == torch.int64 and targets.is_contiguous() and targets.shape == (B, L), (targets.dtype, targets.shape)
+        assert lens.dtype == torch.int64 and lens.is_contiguous() and lens.numel() == B
+        assert row_loss.dtype == torch.float32 and row_loss.is_contiguous() and row_loss.numel() >= 3 * B * L
+        assert loss.dtype == torch.float32 and loss.is_contiguous() and loss.numel() == 3
+        assert weights is None or (weights.dtype == torch.float32 and weights.numel() == B and weights.is_contiguous())
+        ptrs = lds = ws = logws = None
+        if M:
+            w = normalised_weights([1.0] * M if teacher_weights is None else teacher_weights)
+            assert len(w) == M, (len(w), M)
+            rows = []
+            for x in teachers:
+                assert x.dtype == torch.float32 and x.shape == logits.shape and x.device == logits.device, (x.dtype, x.shape)
+                x2 = x.view(B * L, V) if x.is_contiguous() else x.reshape(B * L, V)
+                assert x2.data_ptr() == x.data_ptr() and (x2.stride(1) == 1 or V == 1), 'teacher rows must be equally strided, unit column stride'
+                rows.append(x2)
+            ptrs = (C.c_void_p * M)(*[x.data_ptr() for x in rows])
+            lds = (C.c_int64 * M)(*[x.stride(0) for x in rows])
+            ws = (C.c_float * M)(*w)
+            logws = (C.c_float * M)(*[math.log(x) for x in w])
+        self._check(self.lib.dlsg_ce_ragged_soft(_p(logits), _p(targets), _p(lens), _p(weights), _p(dlogits), _p(row_loss), _p(loss),
+                                                 B, L, V, int(time_major), f32(smoothing), f32(alpha), ptrs, lds, ws, logws, M, int(mode),
+                                                 self._stream()), 'ce_ragged_soft')
+
     def cider_d(self, ids, clip_idx, end_id, tables, out):
         """out[r] (float64) = CIDEr-D of the words of ids[r] (int64 (R, L), L <= 64, unit column stride; the words before the first
         end_id) against the references of clip clip_idx[r] (int32) in `tables` (a scoring.DeviceCiderD)"""

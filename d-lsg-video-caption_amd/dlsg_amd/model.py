@@ -633,7 +633,7 @@ class Trainer(object):
 
     def __init__(self, model, lr=1.6e-4, betas=(0.5, 0.9), eps=1e-8, process_group=None, world_size=1, use_graphs=False,
                  device_coins=None, graph_fallback=False, comm='auto', check_every=100, rehearse_ranks=0, max_grad_norm=None,
-                 clip_grad_value=None):
+                 clip_grad_value=None, label_smoothing=0.0, teacher=None, distill_weight=0.0):
         """comm: how the gradient buckets are summed over ranks.
           'rccl'  -- librccl through the C ABI (dlsg_allreduce_bucket) on a side stream forked by an event: the collectives
                      are part of the captured step, so one iteration is ONE hipGraph replay and a bucket's all-reduce runs
@@ -655,8 +655,46 @@ class Trainer(object):
           step whose gradient holds an inf or a NaN updates nothing -- weights and both moments keep their bits -- and adds one
           to the device counter `skipped_steps`.  `t` advances on a skipped step all the same: the bias corrections are sent
           from the host before the outcome exists, so the step after a skipped one uses corrections one step further on.
-          With both None the step issues exactly the launches it issued before these options existed."""
+          With both None the step issues exactly the launches it issued before these options existed.
+        label_smoothing: eps in [0, 1) -- the loss is the CrossEntropy against (1 - eps) * onehot + eps / V at every counted
+          position, `torch.nn.CrossEntropyLoss(label_smoothing=eps)`.
+        teacher, distill_weight: word-level knowledge distillation (Kim & Rush 2016).  teacher is an `Ensemble`, or one model
+          (wrapped as `Ensemble([model])`), of the trained model's vocabulary and device; distill_weight = alpha in (0, 1] is its
+          share of the target row: (1 - alpha) * (the hard or smoothed target) + alpha * q, q the members' word distributions
+          combined by the ensemble's weights and mode ('logprob': renormalised).  Every step runs the members' teacher-forced
+          forward passes without dropout first (`Ensemble.teacher_logits`; their `.training` flags, parameters and `.grad` are
+          left alone: the teacher gets no gradient, no Adam moments and no all-reduce, and each rank runs it on its own shard),
+          then the student, then one `dlsg_ce_ragged_soft` launch in place of the CrossEntropy's -- all inside the captured
+          step with use_graphs.  The teacher is ALWAYS teacher-forced on the ground truth, also when tf_ratio < 1 feeds the
+          student its own words at some positions (the usual word-level recipe: q is the teacher's answer to the reference
+          prefix).  With either option on, `step` returns the mixed loss and `last_loss_parts` is a 3-float device view {mixed
+          loss, plain NLL of the targets, CrossEntropy against q} of the last step -- the NLL stays comparable with a run
+          without the options.  seq_weights, seq_per_clip, extra_dlogits and clipping compose as before.  With the defaults
+          (0.0, None, 0.0) the step issues exactly the launches it issued before these options existed."""
         assert comm in ('auto', 'rccl', 'torch'), comm
+        eps_ls, alpha = float(label_smoothing), float(distill_weight)
+        if not 0.0 <= eps_ls < 1.0:
+            raise ValueError('label_smoothing must be in [0, 1), not %r' % (label_smoothing,))
+        if not 0.0 <= alpha <= 1.0:
+            raise ValueError('distill_weight must be in [0, 1], not %r' % (distill_weight,))
+        if (alpha > 0.0) != (teacher is not None):
+            raise ValueError('distill_weight > 0 needs a teacher, and a teacher needs distill_weight > 0 (got %r, %s)'
+                             % (distill_weight, 'a teacher' if teacher is not None else 'no teacher'))
+        if teacher is not None:
+            from .ensemble import Ensemble, _device
+            if not isinstance(teacher, Ensemble):
+                teacher = Ensemble([teacher])
+            if any(m is model for m in teacher.members):
+                raise ValueError('the trained model is a member of its own teacher: distil from a copy (copy.deepcopy)')
+            v0, v = model.decoder.vocab, teacher.decoder.vocab
+            if len(v0) != len(v) or v0.word2idx != v.word2idx or v0.idx2word != v.idx2word:
+                raise ValueError("the teacher's vocabulary differs from the model's")
+            if _device(teacher.members[0]) != _device(model):
+                raise ValueError('the teacher is on %s, the model on %s' % (_device(teacher.members[0]), _device(model)))
+        self.label_smoothing, self.teacher, self.distill_weight = eps_ls, teacher, alpha
+        self._soft = eps_ls > 0.0 or teacher is not None    # the loss launch is dlsg_ce_ragged_soft
+        self._teacher_flats = []
+        self.last_loss_parts = None
         if max_grad_norm is not None and clip_grad_value is not None:
             raise ValueError('max_grad_norm and clip_grad_value exclude each other: set at most one')
         if max_grad_norm is not None and not float(max_grad_norm) >= 0.0:
@@ -744,6 +782,7 @@ class Trainer(object):
             self.m.copy_(old_m); self.v.copy_(old_v)      # same layout (only the frozen set changed): keep the moments
         self._arena = model._flat
         self._graphs = None
+        self._bind_teacher()
         # contiguous arena range of each backward bucket (named_parameters order == arena order)
         self._ranges = {}
         frozen = []
@@ -799,9 +838,23 @@ class Trainer(object):
             out.append((cur, hi))
         return out
 
+    def _bind_teacher(self):
+        """flatten every teacher member (never inside a capture) and note its arena: captured graphs hold addresses into it"""
+        if self.teacher is not None:
+            for m in self.teacher.members:
+                m.flatten_parameters_()
+            self._teacher_flats = [(m, m._flat) for m in self.teacher.members]
+
     def _check_binding(self):
         model = self.model
         model.flatten_parameters_()
+        if self.teacher is not None:
+            for m in self.teacher.members:
+                m.flatten_parameters_()
+            if any(m._flat is not flat for m, flat in self._teacher_flats):
+                # a member re-packed its parameters (load_state_dict into a copy, .to()): graphs captured on the old arena go
+                self._graphs = None
+                self._bind_teacher()
         frozen = tuple((model._offsets[n], model._offsets[n] + (p.numel() + _ALIGN - 1) // _ALIGN * _ALIGN)
                        for n, p in model.named_parameters() if not p.requires_grad)
         if self._arena is not model._flat or frozen != self._frozen:
@@ -1051,13 +1104,25 @@ class Trainer(object):
         # seq_per_clip = n > 1: frames / regions hold B clips, captions / cap_lens / seq_weights their B*n caption rows
         # a bucket handed to a reduction (or closing a graph segment) must be complete: deferred weight gradients go out there
         model._flush_at_buckets = self._comm_mode() != 'none' or self.force_graph_cuts
+        teachers = ()
+        if self.teacher is not None:
+            # the teacher first: its workspaces are free again before the student allocates; only the members' logits stay
+            teachers = self.teacher.teacher_logits(frames, regions, captions, seq_per_clip=seq_per_clip)
         model._engine_forward(frames, regions, captions, L, coins, training, seed, sv, dev_coins, outputs=False, seq_per_clip=seq_per_clip)
         s = sv['dec']
         Bn = captions.shape[0]
         dl = torch.empty_like(s['LOGITS'])
-        row_loss = torch.empty(L * Bn, dtype=torch.float32, device=dl.device)
-        loss = torch.empty(1, dtype=torch.float32, device=dl.device)
-        if seq_weights is None:
+        row_loss = torch.empty((3 if self._soft else 1) * L * Bn, dtype=torch.float32, device=dl.device)
+        loss = torch.empty(3 if self._soft else 1, dtype=torch.float32, device=dl.device)
+        if self._soft:
+            from .ensemble import MODES
+            ops.ce_ragged_soft(s['LOGITS'], captions, cap_lens, dl, row_loss, loss, time_major=True, smoothing=self.label_smoothing,
+                               weights=seq_weights, teachers=teachers,
+                               teacher_weights=self.teacher.weights if teachers else None,
+                               mode=MODES[self.teacher.mode] if teachers else 0, alpha=self.distill_weight)
+            self.last_loss_parts = loss
+            loss = loss[0:1]
+        elif seq_weights is None:
             ops.ce_ragged(s['LOGITS'], captions, cap_lens, dl, row_loss, loss, time_major=True)
         else:
             # policy gradient of self-critical training: caption b's CrossEntropy weighted by its advantage
@@ -1133,11 +1198,11 @@ class Trainer(object):
         for w in self._works:
             w.wait()
         self._join_comm()
-        if not self._clip:
+        if not self._clip and not self._soft:
             self._adam(self.t)
             return loss
-        # a clipping trainer's eager step (a batch of another shape than the captured one, or use_graphs=False) reads the bias
-        # corrections from device words the host computed, as the captured step does: one arithmetic for both, so the two forms
+        # a clipping (or label-smoothing / distilling) trainer's eager step (a batch of another shape than the captured one, or
+        # use_graphs=False) reads the bias corrections from device words the host computed, as the captured step does: one arithmetic for both, so the two forms
         # of a step give the same bits (dlsg_adam's own float powf / sqrtf differ from them in the last place)
         hyper = _h2d(self._hyper(), torch.float32, captions.device)
         self._clip_grads()
@@ -1217,6 +1282,7 @@ class Trainer(object):
             self._comm_pending = False
             raise
         self._graphs, self._loss = graphs, loss
+        st['parts'] = self.last_loss_parts        # (the captured launch's three floats: every replay rewrites them)
         self._adam_in_graph = mode != 'torch'
 
     def _capture_agreed(self, frames, regions, captions, cap_lens, hook, weighted=False, seq_per_clip=1):
@@ -1327,6 +1393,7 @@ class Trainer(object):
         if weighted:
             st['weights'].copy_(seq_weights, non_blocking=True)
         self._send_scalars(coins, seed, self._hyper())
+        self.last_loss_parts = st['parts']
         self._works = []
         for g, key in self._graphs:
             g.replay()

@@ -48,6 +48,9 @@ class SCSTTrainer(object):
         if unknown:
             raise ValueError('sample_options: unknown keys %s (top_k, top_p, min_len, no_repeat_ngram)' % unknown)
         check_sample_options(model.decoder.max_words, vocab_size=model.decoder.vocab_size, **self.sample_options)
+        if trainer_kwargs.get('label_smoothing') or trainer_kwargs.get('teacher') is not None or trainer_kwargs.get('distill_weight'):
+            raise ValueError('label_smoothing / teacher / distill_weight are options of the CrossEntropy step (Trainer): the '
+                             'policy gradient against a smoothed or a teacher\'s target row is not one')
         self.trainer = Trainer(model, **trainer_kwargs)
         self._sampler = self._greedy = None
 

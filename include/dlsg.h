@@ -728,6 +728,29 @@ int dlsg_ce_ragged(const float* logits, const int64_t* targets, const int64_t* l
  * With every weight 1 the results are bit-identical to dlsg_ce_ragged. */
 int dlsg_ce_ragged_weighted(const float* logits, const int64_t* targets, const int64_t* lens, const float* weights, float* dlogits,
                             float* row_loss, float* loss, int B, int L, int V, int time_major, void* stream);
+/* dlsg_ce_ragged_weighted against a SOFT target row: label smoothing and word-level distillation of an ensemble (Kim & Rush 2016).
+ * Rows, layout, the ragged rule and ntot are dlsg_ce_ragged's; weights is optional (NULL: every caption weighs 1).  Per counted
+ * row, with p = softmax(x), lse its log-sum-exp and l_m = x_m - lse_m the log-probabilities of teacher m, whose row for student
+ * row r is teacher[m] + r * teacher_ld[m] (same row order as logits):
+ *   h_j = (1 - smoothing) [j == tgt] + smoothing / V                  (torch's cross_entropy(label_smoothing=))
+ *   q_j = sum_m w[m] softmax(x_m)_j                                   mode 0 ("prob"): the weighted mean probability
+ *   q_j = exp(a_j) / sum_i exp(a_i),  a_j = sum_m w[m] l_mj           mode 1 ("logprob"): the weighted geometric mean, RENORMALISED
+ *                                                                     (around the row maximum of a: finite when members disagree)
+ *   r_j = (1 - alpha) h_j + alpha q_j                                 the target row, sums to 1
+ *   dlogits_j = (p_j - r_j) weights[b] / ntot
+ * loss[0..2] = the sums over the rows, in a fixed order, of weights[b] / ntot times
+ *   {sum_j r_j (lse - x_j),  lse - x_tgt,  sum_j q_j (lse - x_j)}: the mixed loss, the plain NLL of the targets (what
+ * dlsg_ce_ragged_weighted reports on these logits) and the CrossEntropy against the teacher (0 when M == 0).  row_loss is scratch
+ * of 3 * B * L floats.  Padded rows get zero dlogits and zero losses; a target outside [0, V) makes its row's losses and gradient
+ * NaN.  teacher, teacher_ld, w (normalised to sum 1), logw = log(w): HOST arrays of M entries, read during the call and passed to
+ * the kernel by value (a captured launch keeps them), as dlsg_beam_select_ens takes them; the loss reads w only.  No atomics,
+ * fixed-order reductions.  The student row is read three times; a teacher row three times in mode 0, four in mode 1.
+ * EINVAL for M outside 0..DLSG_ENS_MAX, mode outside {0, 1}, smoothing outside [0, 1), alpha outside [0, 1], alpha > 0 with M == 0,
+ * M > 0 with alpha == 0.  B * L == 0 launches nothing. */
+int dlsg_ce_ragged_soft(const float* logits, const int64_t* targets, const int64_t* lens, const float* weights, float* dlogits,
+                        float* row_loss, float* loss, int B, int L, int V, int time_major, float smoothing, float alpha,
+                        const float* const* teacher, const int64_t* teacher_ld, const float* w, const float* logw, int M, int mode,
+                        void* stream);
 /* CIDEr-D corpus tables of a training run (self-critical reward on the device; built once by scoring.DeviceCiderD).  An n-gram
  * of word ids w_0..w_{k-1} (k <= 4) is the key sum_j s_j << 16 j with s_j = w_j for j < k and 0xFFFF past the order; only
  * n-grams made of in-vocabulary words are listed.  Corpus table: the sorted keys and their idf, log_n - log(max(1, df)).
