@@ -1262,6 +1262,153 @@ __global__ __launch_bounds__(64 * K) void beam_select_ens_kernel(const dlsg_beam
     }
 }
 
+// Diverse (group) beam search (dlsg_beam_select_groups): the K beams of a clip are G groups of KG = K / G consecutive rows.
+// Phase 1 is beam_select_ens_kernel's, wave w for row w: every row's K best (c + last_lp, class) in LDS.  Phase 2, wave 0: the
+// groups in order; lane i < KG * K holds candidate i of the group (row within the group, then rank; step 0: the K entries of the
+// clip's one list, parent = the group's first row), key = lp, minus diversity * cnt[class] where the parent is live and cnt, the
+// number of picks of that class by earlier groups at this step from live parents, is not 0 (diversity = +inf: the key is -inf).
+// KG rounds of wave_argmax over (key, lane); a -inf key is no candidate, a slot left over takes candidate slot q of the group at
+// log-prob -inf and is not counted.  new_lp is lp, not the key.  The picks so far (at most K) are wave-uniform registers.
+// G = 1: no class is ever counted, so every key is its lp and the launch chooses what beam_select_ens_kernel chooses.
+template <int K>
+__global__ __launch_bounds__(64 * K) void beam_select_groups_kernel(const dlsg_beam_select_args a, const EnsPack e,
+                                                                      const int64_t* __restrict__ hist_in, int64_t* __restrict__ hist_out,
+                                                                      int L, int t, int g, int min_len, int G, float diversity) {
+    __shared__ float cand_lp[K * K];
+    __shared__ int cand_cls[K * K];
+    __shared__ int hist[K][BEAM_MAXL];
+    __shared__ int ban[K][BEAM_MAXL + 1];
+    __shared__ int nban[K];
+    __shared__ float lse_s[K][DLSG_ENS_MAX];
+    const int b = blockIdx.x, k = K, V = a.V;
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const int nbeam = a.first ? 1 : k;
+    const int64_t row = (int64_t)b * k + w;
+    const bool ended = !a.first && a.last[row] == a.end;
+    const bool ngram = g > 0 && t >= g;
+    if (ngram) hist[w][lane] = lane < t ? (int)hist_in[row * L + lane] : -1;
+    __syncthreads();
+    if (w < nbeam && !ended) {
+        int n = 0;
+        if (ngram) {
+            bool hit = lane <= t - g;
+            for (int j = 0; hit && j < g - 1; ++j) hit = hist[w][lane + j] == hist[w][t - g + 1 + j];
+            const unsigned long long m = __ballot(hit);
+            if (hit) ban[w][__popcll(m & ((1ull << lane) - 1ull))] = hist[w][lane + g - 1];
+            n = __popcll(m);
+        }
+        if (lane == 0) {
+            if (t < min_len) ban[w][n++] = a.end;
+            nban[w] = n;
+        }
+    }
+    __syncthreads();
+    if (w < nbeam) {
+        const float base = a.first ? 0.f : a.last_lp[row];
+        if (ended) {
+            if (lane < k) {
+                cand_lp[w * k + lane] = lane == 0 ? base : -INFINITY;
+                cand_cls[w * k + lane] = lane == 0 ? a.end : (lane - 1 < a.end ? lane - 1 : lane);
+            }
+        } else {
+            for (int m = 0; m < e.M; ++m) {
+                const float* x = e.x[m] + row * e.ld[m];
+                float mx = -INFINITY;
+                for (int j = lane; j < V; j += 64) mx = fmaxf(mx, x[j]);
+                mx = dlsg::wave_max(mx);
+                float sum = 0.f;
+                for (int j = lane; j < V; j += 64) sum += expf(x[j] - mx);
+                sum = dlsg::wave_sum(sum);
+                lse_s[w][m] = logf(sum) + mx;
+            }
+            const float* x[DLSG_ENS_MAX];
+            float lse[DLSG_ENS_MAX];
+#pragma unroll
+            for (int m = 0; m < DLSG_ENS_MAX; ++m) {
+                x[m] = m < e.M ? e.x[m] + row * e.ld[m] : nullptr;
+                lse[m] = m < e.M ? lse_s[w][m] : 0.f;
+            }
+            float tv[K], bv[K];
+            int ti[K], bi[K];
+#pragma unroll
+            for (int q = 0; q < K; ++q) { tv[q] = -INFINITY; ti[q] = 0x7fffffff; }
+            for (int j = lane; j < V; j += 64) {
+                float c;
+                if (e.mode == 0) {
+                    float v[DLSG_ENS_MAX], mx = -INFINITY, sum = 0.f;
+#pragma unroll
+                    for (int m = 0; m < DLSG_ENS_MAX; ++m)
+                        if (m < e.M) { v[m] = (x[m][j] - lse[m]) + e.logw[m]; mx = fmaxf(mx, v[m]); }
+#pragma unroll
+                    for (int m = 0; m < DLSG_ENS_MAX; ++m)
+                        if (m < e.M) sum += expf(v[m] - mx);
+                    c = mx == -INFINITY ? -INFINITY : mx + logf(sum);
+                } else {
+                    c = 0.f;
+#pragma unroll
+                    for (int m = 0; m < DLSG_ENS_MAX; ++m)
+                        if (m < e.M) c += e.w[m] * (x[m][j] - lse[m]);
+                }
+                beam_topk_push<K>(tv, ti, c, j, ban[w], nban[w]);
+            }
+            beam_topk_merge<K>(tv, ti, bv, bi);
+            if (lane == 0) {
+#pragma unroll
+                for (int q = 0; q < K; ++q) {
+                    cand_lp[w * k + q] = bv[q] + base;
+                    cand_cls[w * k + q] = bi[q];
+                }
+            }
+        }
+    }
+    __syncthreads();
+    if (w == 0) {
+        const int kg = k / G;
+        const int n = a.first ? k : kg * k;                   // candidates of one group (<= 64: one per lane)
+        int mypick = -1;                                      // lane s: the s-th class counted at this step
+        int npicked = 0, n_end = 0;                           // (wave-uniform; at most k)
+        for (int gr = 0; gr < G; ++gr) {
+            const int first_row = gr * kg;                    // the group's first row within the clip
+            const bool have = lane < n;
+            const int ci = !have ? 0 : a.first ? lane : first_row * k + lane;      // this lane's slot in cand_lp / cand_cls
+            const int par = !have || a.first ? first_row : first_row + lane / k;   // and its parent within the clip
+            const int mycls = cand_cls[ci];
+            int cnt = 0;
+            for (int q = 0; q < npicked; ++q) cnt += __builtin_amdgcn_readlane(mypick, q) == mycls;
+            float key = have ? cand_lp[ci] : -INFINITY;
+            if (cnt > 0 && (a.first || a.last[(int64_t)b * k + par] != a.end))
+                key = diversity == INFINITY ? -INFINITY : key - __fmul_rn(diversity, (float)cnt);
+            int idx = key == -INFINITY ? 0x7fffffff : lane;   // a -inf key is no candidate
+            for (int q = 0; q < kg; ++q) {                    // (keys are taken once per group: a pick counts from the next group on)
+                float bv = key;
+                int bi = idx;
+                wave_argmax(bv, bi);
+                if (lane == bi) key = -INFINITY, idx = 0x7fffffff;
+                const bool fill = bi == 0x7fffffff;            // fewer than kg candidates: slot q of the group, log-prob -inf
+                if (fill) bi = q;
+                const int sl = a.first ? bi : first_row * k + bi;
+                const int pb = a.first ? first_row : first_row + bi / k;
+                const int cls = cand_cls[sl];
+                const int64_t o = (int64_t)b * k + first_row + q;
+                if (lane == 0) {
+                    a.pred[o] = cls;
+                    a.new_lp[o] = fill ? -INFINITY : cand_lp[sl];
+                    a.back[o] = pb;
+                    a.rows[o] = (int64_t)b * k + pb;
+                }
+                if (lane < L)
+                    hist_out[o * L + lane] = lane < t ? hist_in[((int64_t)b * k + pb) * L + lane] : (lane == t ? (int64_t)cls : (int64_t)a.end);
+                n_end += cls == a.end;
+                if (!fill && (a.first || a.last[(int64_t)b * k + pb] != a.end)) {
+                    if (lane == npicked) mypick = cls;
+                    ++npicked;
+                }
+            }
+        }
+        if (lane == 0 && a.ended_count) atomicAdd(a.ended_count, n_end);
+    }
+}
+
 // The n best of each clip's k finished beams, by score = lp / len^alpha (double, stored as float), descending, ties to the lower
 // beam: one wave per clip.  len = tokens up to and including the first `end` of the beam's history row, L without one.
 __global__ __launch_bounds__(64) void beam_finalize_kernel(const int64_t* __restrict__ hist, const float* __restrict__ lp, int k, int L,
@@ -1776,6 +1923,32 @@ extern "C" int dlsg_beam_select_ens(const dlsg_beam_select_args* a, const float*
     return DLSG_OK;
 }
 #undef BEAM_ENS_CASE
+#define BEAM_GROUPS_CASE(KK) \
+    case KK: hipLaunchKernelGGL(beam_select_groups_kernel<KK>, dim3(a->B), dim3(64 * KK), 0, ST(stream), *a, e, hist_in, hist_out, L, t, \
+                                no_repeat_ngram, min_len, groups, diversity); break;
+extern "C" int dlsg_beam_select_groups(const dlsg_beam_select_args* a, const float* const* logits, const int64_t* ld, const float* w,
+                                       const float* logw, int M, int mode, const int64_t* hist_in, int64_t* hist_out, int L, int t,
+                                       int no_repeat_ngram, int min_len, int groups, float diversity, void* stream) {
+    if (!a || a->k < 1 || a->k > BEAM_MAXK || a->V < a->k) return DLSG_EINVAL;
+    if (!logits || !ld || !w || !logw || M < 1 || M > DLSG_ENS_MAX || (mode != 0 && mode != 1)) return DLSG_EINVAL;
+    if (!hist_out || L < 1 || L > BEAM_MAXL || t < 0 || t >= L || no_repeat_ngram < 0 || min_len < 0) return DLSG_EINVAL;
+    if ((a->first != 0) != (t == 0) || (t > 0 && (!hist_in || hist_in == hist_out))) return DLSG_EINVAL;
+    if (groups < 1 || a->k % groups != 0 || !(diversity >= 0.f)) return DLSG_EINVAL;     // (NaN fails the comparison)
+    EnsPack e = {};
+    for (int m = 0; m < M; ++m) {
+        if (!logits[m]) return DLSG_EINVAL;
+        e.x[m] = logits[m]; e.ld[m] = ld[m]; e.w[m] = w[m]; e.logw[m] = logw[m];
+    }
+    e.M = M; e.mode = mode;
+    if (a->B == 0) return DLSG_OK;
+    switch (a->k) {
+        BEAM_GROUPS_CASE(1) BEAM_GROUPS_CASE(2) BEAM_GROUPS_CASE(3) BEAM_GROUPS_CASE(4)
+        BEAM_GROUPS_CASE(5) BEAM_GROUPS_CASE(6) BEAM_GROUPS_CASE(7) BEAM_GROUPS_CASE(8)
+    }
+    DLSG_CHECK_LAUNCH();
+    return DLSG_OK;
+}
+#undef BEAM_GROUPS_CASE
 extern "C" int dlsg_beam_finalize(const int64_t* hist, const float* lp, int B, int k, int L, int64_t end, double alpha, int n,
                                   int64_t* ids, float* scores, int64_t* lens, void* stream) {
     if (!hist || !lp || !ids || !scores || !lens || B < 0 || k < 1 || k > BEAM_MAXK || L < 1 || L > BEAM_MAXL || n < 1 || n > k)

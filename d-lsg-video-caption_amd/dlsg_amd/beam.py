@@ -153,7 +153,7 @@ def beam_finish(model, preds, backs, lps, ended, done, B, k, R, L, extras):
 MAX_BEAM, MAX_WORDS = 8, 64          # limits of dlsg_beam_select_hist / dlsg_beam_finalize
 
 
-def check_nbest_options(k, L, n_best=None, length_penalty=0.0, no_repeat_ngram=0, min_len=0):
+def check_nbest_options(k, L, n_best=None, length_penalty=0.0, no_repeat_ngram=0, min_len=0, num_groups=1, diversity_penalty=0.0):
     """ValueError for what `beam_nbest` cannot run; returns n"""
     n = k if n_best is None else n_best
     if not 1 <= k <= MAX_BEAM:
@@ -166,11 +166,18 @@ def check_nbest_options(k, L, n_best=None, length_penalty=0.0, no_repeat_ngram=0
         raise ValueError('no_repeat_ngram (%d) and min_len (%d) must not be negative' % (no_repeat_ngram, min_len))
     if min_len >= L:
         raise ValueError('min_len %d leaves no room for <end> in max_words %d' % (min_len, L))
+    if not 1 <= num_groups <= k or k % num_groups:
+        raise ValueError('num_groups %r: diverse beam search splits the %d beams into 1 .. %d groups of equal size' % (num_groups, k, k))
+    if not diversity_penalty >= 0.0:                                   # (NaN fails the comparison)
+        raise ValueError('diversity_penalty (%r) must not be negative or NaN' % (diversity_penalty,))
+    if diversity_penalty > 0.0 and num_groups == 1:
+        raise ValueError('diversity_penalty %r does nothing with one group: set num_groups' % (diversity_penalty,))
     return n
 
 
 @torch.no_grad()
-def beam_nbest(model, visual_feats, region_feats, n_best=None, length_penalty=0.0, no_repeat_ngram=0, min_len=0, beam_size=None):
+def beam_nbest(model, visual_feats, region_feats, n_best=None, length_penalty=0.0, no_repeat_ngram=0, min_len=0, beam_size=None,
+               num_groups=1, diversity_penalty=0.0):
     """The n best of the k beams of every clip: (ids (B, n, L) int64, padded with <end>; scores (B, n) float32 =
     log-prob / len^length_penalty, descending; lens (B, n) int64 = tokens up to and including the first <end>, else L), device
     tensors.  no_repeat_ngram = g: no caption repeats a g-gram; min_len: no <end> before that many words.  A banned word takes
@@ -178,10 +185,14 @@ def beam_nbest(model, visual_feats, region_feats, n_best=None, length_penalty=0.
     has ended a step only appends <end> at log-prob 0, so with the options off the rows are the reference's beams, end-padded.
     beam_size: the number of beams, default the decoder's.  Because nothing is read back, the persistent BiLSTM's time-out word
     is not looked at here: call `model.ops.check_persistent()` where the ids are copied to the host (`scoring.gather_results`
-    does)."""
+    does).
+    num_groups = G > 1: diverse beam search (Vijayakumar et al. 2016) -- the beams are G groups of beam_size / G, chosen one
+    group after another at every word; a word that earlier groups chose at that step costs a later group `diversity_penalty` per
+    choice (inf: it is excluded).  The penalty steers the choice only: scores stay log-prob / len^length_penalty, and the n best
+    are ranked over all groups together.  One `beam_select_groups` launch per step; num_groups = 1 launches what it always did."""
     dec = model.decoder
     k, L = dec.beam_size if beam_size is None else beam_size, dec.max_words
-    n = check_nbest_options(k, L, n_best, length_penalty, no_repeat_ngram, min_len)
+    n = check_nbest_options(k, L, n_best, length_penalty, no_repeat_ngram, min_len, num_groups, diversity_penalty)
     mems, sv, seed, _ = _encode(model, visual_feats, region_feats)
     ops = model.ops
     advance, B, R, _ = _beam_setup(model, mems, sv, seed, k)
@@ -195,8 +206,12 @@ def beam_nbest(model, visual_feats, region_feats, n_best=None, length_penalty=0.
     words = torch.full((R,), dec.vocab('<start>'), dtype=torch.int64, device=dev)
     for t in range(L):
         logits = advance(t, words, rows)
-        ops.beam_select_hist(logits, words, lps[t % 2], preds[t % 2], lps[(t + 1) % 2], back, rows, k, end, hist[t % 2],
-                             hist[(t + 1) % 2], t, no_repeat_ngram, min_len)
+        if num_groups == 1:
+            ops.beam_select_hist(logits, words, lps[t % 2], preds[t % 2], lps[(t + 1) % 2], back, rows, k, end, hist[t % 2],
+                                 hist[(t + 1) % 2], t, no_repeat_ngram, min_len)
+        else:
+            ops.beam_select_groups([logits], [1.0], 0, words, lps[t % 2], preds[t % 2], lps[(t + 1) % 2], back, rows, k, end,
+                                   hist[t % 2], hist[(t + 1) % 2], t, no_repeat_ngram, min_len, num_groups, float(diversity_penalty))
         words = preds[t % 2]
     ids = torch.empty(B, n, L, dtype=torch.int64, device=dev)
     scores = torch.empty(B, n, dtype=torch.float32, device=dev)
@@ -207,15 +222,16 @@ def beam_nbest(model, visual_feats, region_feats, n_best=None, length_penalty=0.
 
 @torch.no_grad()
 def ensemble_nbest(models, weights, mode, visual_feats, region_feats, n_best=None, length_penalty=0.0, no_repeat_ngram=0, min_len=0,
-                   beam_size=None):
+                   beam_size=None, num_groups=1, diversity_penalty=0.0):
     """`beam_nbest` with several models that decode one caption: every member runs its own encoder and its own decode step on the
     shared words and back-pointer rows (its own state slots; any of the model classes, any hidden sizes), and one
     `beam_select_ens` launch per step combines the members' logit rows -- mode 0: log of the weighted mean probability, mode 1:
     weighted mean log-probability -- and chooses the beams.  One set of preds / hist / back / rows / lps; no host synchronisation.
-    The members share vocabulary, max_words and device (`ensemble.Ensemble` checks that); beam_size defaults to the first member's."""
+    The members share vocabulary, max_words and device (`ensemble.Ensemble` checks that); beam_size defaults to the first member's.
+    num_groups, diversity_penalty: diverse beam search as in `beam_nbest`, on the combined values (`beam_select_groups`)."""
     dec = models[0].decoder
     k, L = dec.beam_size if beam_size is None else beam_size, dec.max_words
-    n = check_nbest_options(k, L, n_best, length_penalty, no_repeat_ngram, min_len)
+    n = check_nbest_options(k, L, n_best, length_penalty, no_repeat_ngram, min_len, num_groups, diversity_penalty)
     steps = []
     for model in models:
         mems, sv, seed, _ = _encode(model, visual_feats, region_feats)
@@ -232,8 +248,12 @@ def ensemble_nbest(models, weights, mode, visual_feats, region_feats, n_best=Non
     words = torch.full((R,), dec.vocab('<start>'), dtype=torch.int64, device=dev)
     for t in range(L):
         logits = [advance(t, words, rows) for advance in steps]
-        ops.beam_select_ens(logits, weights, mode, words, lps[t % 2], preds[t % 2], lps[(t + 1) % 2], back, rows, k, end, hist[t % 2],
-                            hist[(t + 1) % 2], t, no_repeat_ngram, min_len)
+        if num_groups == 1:
+            ops.beam_select_ens(logits, weights, mode, words, lps[t % 2], preds[t % 2], lps[(t + 1) % 2], back, rows, k, end,
+                                hist[t % 2], hist[(t + 1) % 2], t, no_repeat_ngram, min_len)
+        else:
+            ops.beam_select_groups(logits, weights, mode, words, lps[t % 2], preds[t % 2], lps[(t + 1) % 2], back, rows, k, end,
+                                   hist[t % 2], hist[(t + 1) % 2], t, no_repeat_ngram, min_len, num_groups, float(diversity_penalty))
         words = preds[t % 2]
     ids = torch.empty(B, n, L, dtype=torch.int64, device=dev)
     scores = torch.empty(B, n, dtype=torch.float32, device=dev)

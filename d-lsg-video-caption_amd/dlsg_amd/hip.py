@@ -572,6 +572,33 @@ class HipOps(object):
         self._check(self.lib.dlsg_beam_select_ens(C.byref(a), ptrs, lds, ws, logws, M, int(mode), _p(hist_in), _p(hist_out), L, int(t),
                                                   int(no_repeat_ngram), int(min_len), self._stream()), 'dlsg_beam_select_ens')
 
+    def beam_select_groups(self, logits_list, weights, mode, last, last_lp, pred, new_lp, back, rows, k, end, hist_in, hist_out, t,
+                           no_repeat_ngram=0, min_len=0, num_groups=1, diversity_penalty=0.0, ended_count=None):
+        """`beam_select_ens` for diverse beam search: the k beams of a clip are `num_groups` groups of consecutive rows, chosen one
+        group after another; a word that earlier groups chose at this step from live beams costs a later group
+        `diversity_penalty` per choice (inf: it is excluded).  new_lp stays the log-prob without the penalty (see include/dlsg.h).
+        A single model passes one logits array and weights [1.0]."""
+        a = abi.dlsg_beam_select_args()
+        M = len(logits_list)
+        R, V = logits_list[0].shape
+        L = hist_out.shape[1]
+        for h in (hist_in, hist_out):
+            assert h.dtype == torch.int64 and h.is_contiguous() and h.shape == (R, L), (h.dtype, h.shape)
+        for x in logits_list:
+            assert x.dtype == torch.float32 and x.shape == (R, V) and x.stride(1) == 1 and x.device == hist_out.device, (x.dtype, x.shape)
+        assert len(weights) == M, (len(weights), M)
+        w = normalised_weights(weights)
+        a.last, a.last_lp = _p(last), _p(last_lp)
+        a.pred, a.new_lp, a.back, a.rows, a.ended_count = _p(pred), _p(new_lp), _p(back), _p(rows), _p(ended_count)
+        a.B, a.k, a.V, a.end, a.first = R // k, k, V, end, int(t == 0)
+        ptrs = (C.c_void_p * M)(*[x.data_ptr() for x in logits_list])
+        lds = (C.c_int64 * M)(*[x.stride(0) for x in logits_list])
+        ws = (C.c_float * M)(*w)
+        logws = (C.c_float * M)(*[math.log(x) for x in w])
+        self._check(self.lib.dlsg_beam_select_groups(C.byref(a), ptrs, lds, ws, logws, M, int(mode), _p(hist_in), _p(hist_out), L, int(t),
+                                                     int(no_repeat_ngram), int(min_len), int(num_groups), C.c_float(diversity_penalty),
+                                                     self._stream()), 'dlsg_beam_select_groups')
+
     def beam_finalize(self, hist, lp, k, end, alpha, ids, scores, lens):
         """the n = ids.shape[1] best of each clip's k beams by lp / len^alpha: ids (B, n, L), scores (B, n), lens (B, n)."""
         R, L = hist.shape

@@ -566,8 +566,8 @@ def convert_prediction(prediction):
 
 def gather_results(net, eval_loader, decode=None):
     """evaluate.py:62-78 / 101-117: greedy or beam inference over the eval loader -> OrderedDict video id -> sentence.
-    `decode`: a dict of `beam_search` options (beam_size, length_penalty, no_repeat_ngram, min_len); the captions are then the
-    best beam of that search."""
+    `decode`: a dict of `beam_search` options (beam_size, length_penalty, no_repeat_ngram, min_len, num_groups,
+    diversity_penalty); the captions are then the best beam of that search."""
     import torch
     result = collections.OrderedDict()
     dec = (net.module if hasattr(net, 'module') else net).decoder

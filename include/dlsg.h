@@ -841,6 +841,26 @@ int dlsg_beam_select_hist(const dlsg_beam_select_args* a, const int64_t* hist_in
 int dlsg_beam_select_ens(const dlsg_beam_select_args* a, const float* const* logits, const int64_t* ld, const float* w,
                          const float* logw, int M, int mode, const int64_t* hist_in, int64_t* hist_out, int L, int t,
                          int no_repeat_ngram, int min_len, void* stream);
+/* dlsg_beam_select_ens for diverse (group) beam search (Vijayakumar et al. 2016).  The k beams of a clip are `groups` = G groups of
+ * k' = k / G: group y owns rows b*k + y*k' .. b*k + y*k' + k' - 1 on input and on output, and a beam's parent is a row of its own
+ * group.  Phase 1 is dlsg_beam_select_ens's: every input row's k best (c, class) -- combined over the M members in `mode`, the two
+ * bans, ties to the lower class, an ended row offers only `end` at 0 -- each offered at lp = c + last_lp[row] (float32).  At step 0
+ * only the clip's first row is read; its list serves every group, with the group's first row as parent.  Phase 2, the groups in
+ * order y = 0 .. G-1, with a count cnt[class] that starts empty at every step: the candidates of y are the k' * k entries of its rows'
+ * lists (row within the group, then rank); key = lp if the parent row has ended or cnt[class] == 0, else lp - diversity * cnt[class]
+ * in float32 (the product rounded, then the difference), and -inf for diversity = +inf.  The k' best keys are chosen, larger first,
+ * ties to the lower candidate; a -inf key is no candidate, and a slot q left over takes candidate q of the group with new_lp = -inf.
+ * Output slot o = b*k + y*k' + q: pred = the class, new_lp = lp -- NOT the key: the penalty steers the choice only, so the log-probs
+ * stay comparable across groups and with the other searches --, back = the parent's index within the clip, rows = b*k + back,
+ * hist_out[o] and ended_count as dlsg_beam_select_hist.  After y has chosen, each of its picks (not a left-over slot) whose parent
+ * was live adds one to cnt[its class] (at step 0 every pick): an `end` that continues an ended beam is neither penalised nor
+ * counted, a fresh `end` counts like any word.  Penalties only lower values and at most k - k' classes are counted, so the k' best
+ * keys of a group lie inside its rows' k best: the vocabulary is read exactly as by dlsg_beam_select_ens.  groups == 1 gives that
+ * call's bits.  One workgroup per clip, phase 2 in one wave; no atomics but ended_count's; deterministic.
+ * EINVAL for what dlsg_beam_select_ens refuses, groups < 1, k % groups != 0, diversity negative or NaN. */
+int dlsg_beam_select_groups(const dlsg_beam_select_args* a, const float* const* logits, const int64_t* ld, const float* w,
+                            const float* logw, int M, int mode, const int64_t* hist_in, int64_t* hist_out, int L, int t,
+                            int no_repeat_ngram, int min_len, int groups, float diversity, void* stream);
 /* After the last step: the n <= k best beams of every clip by score = lp / len^alpha (computed in double, stored as float),
  * descending, ties to the lower beam.  hist (B*k, L) the final history, lp (B*k) the final log-probs; len = tokens up to and
  * including the first `end`, L without one.  Out: ids (B, n, L) int64, scores (B, n), lens (B, n) int64.  One wave per clip. */
