@@ -1,0 +1,252 @@
+// The phases of a beam-search step (gfx950), one definition each: the four step kernels of beam.hip are compositions of them, and
+// the filtered sampler (sample.hip) bans words by the same rule.  A step is one workgroup per clip and one wave per beam row:
+// every row offers its K best (log-prob, class) candidates in LDS, then wave 0 takes the K best of the clip's candidates.
+#pragma once
+#include "common.hpp"
+#include "dlsg.h"
+
+namespace dlsg {
+
+constexpr int BEAM_MAXK = 8;
+constexpr int BEAM_MAXL = 64;           // history positions: lane i of a row's wave holds token i
+
+// (value, index) order of the search: larger value first, ties to the smaller index (torch.topk on equal log-probs is not
+// specified; the oracle and the reference fixtures agree with this rule on every golden case)
+__device__ __forceinline__ bool beam_better(float v, int i, float bv, int bi) { return v > bv || (v == bv && i < bi); }
+
+template <int CTRL>
+__device__ __forceinline__ int dpp_i32(int v) { return __builtin_amdgcn_update_dpp(0, v, CTRL, 0xF, 0xF, true); }
+__device__ __forceinline__ int wave_min_i32(int v) {
+    v = min(v, dpp_i32<0xB1>(v));
+    v = min(v, dpp_i32<0x4E>(v));
+    v = min(v, dpp_i32<0x141>(v));
+    v = min(v, dpp_i32<0x140>(v));
+    return min(min(__builtin_amdgcn_readlane(v, 0), __builtin_amdgcn_readlane(v, 16)),
+               min(__builtin_amdgcn_readlane(v, 32), __builtin_amdgcn_readlane(v, 48)));
+}
+// the best (value, index) pair of the wave, to every lane: two DPP reductions instead of twelve ds_bpermute round trips
+__device__ __forceinline__ void wave_argmax(float& v, int& i) {
+    const float m = dlsg::wave_max(v);
+    i = wave_min_i32(v == m ? i : 0x7fffffff);
+    v = m;
+}
+
+// ------------------------------------------------------------------------------------------------ ban list
+// The classes a row may not choose, by ONE wave from the row's history in LDS (hist[i] = token i for i < t, -1 behind): with
+// g = no_repeat_ngram, every h[i + g - 1] whose g - 1 predecessors equal the last g - 1 tokens of the history (lane i: the g-gram
+// that starts at i), and `end` while t < min_len.  ban holds up to BEAM_MAXL + 1 classes; lane 0 stores their number.
+__device__ __forceinline__ void beam_ban_list(const int* hist, int t, int g, int min_len, int end, int* ban, int* nban) {
+    const int lane = threadIdx.x & 63;
+    int n = 0;
+    if (g > 0 && t >= g) {                                   // (never at step 0)
+        bool hit = lane <= t - g;
+        for (int j = 0; hit && j < g - 1; ++j) hit = hist[lane + j] == hist[t - g + 1 + j];
+        const unsigned long long m = __ballot(hit);
+        if (hit) ban[__popcll(m & ((1ull << lane) - 1ull))] = hist[lane + g - 1];
+        n = __popcll(m);
+    }
+    if (lane == 0) {
+        if (t < min_len) ban[n++] = end;
+        *nban = n;
+    }
+}
+
+// The ban lists of a workgroup's rows, wave w for `row` (every wave calls it: two barriers): the row's history from hist_in
+// (B*k, L) into LDS, then the list of a row that is `live` (searched at this step and not ended).  The LDS arrays come whole and
+// are indexed by w here: handed in as the wave's row pointers they cost two VGPRs, and beam_select_groups_kernel<8> a wave of
+// occupancy (profiles/beam_step_resources_parent_vs_tree.md).
+template <int K>
+__device__ __forceinline__ void beam_row_bans(const int64_t* __restrict__ hist_in, int64_t row, int L, int t, int g, int min_len,
+                                              int end, bool live, int (&hist)[K][BEAM_MAXL], int (&ban)[K][BEAM_MAXL + 1], int (&nban)[K]) {
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    if (g > 0 && t >= g) hist[w][lane] = lane < t ? (int)hist_in[row * L + lane] : -1;
+    __syncthreads();
+    if (live) beam_ban_list(hist[w], t, g, min_len, end, ban[w], &nban[w]);
+    __syncthreads();
+}
+
+// ------------------------------------------------------------------------------------------------ a row's K candidates
+// A beam that has ended offers `end` at its own log-prob and nothing else: the K - 1 other slots are -inf, with classes that are
+// distinct and not `end`.  lp / cls: the row's K slots.
+template <int K>
+__device__ __forceinline__ void beam_offer_ended(const dlsg_beam_select_args& a, int lane, float base, float* lp, int* cls) {
+    if (lane < K) {
+        lp[lane] = lane == 0 ? base : -INFINITY;
+        cls[lane] = lane == 0 ? a.end : (lane - 1 < a.end ? lane - 1 : lane);
+    }
+}
+// a live beam offers the wave's K best (value, class) at value + base
+template <int K>
+__device__ __forceinline__ void beam_offer_live(int lane, const float (&bv)[K], const int (&bi)[K], float base, float* lp, int* cls) {
+    if (lane == 0) {
+#pragma unroll
+        for (int c = 0; c < K; ++c) {
+            lp[c] = bv[c] + base;
+            cls[c] = bi[c];
+        }
+    }
+}
+
+// A lane's K best of the elements it has seen, sorted: empty, then one push per element, then the wave's K best by merge.
+template <int K>
+__device__ __forceinline__ void beam_topk_clear(float (&tv)[K], int (&ti)[K]) {
+#pragma unroll
+    for (int q = 0; q < K; ++q) { tv[q] = -INFINITY; ti[q] = 0x7fffffff; }
+}
+// BAN: the classes in ban[0..nban) count as -inf.  The list is looked at only for an element that would enter the lane's K best.
+template <int K, bool BAN>
+__device__ __forceinline__ void beam_topk_push(float (&tv)[K], int (&ti)[K], float cv, int ci, const int* ban, int nban) {
+    if (!beam_better(cv, ci, tv[K - 1], ti[K - 1])) return;
+    if constexpr (BAN) {
+        for (int q = 0; q < nban; ++q) cv = ban[q] == ci ? -INFINITY : cv;
+        if (!beam_better(cv, ci, tv[K - 1], ti[K - 1])) return;
+    }
+#pragma unroll
+    for (int q = 0; q < K; ++q) {                           // one bubble pass keeps tv sorted
+        const bool up = beam_better(cv, ci, tv[q], ti[q]);
+        const float nv = up ? tv[q] : cv;
+        const int ni = up ? ti[q] : ci;
+        tv[q] = up ? cv : tv[q];
+        ti[q] = up ? ci : ti[q];
+        cv = nv; ci = ni;
+    }
+}
+// the K best of the wave from the lanes' sorted lists (which it consumes): K rounds over the lanes' heads
+template <int K>
+__device__ __forceinline__ void beam_topk_merge(float (&tv)[K], int (&ti)[K], float (&outv)[K], int (&outi)[K]) {
+#pragma unroll
+    for (int c = 0; c < K; ++c) {
+        float bv = tv[0];
+        int bi = ti[0];
+        wave_argmax(bv, bi);
+        outv[c] = bv; outi[c] = bi;
+        if (ti[0] == bi && bi != 0x7fffffff) {               // the winning lane pops its head
+#pragma unroll
+            for (int q = 0; q + 1 < K; ++q) { tv[q] = tv[q + 1]; ti[q] = ti[q + 1]; }
+            tv[K - 1] = -INFINITY; ti[K - 1] = 0x7fffffff;
+        }
+    }
+}
+
+// One model's row: the K best classes of a V-wide logit row and the row's log-sum-exp, ONE wave.  The row is read twice (maximum +
+// each lane's own K best in the first pass, the exponential sum in the second -- same summation order as a plain strided loop, so
+// the log-probs are bit-identical to a 2 + K pass form), then the merge.  The selection is on raw logits; the caller subtracts lse.
+// With a ban list the row's maximum and exponential sum stay those of the whole row.
+template <int K, bool BAN = false>
+__device__ __forceinline__ void beam_row_topk(const float* x, int V, int lane, float& lse, float (&outv)[K], int (&outi)[K],
+                                              const int* ban = nullptr, int nban = 0) {
+    float tv[K];
+    int ti[K];
+    beam_topk_clear<K>(tv, ti);
+    float m = -INFINITY;
+    for (int j = lane; j < V; j += 64) {
+        const float cv = x[j];
+        m = fmaxf(m, cv);
+        beam_topk_push<K, BAN>(tv, ti, cv, j, ban, nban);
+    }
+    m = dlsg::wave_max(m);
+    float sum = 0.f;
+    for (int j = lane; j < V; j += 64) sum += expf(x[j] - m);
+    sum = dlsg::wave_sum(sum);
+    lse = logf(sum) + m;
+    beam_topk_merge<K>(tv, ti, outv, outi);
+}
+
+// An ensemble's row: a live beam's V candidate values are combined from M logit rows, one per member.  Per member the row's
+// log-sum-exp in beam_row_topk's order (strided maximum + wave_max, strided exponential sum + wave_sum), then per class, in member
+// order and float32,
+//   mode 0: c = mx + logf(sum_m expf(v_m - mx)),  v_m = (x_m - lse_m) + logw_m,  mx = max_m v_m   (log of the weighted mean probability)
+//   mode 1: c = sum_m w_m (x_m - lse_m)                                                          (weighted mean log-probability)
+// and the K best unbanned c of the row.  With one member of weight 1 both modes give c = x - lse exactly, the value the one-model
+// step ranks by (on raw logits: it reads the row twice, not three times).  The M pointers, strides and weights travel by value in
+// the argument block; lse_s: the row's DLSG_ENS_MAX floats of LDS (the member loop that fills it is not unrolled).
+struct EnsPack {
+    const float* x[DLSG_ENS_MAX];
+    int64_t ld[DLSG_ENS_MAX];
+    float w[DLSG_ENS_MAX], logw[DLSG_ENS_MAX];
+    int M, mode;
+};
+template <int K>
+__device__ __forceinline__ void beam_ens_row_topk(const EnsPack& e, int64_t row, int V, int lane, float* lse_s, const int* ban,
+                                                  int nban, float (&bv)[K], int (&bi)[K]) {
+    for (int m = 0; m < e.M; ++m) {                          // every lane writes the wave's value and reads back its own store
+        const float* x = e.x[m] + row * e.ld[m];
+        float mx = -INFINITY;
+        for (int j = lane; j < V; j += 64) mx = fmaxf(mx, x[j]);
+        mx = dlsg::wave_max(mx);
+        float sum = 0.f;
+        for (int j = lane; j < V; j += 64) sum += expf(x[j] - mx);
+        sum = dlsg::wave_sum(sum);
+        lse_s[m] = logf(sum) + mx;
+    }
+    const float* x[DLSG_ENS_MAX];
+    float lse[DLSG_ENS_MAX];
+#pragma unroll
+    for (int m = 0; m < DLSG_ENS_MAX; ++m) {
+        x[m] = m < e.M ? e.x[m] + row * e.ld[m] : nullptr;
+        lse[m] = m < e.M ? lse_s[m] : 0.f;
+    }
+    float tv[K];
+    int ti[K];
+    beam_topk_clear<K>(tv, ti);
+    for (int j = lane; j < V; j += 64) {
+        float c;
+        if (e.mode == 0) {
+            float v[DLSG_ENS_MAX], mx = -INFINITY, sum = 0.f;
+#pragma unroll
+            for (int m = 0; m < DLSG_ENS_MAX; ++m)
+                if (m < e.M) { v[m] = (x[m][j] - lse[m]) + e.logw[m]; mx = fmaxf(mx, v[m]); }
+#pragma unroll
+            for (int m = 0; m < DLSG_ENS_MAX; ++m)
+                if (m < e.M) sum += expf(v[m] - mx);
+            c = mx == -INFINITY ? -INFINITY : mx + logf(sum);
+        } else {
+            c = 0.f;
+#pragma unroll
+            for (int m = 0; m < DLSG_ENS_MAX; ++m)
+                if (m < e.M) c += e.w[m] * (x[m][j] - lse[m]);
+        }
+        beam_topk_push<K, true>(tv, ti, c, j, ban, nban);
+    }
+    beam_topk_merge<K>(tv, ti, bv, bi);
+}
+
+// ------------------------------------------------------------------------------------------------ the clip's K best
+// Row o of hist_out (B*k, L): the parent's row of hist_in up to t, the chosen class at t, `end` behind it (step 0 writes whole
+// rows, so the search fills its own buffers).  One wave.
+__device__ __forceinline__ void beam_write_hist(const int64_t* __restrict__ hist_in, int64_t* __restrict__ hist_out, int64_t o,
+                                                int64_t parent, int L, int t, int lane, int cls, int end) {
+    if (lane < L) hist_out[o * L + lane] = lane < t ? hist_in[parent * L + lane] : (lane == t ? (int64_t)cls : (int64_t)end);
+}
+
+// The K best of the clip's nbeam * K candidates, by wave 0: pred, new_lp, back and rows of the clip's K new beams, and the number
+// of `end` among them onto ended_count.  HIST: the new beams' history rows as well.
+template <int K, bool HIST>
+__device__ __forceinline__ void beam_flat_merge(const dlsg_beam_select_args& a, int nbeam, int lane, const float* cand_lp,
+                                                const int* cand_cls, const int64_t* __restrict__ hist_in,
+                                                int64_t* __restrict__ hist_out, int L, int t) {
+    const int b = blockIdx.x, k = K, n = nbeam * k;
+    float v = lane < n ? cand_lp[lane] : -INFINITY;
+    int idx = lane < n ? lane : 0x7fffffff;
+    int n_end = 0;
+    for (int c = 0; c < k; ++c) {
+        float bv = v;
+        int bi = idx;
+        wave_argmax(bv, bi);
+        if (lane == bi) v = -INFINITY, idx = 0x7fffffff;        // remove the winner (it can win only once)
+        if (bi == 0x7fffffff) bi = c < n ? c : 0;               // fewer than k finite candidates: any slot, log-prob -inf
+        const int cls = cand_cls[bi];
+        const int64_t o = (int64_t)b * k + c;
+        if (lane == 0) {
+            a.pred[o] = cls;
+            a.new_lp[o] = bv;
+            a.back[o] = bi / k;
+            a.rows[o] = (int64_t)b * k + bi / k;
+        }
+        if constexpr (HIST) beam_write_hist(hist_in, hist_out, o, (int64_t)b * k + bi / k, L, t, lane, cls, a.end);
+        n_end += cls == a.end;
+    }
+    if (lane == 0 && a.ended_count) atomicAdd(a.ended_count, n_end);
+}
+
+}  // namespace dlsg

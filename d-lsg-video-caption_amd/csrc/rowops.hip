@@ -873,566 +873,6 @@ __global__ __launch_bounds__(256) void log_softmax_kernel(const float* __restric
     for (int j = threadIdx.x; j < V; j += blockDim.x) y[j] = x[j] - lse;
 }
 
-// ------------------------------------------------------------------------------------------------ beam search step
-// One workgroup per batch item, one wave per live beam (BeamSearch.search, allennlp_beamsearch.py:140-260 with
-// per_node_beam_size == beam_size): log-softmax of the beam's logits row, its top-k classes (a finished beam offers
-// <end> at log-prob 0 and nothing else), then the top-k of the k*k summed candidates, back-pointers and the row
-// indices that reorder the recurrent state.  Ties resolve to the lower index.
-constexpr int BEAM_MAXK = 8;
-
-// (value, index) order of the search: larger value first, ties to the smaller index (torch.topk on equal log-probs is not
-// specified; the oracle and the reference fixtures agree with this rule on every golden case)
-__device__ __forceinline__ bool beam_better(float v, int i, float bv, int bi) { return v > bv || (v == bv && i < bi); }
-
-template <int CTRL>
-__device__ __forceinline__ int dpp_i32(int v) { return __builtin_amdgcn_update_dpp(0, v, CTRL, 0xF, 0xF, true); }
-__device__ __forceinline__ int wave_min_i32(int v) {
-    v = min(v, dpp_i32<0xB1>(v));
-    v = min(v, dpp_i32<0x4E>(v));
-    v = min(v, dpp_i32<0x141>(v));
-    v = min(v, dpp_i32<0x140>(v));
-    return min(min(__builtin_amdgcn_readlane(v, 0), __builtin_amdgcn_readlane(v, 16)),
-               min(__builtin_amdgcn_readlane(v, 32), __builtin_amdgcn_readlane(v, 48)));
-}
-// the best (value, index) pair of the wave, to every lane: two DPP reductions instead of twelve ds_bpermute round trips
-__device__ __forceinline__ void wave_argmax(float& v, int& i) {
-    const float m = dlsg::wave_max(v);
-    i = wave_min_i32(v == m ? i : 0x7fffffff);
-    v = m;
-}
-
-// One row of the search: the K best classes of a V-wide logit row and the row's log-sum-exp, ONE wave.  The row is read twice
-// (maximum + each lane's own K best in the first pass, the exponential sum in the second -- same summation order as a plain
-// strided loop, so the log-probs are bit-identical to the previous 2 + K pass form), then K merge rounds over the lanes' heads.
-// BAN (dlsg_beam_select_hist): the classes in ban[0..nban) count as -inf.  The list is looked at only for an element that
-// would enter the lane's K best; the row's maximum and exponential sum stay those of the whole row.
-template <int K, bool BAN = false>
-__device__ __forceinline__ void beam_row_topk(const float* x, int V, int lane, float& lse, float (&outv)[K], int (&outi)[K],
-                                              const int* ban = nullptr, int nban = 0) {
-    float tv[K];
-    int ti[K];
-#pragma unroll
-    for (int q = 0; q < K; ++q) { tv[q] = -INFINITY; ti[q] = 0x7fffffff; }
-    float m = -INFINITY;
-    for (int j = lane; j < V; j += 64) {
-        float cv = x[j];
-        int ci = j;
-        m = fmaxf(m, cv);
-        if (beam_better(cv, ci, tv[K - 1], ti[K - 1])) {
-            if constexpr (BAN) {
-                for (int q = 0; q < nban; ++q) cv = ban[q] == ci ? -INFINITY : cv;
-                if (!beam_better(cv, ci, tv[K - 1], ti[K - 1])) continue;
-            }
-#pragma unroll
-            for (int q = 0; q < K; ++q) {                       // one bubble pass keeps tv sorted
-                const bool up = beam_better(cv, ci, tv[q], ti[q]);
-                const float nv = up ? tv[q] : cv;
-                const int ni = up ? ti[q] : ci;
-                tv[q] = up ? cv : tv[q];
-                ti[q] = up ? ci : ti[q];
-                cv = nv; ci = ni;
-            }
-        }
-    }
-    m = dlsg::wave_max(m);
-    float sum = 0.f;
-    for (int j = lane; j < V; j += 64) sum += expf(x[j] - m);
-    sum = dlsg::wave_sum(sum);
-    lse = logf(sum) + m;
-#pragma unroll
-    for (int c = 0; c < K; ++c) {
-        float bv = tv[0];
-        int bi = ti[0];
-        wave_argmax(bv, bi);
-        outv[c] = bv; outi[c] = bi;
-        if (ti[0] == bi && bi != 0x7fffffff) {                  // the winning lane pops its head
-#pragma unroll
-            for (int q = 0; q + 1 < K; ++q) { tv[q] = tv[q + 1]; ti[q] = ti[q + 1]; }
-            tv[K - 1] = -INFINITY; ti[K - 1] = 0x7fffffff;
-        }
-    }
-}
-
-template <int K>
-__global__ __launch_bounds__(64 * K) void beam_select_kernel(const dlsg_beam_select_args a) {
-    __shared__ float cand_lp[K * K];
-    __shared__ int cand_cls[K * K];
-    const int b = blockIdx.x, k = K, V = a.V;
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const int nbeam = a.first ? 1 : k;                      // step 0: the k rows of a group are identical, use row 0
-    if (w < nbeam) {
-        const int64_t row = (int64_t)b * k + w;
-        const float* x = a.logits + row * a.ld;
-        const bool ended = !a.first && a.last[row] == a.end;
-        const float base = a.first ? 0.f : a.last_lp[row];
-        if (ended) {
-            if (lane < k) {
-                cand_lp[w * k + lane] = lane == 0 ? base : -INFINITY;
-                cand_cls[w * k + lane] = lane == 0 ? a.end : (lane - 1 < a.end ? lane - 1 : lane);
-            }
-        } else {
-            float lse, bv[K];
-            int bi[K];
-            beam_row_topk<K>(x, V, lane, lse, bv, bi);
-            if (lane == 0) {
-#pragma unroll
-                for (int c = 0; c < K; ++c) {
-                    cand_lp[w * k + c] = (bv[c] - lse) + base;
-                    cand_cls[w * k + c] = bi[c];
-                }
-            }
-        }
-    }
-    __syncthreads();
-    if (w == 0) {
-        const int n = nbeam * k;
-        float v = lane < n ? cand_lp[lane] : -INFINITY;
-        int idx = lane < n ? lane : 0x7fffffff;
-        int n_end = 0;
-        for (int c = 0; c < k; ++c) {
-            float bv = v;
-            int bi = idx;
-            wave_argmax(bv, bi);
-            if (lane == bi) v = -INFINITY, idx = 0x7fffffff;        // remove the winner (it can win only once)
-            if (bi == 0x7fffffff) bi = c < n ? c : 0;               // fewer than k finite candidates: any slot, log-prob -inf
-            const int cls = cand_cls[bi];
-            if (lane == 0) {
-                const int64_t o = (int64_t)b * k + c;
-                a.pred[o] = cls;
-                a.new_lp[o] = bv;
-                a.back[o] = bi / k;
-                a.rows[o] = (int64_t)b * k + bi / k;
-            }
-            n_end += cls == a.end;
-        }
-        if (lane == 0 && a.ended_count) atomicAdd(a.ended_count, n_end);
-    }
-}
-
-// The step with a token history that travels with the beams, a repeated-n-gram ban and a minimum length.  hist_in / hist_out
-// (B*k, L) int64, ping-pong: new beam c gets its parent's row with hist[t] = pred and `end` at every position after t (step 0
-// writes whole rows, so the search fills its own buffers).  Each live beam's wave lists the classes it may not choose in LDS:
-// with g = no_repeat_ngram, every h[i + g - 1] whose g - 1 predecessors equal the last g - 1 tokens of the history, and
-// `end` while t < min_len.  g = 0 and min_len = 0 give the bits of beam_select_kernel.
-constexpr int BEAM_MAXL = 64;
-template <int K>
-__global__ __launch_bounds__(64 * K) void beam_select_hist_kernel(const dlsg_beam_select_args a, const int64_t* __restrict__ hist_in,
-                                                                    int64_t* __restrict__ hist_out, int L, int t, int g, int min_len) {
-    __shared__ float cand_lp[K * K];
-    __shared__ int cand_cls[K * K];
-    __shared__ int hist[K][BEAM_MAXL];
-    __shared__ int ban[K][BEAM_MAXL + 1];
-    __shared__ int nban[K];
-    const int b = blockIdx.x, k = K, V = a.V;
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const int nbeam = a.first ? 1 : k;
-    const int64_t row = (int64_t)b * k + w;
-    const bool ended = !a.first && a.last[row] == a.end;
-    const bool ngram = g > 0 && t >= g;                      // (never at step 0)
-    if (ngram) hist[w][lane] = lane < t ? (int)hist_in[row * L + lane] : -1;
-    __syncthreads();
-    if (w < nbeam && !ended) {
-        int n = 0;
-        if (ngram) {                                         // lane i: the g-gram that starts at i ends in a class to ban if its
-            bool hit = lane <= t - g;                        // first g - 1 tokens are the last g - 1 of the history
-            for (int j = 0; hit && j < g - 1; ++j) hit = hist[w][lane + j] == hist[w][t - g + 1 + j];
-            const unsigned long long m = __ballot(hit);
-            if (hit) ban[w][__popcll(m & ((1ull << lane) - 1ull))] = hist[w][lane + g - 1];
-            n = __popcll(m);
-        }
-        if (lane == 0) {
-            if (t < min_len) ban[w][n++] = a.end;
-            nban[w] = n;
-        }
-    }
-    __syncthreads();
-    if (w < nbeam) {
-        const float* x = a.logits + row * a.ld;
-        const float base = a.first ? 0.f : a.last_lp[row];
-        if (ended) {
-            if (lane < k) {
-                cand_lp[w * k + lane] = lane == 0 ? base : -INFINITY;
-                cand_cls[w * k + lane] = lane == 0 ? a.end : (lane - 1 < a.end ? lane - 1 : lane);
-            }
-        } else {
-            float lse, bv[K];
-            int bi[K];
-            beam_row_topk<K, true>(x, V, lane, lse, bv, bi, ban[w], nban[w]);
-            if (lane == 0) {
-#pragma unroll
-                for (int c = 0; c < K; ++c) {
-                    cand_lp[w * k + c] = (bv[c] - lse) + base;
-                    cand_cls[w * k + c] = bi[c];
-                }
-            }
-        }
-    }
-    __syncthreads();
-    if (w == 0) {
-        const int n = nbeam * k;
-        float v = lane < n ? cand_lp[lane] : -INFINITY;
-        int idx = lane < n ? lane : 0x7fffffff;
-        int n_end = 0;
-        for (int c = 0; c < k; ++c) {
-            float bv = v;
-            int bi = idx;
-            wave_argmax(bv, bi);
-            if (lane == bi) v = -INFINITY, idx = 0x7fffffff;
-            if (bi == 0x7fffffff) bi = c < n ? c : 0;
-            const int cls = cand_cls[bi];
-            const int64_t o = (int64_t)b * k + c;
-            if (lane == 0) {
-                a.pred[o] = cls;
-                a.new_lp[o] = bv;
-                a.back[o] = bi / k;
-                a.rows[o] = (int64_t)b * k + bi / k;
-            }
-            if (lane < L)
-                hist_out[o * L + lane] = lane < t ? hist_in[((int64_t)b * k + bi / k) * L + lane] : (lane == t ? (int64_t)cls : (int64_t)a.end);
-            n_end += cls == a.end;
-        }
-        if (lane == 0 && a.ended_count) atomicAdd(a.ended_count, n_end);
-    }
-}
-
-// The step of an ensemble (dlsg_beam_select_ens): beam_select_hist_kernel, but a live beam's V candidate values are combined from
-// M logit rows, one per member.  Per member the row's log-sum-exp in beam_row_topk's order (strided maximum + wave_max, strided
-// exponential sum + wave_sum), then per class, in member order and float32,
-//   mode 0: c = mx + logf(sum_m expf(v_m - mx)),  v_m = (x_m - lse_m) + logw_m,  mx = max_m v_m   (log of the weighted mean probability)
-//   mode 1: c = sum_m w_m (x_m - lse_m)                                                          (weighted mean log-probability)
-// and the K best unbanned c of the row, by beam_row_topk's insert and merge (restated in the two helpers below, because the
-// existing kernels' code is pinned).  With one member of weight 1 both modes give c = x - lse exactly, so the launch returns
-// what beam_select_hist_kernel returns.  The M pointers, strides and weights travel by value in the argument block.
-struct EnsPack {
-    const float* x[DLSG_ENS_MAX];
-    int64_t ld[DLSG_ENS_MAX];
-    float w[DLSG_ENS_MAX], logw[DLSG_ENS_MAX];
-    int M, mode;
-};
-
-// (cv, ci) into a lane's sorted K best unless it is banned: the loop body of beam_row_topk<K, true>
-template <int K>
-__device__ __forceinline__ void beam_topk_push(float (&tv)[K], int (&ti)[K], float cv, int ci, const int* ban, int nban) {
-    if (!beam_better(cv, ci, tv[K - 1], ti[K - 1])) return;
-    for (int q = 0; q < nban; ++q) cv = ban[q] == ci ? -INFINITY : cv;
-    if (!beam_better(cv, ci, tv[K - 1], ti[K - 1])) return;
-#pragma unroll
-    for (int q = 0; q < K; ++q) {
-        const bool up = beam_better(cv, ci, tv[q], ti[q]);
-        const float nv = up ? tv[q] : cv;
-        const int ni = up ? ti[q] : ci;
-        tv[q] = up ? cv : tv[q];
-        ti[q] = up ? ci : ti[q];
-        cv = nv; ci = ni;
-    }
-}
-// the K best of the wave from the lanes' sorted lists: the merge rounds of beam_row_topk
-template <int K>
-__device__ __forceinline__ void beam_topk_merge(float (&tv)[K], int (&ti)[K], float (&outv)[K], int (&outi)[K]) {
-#pragma unroll
-    for (int c = 0; c < K; ++c) {
-        float bv = tv[0];
-        int bi = ti[0];
-        wave_argmax(bv, bi);
-        outv[c] = bv; outi[c] = bi;
-        if (ti[0] == bi && bi != 0x7fffffff) {
-#pragma unroll
-            for (int q = 0; q + 1 < K; ++q) { tv[q] = tv[q + 1]; ti[q] = ti[q + 1]; }
-            tv[K - 1] = -INFINITY; ti[K - 1] = 0x7fffffff;
-        }
-    }
-}
-
-template <int K>
-__global__ __launch_bounds__(64 * K) void beam_select_ens_kernel(const dlsg_beam_select_args a, const EnsPack e,
-                                                                   const int64_t* __restrict__ hist_in, int64_t* __restrict__ hist_out,
-                                                                   int L, int t, int g, int min_len) {
-    __shared__ float cand_lp[K * K];
-    __shared__ int cand_cls[K * K];
-    __shared__ int hist[K][BEAM_MAXL];
-    __shared__ int ban[K][BEAM_MAXL + 1];
-    __shared__ int nban[K];
-    __shared__ float lse_s[K][DLSG_ENS_MAX];                 // (in LDS: the member loop that fills it is not unrolled)
-    const int b = blockIdx.x, k = K, V = a.V;
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const int nbeam = a.first ? 1 : k;
-    const int64_t row = (int64_t)b * k + w;
-    const bool ended = !a.first && a.last[row] == a.end;
-    const bool ngram = g > 0 && t >= g;
-    if (ngram) hist[w][lane] = lane < t ? (int)hist_in[row * L + lane] : -1;
-    __syncthreads();
-    if (w < nbeam && !ended) {
-        int n = 0;
-        if (ngram) {
-            bool hit = lane <= t - g;
-            for (int j = 0; hit && j < g - 1; ++j) hit = hist[w][lane + j] == hist[w][t - g + 1 + j];
-            const unsigned long long m = __ballot(hit);
-            if (hit) ban[w][__popcll(m & ((1ull << lane) - 1ull))] = hist[w][lane + g - 1];
-            n = __popcll(m);
-        }
-        if (lane == 0) {
-            if (t < min_len) ban[w][n++] = a.end;
-            nban[w] = n;
-        }
-    }
-    __syncthreads();
-    if (w < nbeam) {
-        const float base = a.first ? 0.f : a.last_lp[row];
-        if (ended) {
-            if (lane < k) {
-                cand_lp[w * k + lane] = lane == 0 ? base : -INFINITY;
-                cand_cls[w * k + lane] = lane == 0 ? a.end : (lane - 1 < a.end ? lane - 1 : lane);
-            }
-        } else {
-            for (int m = 0; m < e.M; ++m) {                  // every lane writes the wave's value and reads back its own store
-                const float* x = e.x[m] + row * e.ld[m];
-                float mx = -INFINITY;
-                for (int j = lane; j < V; j += 64) mx = fmaxf(mx, x[j]);
-                mx = dlsg::wave_max(mx);
-                float sum = 0.f;
-                for (int j = lane; j < V; j += 64) sum += expf(x[j] - mx);
-                sum = dlsg::wave_sum(sum);
-                lse_s[w][m] = logf(sum) + mx;
-            }
-            const float* x[DLSG_ENS_MAX];
-            float lse[DLSG_ENS_MAX];
-#pragma unroll
-            for (int m = 0; m < DLSG_ENS_MAX; ++m) {
-                x[m] = m < e.M ? e.x[m] + row * e.ld[m] : nullptr;
-                lse[m] = m < e.M ? lse_s[w][m] : 0.f;
-            }
-            float tv[K], bv[K];
-            int ti[K], bi[K];
-#pragma unroll
-            for (int q = 0; q < K; ++q) { tv[q] = -INFINITY; ti[q] = 0x7fffffff; }
-            for (int j = lane; j < V; j += 64) {
-                float c;
-                if (e.mode == 0) {
-                    float v[DLSG_ENS_MAX], mx = -INFINITY, sum = 0.f;
-#pragma unroll
-                    for (int m = 0; m < DLSG_ENS_MAX; ++m)
-                        if (m < e.M) { v[m] = (x[m][j] - lse[m]) + e.logw[m]; mx = fmaxf(mx, v[m]); }
-#pragma unroll
-                    for (int m = 0; m < DLSG_ENS_MAX; ++m)
-                        if (m < e.M) sum += expf(v[m] - mx);
-                    c = mx == -INFINITY ? -INFINITY : mx + logf(sum);
-                } else {
-                    c = 0.f;
-#pragma unroll
-                    for (int m = 0; m < DLSG_ENS_MAX; ++m)
-                        if (m < e.M) c += e.w[m] * (x[m][j] - lse[m]);
-                }
-                beam_topk_push<K>(tv, ti, c, j, ban[w], nban[w]);
-            }
-            beam_topk_merge<K>(tv, ti, bv, bi);
-            if (lane == 0) {
-#pragma unroll
-                for (int q = 0; q < K; ++q) {
-                    cand_lp[w * k + q] = bv[q] + base;
-                    cand_cls[w * k + q] = bi[q];
-                }
-            }
-        }
-    }
-    __syncthreads();
-    if (w == 0) {
-        const int n = nbeam * k;
-        float v = lane < n ? cand_lp[lane] : -INFINITY;
-        int idx = lane < n ? lane : 0x7fffffff;
-        int n_end = 0;
-        for (int c = 0; c < k; ++c) {
-            float bv = v;
-            int bi = idx;
-            wave_argmax(bv, bi);
-            if (lane == bi) v = -INFINITY, idx = 0x7fffffff;
-            if (bi == 0x7fffffff) bi = c < n ? c : 0;
-            const int cls = cand_cls[bi];
-            const int64_t o = (int64_t)b * k + c;
-            if (lane == 0) {
-                a.pred[o] = cls;
-                a.new_lp[o] = bv;
-                a.back[o] = bi / k;
-                a.rows[o] = (int64_t)b * k + bi / k;
-            }
-            if (lane < L)
-                hist_out[o * L + lane] = lane < t ? hist_in[((int64_t)b * k + bi / k) * L + lane] : (lane == t ? (int64_t)cls : (int64_t)a.end);
-            n_end += cls == a.end;
-        }
-        if (lane == 0 && a.ended_count) atomicAdd(a.ended_count, n_end);
-    }
-}
-
-// Diverse (group) beam search (dlsg_beam_select_groups): the K beams of a clip are G groups of KG = K / G consecutive rows.
-// Phase 1 is beam_select_ens_kernel's, wave w for row w: every row's K best (c + last_lp, class) in LDS.  Phase 2, wave 0: the
-// groups in order; lane i < KG * K holds candidate i of the group (row within the group, then rank; step 0: the K entries of the
-// clip's one list, parent = the group's first row), key = lp, minus diversity * cnt[class] where the parent is live and cnt, the
-// number of picks of that class by earlier groups at this step from live parents, is not 0 (diversity = +inf: the key is -inf).
-// KG rounds of wave_argmax over (key, lane); a -inf key is no candidate, a slot left over takes candidate slot q of the group at
-// log-prob -inf and is not counted.  new_lp is lp, not the key.  The picks so far (at most K) are wave-uniform registers.
-// G = 1: no class is ever counted, so every key is its lp and the launch chooses what beam_select_ens_kernel chooses.
-template <int K>
-__global__ __launch_bounds__(64 * K) void beam_select_groups_kernel(const dlsg_beam_select_args a, const EnsPack e,
-                                                                      const int64_t* __restrict__ hist_in, int64_t* __restrict__ hist_out,
-                                                                      int L, int t, int g, int min_len, int G, float diversity) {
-    __shared__ float cand_lp[K * K];
-    __shared__ int cand_cls[K * K];
-    __shared__ int hist[K][BEAM_MAXL];
-    __shared__ int ban[K][BEAM_MAXL + 1];
-    __shared__ int nban[K];
-    __shared__ float lse_s[K][DLSG_ENS_MAX];
-    const int b = blockIdx.x, k = K, V = a.V;
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const int nbeam = a.first ? 1 : k;
-    const int64_t row = (int64_t)b * k + w;
-    const bool ended = !a.first && a.last[row] == a.end;
-    const bool ngram = g > 0 && t >= g;
-    if (ngram) hist[w][lane] = lane < t ? (int)hist_in[row * L + lane] : -1;
-    __syncthreads();
-    if (w < nbeam && !ended) {
-        int n = 0;
-        if (ngram) {
-            bool hit = lane <= t - g;
-            for (int j = 0; hit && j < g - 1; ++j) hit = hist[w][lane + j] == hist[w][t - g + 1 + j];
-            const unsigned long long m = __ballot(hit);
-            if (hit) ban[w][__popcll(m & ((1ull << lane) - 1ull))] = hist[w][lane + g - 1];
-            n = __popcll(m);
-        }
-        if (lane == 0) {
-            if (t < min_len) ban[w][n++] = a.end;
-            nban[w] = n;
-        }
-    }
-    __syncthreads();
-    if (w < nbeam) {
-        const float base = a.first ? 0.f : a.last_lp[row];
-        if (ended) {
-            if (lane < k) {
-                cand_lp[w * k + lane] = lane == 0 ? base : -INFINITY;
-                cand_cls[w * k + lane] = lane == 0 ? a.end : (lane - 1 < a.end ? lane - 1 : lane);
-            }
-        } else {
-            for (int m = 0; m < e.M; ++m) {
-                const float* x = e.x[m] + row * e.ld[m];
-                float mx = -INFINITY;
-                for (int j = lane; j < V; j += 64) mx = fmaxf(mx, x[j]);
-                mx = dlsg::wave_max(mx);
-                float sum = 0.f;
-                for (int j = lane; j < V; j += 64) sum += expf(x[j] - mx);
-                sum = dlsg::wave_sum(sum);
-                lse_s[w][m] = logf(sum) + mx;
-            }
-            const float* x[DLSG_ENS_MAX];
-            float lse[DLSG_ENS_MAX];
-#pragma unroll
-            for (int m = 0; m < DLSG_ENS_MAX; ++m) {
-                x[m] = m < e.M ? e.x[m] + row * e.ld[m] : nullptr;
-                lse[m] = m < e.M ? lse_s[w][m] : 0.f;
-            }
-            float tv[K], bv[K];
-            int ti[K], bi[K];
-#pragma unroll
-            for (int q = 0; q < K; ++q) { tv[q] = -INFINITY; ti[q] = 0x7fffffff; }
-            for (int j = lane; j < V; j += 64) {
-                float c;
-                if (e.mode == 0) {
-                    float v[DLSG_ENS_MAX], mx = -INFINITY, sum = 0.f;
-#pragma unroll
-                    for (int m = 0; m < DLSG_ENS_MAX; ++m)
-                        if (m < e.M) { v[m] = (x[m][j] - lse[m]) + e.logw[m]; mx = fmaxf(mx, v[m]); }
-#pragma unroll
-                    for (int m = 0; m < DLSG_ENS_MAX; ++m)
-                        if (m < e.M) sum += expf(v[m] - mx);
-                    c = mx == -INFINITY ? -INFINITY : mx + logf(sum);
-                } else {
-                    c = 0.f;
-#pragma unroll
-                    for (int m = 0; m < DLSG_ENS_MAX; ++m)
-                        if (m < e.M) c += e.w[m] * (x[m][j] - lse[m]);
-                }
-                beam_topk_push<K>(tv, ti, c, j, ban[w], nban[w]);
-            }
-            beam_topk_merge<K>(tv, ti, bv, bi);
-            if (lane == 0) {
-#pragma unroll
-                for (int q = 0; q < K; ++q) {
-                    cand_lp[w * k + q] = bv[q] + base;
-                    cand_cls[w * k + q] = bi[q];
-                }
-            }
-        }
-    }
-    __syncthreads();
-    if (w == 0) {
-        const int kg = k / G;
-        const int n = a.first ? k : kg * k;                   // candidates of one group (<= 64: one per lane)
-        int mypick = -1;                                      // lane s: the s-th class counted at this step
-        int npicked = 0, n_end = 0;                           // (wave-uniform; at most k)
-        for (int gr = 0; gr < G; ++gr) {
-            const int first_row = gr * kg;                    // the group's first row within the clip
-            const bool have = lane < n;
-            const int ci = !have ? 0 : a.first ? lane : first_row * k + lane;      // this lane's slot in cand_lp / cand_cls
-            const int par = !have || a.first ? first_row : first_row + lane / k;   // and its parent within the clip
-            const int mycls = cand_cls[ci];
-            int cnt = 0;
-            for (int q = 0; q < npicked; ++q) cnt += __builtin_amdgcn_readlane(mypick, q) == mycls;
-            float key = have ? cand_lp[ci] : -INFINITY;
-            if (cnt > 0 && (a.first || a.last[(int64_t)b * k + par] != a.end))
-                key = diversity == INFINITY ? -INFINITY : key - __fmul_rn(diversity, (float)cnt);
-            int idx = key == -INFINITY ? 0x7fffffff : lane;   // a -inf key is no candidate
-            for (int q = 0; q < kg; ++q) {                    // (keys are taken once per group: a pick counts from the next group on)
-                float bv = key;
-                int bi = idx;
-                wave_argmax(bv, bi);
-                if (lane == bi) key = -INFINITY, idx = 0x7fffffff;
-                const bool fill = bi == 0x7fffffff;            // fewer than kg candidates: slot q of the group, log-prob -inf
-                if (fill) bi = q;
-                const int sl = a.first ? bi : first_row * k + bi;
-                const int pb = a.first ? first_row : first_row + bi / k;
-                const int cls = cand_cls[sl];
-                const int64_t o = (int64_t)b * k + first_row + q;
-                if (lane == 0) {
-                    a.pred[o] = cls;
-                    a.new_lp[o] = fill ? -INFINITY : cand_lp[sl];
-                    a.back[o] = pb;
-                    a.rows[o] = (int64_t)b * k + pb;
-                }
-                if (lane < L)
-                    hist_out[o * L + lane] = lane < t ? hist_in[((int64_t)b * k + pb) * L + lane] : (lane == t ? (int64_t)cls : (int64_t)a.end);
-                n_end += cls == a.end;
-                if (!fill && (a.first || a.last[(int64_t)b * k + pb] != a.end)) {
-                    if (lane == npicked) mypick = cls;
-                    ++npicked;
-                }
-            }
-        }
-        if (lane == 0 && a.ended_count) atomicAdd(a.ended_count, n_end);
-    }
-}
-
-// The n best of each clip's k finished beams, by score = lp / len^alpha (double, stored as float), descending, ties to the lower
-// beam: one wave per clip.  len = tokens up to and including the first `end` of the beam's history row, L without one.
-__global__ __launch_bounds__(64) void beam_finalize_kernel(const int64_t* __restrict__ hist, const float* __restrict__ lp, int k, int L,
-                                                           int64_t end, double alpha, int n, int64_t* __restrict__ ids,
-                                                           float* __restrict__ scores, int64_t* __restrict__ lens) {
-    const int b = blockIdx.x, lane = threadIdx.x;
-    float sc[BEAM_MAXK];
-    int len[BEAM_MAXK];
-    for (int c = 0; c < k; ++c) {
-        const int64_t row = (int64_t)b * k + c;
-        const unsigned long long m = __ballot(lane < L && hist[row * L + lane] == end);
-        len[c] = m ? __ffsll((long long)m) : L;
-        sc[c] = (float)((double)lp[row] / pow((double)len[c], alpha));
-    }
-    for (int c = 0; c < k; ++c) {
-        int rank = 0;
-        for (int d = 0; d < k; ++d) rank += d != c && beam_better(sc[d], d, sc[c], c);
-        if (rank >= n) continue;
-        const int64_t o = (int64_t)b * n + rank;
-        if (lane < L) ids[o * L + lane] = hist[((int64_t)b * k + c) * L + lane];
-        if (lane == 0) { scores[o] = sc[c]; lens[o] = len[c]; }
-    }
-}
-
 // dst_i[r, :] = src_i[rows[r], :] for up to four (src, dst, width) triples in one launch (blockIdx.y selects)
 __global__ void gather_rows_multi_kernel(const dlsg_gather_multi_args a) {
     const int i = blockIdx.y, r = blockIdx.x;
@@ -1862,99 +1302,6 @@ extern "C" int dlsg_ce_ragged_weighted(const float* logits, const int64_t* targe
 extern "C" int dlsg_log_softmax(const float* logits, float* out, int rows, int V, void* stream) {
     if (rows == 0) return DLSG_OK;
     hipLaunchKernelGGL(log_softmax_kernel, dim3(rows), dim3(256), 0, ST(stream), logits, out, V);
-    DLSG_CHECK_LAUNCH();
-    return DLSG_OK;
-}
-extern "C" int dlsg_beam_select(const dlsg_beam_select_args* a, void* stream) {
-    if (!a || a->k < 1 || a->k > BEAM_MAXK || a->V < a->k) return DLSG_EINVAL;
-    if (a->B == 0) return DLSG_OK;
-    switch (a->k) {
-        case 1: hipLaunchKernelGGL(beam_select_kernel<1>, dim3(a->B), dim3(64), 0, ST(stream), *a); break;
-        case 2: hipLaunchKernelGGL(beam_select_kernel<2>, dim3(a->B), dim3(128), 0, ST(stream), *a); break;
-        case 3: hipLaunchKernelGGL(beam_select_kernel<3>, dim3(a->B), dim3(192), 0, ST(stream), *a); break;
-        case 4: hipLaunchKernelGGL(beam_select_kernel<4>, dim3(a->B), dim3(256), 0, ST(stream), *a); break;
-        case 5: hipLaunchKernelGGL(beam_select_kernel<5>, dim3(a->B), dim3(320), 0, ST(stream), *a); break;
-        case 6: hipLaunchKernelGGL(beam_select_kernel<6>, dim3(a->B), dim3(384), 0, ST(stream), *a); break;
-        case 7: hipLaunchKernelGGL(beam_select_kernel<7>, dim3(a->B), dim3(448), 0, ST(stream), *a); break;
-        default: hipLaunchKernelGGL(beam_select_kernel<8>, dim3(a->B), dim3(512), 0, ST(stream), *a); break;
-    }
-    DLSG_CHECK_LAUNCH();
-    return DLSG_OK;
-}
-#define BEAM_HIST_CASE(KK) \
-    case KK: hipLaunchKernelGGL(beam_select_hist_kernel<KK>, dim3(a->B), dim3(64 * KK), 0, ST(stream), *a, hist_in, hist_out, L, t, \
-                                no_repeat_ngram, min_len); break;
-extern "C" int dlsg_beam_select_hist(const dlsg_beam_select_args* a, const int64_t* hist_in, int64_t* hist_out, int L, int t,
-                                     int no_repeat_ngram, int min_len, void* stream) {
-    if (!a || a->k < 1 || a->k > BEAM_MAXK || a->V < a->k) return DLSG_EINVAL;
-    if (!hist_out || L < 1 || L > BEAM_MAXL || t < 0 || t >= L || no_repeat_ngram < 0 || min_len < 0) return DLSG_EINVAL;
-    if ((a->first != 0) != (t == 0) || (t > 0 && (!hist_in || hist_in == hist_out))) return DLSG_EINVAL;
-    if (a->B == 0) return DLSG_OK;
-    switch (a->k) {
-        BEAM_HIST_CASE(1) BEAM_HIST_CASE(2) BEAM_HIST_CASE(3) BEAM_HIST_CASE(4)
-        BEAM_HIST_CASE(5) BEAM_HIST_CASE(6) BEAM_HIST_CASE(7) BEAM_HIST_CASE(8)
-    }
-    DLSG_CHECK_LAUNCH();
-    return DLSG_OK;
-}
-#undef BEAM_HIST_CASE
-#define BEAM_ENS_CASE(KK) \
-    case KK: hipLaunchKernelGGL(beam_select_ens_kernel<KK>, dim3(a->B), dim3(64 * KK), 0, ST(stream), *a, e, hist_in, hist_out, L, t, \
-                                no_repeat_ngram, min_len); break;
-extern "C" int dlsg_beam_select_ens(const dlsg_beam_select_args* a, const float* const* logits, const int64_t* ld, const float* w,
-                                    const float* logw, int M, int mode, const int64_t* hist_in, int64_t* hist_out, int L, int t,
-                                    int no_repeat_ngram, int min_len, void* stream) {
-    if (!a || a->k < 1 || a->k > BEAM_MAXK || a->V < a->k) return DLSG_EINVAL;
-    if (!logits || !ld || !w || !logw || M < 1 || M > DLSG_ENS_MAX || (mode != 0 && mode != 1)) return DLSG_EINVAL;
-    if (!hist_out || L < 1 || L > BEAM_MAXL || t < 0 || t >= L || no_repeat_ngram < 0 || min_len < 0) return DLSG_EINVAL;
-    if ((a->first != 0) != (t == 0) || (t > 0 && (!hist_in || hist_in == hist_out))) return DLSG_EINVAL;
-    EnsPack e = {};
-    for (int m = 0; m < M; ++m) {
-        if (!logits[m]) return DLSG_EINVAL;
-        e.x[m] = logits[m]; e.ld[m] = ld[m]; e.w[m] = w[m]; e.logw[m] = logw[m];
-    }
-    e.M = M; e.mode = mode;
-    if (a->B == 0) return DLSG_OK;
-    switch (a->k) {
-        BEAM_ENS_CASE(1) BEAM_ENS_CASE(2) BEAM_ENS_CASE(3) BEAM_ENS_CASE(4)
-        BEAM_ENS_CASE(5) BEAM_ENS_CASE(6) BEAM_ENS_CASE(7) BEAM_ENS_CASE(8)
-    }
-    DLSG_CHECK_LAUNCH();
-    return DLSG_OK;
-}
-#undef BEAM_ENS_CASE
-#define BEAM_GROUPS_CASE(KK) \
-    case KK: hipLaunchKernelGGL(beam_select_groups_kernel<KK>, dim3(a->B), dim3(64 * KK), 0, ST(stream), *a, e, hist_in, hist_out, L, t, \
-                                no_repeat_ngram, min_len, groups, diversity); break;
-extern "C" int dlsg_beam_select_groups(const dlsg_beam_select_args* a, const float* const* logits, const int64_t* ld, const float* w,
-                                       const float* logw, int M, int mode, const int64_t* hist_in, int64_t* hist_out, int L, int t,
-                                       int no_repeat_ngram, int min_len, int groups, float diversity, void* stream) {
-    if (!a || a->k < 1 || a->k > BEAM_MAXK || a->V < a->k) return DLSG_EINVAL;
-    if (!logits || !ld || !w || !logw || M < 1 || M > DLSG_ENS_MAX || (mode != 0 && mode != 1)) return DLSG_EINVAL;
-    if (!hist_out || L < 1 || L > BEAM_MAXL || t < 0 || t >= L || no_repeat_ngram < 0 || min_len < 0) return DLSG_EINVAL;
-    if ((a->first != 0) != (t == 0) || (t > 0 && (!hist_in || hist_in == hist_out))) return DLSG_EINVAL;
-    if (groups < 1 || a->k % groups != 0 || !(diversity >= 0.f)) return DLSG_EINVAL;     // (NaN fails the comparison)
-    EnsPack e = {};
-    for (int m = 0; m < M; ++m) {
-        if (!logits[m]) return DLSG_EINVAL;
-        e.x[m] = logits[m]; e.ld[m] = ld[m]; e.w[m] = w[m]; e.logw[m] = logw[m];
-    }
-    e.M = M; e.mode = mode;
-    if (a->B == 0) return DLSG_OK;
-    switch (a->k) {
-        BEAM_GROUPS_CASE(1) BEAM_GROUPS_CASE(2) BEAM_GROUPS_CASE(3) BEAM_GROUPS_CASE(4)
-        BEAM_GROUPS_CASE(5) BEAM_GROUPS_CASE(6) BEAM_GROUPS_CASE(7) BEAM_GROUPS_CASE(8)
-    }
-    DLSG_CHECK_LAUNCH();
-    return DLSG_OK;
-}
-#undef BEAM_GROUPS_CASE
-extern "C" int dlsg_beam_finalize(const int64_t* hist, const float* lp, int B, int k, int L, int64_t end, double alpha, int n,
-                                  int64_t* ids, float* scores, int64_t* lens, void* stream) {
-    if (!hist || !lp || !ids || !scores || !lens || B < 0 || k < 1 || k > BEAM_MAXK || L < 1 || L > BEAM_MAXL || n < 1 || n > k)
-        return DLSG_EINVAL;
-    if (B == 0) return DLSG_OK;
-    hipLaunchKernelGGL(beam_finalize_kernel, dim3(B), dim3(64), 0, ST(stream), hist, lp, k, L, end, alpha, n, ids, scores, lens);
     DLSG_CHECK_LAUNCH();
     return DLSG_OK;
 }

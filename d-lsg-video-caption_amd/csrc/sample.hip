@@ -6,6 +6,7 @@
 #include <math.h>
 #include <mutex>
 
+#include "beam.hpp"
 #include "common.hpp"
 #include "dlsg.h"
 
@@ -14,7 +15,7 @@ using namespace dlsg;
 namespace {
 
 constexpr int SF_THREADS = 256;
-constexpr int SF_MAXL = 64;             // history positions: lane i of wave 0 holds word i
+constexpr int SF_MAXL = BEAM_MAXL;      // history positions: lane i of wave 0 holds word i
 
 // u < v as floats  <=>  ord_key(u) < ord_key(v) as unsigned, for everything but NaN (staging turns NaN into -inf, -0 into +0)
 __device__ __forceinline__ uint32_t ord_key(float z) {
@@ -144,24 +145,10 @@ __global__ __launch_bounds__(SF_THREADS) void sample_filter_embed_kernel(
     const float sc = gumbel ? 1.f / tau : 1.f;
     int par = 0;
 
-    // ---- the classes this row may not choose (the rule of beam_select_hist_kernel on the row's own words)
-    const bool ngram = g > 0 && t >= g;
-    if (ngram && tid < SF_MAXL) hs[tid] = tid < t ? (int)hist[(int64_t)tid * hist_stride + r] : -1;
+    // ---- the classes this row may not choose: the beam search's rule (beam_ban_list, beam.hpp) on the row's own words
+    if (g > 0 && t >= g && tid < SF_MAXL) hs[tid] = tid < t ? (int)hist[(int64_t)tid * hist_stride + r] : -1;
     __syncthreads();
-    if (w == 0) {
-        int n = 0;
-        if (ngram) {                                         // lane i: the g-gram that starts at i ends in a class to ban if its
-            bool hit = lane <= t - g;                        // first g - 1 words are the last g - 1 of the history
-            for (int j = 0; hit && j < g - 1; ++j) hit = hs[lane + j] == hs[t - g + 1 + j];
-            const unsigned long long mk = __ballot(hit);
-            if (hit) ban[__popcll(mk & ((1ull << lane) - 1ull))] = hs[lane + g - 1];
-            n = __popcll(mk);
-        }
-        if (lane == 0) {
-            if (t < min_len) ban[n++] = (int)end_id;
-            nban_s = n;
-        }
-    }
+    if (w == 0) beam_ban_list(hs, t, g, min_len, (int)end_id, ban, &nban_s);
     __syncthreads();
     const int nban = nban_s;
 

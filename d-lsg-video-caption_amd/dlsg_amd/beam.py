@@ -175,6 +175,46 @@ def check_nbest_options(k, L, n_best=None, length_penalty=0.0, no_repeat_ngram=0
     return n
 
 
+def _nbest_search(models, weights, mode, visual_feats, region_feats, n_best, length_penalty, no_repeat_ngram, min_len, beam_size,
+                  num_groups, diversity_penalty):
+    """The search of `beam_nbest` (weights None: one model) and `ensemble_nbest`: every model steps its own state on the shared
+    words and back-pointer rows, one select launch per step chooses the beams, `beam_finalize` ranks them."""
+    dec = models[0].decoder
+    k, L = dec.beam_size if beam_size is None else beam_size, dec.max_words
+    n = check_nbest_options(k, L, n_best, length_penalty, no_repeat_ngram, min_len, num_groups, diversity_penalty)
+    steps = []
+    for model in models:
+        mems, sv, seed, _ = _encode(model, visual_feats, region_feats)
+        advance, B, R, _ = _beam_setup(model, mems, sv, seed, k)
+        steps.append(advance)
+    ops = models[0].ops
+    end = dec.vocab('<end>')
+    dev = mems[0].device
+    preds = torch.empty(2, R, dtype=torch.int64, device=dev)       # ping-pong: the history keeps the tokens
+    hist = torch.empty(2, R, L, dtype=torch.int64, device=dev)     # filled by step 0
+    back = torch.empty(R, dtype=torch.int64, device=dev)
+    rows = torch.empty(R, dtype=torch.int64, device=dev)
+    lps = torch.zeros(2, R, dtype=torch.float32, device=dev)
+    words = torch.full((R,), dec.vocab('<start>'), dtype=torch.int64, device=dev)
+    for t in range(L):
+        logits = [advance(t, words, rows) for advance in steps]
+        step = (words, lps[t % 2], preds[t % 2], lps[(t + 1) % 2], back, rows, k, end, hist[t % 2], hist[(t + 1) % 2], t,
+                no_repeat_ngram, min_len)
+        if num_groups > 1:                                             # (a single model: one member of weight 1)
+            ops.beam_select_groups(logits, [1.0] if weights is None else weights, mode, *step, num_groups,
+                                   float(diversity_penalty))
+        elif weights is None:
+            ops.beam_select_hist(logits[0], *step)                     # (reads a logit row twice, the ensemble step three times)
+        else:
+            ops.beam_select_ens(logits, weights, mode, *step)
+        words = preds[t % 2]
+    ids = torch.empty(B, n, L, dtype=torch.int64, device=dev)
+    scores = torch.empty(B, n, dtype=torch.float32, device=dev)
+    lens = torch.empty(B, n, dtype=torch.int64, device=dev)
+    ops.beam_finalize(hist[L % 2], lps[L % 2], k, end, float(length_penalty), ids, scores, lens)
+    return ids, scores, lens
+
+
 @torch.no_grad()
 def beam_nbest(model, visual_feats, region_feats, n_best=None, length_penalty=0.0, no_repeat_ngram=0, min_len=0, beam_size=None,
                num_groups=1, diversity_penalty=0.0):
@@ -190,34 +230,8 @@ def beam_nbest(model, visual_feats, region_feats, n_best=None, length_penalty=0.
     group after another at every word; a word that earlier groups chose at that step costs a later group `diversity_penalty` per
     choice (inf: it is excluded).  The penalty steers the choice only: scores stay log-prob / len^length_penalty, and the n best
     are ranked over all groups together.  One `beam_select_groups` launch per step; num_groups = 1 launches what it always did."""
-    dec = model.decoder
-    k, L = dec.beam_size if beam_size is None else beam_size, dec.max_words
-    n = check_nbest_options(k, L, n_best, length_penalty, no_repeat_ngram, min_len, num_groups, diversity_penalty)
-    mems, sv, seed, _ = _encode(model, visual_feats, region_feats)
-    ops = model.ops
-    advance, B, R, _ = _beam_setup(model, mems, sv, seed, k)
-    end = dec.vocab('<end>')
-    dev = mems[0].device
-    preds = torch.empty(2, R, dtype=torch.int64, device=dev)       # ping-pong: the history keeps the tokens
-    hist = torch.empty(2, R, L, dtype=torch.int64, device=dev)     # filled by step 0
-    back = torch.empty(R, dtype=torch.int64, device=dev)
-    rows = torch.empty(R, dtype=torch.int64, device=dev)
-    lps = torch.zeros(2, R, dtype=torch.float32, device=dev)
-    words = torch.full((R,), dec.vocab('<start>'), dtype=torch.int64, device=dev)
-    for t in range(L):
-        logits = advance(t, words, rows)
-        if num_groups == 1:
-            ops.beam_select_hist(logits, words, lps[t % 2], preds[t % 2], lps[(t + 1) % 2], back, rows, k, end, hist[t % 2],
-                                 hist[(t + 1) % 2], t, no_repeat_ngram, min_len)
-        else:
-            ops.beam_select_groups([logits], [1.0], 0, words, lps[t % 2], preds[t % 2], lps[(t + 1) % 2], back, rows, k, end,
-                                   hist[t % 2], hist[(t + 1) % 2], t, no_repeat_ngram, min_len, num_groups, float(diversity_penalty))
-        words = preds[t % 2]
-    ids = torch.empty(B, n, L, dtype=torch.int64, device=dev)
-    scores = torch.empty(B, n, dtype=torch.float32, device=dev)
-    lens = torch.empty(B, n, dtype=torch.int64, device=dev)
-    ops.beam_finalize(hist[L % 2], lps[L % 2], k, end, float(length_penalty), ids, scores, lens)
-    return ids, scores, lens
+    return _nbest_search([model], None, 0, visual_feats, region_feats, n_best, length_penalty, no_repeat_ngram, min_len, beam_size,
+                         num_groups, diversity_penalty)
 
 
 @torch.no_grad()
@@ -229,37 +243,8 @@ def ensemble_nbest(models, weights, mode, visual_feats, region_feats, n_best=Non
     weighted mean log-probability -- and chooses the beams.  One set of preds / hist / back / rows / lps; no host synchronisation.
     The members share vocabulary, max_words and device (`ensemble.Ensemble` checks that); beam_size defaults to the first member's.
     num_groups, diversity_penalty: diverse beam search as in `beam_nbest`, on the combined values (`beam_select_groups`)."""
-    dec = models[0].decoder
-    k, L = dec.beam_size if beam_size is None else beam_size, dec.max_words
-    n = check_nbest_options(k, L, n_best, length_penalty, no_repeat_ngram, min_len, num_groups, diversity_penalty)
-    steps = []
-    for model in models:
-        mems, sv, seed, _ = _encode(model, visual_feats, region_feats)
-        advance, B, R, _ = _beam_setup(model, mems, sv, seed, k)
-        steps.append(advance)
-    ops = models[0].ops
-    end = dec.vocab('<end>')
-    dev = mems[0].device
-    preds = torch.empty(2, R, dtype=torch.int64, device=dev)
-    hist = torch.empty(2, R, L, dtype=torch.int64, device=dev)
-    back = torch.empty(R, dtype=torch.int64, device=dev)
-    rows = torch.empty(R, dtype=torch.int64, device=dev)
-    lps = torch.zeros(2, R, dtype=torch.float32, device=dev)
-    words = torch.full((R,), dec.vocab('<start>'), dtype=torch.int64, device=dev)
-    for t in range(L):
-        logits = [advance(t, words, rows) for advance in steps]
-        if num_groups == 1:
-            ops.beam_select_ens(logits, weights, mode, words, lps[t % 2], preds[t % 2], lps[(t + 1) % 2], back, rows, k, end,
-                                hist[t % 2], hist[(t + 1) % 2], t, no_repeat_ngram, min_len)
-        else:
-            ops.beam_select_groups(logits, weights, mode, words, lps[t % 2], preds[t % 2], lps[(t + 1) % 2], back, rows, k, end,
-                                   hist[t % 2], hist[(t + 1) % 2], t, no_repeat_ngram, min_len, num_groups, float(diversity_penalty))
-        words = preds[t % 2]
-    ids = torch.empty(B, n, L, dtype=torch.int64, device=dev)
-    scores = torch.empty(B, n, dtype=torch.float32, device=dev)
-    lens = torch.empty(B, n, dtype=torch.int64, device=dev)
-    ops.beam_finalize(hist[L % 2], lps[L % 2], k, end, float(length_penalty), ids, scores, lens)
-    return ids, scores, lens
+    return _nbest_search(models, weights, mode, visual_feats, region_feats, n_best, length_penalty, no_repeat_ngram, min_len, beam_size,
+                         num_groups, diversity_penalty)
 
 
 def beam_search(model, visual_feats, region_feats, beam_size=None, **options):

@@ -520,14 +520,36 @@ class HipOps(object):
         return parts
 
     # ------------------------------------------------------------------ beam search
-    def beam_select(self, logits, last, last_lp, pred, new_lp, back, rows, k, end, first=False, ended_count=None):
-        """one beam-search step for every batch item (see include/dlsg.h): logits (B*k,V) -> pred/new_lp/back/rows (B*k)."""
+    @staticmethod
+    def _beam_args(R, V, last, last_lp, pred, new_lp, back, rows, k, end, first, ended_count, logits=None, hist=()):
+        """dlsg_beam_select_args of one step on R = B*k rows; logits: the one model's (R, V) rows (an ensemble passes its own);
+        hist: the step's two (R, L) history buffers, which are checked"""
+        for h in hist:
+            assert h.dtype == torch.int64 and h.is_contiguous() and h.shape == (R, hist[1].shape[1]), (h.dtype, h.shape)
         a = abi.dlsg_beam_select_args()
-        R, V = logits.shape
-        a.logits, a.ld = _p(logits), logits.stride(0)
+        if logits is not None:
+            a.logits, a.ld = _p(logits), logits.stride(0)
         a.last, a.last_lp = _p(last), _p(last_lp)
         a.pred, a.new_lp, a.back, a.rows, a.ended_count = _p(pred), _p(new_lp), _p(back), _p(rows), _p(ended_count)
         a.B, a.k, a.V, a.end, a.first = R // k, k, V, end, int(first)
+        return a
+
+    @staticmethod
+    def _beam_members(logits_list, weights, device):
+        """checks the members' (R, V) logits -> R, V and the ctypes arguments (pointers, strides, weights normalised in float64,
+        their logs, M) of dlsg_beam_select_ens / _groups"""
+        M = len(logits_list)
+        R, V = logits_list[0].shape
+        for x in logits_list:
+            assert x.dtype == torch.float32 and x.shape == (R, V) and x.stride(1) == 1 and x.device == device, (x.dtype, x.shape)
+        assert len(weights) == M, (len(weights), M)
+        w = normalised_weights(weights)
+        return R, V, ((C.c_void_p * M)(*[x.data_ptr() for x in logits_list]), (C.c_int64 * M)(*[x.stride(0) for x in logits_list]),
+                      (C.c_float * M)(*w), (C.c_float * M)(*[math.log(x) for x in w]), M)
+
+    def beam_select(self, logits, last, last_lp, pred, new_lp, back, rows, k, end, first=False, ended_count=None):
+        """one beam-search step for every batch item (see include/dlsg.h): logits (B*k,V) -> pred/new_lp/back/rows (B*k)."""
+        a = self._beam_args(*logits.shape, last, last_lp, pred, new_lp, back, rows, k, end, first, ended_count, logits)
         self._check(self.lib.dlsg_beam_select(C.byref(a), self._stream()), 'dlsg_beam_select')
 
     def beam_select_hist(self, logits, last, last_lp, pred, new_lp, back, rows, k, end, hist_in, hist_out, t, no_repeat_ngram=0,
@@ -535,41 +557,19 @@ class HipOps(object):
         """`beam_select` at step t (t == 0 is the first step) with the beams' token history: hist_out[c] = hist_in[parent of c]
         with hist[t] = pred and `end` behind it ((B*k, L) int64, two buffers), a repeated-n-gram ban and a minimum length (see
         include/dlsg.h)."""
-        a = abi.dlsg_beam_select_args()
         R, V = logits.shape
-        L = hist_out.shape[1]
-        for h in (hist_in, hist_out):
-            assert h.dtype == torch.int64 and h.is_contiguous() and h.shape == (R, L), (h.dtype, h.shape)
-        a.logits, a.ld = _p(logits), logits.stride(0)
-        a.last, a.last_lp = _p(last), _p(last_lp)
-        a.pred, a.new_lp, a.back, a.rows, a.ended_count = _p(pred), _p(new_lp), _p(back), _p(rows), _p(ended_count)
-        a.B, a.k, a.V, a.end, a.first = R // k, k, V, end, int(t == 0)
-        self._check(self.lib.dlsg_beam_select_hist(C.byref(a), _p(hist_in), _p(hist_out), L, int(t), int(no_repeat_ngram), int(min_len),
-                                                   self._stream()), 'dlsg_beam_select_hist')
+        a = self._beam_args(R, V, last, last_lp, pred, new_lp, back, rows, k, end, t == 0, ended_count, logits, (hist_in, hist_out))
+        self._check(self.lib.dlsg_beam_select_hist(C.byref(a), _p(hist_in), _p(hist_out), hist_out.shape[1], int(t), int(no_repeat_ngram),
+                                                   int(min_len), self._stream()), 'dlsg_beam_select_hist')
 
     def beam_select_ens(self, logits_list, weights, mode, last, last_lp, pred, new_lp, back, rows, k, end, hist_in, hist_out, t,
                         no_repeat_ngram=0, min_len=0, ended_count=None):
         """`beam_select_hist` for an ensemble: the candidates of beam row r are combined from logits_list[m][r], one (R, V) float32
         array per member, with `weights` (positive, normalised here in float64) -- mode 0: log of the weighted mean probability,
         mode 1: weighted mean log-probability (see include/dlsg.h)."""
-        a = abi.dlsg_beam_select_args()
-        M = len(logits_list)
-        R, V = logits_list[0].shape
-        L = hist_out.shape[1]
-        for h in (hist_in, hist_out):
-            assert h.dtype == torch.int64 and h.is_contiguous() and h.shape == (R, L), (h.dtype, h.shape)
-        for x in logits_list:
-            assert x.dtype == torch.float32 and x.shape == (R, V) and x.stride(1) == 1 and x.device == hist_out.device, (x.dtype, x.shape)
-        assert len(weights) == M, (len(weights), M)
-        w = normalised_weights(weights)
-        a.last, a.last_lp = _p(last), _p(last_lp)
-        a.pred, a.new_lp, a.back, a.rows, a.ended_count = _p(pred), _p(new_lp), _p(back), _p(rows), _p(ended_count)
-        a.B, a.k, a.V, a.end, a.first = R // k, k, V, end, int(t == 0)
-        ptrs = (C.c_void_p * M)(*[x.data_ptr() for x in logits_list])
-        lds = (C.c_int64 * M)(*[x.stride(0) for x in logits_list])
-        ws = (C.c_float * M)(*w)
-        logws = (C.c_float * M)(*[math.log(x) for x in w])
-        self._check(self.lib.dlsg_beam_select_ens(C.byref(a), ptrs, lds, ws, logws, M, int(mode), _p(hist_in), _p(hist_out), L, int(t),
+        R, V, members = self._beam_members(logits_list, weights, hist_out.device)
+        a = self._beam_args(R, V, last, last_lp, pred, new_lp, back, rows, k, end, t == 0, ended_count, hist=(hist_in, hist_out))
+        self._check(self.lib.dlsg_beam_select_ens(C.byref(a), *members, int(mode), _p(hist_in), _p(hist_out), hist_out.shape[1], int(t),
                                                   int(no_repeat_ngram), int(min_len), self._stream()), 'dlsg_beam_select_ens')
 
     def beam_select_groups(self, logits_list, weights, mode, last, last_lp, pred, new_lp, back, rows, k, end, hist_in, hist_out, t,
@@ -578,26 +578,11 @@ class HipOps(object):
         group after another; a word that earlier groups chose at this step from live beams costs a later group
         `diversity_penalty` per choice (inf: it is excluded).  new_lp stays the log-prob without the penalty (see include/dlsg.h).
         A single model passes one logits array and weights [1.0]."""
-        a = abi.dlsg_beam_select_args()
-        M = len(logits_list)
-        R, V = logits_list[0].shape
-        L = hist_out.shape[1]
-        for h in (hist_in, hist_out):
-            assert h.dtype == torch.int64 and h.is_contiguous() and h.shape == (R, L), (h.dtype, h.shape)
-        for x in logits_list:
-            assert x.dtype == torch.float32 and x.shape == (R, V) and x.stride(1) == 1 and x.device == hist_out.device, (x.dtype, x.shape)
-        assert len(weights) == M, (len(weights), M)
-        w = normalised_weights(weights)
-        a.last, a.last_lp = _p(last), _p(last_lp)
-        a.pred, a.new_lp, a.back, a.rows, a.ended_count = _p(pred), _p(new_lp), _p(back), _p(rows), _p(ended_count)
-        a.B, a.k, a.V, a.end, a.first = R // k, k, V, end, int(t == 0)
-        ptrs = (C.c_void_p * M)(*[x.data_ptr() for x in logits_list])
-        lds = (C.c_int64 * M)(*[x.stride(0) for x in logits_list])
-        ws = (C.c_float * M)(*w)
-        logws = (C.c_float * M)(*[math.log(x) for x in w])
-        self._check(self.lib.dlsg_beam_select_groups(C.byref(a), ptrs, lds, ws, logws, M, int(mode), _p(hist_in), _p(hist_out), L, int(t),
-                                                     int(no_repeat_ngram), int(min_len), int(num_groups), C.c_float(diversity_penalty),
-                                                     self._stream()), 'dlsg_beam_select_groups')
+        R, V, members = self._beam_members(logits_list, weights, hist_out.device)
+        a = self._beam_args(R, V, last, last_lp, pred, new_lp, back, rows, k, end, t == 0, ended_count, hist=(hist_in, hist_out))
+        self._check(self.lib.dlsg_beam_select_groups(C.byref(a), *members, int(mode), _p(hist_in), _p(hist_out), hist_out.shape[1],
+                                                     int(t), int(no_repeat_ngram), int(min_len), int(num_groups),
+                                                     C.c_float(diversity_penalty), self._stream()), 'dlsg_beam_select_groups')
 
     def beam_finalize(self, hist, lp, k, end, alpha, ids, scores, lens):
         """the n = ids.shape[1] best of each clip's k beams by lp / len^alpha: ids (B, n, L), scores (B, n), lens (B, n)."""
