@@ -1,10 +1,11 @@
 // Row-wise / pointwise kernels of the D-LSG hot path (gfx950): tanh+LayerNorm(+PE)(+dropout) forward/backward,
-// strided softmax, LSTM cell pointwise, embedding gather/scatter, argmax, ragged cross entropy, Adam.
+// strided softmax, LSTM cell pointwise, embedding gather/scatter, ragged cross entropy, Adam.
 // All are HBM/L2-bound streaming kernels: one pass over the row held in registers, float4 where aligned.
 #include <type_traits>
 
 #include "common.hpp"
 #include "dlsg.h"
+#include "wordpick.hpp"
 
 using namespace dlsg;
 
@@ -527,12 +528,7 @@ __global__ void embed_fwd_kernel(const float* __restrict__ E, const int64_t* __r
                                  int64_t ldo, int W, float p, uint64_t seed, uint32_t site, int64_t row0, const uint64_t* seed_ptr) {
     if (seed_ptr) seed += *seed_ptr;
     const int r = blockIdx.x;
-    const int64_t id = ids[r];
-    for (int j = threadIdx.x; j < W; j += blockDim.x) {
-        float v = E[id * W + j];
-        if (p > 0.f) v *= drop_scale(seed, site, (uint64_t)(row0 + r) * W + j, p);
-        out[(int64_t)r * ldo + j] = v;
-    }
+    embed_row(E, ids[r], out, ldo, W, r, p, seed, site, row0, blockDim.x);
 }
 // dE[ids[r], :] += drop(dout[r, :]) without atomics, so that a step is bit-reproducible (float atomics add in arrival order:
 // the word-embedding gradient differed in the last bit between runs of the same step).  One wave per row.  The first row that
@@ -594,159 +590,6 @@ __global__ __launch_bounds__(1024) void embed_bwd_kernel(const float* __restrict
             }
         }
         if (j < W) dE[id * W + j] += acc;
-    }
-}
-
-// first maximum wins (torch.max / argmax tie rule on CPU and GPU for exact ties: lowest index)
-__global__ __launch_bounds__(256) void argmax_kernel(const float* __restrict__ logits, int64_t ld, int64_t* __restrict__ ids,
-                                                     int V) {
-    __shared__ float bv[4];
-    __shared__ int bi[4];
-    const int r = blockIdx.x;
-    const float* x = logits + (int64_t)r * ld;
-    float best = -INFINITY;
-    int idx = 0x7fffffff;
-    for (int j = threadIdx.x; j < V; j += blockDim.x) {
-        const float v = x[j];
-        if (v > best || (v == best && j < idx)) { best = v; idx = j; }
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const float ov = __shfl_xor(best, o, 64);
-        const int oi = __shfl_xor(idx, o, 64);
-        if (ov > best || (ov == best && oi < idx)) { best = ov; idx = oi; }
-    }
-    const int w = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) { bv[w] = best; bi[w] = idx; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int k = 1; k < 4; ++k)
-            if (bv[k] > best || (bv[k] == best && bi[k] < idx)) { best = bv[k]; idx = bi[k]; }
-        ids[r] = idx == 0x7fffffff ? 0 : idx;            // no maximum (a row of NaN / -inf): 0, as torch.argmax gives for -inf rows
-    }
-}
-
-// scheduled sampling select + embedding gather: one block per batch row
-__global__ __launch_bounds__(256) void select_embed_kernel(const float* __restrict__ logits, int64_t ld, int V,
-                                                           const int64_t* __restrict__ captions, int L, int t,
-                                                           const int32_t* __restrict__ coins, const float* __restrict__ E,
-                                                           int64_t* __restrict__ ids_out, float* __restrict__ out,
-                                                           int64_t ldo, int W, float p, uint64_t seed, uint32_t site,
-                                                           int64_t row0, const uint64_t* seed_ptr, int prefilled) {
-    __shared__ float bv[4];
-    __shared__ int bi[4];
-    __shared__ int64_t chosen;
-    if (prefilled && coins[t] != 0) return;      // teacher-forced step whose word the caller embedded up front: nothing to do
-    if (seed_ptr) seed += *seed_ptr;
-    const int r = blockIdx.x;
-    if (coins[t] != 0) {
-        if (threadIdx.x == 0) chosen = captions[(int64_t)r * L + t];
-    } else {
-        const float* x = logits + (int64_t)r * ld;
-        float best = -INFINITY;
-        int idx = 0x7fffffff;
-        for (int j = threadIdx.x; j < V; j += blockDim.x) {
-            const float v = x[j];
-            if (v > best || (v == best && j < idx)) { best = v; idx = j; }
-        }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            const float ov = __shfl_xor(best, o, 64);
-            const int oi = __shfl_xor(idx, o, 64);
-            if (ov > best || (ov == best && oi < idx)) { best = ov; idx = oi; }
-        }
-        const int w = threadIdx.x >> 6;
-        if ((threadIdx.x & 63) == 0) { bv[w] = best; bi[w] = idx; }
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            for (int k = 1; k < 4; ++k)
-                if (bv[k] > best || (bv[k] == best && bi[k] < idx)) { best = bv[k]; idx = bi[k]; }
-            chosen = idx == 0x7fffffff ? 0 : idx;        // no maximum (a row of NaN / -inf): word 0, not an out-of-range row of E
-        }
-    }
-    __syncthreads();
-    const int64_t id = chosen;
-    if (threadIdx.x == 0) ids_out[r] = id;
-    for (int j = threadIdx.x; j < W; j += blockDim.x) {
-        float v = E[id * W + j];
-        if (p > 0.f) v *= drop_scale(seed, site, (uint64_t)(row0 + r) * W + j, p);
-        out[(int64_t)r * ldo + j] = v;
-    }
-}
-
-// (m, s) of an online log-sum-exp merged with (om, os); an empty side (max -inf) contributes nothing
-__device__ __forceinline__ void lse_merge(float& m, float& s, float om, float os) {
-    const float nm = fmaxf(m, om);
-    s = (m == -INFINITY ? 0.f : s * __expf(m - nm)) + (om == -INFINITY ? 0.f : os * __expf(om - nm));
-    m = nm;
-}
-
-// sampled word step (self-critical training): id = argmax_j (x_j / tau + g_j) with Gumbel noise g_j = -log(-log u_j), u_j from
-// the counter hash keyed (seed, site_sample, (row0 + r) * V + j) -- one pass over the row, the same word whatever the reduction
-// order (a replayed graph draws what the eager launch drew).  The same pass keeps an online max / sum-exp of x / tau for
-// logp[r] = log softmax(x / tau)[id].  tau == 0: argmax_kernel's choice (first maximum), logp of the untempered softmax.  Then
-// the gather of E[id] under the word-dropout stream of embed_fwd / select_embed (row row0 + r), and lens[r] (L on entry)
-// becomes t + 1 at the row's first end_id.  One block of 256 per row.
-__global__ __launch_bounds__(256) void sample_embed_kernel(const float* __restrict__ logits, int64_t ld, int V, float tau,
-                                                           const float* __restrict__ E, int64_t* __restrict__ ids_out,
-                                                           float* __restrict__ out, int64_t ldo, int W, float* __restrict__ logp,
-                                                           int64_t* __restrict__ lens, int t, int64_t end_id, float p,
-                                                           uint64_t seed, uint32_t site_word, uint32_t site_sample, int64_t row0,
-                                                           const uint64_t* seed_ptr) {
-    __shared__ float bv[4], bm[4], bs[4];
-    __shared__ int bi[4];
-    __shared__ int64_t chosen;
-    if (seed_ptr) seed += *seed_ptr;
-    const int r = blockIdx.x;
-    const float* x = logits + (int64_t)r * ld;
-    const bool gumbel = tau > 0.f;
-    const float sc = gumbel ? 1.f / tau : 1.f;
-    const uint64_t key0 = (uint64_t)(row0 + r) * (uint64_t)V;
-    float best = -INFINITY, m = -INFINITY, s = 0.f;
-    int idx = 0x7fffffff;
-    for (int j = threadIdx.x; j < V; j += blockDim.x) {
-        const float z = x[j] * sc;
-        float key = z;
-        if (gumbel) {
-            // u = (hi + 1/2) 2^-24 in (0, 1).  hi + 1/2 needs 25 bits above 2^23: there -log u = -log1p(-(1 - u)) with
-            // 1 - u = (2^24 - 1 - hi + 1/2) 2^-24 exact, so u never rounds to 1 and the noise stays finite
-            const uint32_t hi = counter_hash(seed, site_sample, key0 + j) >> 8;
-            const float e = hi < (1u << 23) ? -logf(((float)hi + 0.5f) * (1.0f / 16777216.0f))
-                                            : -log1pf(-((float)(0xFFFFFFu - hi) + 0.5f) * (1.0f / 16777216.0f));
-            key = z - logf(e);                          // a -inf logit stays -inf: never drawn
-        }
-        if (key > best || (key == best && j < idx)) { best = key; idx = j; }
-        if (z > m) { s = s * __expf(m - z) + 1.f; m = z; }
-        else if (z > -INFINITY) s += __expf(z - m);
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const float ov = __shfl_xor(best, o, 64);
-        const int oi = __shfl_xor(idx, o, 64);
-        if (ov > best || (ov == best && oi < idx)) { best = ov; idx = oi; }
-        const float om = __shfl_xor(m, o, 64), os = __shfl_xor(s, o, 64);
-        lse_merge(m, s, om, os);
-    }
-    const int w = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) { bv[w] = best; bi[w] = idx; bm[w] = m; bs[w] = s; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int k = 1; k < 4; ++k) {
-            if (bv[k] > best || (bv[k] == best && bi[k] < idx)) { best = bv[k]; idx = bi[k]; }
-            lse_merge(m, s, bm[k], bs[k]);
-        }
-        const int64_t id = idx == 0x7fffffff ? 0 : idx;   // no maximum (a row of NaN / -inf): word 0, not an out-of-range row of E
-        chosen = id;
-        ids_out[r] = id;
-        logp[r] = x[id] * sc - m - logf(s);
-        if (id == end_id && lens[r] > t) lens[r] = t + 1;
-    }
-    __syncthreads();
-    const int64_t id = chosen;
-    for (int j = threadIdx.x; j < W; j += blockDim.x) {
-        float v = E[id * W + j];
-        if (p > 0.f) v *= drop_scale(seed, site_word, (uint64_t)(row0 + r) * W + j, p);
-        out[(int64_t)r * ldo + j] = v;
     }
 }
 
@@ -1213,32 +1056,6 @@ extern "C" int dlsg_embed_bwd(const float* dout, int64_t lddo, const int64_t* id
     const int threads = W >= 1024 ? 1024 : (W + 63) / 64 * 64;           // one wave per 64 columns
     hipLaunchKernelGGL(embed_bwd_kernel, dim3(rows), dim3(threads), 0, ST(stream), dout, lddo, ids, dE, rows, W, p, seed, site, row0,
                        seed_ptr);
-    DLSG_CHECK_LAUNCH();
-    return DLSG_OK;
-}
-extern "C" int dlsg_select_embed(const float* logits, int64_t ld, int V, const int64_t* captions, int L, int t,
-                                 const int32_t* coins, const float* E, int64_t* ids_out, float* out, int64_t ldo, int rows, int W,
-                                 float p, uint64_t seed, uint32_t site, int64_t row0, const uint64_t* seed_ptr, int prefilled,
-                                 void* stream) {
-    if (rows == 0) return DLSG_OK;
-    hipLaunchKernelGGL(select_embed_kernel, dim3(rows), dim3(256), 0, ST(stream), logits, ld, V, captions, L, t, coins, E, ids_out,
-                       out, ldo, W, p, seed, site, row0, seed_ptr, prefilled);
-    DLSG_CHECK_LAUNCH();
-    return DLSG_OK;
-}
-extern "C" int dlsg_sample_embed(const float* logits, int64_t ld, int V, float temperature, const float* E, int64_t* ids_out, float* out,
-                                 int64_t ldo, int W, float* logp, int64_t* lens, int t, int64_t end_id, int rows, float p, uint64_t seed,
-                                 uint32_t site_word, uint32_t site_sample, int64_t row0, const uint64_t* seed_ptr, void* stream) {
-    if (rows == 0) return DLSG_OK;
-    if (V < 1 || W < 0 || !(temperature >= 0.f)) return DLSG_EINVAL;
-    hipLaunchKernelGGL(sample_embed_kernel, dim3(rows), dim3(256), 0, ST(stream), logits, ld, V, temperature, E, ids_out, out, ldo, W,
-                       logp, lens, t, end_id, p, seed, site_word, site_sample, row0, seed_ptr);
-    DLSG_CHECK_LAUNCH();
-    return DLSG_OK;
-}
-extern "C" int dlsg_argmax(const float* logits, int64_t ld, int64_t* ids, int rows, int V, void* stream) {
-    if (rows == 0) return DLSG_OK;
-    hipLaunchKernelGGL(argmax_kernel, dim3(rows), dim3(256), 0, ST(stream), logits, ld, ids, V);
     DLSG_CHECK_LAUNCH();
     return DLSG_OK;
 }

@@ -1,14 +1,17 @@
-// Filtered sampled word step (gfx950): dlsg_sample_embed with a repeated-n-gram ban, a minimum length, top-k and nucleus (top-p)
-// truncation in front of the Gumbel-max draw.  One workgroup of 256 per row holds the row's tempered logits in LDS and finds the
-// two thresholds without sorting: a descent over an order-preserving uint32 image of the float, two bits per round, each
-// round one pass over the candidates still undecided and one fixed-order block reduction (an integer count for top-k, a float
-// mass for top-p).  No atomics anywhere: two launches, or an eager launch and a graph replay, give the same bits.
+// The kernels that choose the next word from a row of logits and write its embedding (gfx950), one workgroup of 256 per row, each
+// a composition of the phases of wordpick.hpp: dlsg_argmax (greedy), dlsg_select_embed (scheduled sampling: the caption's word or
+// the greedy one), dlsg_sample_embed (Gumbel-max draw with its log-prob) and dlsg_sample_filter_embed, the draw behind a
+// repeated-n-gram ban, a minimum length, top-k and nucleus (top-p) truncation.  The filtered step holds the row's tempered logits in
+// LDS and finds the two thresholds without sorting: a descent over an order-preserving uint32 image of the float, two bits per
+// round, each round one pass over the candidates still undecided and one fixed-order block reduction (an integer count for top-k,
+// a float mass for top-p).  No atomics anywhere: two launches, or an eager launch and a graph replay, give the same bits.
 #include <math.h>
 #include <mutex>
 
 #include "beam.hpp"
 #include "common.hpp"
 #include "dlsg.h"
+#include "wordpick.hpp"
 
 using namespace dlsg;
 
@@ -119,14 +122,68 @@ __device__ __forceinline__ uint32_t descend(float* zs, int& cnt, float m, int k,
     return T;
 }
 
-// (m, s) of an online log-sum-exp merged with (om, os), as in sample_embed_kernel
-__device__ __forceinline__ void lse_merge(float& m, float& s, float om, float os) {
-    const float nm = fmaxf(m, om);
-    s = (m == -INFINITY ? 0.f : s * __expf(m - nm)) + (om == -INFINITY ? 0.f : os * __expf(om - nm));
-    m = nm;
+// ids[r] = the row's first maximum
+__global__ __launch_bounds__(256) void argmax_kernel(const float* __restrict__ logits, int64_t ld, int64_t* __restrict__ ids,
+                                                     int V) {
+    __shared__ float bv[4];
+    __shared__ int bi[4];
+    const int r = blockIdx.x;
+    const int id = first_max_row(logits + (int64_t)r * ld, V, bv, bi);
+    if (threadIdx.x == 0) ids[r] = id;
 }
 
-// hist: the row's earlier words, time-major: word i of row r at hist[i * hist_stride + r], i < t.
+// scheduled sampling select + embedding gather: one block per batch row
+__global__ __launch_bounds__(256) void select_embed_kernel(const float* __restrict__ logits, int64_t ld, int V,
+                                                           const int64_t* __restrict__ captions, int L, int t,
+                                                           const int32_t* __restrict__ coins, const float* __restrict__ E,
+                                                           int64_t* __restrict__ ids_out, float* __restrict__ out,
+                                                           int64_t ldo, int W, float p, uint64_t seed, uint32_t site,
+                                                           int64_t row0, const uint64_t* seed_ptr, int prefilled) {
+    __shared__ float bv[4];
+    __shared__ int bi[4];
+    __shared__ int64_t chosen;
+    if (prefilled && coins[t] != 0) return;      // teacher-forced step whose word the caller embedded up front: nothing to do
+    if (seed_ptr) seed += *seed_ptr;
+    const int r = blockIdx.x;
+    if (coins[t] != 0) {
+        if (threadIdx.x == 0) chosen = captions[(int64_t)r * L + t];
+    } else {
+        const int id = first_max_row(logits + (int64_t)r * ld, V, bv, bi);
+        if (threadIdx.x == 0) chosen = id;
+    }
+    __syncthreads();
+    const int64_t id = chosen;
+    if (threadIdx.x == 0) ids_out[r] = id;
+    embed_row(E, id, out, ldo, W, r, p, seed, site, row0, blockDim.x);
+}
+
+// sampled word step (self-critical training): WordDraw (wordpick.hpp) over the whole row, then the gather of E[id] under the
+// word-dropout stream of embed_fwd / select_embed (row row0 + r).  One block of 256 per row.
+__global__ __launch_bounds__(256) void sample_embed_kernel(const float* __restrict__ logits, int64_t ld, int V, float tau,
+                                                           const float* __restrict__ E, int64_t* __restrict__ ids_out,
+                                                           float* __restrict__ out, int64_t ldo, int W, float* __restrict__ logp,
+                                                           int64_t* __restrict__ lens, int t, int64_t end_id, float p,
+                                                           uint64_t seed, uint32_t site_word, uint32_t site_sample, int64_t row0,
+                                                           const uint64_t* seed_ptr) {
+    __shared__ float bv[4], bm[4], bs[4];
+    __shared__ int bi[4];
+    __shared__ int64_t chosen;
+    if (seed_ptr) seed += *seed_ptr;
+    const int r = blockIdx.x;
+    const float* x = logits + (int64_t)r * ld;
+    WordDraw d(tau, seed, site_sample, row0 + r, V);
+    for (int j = threadIdx.x; j < V; j += blockDim.x) d.step<false>(j, x[j]);
+    d.wave();
+    const int64_t id = d.block(bv, bi, bm, bs);
+    if (threadIdx.x == 0) {
+        chosen = id;
+        d.commit(id, x, false, r, ids_out, logp, lens, t, end_id);
+    }
+    __syncthreads();
+    embed_row(E, chosen, out, ldo, W, r, p, seed, site_word, row0, blockDim.x);
+}
+
+// The filtered step.  hist: the row's earlier words, time-major: word i of row r at hist[i * hist_stride + r], i < t.
 __global__ __launch_bounds__(SF_THREADS) void sample_filter_embed_kernel(
     const float* __restrict__ logits, int64_t ld, int V, float tau, const float* __restrict__ E, int64_t* __restrict__ ids_out,
     float* __restrict__ out, int64_t ldo, int W, float* __restrict__ logp, int64_t* __restrict__ lens, int t, int64_t end_id, float p,
@@ -141,8 +198,7 @@ __global__ __launch_bounds__(SF_THREADS) void sample_filter_embed_kernel(
     if (seed_ptr) seed += *seed_ptr;
     const int r = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const float* x = logits + (int64_t)r * ld;
-    const bool gumbel = tau > 0.f;
-    const float sc = gumbel ? 1.f / tau : 1.f;
+    WordDraw d(tau, seed, site_sample, row0 + r, V);
     int par = 0;
 
     // ---- the classes this row may not choose: the beam search's rule (beam_ban_list, beam.hpp) on the row's own words
@@ -155,13 +211,13 @@ __global__ __launch_bounds__(SF_THREADS) void sample_filter_embed_kernel(
     // ---- thresholds.  A word is kept iff it is alive (finite, not banned) and ord_key(z) >= T.
     // alive(j, z): z_j = x_j / tau (+ 0: -0 becomes +0, so equal values have equal images), false for NaN, -inf and banned words
     auto alive = [&](int j, float& z) {
-        z = x[j] * sc + 0.f;
+        z = x[j] * d.sc + 0.f;
         bool dead = !(z > -INFINITY);
         for (int b = 0; b < nban; ++b) dead |= ban[b] == j;
         return !dead;
     };
     uint32_t T = 0;
-    if (gumbel && (top_k > 0 || top_p < 1.f)) {
+    if (d.gumbel && (top_k > 0 || top_p < 1.f)) {
         // stage the alive words as this thread's candidate list; the row's maximum and the number of alive words
         float m = -INFINITY;
         int cnt = 0;
@@ -200,62 +256,60 @@ __global__ __launch_bounds__(SF_THREADS) void sample_filter_embed_kernel(
         }
     }
 
-    // ---- the draw over the kept set, with sample_embed_kernel's noise and its online log-sum-exp
-    const uint64_t key0 = (uint64_t)(row0 + r) * (uint64_t)V;
-    float best = -INFINITY, m = -INFINITY, s = 0.f;
-    int idx = 0x7fffffff, nk = 0;
+    // ---- the draw over the kept words, counted
+    int nk = 0;
     for (int j = tid; j < V; j += SF_THREADS) {
-        float zl;
-        if (!alive(j, zl) || ord_key(zl) < T) continue;
+        float z;
+        if (!alive(j, z) || ord_key(z) < T) continue;
         ++nk;
-        // the arithmetic below is sample_embed_kernel's, statement for statement: whatever the compiler contracts there it
-        // contracts here, and the two kernels agree to the bit
-        const float z = x[j] * sc;
-        float key = z;
-        if (gumbel) {
-            const uint32_t hi = counter_hash(seed, site_sample, key0 + j) >> 8;
-            const float e = hi < (1u << 23) ? -logf(((float)hi + 0.5f) * (1.0f / 16777216.0f))
-                                            : -log1pf(-((float)(0xFFFFFFu - hi) + 0.5f) * (1.0f / 16777216.0f));
-            key = z - logf(e);
-        }
-        if (key > best || (key == best && j < idx)) { best = key; idx = j; }
-        if (z > m) { s = s * __expf(m - z) + 1.f; m = z; }
-        else s += __expf(z - m);
+        d.step<true>(j, x[j]);                               // (alive: finite)
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const float ov = __shfl_xor(best, o, 64);
-        const int oi = __shfl_xor(idx, o, 64);
-        if (ov > best || (ov == best && oi < idx)) { best = ov; idx = oi; }
-        const float om = __shfl_xor(m, o, 64), os = __shfl_xor(s, o, 64);
-        lse_merge(m, s, om, os);
-    }
+    d.wave();
     nk = wave_sum_i32(nk);
-    if (lane == 0) { bv[w] = best; bi[w] = idx; bm[w] = m; bs[w] = s; bn[w] = nk; }
-    __syncthreads();
+    if (lane == 0) bn[w] = nk;
+    const int64_t id = d.block(bv, bi, bm, bs);              // (nothing kept: word 0)
     if (tid == 0) {
-        for (int k = 1; k < 4; ++k) {
-            if (bv[k] > best || (bv[k] == best && bi[k] < idx)) { best = bv[k]; idx = bi[k]; }
-            lse_merge(m, s, bm[k], bs[k]);
-        }
-        const int64_t id = idx == 0x7fffffff ? 0 : idx;      // nothing to keep: word 0, as sample_embed_kernel
-        chosen = id;
-        ids_out[r] = id;
         const int nkept = (bn[0] + bn[1]) + (bn[2] + bn[3]);
-        logp[r] = nkept == 1 ? 0.f : x[id] * sc - m - logf(s);   // one word left: probability 1, whatever x * sc rounds to
+        chosen = id;
         if (kept) kept[r] = nkept;
-        if (id == end_id && lens[r] > t) lens[r] = t + 1;
+        d.commit(id, x, nkept == 1, r, ids_out, logp, lens, t, end_id);
     }
     __syncthreads();
-    const int64_t id = chosen;
-    for (int j = tid; j < W; j += SF_THREADS) {
-        float v = E[id * W + j];
-        if (p > 0.f) v *= drop_scale(seed, site_word, (uint64_t)(row0 + r) * W + j, p);
-        out[(int64_t)r * ldo + j] = v;
-    }
+    embed_row(E, chosen, out, ldo, W, r, p, seed, site_word, row0, SF_THREADS);
 }
 
+// what the two sampled steps ask of their common arguments
+bool sample_args_ok(int V, int W, float temperature) { return V >= 1 && W >= 0 && temperature >= 0.f; }
+#define ST(s) reinterpret_cast<hipStream_t>(s)
+
 }  // namespace
+
+extern "C" int dlsg_select_embed(const float* logits, int64_t ld, int V, const int64_t* captions, int L, int t,
+                                 const int32_t* coins, const float* E, int64_t* ids_out, float* out, int64_t ldo, int rows, int W,
+                                 float p, uint64_t seed, uint32_t site, int64_t row0, const uint64_t* seed_ptr, int prefilled,
+                                 void* stream) {
+    if (rows == 0) return DLSG_OK;
+    hipLaunchKernelGGL(select_embed_kernel, dim3(rows), dim3(256), 0, ST(stream), logits, ld, V, captions, L, t, coins, E, ids_out,
+                       out, ldo, W, p, seed, site, row0, seed_ptr, prefilled);
+    DLSG_CHECK_LAUNCH();
+    return DLSG_OK;
+}
+extern "C" int dlsg_sample_embed(const float* logits, int64_t ld, int V, float temperature, const float* E, int64_t* ids_out, float* out,
+                                 int64_t ldo, int W, float* logp, int64_t* lens, int t, int64_t end_id, int rows, float p, uint64_t seed,
+                                 uint32_t site_word, uint32_t site_sample, int64_t row0, const uint64_t* seed_ptr, void* stream) {
+    if (rows == 0) return DLSG_OK;
+    if (!sample_args_ok(V, W, temperature)) return DLSG_EINVAL;
+    hipLaunchKernelGGL(sample_embed_kernel, dim3(rows), dim3(256), 0, ST(stream), logits, ld, V, temperature, E, ids_out, out, ldo, W,
+                       logp, lens, t, end_id, p, seed, site_word, site_sample, row0, seed_ptr);
+    DLSG_CHECK_LAUNCH();
+    return DLSG_OK;
+}
+extern "C" int dlsg_argmax(const float* logits, int64_t ld, int64_t* ids, int rows, int V, void* stream) {
+    if (rows == 0) return DLSG_OK;
+    hipLaunchKernelGGL(argmax_kernel, dim3(rows), dim3(256), 0, ST(stream), logits, ld, ids, V);
+    DLSG_CHECK_LAUNCH();
+    return DLSG_OK;
+}
 
 extern "C" int dlsg_sample_filter_embed(const float* logits, int64_t ld, int V, float temperature, const float* E, int64_t* ids_out,
                                         float* out, int64_t ldo, int W, float* logp, int64_t* lens, int t, int64_t end_id, int rows,
@@ -263,7 +317,7 @@ extern "C" int dlsg_sample_filter_embed(const float* logits, int64_t ld, int V, 
                                         const uint64_t* seed_ptr, int top_k, float top_p, int min_len, int no_repeat_ngram,
                                         const int64_t* hist, int64_t hist_stride, int32_t* kept, void* stream) {
     if (rows == 0) return DLSG_OK;
-    if (V < 1 || V > DLSG_SAMPLE_FILTER_MAXV || W < 0 || !(temperature >= 0.f) || top_k < 0 || !(top_p > 0.f && top_p <= 1.f) ||
+    if (!sample_args_ok(V, W, temperature) || V > DLSG_SAMPLE_FILTER_MAXV || top_k < 0 || !(top_p > 0.f && top_p <= 1.f) ||
         min_len < 0 || no_repeat_ngram < 0 || t < 0 || t >= SF_MAXL || (no_repeat_ngram > 0 && t > 0 && (!hist || hist_stride < rows)))
         return DLSG_EINVAL;
     static std::once_flag once;
@@ -273,7 +327,7 @@ extern "C" int dlsg_sample_filter_embed(const float* logits, int64_t ld, int V, 
                                       hipFuncAttributeMaxDynamicSharedMemorySize, DLSG_SAMPLE_FILTER_MAXV * 4);
     });
     if (attr_rc != hipSuccess) return DLSG_ELAUNCH;
-    hipLaunchKernelGGL(sample_filter_embed_kernel, dim3(rows), dim3(SF_THREADS), (size_t)V * 4, reinterpret_cast<hipStream_t>(stream),
+    hipLaunchKernelGGL(sample_filter_embed_kernel, dim3(rows), dim3(SF_THREADS), (size_t)V * 4, ST(stream),
                        logits, ld, V, temperature, E, ids_out, out, ldo, W, logp, lens, t, end_id, p, seed, site_word, site_sample,
                        row0, seed_ptr, top_k, top_p, min_len, no_repeat_ngram, hist, hist_stride, kept);
     DLSG_CHECK_LAUNCH();

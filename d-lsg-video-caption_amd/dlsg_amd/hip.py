@@ -1087,18 +1087,25 @@ class HipOps(object):
         rows, V = logits.shape
         self._check(self.lib.dlsg_argmax(_p(logits), i64(logits.stride(0)), _p(ids), rows, V, self._stream()), 'argmax')
 
+    def _sample_args(self, logits, E, ids_out, out, logp, lens, t, end_id, temperature, p, seed, site, site_sample, row0):
+        """what `sample_embed` and `sample_filter_embed` ask of their common arguments, and the arguments their entry points
+        share (everything in front of the filter's controls)"""
+        rows, V = logits.shape
+        assert E.shape[0] >= V and E.is_contiguous() and ids_out.numel() == rows and logp.numel() == rows and lens.numel() == rows
+        assert ids_out.dtype == torch.int64 and lens.dtype == torch.int64 and out.shape == (rows, E.shape[1])
+        sd, sp = _seed(seed)
+        vp = C.c_void_p                                     # (none of the six is None)
+        return (vp(logits.data_ptr()), i64(logits.stride(0)), V, f32(temperature), vp(E.data_ptr()), vp(ids_out.data_ptr()),
+                vp(out.data_ptr()), i64(out.stride(0)), out.shape[1], vp(logp.data_ptr()), vp(lens.data_ptr()), int(t), i64(end_id),
+                rows, f32(p), u64(sd), u32(site), u32(site_sample), i64(row0), sp)
+
     def sample_embed(self, logits, E, ids_out, out, logp, lens, t, end_id, temperature=1.0, p=0.0, seed=0, site=0, site_sample=0,
                      row0=0):
         """ids_out[r] ~ softmax(logits[r] / temperature) (Gumbel-max on the (seed, site_sample, row0 + r) noise; 0: argmax),
         logp[r] = its log-probability, out[r] = drop(E[id]) on the word-dropout rows row0 + r, lens[r] = t + 1 at the first end_id
         (the caller sets lens to L)."""
-        rows, V = logits.shape
-        assert E.shape[0] >= V and E.is_contiguous() and ids_out.numel() == rows and logp.numel() == rows and lens.numel() == rows
-        assert ids_out.dtype == torch.int64 and lens.dtype == torch.int64 and out.shape == (rows, E.shape[1])
-        sd, sp = _seed(seed)
-        self._check(self.lib.dlsg_sample_embed(_p(logits), i64(logits.stride(0)), V, f32(temperature), _p(E), _p(ids_out), _p(out),
-                                               i64(out.stride(0)), out.shape[1], _p(logp), _p(lens), int(t), i64(end_id), rows, f32(p),
-                                               u64(sd), u32(site), u32(site_sample), i64(row0), sp, self._stream()), 'sample_embed')
+        args = self._sample_args(logits, E, ids_out, out, logp, lens, t, end_id, temperature, p, seed, site, site_sample, row0)
+        self._check(self.lib.dlsg_sample_embed(*args, self._stream()), 'sample_embed')
 
     def sample_filter_embed(self, logits, E, ids_out, out, logp, lens, t, end_id, temperature=1.0, p=0.0, seed=0, site=0, site_sample=0,
                             row0=0, top_k=0, top_p=1.0, min_len=0, no_repeat_ngram=0, hist=None, kept=None):
@@ -1109,17 +1116,13 @@ class HipOps(object):
         rows, V = logits.shape
         if V > SAMPLE_FILTER_MAXV:
             raise ValueError('sample_filter_embed holds a row of logits in LDS: vocabulary %d > %d' % (V, SAMPLE_FILTER_MAXV))
-        assert E.shape[0] >= V and E.is_contiguous() and ids_out.numel() == rows and logp.numel() == rows and lens.numel() == rows
-        assert ids_out.dtype == torch.int64 and lens.dtype == torch.int64 and out.shape == (rows, E.shape[1])
+        args = self._sample_args(logits, E, ids_out, out, logp, lens, t, end_id, temperature, p, seed, site, site_sample, row0)
         assert kept is None or (kept.dtype == torch.int32 and kept.numel() == rows and kept.is_contiguous())
         if no_repeat_ngram > 0 and t > 0:
             assert hist is not None and hist.dtype == torch.int64 and hist.shape[0] >= t and hist.shape[1] == rows and \
                 hist.stride(1) == 1, 'hist: the rows\' earlier words, (>= t, rows) int64'
-        sd, sp = _seed(seed)
         self._check(self.lib.dlsg_sample_filter_embed(
-            _p(logits), i64(logits.stride(0)), V, f32(temperature), _p(E), _p(ids_out), _p(out), i64(out.stride(0)), out.shape[1],
-            _p(logp), _p(lens), int(t), i64(end_id), rows, f32(p), u64(sd), u32(site), u32(site_sample), i64(row0), sp, int(top_k),
-            f32(top_p), int(min_len), int(no_repeat_ngram), _p(hist) if hist is not None else None,
+            *args, int(top_k), f32(top_p), int(min_len), int(no_repeat_ngram), _p(hist) if hist is not None else None,
             i64(hist.stride(0) if hist is not None else 0), _p(kept) if kept is not None else None, self._stream()),
             'sample_filter_embed')
 
