@@ -4,6 +4,8 @@
 // launch and on graph replay.
 #include <math.h>
 
+#include <mutex>
+
 #include "common.hpp"
 #include "dlsg.h"
 
@@ -181,6 +183,225 @@ __global__ __launch_bounds__(256) void scst_advantage_kernel(const double* __res
     }
 }
 
+// lane `j`'s value of v, j wave-uniform: two v_readlane, no trip through the LDS crossbar (unlike __shfl with a register index)
+__device__ __forceinline__ uint64_t lane_u64(uint64_t v, int j) {
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, j);
+    const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(v >> 32), j);
+    return (uint64_t)hi << 32 | lo;
+}
+__device__ __forceinline__ double lane_f64(double v, int j) { return __longlong_as_double((long long)lane_u64((uint64_t)__double_as_longlong(v), j)); }
+
+// find_key for NQ keys in lockstep (n >= 1): the halving lower bound probes at a sequence of lengths that is the same for every
+// key, so the NQ loads of a step do not depend on one another and are in flight together; reads only inside [0, n)
+template <int NQ>
+__device__ __forceinline__ void find_keys(const uint64_t* keys, int64_t n, const uint64_t (&key)[NQ], int64_t (&pos)[NQ]) {
+    int64_t base[NQ];
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) base[q] = 0;
+    for (int64_t len = n; len > 1;) {
+        const int64_t half = len >> 1;
+#pragma unroll
+        for (int q = 0; q < NQ; ++q) base[q] += keys[base[q] + half] < key[q] ? half : 0;
+        len -= half;
+    }
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) {
+        const int64_t p = base[q] + (keys[base[q]] < key[q] ? 1 : 0);
+        pos[q] = p < n && keys[p] == key[q] ? p : -1;
+    }
+}
+
+constexpr int CONS_MAXN = 32;           // candidates per clip: 32 x 4 orders x 64 positions x 16 B = 128 KiB of staged vectors
+
+// dynamic LDS of cider_consensus_kernel for n candidates: keys and weights [n][4][64], norms and per-order sums [n][4], weight,
+// utility row and expected utility [n], length [n]; every carve offset is a multiple of 8, the total of 16
+constexpr int cons_lds_bytes(int n) { return (n * (4 * CIDER_MAXL * 16 + 4 * 8 * 2 + 3 * 8 + 4) + 15) & ~15; }
+
+// One workgroup per clip, its n candidates' tf-idf vectors staged in LDS.
+// Phase A, per candidate: cider_d_kernel's row front end -- lane i of wave k holds the order-(k + 1) n-gram at position i, its
+// count, whether this is its first position -- then the candidate's (key, count) entries, one per position (0 away from a first
+// position), and its length go to LDS; the counts become weights by a bisection for the idf in the corpus table, the entries
+// dealt over all threads; wave k sums the candidates' order-(k + 1) norms.  An id outside [0, vocab) is the word
+// 0xFFFF here as well, but it MATCHES itself (within the candidate and across candidates): only the corpus lookup is left out
+// for a key that holds it (a key with 0xFFFF in a used slot may equal a shorter n-gram's key, and keys are compared within one
+// order only).
+// Phase B, per ordered pair (i, j): the lane holding position p of i scans j's entries of its order (one LDS read per lane, then
+// at most 64 lane reads) for its key; min(w_i, w_j) w_j is summed over the wave by a butterfly; thread j folds the orders
+// (norms, length penalty, x10 / n) into U[i][j]; thread 0 forms i's expected utility over j != i in index order.  Ranks are
+// counted at the end.
+__global__ __launch_bounds__(CIDER_THREADS) void cider_consensus_kernel(const int64_t* __restrict__ ids, int64_t ld, int n, int L,
+                                                                        int64_t end_id, const dlsg_cider_tables t,
+                                                                        const float* __restrict__ scores, double temperature,
+                                                                        double* __restrict__ util, double* __restrict__ expected,
+                                                                        int64_t* __restrict__ order) {
+    extern __shared__ __attribute__((aligned(16))) char cons_smem[];
+    uint64_t* skey = reinterpret_cast<uint64_t*>(cons_smem);
+    double* sw = reinterpret_cast<double*>(skey + n * 4 * CIDER_MAXL);
+    double* snorm = sw + n * 4 * CIDER_MAXL;
+    double* stot = snorm + n * 4;
+    double* sq = stot + n * 4;                                // weight of a candidate; -1: invalid
+    double* surow = sq + n;
+    double* sexp = surow + n;
+    int* slen = reinterpret_cast<int*>(sexp + n);
+    const int b = blockIdx.x;
+    const int lane = threadIdx.x & 63, k = threadIdx.x >> 6;
+    const int no = t.n;
+    const bool live = k < no;                                 // wave-uniform
+
+    int64_t next = lane < L ? ids[(int64_t)b * n * ld + lane] : end_id;
+    for (int c = 0; c < n; ++c) {
+        const int64_t id = next;                              // (the next candidate's words are on their way meanwhile)
+        if (c + 1 < n && lane < L) next = ids[((int64_t)b * n + c + 1) * ld + lane];
+        const unsigned long long ends = __ballot(lane >= L || id == end_id);
+        const int len = ends ? __builtin_ctzll(ends) : CIDER_MAXL;
+        const bool bad = id < 0 || id >= t.vocab;             // one word outside the vocabulary: never indexes a table
+        const uint32_t w = bad ? CIDER_NONE : (uint32_t)id;
+        uint64_t key = 0;
+        bool kbad = false;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const uint32_t wj = (uint32_t)__shfl((int)w, (lane + j) & 63, 64);
+            const int bj = __shfl((int)bad, (lane + j) & 63, 64);
+            const bool used = j <= k;
+            key |= (uint64_t)(used ? wj : CIDER_NONE) << (16 * j);
+            kbad |= used && bj;
+        }
+        const bool active = live && lane + k < len;
+        int tf = 0;
+        bool first = active;
+        for (int j = 0; j < CIDER_MAXL; ++j) {
+            const uint64_t kj = lane_u64(key, j);
+            if (j + k < len && kj == key) {
+                ++tf;
+                if (j < lane) first = false;
+            }
+        }
+        if (live) {                                           // the count for now; negative: no corpus lookup for this key
+            skey[(c * 4 + k) * CIDER_MAXL + lane] = key;
+            sw[(c * 4 + k) * CIDER_MAXL + lane] = first ? (kbad ? -(double)tf : (double)tf) : 0.0;
+        }
+        if (threadIdx.x == 0) slen[c] = len;
+    }
+    __syncthreads();
+    // The idf lookups, dealt round-robin over the 256 threads, four to a thread at a time: captions are short, so a
+    // lane-per-position bisection per candidate would leave most lanes idle through n dependent chains of global loads; over the
+    // (candidate, order, position < longest caption) entries they are a few rounds.
+    int maxlen = 0;
+    for (int c = 0; c < n; ++c) maxlen = max(maxlen, slen[c]);
+    const int total = n * no * maxlen;
+    for (int e0 = threadIdx.x; e0 < total; e0 += 4 * CIDER_THREADS) {
+        int at[4];
+        double tf[4];
+        uint64_t key[4];
+        int64_t pos[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int e = e0 + q * CIDER_THREADS;
+            at[q] = 0;
+            tf[q] = 0.0;
+            if (e < total) {
+                const int c = e / (no * maxlen), r = e - c * (no * maxlen);
+                at[q] = (c * 4 + r / maxlen) * CIDER_MAXL + r % maxlen;
+                tf[q] = sw[at[q]];
+            }
+            key[q] = skey[at[q]];
+            pos[q] = -1;
+        }
+        if (t.n_grams > 0) find_keys<4>(t.gram_keys, t.n_grams, key, pos);
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            if (tf[q] == 0.0) continue;
+            double idf = t.log_n;                             // not in the corpus, or with the outside word: df = 0
+            if (tf[q] > 0.0 && pos[q] >= 0) idf = t.gram_idf[pos[q]];
+            sw[at[q]] = fabs(tf[q]) * idf;
+        }
+    }
+    __syncthreads();
+    if (live) {
+        for (int c = 0; c < n; ++c) {
+            const double wh = sw[(c * 4 + k) * CIDER_MAXL + lane];
+            const double nh = sqrt(wave_sum_f64(wh * wh));
+            if (lane == 0) snorm[c * 4 + k] = nh;
+        }
+    }
+    if (threadIdx.x < n) {
+        double q = 1.0;
+        if (scores) {
+            const float* s = scores + (int64_t)b * n;
+            float mx = -INFINITY;
+            for (int j = 0; j < n; ++j)
+                if (s[j] > -INFINITY) mx = fmaxf(mx, s[j]);   // (a NaN fails the comparison)
+            const float sc = s[threadIdx.x];
+            if (!(sc > -INFINITY)) q = -1.0;
+            else if (sc == mx || isinf(temperature)) q = 1.0;
+            else q = exp(((double)sc - (double)mx) / temperature);
+        }
+        sq[threadIdx.x] = q;
+    }
+    __syncthreads();
+
+    const double two_s2 = 2.0 * (t.sigma * t.sigma);
+    for (int i = 0; i < n; ++i) {
+        if (live) {
+            const uint64_t key = skey[(i * 4 + k) * CIDER_MAXL + lane];
+            const double wh = sw[(i * 4 + k) * CIDER_MAXL + lane];
+            for (int j = 0; j < n; ++j) {
+                const int m = __builtin_amdgcn_readfirstlane(slen[j]) - k;     // j's entries of this order: wave-uniform
+                const uint64_t kj = skey[(j * 4 + k) * CIDER_MAXL + lane];     // lane p holds j's entry p; those below m are read
+                const double wj = sw[(j * 4 + k) * CIDER_MAXL + lane];
+                double wr = 0.0;                              // at most one match has a nonzero weight: the sum is exact
+                for (int p = 0; p < m; ++p) {
+                    const double wp = lane_f64(wj, p);
+                    wr += lane_u64(kj, p) == key ? wp : 0.0;
+                }
+                const double tot = wave_sum_f64(fmin(wh, wr) * wr);
+                if (lane == 0) stot[j * 4 + k] = tot;
+            }
+        }
+        __syncthreads();
+        if (threadIdx.x < n) {
+            const int j = threadIdx.x;
+            const int li = no >= 2 ? (slen[i] > 0 ? slen[i] - 1 : 0) : 0;      // the scorer's "length": the bigram count
+            const int lj = no >= 2 ? (slen[j] > 0 ? slen[j] - 1 : 0) : 0;
+            const double d = (double)(li - lj);
+            const double pen = exp(-(d * d) / two_s2);
+            double s = 0.0;
+            for (int kk = 0; kk < no; ++kk) {
+                double v = stot[j * 4 + kk];
+                const double ni = snorm[i * 4 + kk], nj = snorm[j * 4 + kk];
+                if (ni != 0.0 && nj != 0.0) v /= ni * nj;
+                s += v * pen;
+            }
+            const double u = s / (double)no * 10.0;
+            surow[j] = u;
+            if (util) util[((int64_t)b * n + i) * n + j] = u;
+        }
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            double e = -INFINITY;
+            if (sq[i] >= 0.0) {
+                double num = 0.0, den = 0.0;
+                for (int j = 0; j < n; ++j) {
+                    if (j == i || !(sq[j] > 0.0)) continue;
+                    num += sq[j] * surow[j];
+                    den += sq[j];
+                }
+                e = den > 0.0 ? num / den : 0.0;
+            }
+            sexp[i] = e;
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x < n) {
+        const int i = threadIdx.x;
+        const double e = sexp[i];
+        int rank = 0;
+        for (int j = 0; j < n; ++j) rank += sexp[j] > e || (sexp[j] == e && j < i);
+        expected[(int64_t)b * n + i] = e;
+        order[(int64_t)b * n + rank] = i;
+    }
+}
+
 }  // namespace
 
 #define ST(s) reinterpret_cast<hipStream_t>(s)
@@ -202,6 +423,27 @@ extern "C" int dlsg_scst_advantage(const double* rewards, const int64_t* lens, c
     if (B < 0 || n < 1 || (!greedy && n < 2) || !rewards || !lens || !adv || !stats) return DLSG_EINVAL;
     if (B == 0) return DLSG_OK;
     hipLaunchKernelGGL(scst_advantage_kernel, dim3(1), dim3(256), 0, ST(stream), rewards, lens, greedy, B, n, adv, stats);
+    DLSG_CHECK_LAUNCH();
+    return DLSG_OK;
+}
+
+extern "C" int dlsg_cider_consensus(const int64_t* ids, int64_t ld, int B, int n, int L, int64_t end_id, const dlsg_cider_tables* t,
+                                    const float* scores, double temperature, double* util, double* expected, int64_t* order,
+                                    void* stream) {
+    if (n < 1 || n > CONS_MAXN || L < 1 || L > CIDER_MAXL || B < 0) return DLSG_EINVAL;
+    if (B == 0) return DLSG_OK;
+    if (!t || !ids || !expected || !order || ld < L || !(temperature > 0.0)) return DLSG_EINVAL;
+    if (t->n < 1 || t->n > 4 || t->vocab < 1 || t->vocab > 65535 || t->n_grams < 0) return DLSG_EINVAL;
+    if (t->n_grams > 0 && (!t->gram_keys || !t->gram_idf)) return DLSG_EINVAL;
+    static std::once_flag once;
+    static hipError_t attr = hipSuccess;
+    std::call_once(once, [] {
+        attr = hipFuncSetAttribute(reinterpret_cast<const void*>(cider_consensus_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                   cons_lds_bytes(CONS_MAXN));
+    });
+    if (attr != hipSuccess) return DLSG_ELAUNCH;
+    hipLaunchKernelGGL(cider_consensus_kernel, dim3(B), dim3(CIDER_THREADS), cons_lds_bytes(n), ST(stream), ids, ld, n, L, end_id, *t,
+                       scores, temperature, util, expected, order);
     DLSG_CHECK_LAUNCH();
     return DLSG_OK;
 }

@@ -7,6 +7,7 @@ from .data import H5File, CaptionSet, ResidentFeatures, StreamedFeatures, TrainL
 from .scst import SCSTTrainer  # noqa: F401
 from .beam import beam_search, beam_nbest  # noqa: F401
 from .ensemble import Ensemble  # noqa: F401
-from .graphs import EnsembleBeamGraph  # noqa: F401
+from .graphs import EnsembleBeamGraph, ConsensusBeamGraph  # noqa: F401
+from .consensus import consensus_rerank, consensus_search  # noqa: F401
 from .scoring import DeviceCaptionMetrics, MixedReward, DeviceMixedReward  # noqa: F401
 from .scoring import CiderD, DeviceCiderD, CaptionScorer, convert_data_to_coco_scorer_format, convert_prediction, evaluate  # noqa: F401

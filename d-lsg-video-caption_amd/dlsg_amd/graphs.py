@@ -1,7 +1,8 @@
 """hipGraph capture and replay, in one place: entering and leaving the process's capture stream, the eager warm-up, capturing one
 graph or a chain of segments, dropping a capture whose body raised, staging inputs into the static buffers a graph reads --
-and the captured forms of inference built on it (GreedyGraph, SampleGraph, BeamGraph, NBestBeamGraph, EnsembleBeamGraph).  The Trainer
-(model.py), the GanTrainer (gan.py) and the SCSTTrainer (scst.py) capture through `capture` / `capture_segments`."""
+and the captured forms of inference built on it (GreedyGraph, SampleGraph, BeamGraph, NBestBeamGraph, EnsembleBeamGraph,
+ConsensusBeamGraph).  The Trainer (model.py), the GanTrainer (gan.py) and the SCSTTrainer (scst.py) capture through `capture` /
+`capture_segments`."""
 import torch
 
 
@@ -198,3 +199,33 @@ class EnsembleBeamGraph(_InferenceGraph):
                                    '(flatten_parameters_ after load_encoder / load_state_dict / .to()); the graph holds addresses '
                                    'into the old arena -- build a new one' % i)
         super()._stage(frames, regions)
+
+
+class ConsensusBeamGraph(_InferenceGraph):
+    """hipGraph-captured `consensus.consensus_search(model_or_ensemble, frames, regions, reward, **options)` for one batch shape: the
+    beam search of a model or an `ensemble.Ensemble` with every beam kept, the `dlsg_cider_consensus` launch and the gathers that
+    reorder the beams.  A replay returns (ids, expected, lens, order) -- static buffers, valid until the next replay -- and
+    synchronises nothing.  Like EnsembleBeamGraph it holds every member's arena and train / eval mode."""
+
+    def __init__(self, model_or_ensemble, frames, regions, reward, **options):
+        self.search, self.reward, self.options = model_or_ensemble, reward, options
+        members = list(getattr(model_or_ensemble, 'members', [model_or_ensemble]))
+        for m in members:
+            m.flatten_parameters_()
+        self.held = [(m, m._flat, m.training) for m in members]
+        super().__init__(members[0], frames, regions)
+
+    def _run(self):
+        from .consensus import consensus_search
+        return consensus_search(self.search, self.frames, self.regions, self.reward, **self.options)
+
+    def valid_for(self, frames, regions):
+        return super().valid_for(frames, regions) and all(a is m._flat and tr == m.training for m, a, tr in self.held)
+
+    def _stage(self, frames, regions):
+        for i, (m, arena, _) in enumerate(self.held):
+            if arena is not m._flat:
+                raise RuntimeError('ConsensusBeamGraph: model %d re-packed its parameter arena after this graph was captured '
+                                   '(flatten_parameters_ after load_encoder / load_state_dict / .to()); the graph holds addresses '
+                                   'into the old arena -- build a new one' % i)
+        _InferenceGraph._stage(self, frames, regions)

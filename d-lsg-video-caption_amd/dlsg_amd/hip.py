@@ -1507,6 +1507,24 @@ class HipOps(object):
         self._check(self.lib.dlsg_cider_d(_p(ids), i64(ids.stride(0)), R, L, _p(clip_idx), i64(end_id), C.byref(cider_tables(tables)),
                                           _p(out), self._stream()), 'cider_d')
 
+    def cider_consensus(self, ids, end_id, tables, scores, temperature, util, expected, order):
+        """consensus ranking of the n candidates ids[b] (int64 (B, n, L), n <= 32, L <= 64, unit word stride, candidate rows
+        equally strided over the whole batch) by CIDEr-D against each other on the corpus idf of `tables` (a scoring.DeviceCiderD):
+        expected (float64 (B, n)) the expected utility of a candidate over the others, weighted exp((scores - max) / temperature)
+        (scores float32 (B, n), None: uniform), order (int64 (B, n)) its descending ranking, util (float64 (B, n, n) or None) the
+        pairwise utilities.  See dlsg_cider_consensus in include/dlsg.h."""
+        assert ids.dim() == 3 and ids.dtype == torch.int64, (ids.dtype, ids.shape)
+        B, n, L = ids.shape
+        ld = max(ids.stride(1), L) if B * n <= 1 else ids.stride(1) if n > 1 else ids.stride(0)      # candidate b n + i at (b n + i) ld
+        assert (ids.stride(2) == 1 or L <= 1) and (ids.stride(0) == n * ld or B <= 1 or n <= 1) and ld >= L, ids.stride()
+        assert scores is None or (scores.dtype == torch.float32 and scores.is_contiguous() and scores.shape == (B, n))
+        assert util is None or (util.dtype == torch.float64 and util.is_contiguous() and util.shape == (B, n, n))
+        assert expected.dtype == torch.float64 and expected.is_contiguous() and expected.shape == (B, n)
+        assert order.dtype == torch.int64 and order.is_contiguous() and order.shape == (B, n)
+        self._check(self.lib.dlsg_cider_consensus(_p(ids), i64(ld), B, n, L, i64(end_id),
+                                                  C.byref(cider_tables(tables)), _p(scores), float(temperature), _p(util),
+                                                  _p(expected), _p(order), self._stream()), 'cider_consensus')
+
     def caption_metrics(self, ids, clip_idx, end_id, tables, scores=None, stats=None, reward=None, weights=None, base=None):
         """BLEU-1..4 and ROUGE_L of the words of ids[r] (as in `cider_d`) against the references of clip clip_idx[r] in `tables` (a
         scoring.DeviceCaptionMetrics).  Outputs, each optional: scores (float64 (R, 5)), stats (int32 (R, 10): correct[4], guess[4],

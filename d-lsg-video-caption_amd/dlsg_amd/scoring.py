@@ -201,9 +201,68 @@ class CiderD(object):
             out[i] = memo[key]
         return out
 
+    def pairwise(self, hyps):
+        """U (n, n) float64 of one clip's candidate captions (tokenized strings) against each other: U[i][j] is what `_score`
+        gives hyps[i] when hyps[j] is the clip's only reference, on the corpus idf.  Not symmetric (the clipping)."""
+        n, sigma = self.n, self.sigma
+        vecs = [self._vec(_ngrams(h.split(), n)) for h in hyps]
+        U = np.zeros((len(hyps), len(hyps)), dtype=np.float64)
+        for i, (vh, nh, lh) in enumerate(vecs):
+            for j, (vr, nr, lr) in enumerate(vecs):
+                pen = math.e ** (-(float(lh - lr) ** 2) / (2 * sigma ** 2))
+                tot = 0.0
+                for k in range(n):
+                    s = sum(min(w, vr[k].get(g, 0.0)) * vr[k].get(g, 0.0) for g, w in vh[k].items())
+                    if nh[k] != 0 and nr[k] != 0:
+                        s /= nh[k] * nr[k]
+                    tot += s * pen
+                U[i, j] = tot / n * 10.0
+        return U
+
+    def consensus(self, hyps, scores=None, temperature=1.0):
+        """Consensus (minimum Bayes risk) ranking of one clip's candidates: (order, expected).  expected[i] is the mean of
+        U[i][j] = `pairwise(hyps)` over the OTHER candidates j, weighted q_j = exp((scores[j] - max valid score) / temperature)
+        (scores None: 1); a candidate whose score is -inf or NaN is invalid: weight 0, expected -inf.  0 where no other candidate
+        has weight.  order sorts expected descending, ties to the lower index (int64).  The host form of
+        `DeviceCiderD.consensus_device`."""
+        if not temperature > 0.0:
+            raise ValueError('consensus temperature %r must be positive' % (temperature,))
+        U = self.pairwise(hyps)
+        q = consensus_weights(scores, len(hyps), temperature)
+        expected = np.full(len(hyps), -np.inf, dtype=np.float64)
+        for i in range(len(hyps)):
+            if q[i] < 0.0:
+                continue
+            num = den = 0.0
+            for j in range(len(hyps)):
+                if j != i and q[j] > 0.0:
+                    num += q[j] * U[i, j]
+                    den += q[j]
+            expected[i] = num / den if den > 0.0 else 0.0
+        order = np.array(sorted(range(len(hyps)), key=lambda i: (-expected[i], i)), dtype=np.int64)
+        return order, expected
+
     def to_device(self, vocab, device='cuda'):
         """the same scorer with device tables over `vocab`'s ids (`DeviceCiderD`); the corpus statistics are not recomputed"""
         return DeviceCiderD(None, vocab, self.n, self.sigma, device, _cider=self)
+
+
+MAX_CANDIDATES, MAX_CANDIDATE_WORDS = 32, 64        # limits of dlsg_cider_consensus
+
+
+def consensus_weights(scores, n, temperature):
+    """the weights of `dlsg_cider_consensus` as a float64 array: 1 without scores, else exp((s - max valid s) / temperature) on
+    the float32 scores, -1 for an invalid (-inf or NaN) one; temperature inf weighs every valid candidate 1"""
+    if scores is None:
+        return np.ones(n, dtype=np.float64)
+    s = np.asarray(scores, dtype=np.float32).astype(np.float64).reshape(n)
+    valid = s > -np.inf                                              # (a NaN fails the comparison)
+    q = np.full(n, -1.0, dtype=np.float64)
+    if valid.any():
+        mx = s[valid].max()
+        for j in np.nonzero(valid)[0]:
+            q[j] = 1.0 if s[j] == mx or math.isinf(temperature) else math.exp((s[j] - mx) / temperature)
+    return q
 
 
 NGRAM_NONE = 0xFFFF             # the key slot of a position past the n-gram's order (and the bound on the vocabulary size)
@@ -328,6 +387,36 @@ class DeviceCiderD(object):
         out = torch.empty(ids.shape[0], dtype=torch.float64, device=ids.device)
         self._ops().cider_d(ids, clip_idx, self.end_id if end_id is None else int(end_id), self, out)
         return out
+
+    def consensus_device(self, ids, scores=None, temperature=1.0, return_utility=False, end_id=None):
+        """Consensus (minimum Bayes risk) ranking of candidate captions against each other -- no references: ids int64 (B, n, L),
+        n <= 32 candidates per clip, L <= 64 (rows as in `scores_device`; a view of a wider buffer will do) -> (order (B, n)
+        int64, expected (B, n) float64[, util (B, n, n) float64]) on ids' device, what `CiderD.consensus` gives per clip for the
+        decoded strings (to rounding, 1e-12), an id outside [0, len(vocab)) being one out-of-vocabulary word that matches
+        itself.  scores: float32 (B, n) log-scores for posterior weights exp((s - max) / temperature), None: uniform; a -inf or
+        NaN score marks a candidate invalid (expected -inf, ranked last).  One launch (`dlsg_cider_consensus`), no host
+        synchronisation (capturable)."""
+        import torch
+        if ids.dim() != 3:
+            raise ValueError('consensus_device ranks ids of shape (B, n, L), not %s' % (tuple(ids.shape),))
+        B, n, L = ids.shape
+        if not 1 <= n <= MAX_CANDIDATES:
+            raise ValueError('consensus_device ranks 1 to %d candidates per clip, not %d' % (MAX_CANDIDATES, n))
+        if not 1 <= L <= MAX_CANDIDATE_WORDS:
+            raise ValueError('consensus_device reads 1 to %d words per candidate, not %d' % (MAX_CANDIDATE_WORDS, L))
+        if not temperature > 0.0:
+            raise ValueError('consensus temperature %r must be positive' % (temperature,))
+        if scores is not None and (scores.dtype != torch.float32 or tuple(scores.shape) != (B, n)):
+            raise ValueError('consensus scores must be float32 of shape %s, not %s %s' % ((B, n), scores.dtype, tuple(scores.shape)))
+        dev = ids.device
+        order = torch.empty(B, n, dtype=torch.int64, device=dev)
+        expected = torch.empty(B, n, dtype=torch.float64, device=dev)
+        util = torch.empty(B, n, n, dtype=torch.float64, device=dev) if return_utility else None
+        if scores is not None:
+            scores = scores.contiguous()
+        self._ops().cider_consensus(ids, self.end_id if end_id is None else int(end_id), self, scores, float(temperature), util,
+                                    expected, order)
+        return (order, expected, util) if return_utility else (order, expected)
 
 
 # ------------------------------------------------------------------------------------------------ BLEU / ROUGE_L on the device
@@ -567,14 +656,25 @@ def convert_prediction(prediction):
 def gather_results(net, eval_loader, decode=None):
     """evaluate.py:62-78 / 101-117: greedy or beam inference over the eval loader -> OrderedDict video id -> sentence.
     `decode`: a dict of `beam_search` options (beam_size, length_penalty, no_repeat_ngram, min_len, num_groups,
-    diversity_penalty); the captions are then the best beam of that search."""
+    diversity_penalty); the captions are then the best beam of that search.  With the key consensus=reward (a `DeviceCiderD`;
+    optionally consensus_weights, consensus_temperature) every beam of that search is kept and the caption is the one the
+    others agree with most: row 0 of `consensus.consensus_search`."""
     import torch
     result = collections.OrderedDict()
     dec = (net.module if hasattr(net, 'module') else net).decoder
+    consensus = None
+    if decode is not None and 'consensus' in decode:
+        decode = dict(decode)
+        consensus = dict(reward=decode.pop('consensus'), weights=decode.pop('consensus_weights', 'uniform'),
+                         temperature=decode.pop('consensus_temperature', 1.0))
     with torch.no_grad():
         for frames, regions, spatials, video_ids in eval_loader:
             if decode is None:
                 outputs = net(frames, regions, None)[0]
+            elif consensus is not None:
+                from .consensus import consensus_search
+                outputs = consensus_search(net.module if hasattr(net, 'module') else net, frames, regions,
+                                           **dict(decode, n_best=1, **consensus))[0][:, 0]
             else:
                 outputs = (net.module if hasattr(net, 'module') else net).beam_search(frames, regions, **dict(decode, n_best=1))[0][:, 0]
             ids = outputs.cpu()                                    # host synchronisation: the time-out word is final too

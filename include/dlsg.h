@@ -777,6 +777,26 @@ int dlsg_cider_d(const int64_t* ids, int64_t ld, int rows, int L, const int32_t*
  * One workgroup, fixed-order sums.  Without greedy n >= 2. */
 int dlsg_scst_advantage(const double* rewards, const int64_t* lens, const double* greedy, int B, int n, float* adv, double* stats,
                         void* stream);
+/* Consensus (minimum Bayes risk) ranking of the n candidate captions of each of B clips by CIDEr-D against EACH OTHER: no
+ * reference table is read, only the corpus idf (gram_keys, gram_idf, log_n), sigma and n of `t`.  Candidate i of clip b is the row
+ * ids + (b n + i) ld, its words as in dlsg_cider_d (those before the first end_id, all L without one).
+ *   U[b][i][j]     what scoring.CiderD._score gives hypothesis i when candidate j is its clip's only reference: tf-idf vectors on
+ *                  the corpus idf (log_n for an n-gram outside the table), sum over n-grams of min(w_i, w_j) w_j divided by both
+ *                  norms when both are nonzero, the sigma length penalty on bigram counts, x10 / t->n.  Not symmetric (clipping).
+ *   q[b][j]        1 with scores == NULL, else exp((s_j - max over the valid s) / temperature) in double (temperature > 0;
+ *                  +infinity weighs every valid candidate 1).  A candidate whose score is -inf or NaN is invalid: weight 0.
+ *   expected[b][i] sum_{j != i} q_j U[b][i][j] / sum_{j != i} q_j, added in index order; 0 when that denominator is 0 (n == 1,
+ *                  every other candidate invalid); -inf for an invalid candidate.
+ *   order[b][:]    the permutation of 0 .. n-1 that sorts expected[b] descending, ties to the lower index.
+ * util (B, n, n) float64 receives U and may be NULL; expected (B, n) float64; order (B, n) int64; scores (B, n) float.
+ * Ids outside [0, vocab) never index a table; UNLIKE dlsg_cider_d, where such a word matches no reference word, all of them are
+ * here one and the same out-of-vocabulary word, which matches itself within a candidate and across candidates, with df = 0
+ * (every n-gram that holds it has idf log_n).  One workgroup of 256 per clip, the candidates' vectors staged in n x 4 KiB of
+ * dynamic LDS, float64, no atomics, fixed-order sums: bit-identical on every launch.  1 <= n <= 32, 1 <= L <= 64, L <= ld, else
+ * DLSG_EINVAL and no launch; B == 0 launches nothing. */
+int dlsg_cider_consensus(const int64_t* ids, int64_t ld, int B, int n, int L, int64_t end_id,
+                         const dlsg_cider_tables* t, const float* scores, double temperature,
+                         double* util, double* expected, int64_t* order, void* stream);
 /* Sentence-level BLEU-1..4 and ROUGE_L (beta = 1.2) of row r of ids (rows as in dlsg_cider_d: int64, row stride ld, the words
  * before the first end_id, L <= 64) against the references of clip clip_idx[r], in float64 and in the operation order of
  * scoring.bleu / scoring.rouge_l.  Reference tables (scoring.DeviceCaptionMetrics): clip c owns references [clip_off[c],
