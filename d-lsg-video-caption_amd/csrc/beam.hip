@@ -1,8 +1,8 @@
-// The beam-search step (gfx950): dlsg_beam_select and its variants with a token history, an ensemble of members and beam
-// groups, and dlsg_beam_finalize.  One workgroup per batch item, one wave per live beam (BeamSearch.search,
-// allennlp_beamsearch.py:140-260 with per_node_beam_size == beam_size): log-softmax of the beam's logits row, its top-k classes (a
-// finished beam offers <end> at log-prob 0 and nothing else), then the top-k of the k*k summed candidates, back-pointers and the
-// row indices that reorder the recurrent state.  Ties resolve to the lower index.  The four kernels are compositions of the
+// The beam-search step (gfx950): dlsg_beam_select and its variants with a token history, Gumbel-perturbed selection (stochastic
+// beam search), an ensemble of members and beam groups, and dlsg_beam_finalize.  One workgroup per batch item, one wave per live
+// beam (BeamSearch.search, allennlp_beamsearch.py:140-260 with per_node_beam_size == beam_size): log-softmax of the beam's logits
+// row, its top-k classes (a finished beam offers <end> at log-prob 0 and nothing else), then the top-k of the k*k summed
+// candidates, back-pointers and the row indices that reorder the recurrent state.  Ties resolve to the lower index.  The step kernels are compositions of the
 // phases in beam.hpp: a tie rule, the ban rule or the -inf slot rule is written once, there.  Each kernel declares only the LDS
 // its phases use.
 #include <type_traits>
@@ -68,6 +68,48 @@ __global__ __launch_bounds__(64 * K) void beam_select_hist_kernel(const dlsg_bea
     }
     __syncthreads();
     if (w == 0) beam_flat_merge<K, true>(a, nbeam, lane, cand_lp, cand_cls, hist_in, hist_out, L, t);
+}
+
+// The step of stochastic beam search (dlsg_beam_select_gumbel): beam_select_hist_kernel's launch, bans and history, but a live
+// row offers the K classes with the largest Gumbel keys at their conditioned perturbed values (beam_offer_gumbel) and the clip
+// keeps the K largest of those, float64, in that order.  last_lp / new_lp carry the log-prob under the tempered, renormalised
+// model, G_in / G_out the perturbed value.  The noise of class j of row r is keyed ((t + 1) * B*K + r) * V + j: with K = 1 the key
+// sample_embed_kernel ranks by at row0 = (t + 1) * B.
+template <int K>
+__global__ __launch_bounds__(64 * K) void beam_select_gumbel_kernel(const dlsg_beam_select_args a, const int64_t* __restrict__ hist_in,
+                                                                      int64_t* __restrict__ hist_out, int L, int t, int g, int min_len,
+                                                                      float tau, uint64_t seed, const uint64_t* __restrict__ seed_ptr,
+                                                                      uint32_t site_sample, const double* __restrict__ G_in,
+                                                                      double* __restrict__ G_out) {
+    __shared__ float cand_lp[K * K];
+    __shared__ int cand_cls[K * K];
+    __shared__ double cand_g[K * K];
+    __shared__ int hist[K][BEAM_MAXL];
+    __shared__ int ban[K][BEAM_MAXL + 1];
+    __shared__ int nban[K];
+    if (seed_ptr) seed += *seed_ptr;
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const int nbeam = a.first ? 1 : K;
+    const int64_t row = (int64_t)blockIdx.x * K + w;
+    const bool ended = !a.first && a.last[row] == a.end;
+    beam_row_bans(hist_in, row, L, t, g, min_len, a.end, w < nbeam && !ended, hist, ban, nban);
+    if (w < nbeam) {
+        const float base = a.first ? 0.f : a.last_lp[row];
+        // the root's perturbed value: Gumbel(0) noise of its own, keyed as class 0 of this row one step before step 0.  (A root
+        // pinned to 0 conditions the largest perturbed value of all captions on being 0: the same sample, but a threshold that
+        // no longer gives unbiased importance weights.)
+        const double T = a.first ? gumbel_noise64(seed, site_sample, (uint64_t)row * (uint64_t)a.V) : G_in[row];
+        if (ended) {
+            beam_offer_ended<K>(a, lane, base, cand_lp + w * K, cand_cls + w * K);
+            if (lane < K) cand_g[w * K + lane] = lane == 0 ? T : -INFINITY;
+        } else {
+            const uint64_t key0 = ((uint64_t)(t + 1) * ((uint64_t)a.B * K) + (uint64_t)row) * (uint64_t)a.V;
+            beam_offer_gumbel<K>(a.logits + row * a.ld, a.V, lane, 1.f / tau, seed, site_sample, key0, ban[w], nban[w], base, T,
+                                 cand_lp + w * K, cand_cls + w * K, cand_g + w * K);
+        }
+    }
+    __syncthreads();
+    if (w == 0) beam_flat_merge<K, true, double>(a, nbeam, lane, cand_g, cand_cls, hist_in, hist_out, L, t, cand_lp, G_out);
 }
 
 // Phase 1 of the ensemble step and of the group step, wave w for row w: beam_select_hist_kernel's, but a live beam's candidates
@@ -252,6 +294,17 @@ extern "C" int dlsg_beam_select_hist(const dlsg_beam_select_args* a, const int64
     if (!beam_args_ok(a) || !beam_hist_ok(a, hist_in, hist_out, L, t, no_repeat_ngram, min_len)) return DLSG_EINVAL;
     if (a->B == 0) return DLSG_OK;
     BEAM_LAUNCH(beam_select_hist_kernel, hist_in, hist_out, L, t, no_repeat_ngram, min_len);
+    DLSG_CHECK_LAUNCH();
+    return DLSG_OK;
+}
+extern "C" int dlsg_beam_select_gumbel(const dlsg_beam_select_args* a, const int64_t* hist_in, int64_t* hist_out, int L, int t,
+                                       int no_repeat_ngram, int min_len, float temperature, uint64_t seed, const uint64_t* seed_ptr,
+                                       uint32_t site_sample, const double* G_in, double* G_out, void* stream) {
+    if (!beam_args_ok(a) || !beam_hist_ok(a, hist_in, hist_out, L, t, no_repeat_ngram, min_len)) return DLSG_EINVAL;
+    if (!(temperature > 0.f) || !G_out || (t > 0 && (!G_in || G_in == G_out))) return DLSG_EINVAL;     // (NaN fails the comparison)
+    if (a->B == 0) return DLSG_OK;
+    BEAM_LAUNCH(beam_select_gumbel_kernel, hist_in, hist_out, L, t, no_repeat_ngram, min_len, temperature, seed, seed_ptr, site_sample,
+                G_in, G_out);
     DLSG_CHECK_LAUNCH();
     return DLSG_OK;
 }

@@ -1,9 +1,12 @@
-// The phases of a beam-search step (gfx950), one definition each: the four step kernels of beam.hip are compositions of them, and
+// The phases of a beam-search step (gfx950), one definition each: the step kernels of beam.hip are compositions of them, and
 // the filtered sampler (sample.hip) bans words by the same rule.  A step is one workgroup per clip and one wave per beam row:
 // every row offers its K best (log-prob, class) candidates in LDS, then wave 0 takes the K best of the clip's candidates.
 #pragma once
+#include <type_traits>
+
 #include "common.hpp"
 #include "dlsg.h"
+#include "wordpick.hpp"
 
 namespace dlsg {
 
@@ -13,6 +16,7 @@ constexpr int BEAM_MAXL = 64;           // history positions: lane i of a row's 
 // (value, index) order of the search: larger value first, ties to the smaller index (torch.topk on equal log-probs is not
 // specified; the oracle and the reference fixtures agree with this rule on every golden case)
 __device__ __forceinline__ bool beam_better(float v, int i, float bv, int bi) { return v > bv || (v == bv && i < bi); }
+__device__ __forceinline__ bool beam_better(double v, int i, double bv, int bi) { return v > bv || (v == bv && i < bi); }
 
 template <int CTRL>
 __device__ __forceinline__ int dpp_i32(int v) { return __builtin_amdgcn_update_dpp(0, v, CTRL, 0xF, 0xF, true); }
@@ -29,6 +33,16 @@ __device__ __forceinline__ void wave_argmax(float& v, int& i) {
     const float m = dlsg::wave_max(v);
     i = wave_min_i32(v == m ? i : 0x7fffffff);
     v = m;
+}
+// the same pair of float64 values (the stochastic step selects by them): a butterfly under beam_better, which is commutative, so
+// every lane ends with the same pair
+__device__ __forceinline__ void wave_argmax(double& v, int& i) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const double ov = __shfl_xor(v, o, 64);
+        const int oi = __shfl_xor(i, o, 64);
+        if (beam_better(ov, oi, v, i)) { v = ov; i = oi; }
+    }
 }
 
 // ------------------------------------------------------------------------------------------------ ban list
@@ -211,6 +225,70 @@ __device__ __forceinline__ void beam_ens_row_topk(const EnsPack& e, int64_t row,
     beam_topk_merge<K>(tv, ti, bv, bi);
 }
 
+// ------------------------------------------------------------------------------------------------ a stochastic row
+// -log(-log u) in float64, u = (hi + 1/2) 2^-24 from the 24 hash bits gumbel_key draws its float32 noise from
+__device__ __forceinline__ double gumbel_noise64(uint64_t seed, uint32_t site, uint64_t ctr) {
+    const uint32_t hi = counter_hash(seed, site, ctr) >> 8;
+    return -log(-log(((double)hi + 0.5) * (1.0 / 16777216.0)));
+}
+// log(1 - exp(a)) for a <= 0
+__device__ __forceinline__ double log1mexp(double a) { return a > -0.6931471805599453 ? log(-expm1(a)) : log1p(-exp(a)); }
+
+// Stochastic beam search (Kool, van Hoof & Welling 2019): a live row's K children, ONE wave.  One pass over the row: z = x * sc as
+// WordDraw tempers it, the K largest gumbel_key(z) (wordpick.hpp: the key the sampler ranks by) and the online (max, sum-exp) of z
+// over the classes that are neither banned nor -inf / NaN.  Such a dead class has key -inf, so that a row with fewer than K live
+// classes still names K distinct ones.  The ban list is scanned for every class, because the log-sum-exp leaves the banned
+// classes out (the filtered sampler's convention).  Then lane c < K works out child c in float64: with phi the parent's
+// log-prob, T its perturbed value and noise = -log(-log u) of the key's own 24 hash bits,
+//   g = phi + (z - lse) + noise,  Z = max of the K values g,  v = T - g + log1mexp(g - Z),  G = T - max(0, v) - log1p(exp(-|v|))
+// -- the children's perturbed values conditioned on their maximum being T; the largest child gets T itself.  lp / cls / G: the
+// row's K slots: phi + ((z - m) - log s) in float32 (the sampler's log-prob), the class, G; a dead slot is -inf in both.
+template <int K>
+__device__ __forceinline__ void beam_offer_gumbel(const float* x, int V, int lane, float sc, uint64_t seed, uint32_t site, uint64_t key0,
+                                                  const int* ban, int nban, float phi, double T, float* lp, int* cls, double* G) {
+    float tv[K], bv[K];
+    int ti[K], bi[K];
+    beam_topk_clear<K>(tv, ti);
+    float m = -INFINITY, s = 0.f;
+    for (int j = lane; j < V; j += 64) {
+        const float z = x[j] * sc;
+        bool dead = !(z > -INFINITY);
+        for (int q = 0; q < nban; ++q) dead |= ban[q] == j;
+        beam_topk_push<K, false>(tv, ti, dead ? -INFINITY : gumbel_key(z, seed, site, key0 + j), j, nullptr, 0);
+        if (!dead) lse_update<true>(m, s, z);
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) lse_merge(m, s, __shfl_xor(m, o, 64), __shfl_xor(s, o, 64));
+    beam_topk_merge<K>(tv, ti, bv, bi);
+    float key = bv[0];
+    int c = bi[0];
+#pragma unroll
+    for (int q = 1; q < K; ++q) {
+        key = lane == q ? bv[q] : key;
+        c = lane == q ? bi[q] : c;
+    }
+    float child = -INFINITY;
+    double g = -INFINITY;
+    if (lane < K && key > -INFINITY) {
+        const float z = x[c] * sc;
+        child = phi + ((z - m) - logf(s));
+        g = (double)phi + (((double)z - (double)m) - log((double)s)) + gumbel_noise64(seed, site, key0 + c);
+    }
+    double Z = -INFINITY;
+#pragma unroll
+    for (int q = 0; q < K; ++q) Z = fmax(Z, __shfl(g, q, 64));
+    if (lane < K) {
+        double gt = -INFINITY;
+        if (g > -INFINITY) {
+            const double v = T - g + log1mexp(g - Z);
+            gt = T - fmax(0.0, v) - log1p(exp(-fabs(v)));
+        }
+        lp[lane] = child;
+        cls[lane] = c;
+        G[lane] = gt;
+    }
+}
+
 // ------------------------------------------------------------------------------------------------ the clip's K best
 // Row o of hist_out (B*k, L): the parent's row of hist_in up to t, the chosen class at t, `end` behind it (step 0 writes whole
 // rows, so the search fills its own buffers).  One wave.
@@ -220,26 +298,34 @@ __device__ __forceinline__ void beam_write_hist(const int64_t* __restrict__ hist
 }
 
 // The K best of the clip's nbeam * K candidates, by wave 0: pred, new_lp, back and rows of the clip's K new beams, and the number
-// of `end` among them onto ended_count.  HIST: the new beams' history rows as well.
-template <int K, bool HIST>
-__device__ __forceinline__ void beam_flat_merge(const dlsg_beam_select_args& a, int nbeam, int lane, const float* cand_lp,
+// of `end` among them onto ended_count.  HIST: the new beams' history rows as well.  The candidates are ranked by cand_key: the
+// log-probs themselves (float), or the stochastic step's perturbed values (double) -- then new_lp is the winner's cand_lp, -inf
+// for a key of -inf, and key_out takes the key.
+template <int K, bool HIST, class T = float>
+__device__ __forceinline__ void beam_flat_merge(const dlsg_beam_select_args& a, int nbeam, int lane, const T* cand_key,
                                                 const int* cand_cls, const int64_t* __restrict__ hist_in,
-                                                int64_t* __restrict__ hist_out, int L, int t) {
+                                                int64_t* __restrict__ hist_out, int L, int t, const float* cand_lp = nullptr,
+                                                T* __restrict__ key_out = nullptr) {
     const int b = blockIdx.x, k = K, n = nbeam * k;
-    float v = lane < n ? cand_lp[lane] : -INFINITY;
+    T v = lane < n ? cand_key[lane] : (T)-INFINITY;
     int idx = lane < n ? lane : 0x7fffffff;
     int n_end = 0;
     for (int c = 0; c < k; ++c) {
-        float bv = v;
+        T bv = v;
         int bi = idx;
         wave_argmax(bv, bi);
-        if (lane == bi) v = -INFINITY, idx = 0x7fffffff;        // remove the winner (it can win only once)
+        if (lane == bi) v = (T)-INFINITY, idx = 0x7fffffff;     // remove the winner (it can win only once)
         if (bi == 0x7fffffff) bi = c < n ? c : 0;               // fewer than k finite candidates: any slot, log-prob -inf
         const int cls = cand_cls[bi];
         const int64_t o = (int64_t)b * k + c;
         if (lane == 0) {
             a.pred[o] = cls;
-            a.new_lp[o] = bv;
+            if constexpr (std::is_same<T, float>::value) {
+                a.new_lp[o] = bv;
+            } else {
+                a.new_lp[o] = bv == (T)-INFINITY ? -INFINITY : cand_lp[bi];
+                key_out[o] = bv;
+            }
             a.back[o] = bi / k;
             a.rows[o] = (int64_t)b * k + bi / k;
         }

@@ -5,9 +5,9 @@ from .model import CapGnnModel, CapBaseline1, CapBaselineModel, Trainer, GreedyG
 from .gan import DiscV2, GanTrainer, GANLambdaHandler, save_checkpoint, load_checkpoint  # noqa: F401
 from .data import H5File, CaptionSet, ResidentFeatures, StreamedFeatures, TrainLoader, EvalLoader, distributed_indices  # noqa: F401
 from .scst import SCSTTrainer  # noqa: F401
-from .beam import beam_search, beam_nbest  # noqa: F401
+from .beam import beam_search, beam_nbest, stochastic_nbest, sample_without_replacement, importance_weights  # noqa: F401
 from .ensemble import Ensemble  # noqa: F401
-from .graphs import EnsembleBeamGraph, ConsensusBeamGraph  # noqa: F401
+from .graphs import EnsembleBeamGraph, ConsensusBeamGraph, StochasticBeamGraph  # noqa: F401
 from .consensus import consensus_rerank, consensus_search  # noqa: F401
 from .scoring import DeviceCaptionMetrics, MixedReward, DeviceMixedReward  # noqa: F401
 from .scoring import CiderD, DeviceCiderD, CaptionScorer, convert_data_to_coco_scorer_format, convert_prediction, evaluate  # noqa: F401

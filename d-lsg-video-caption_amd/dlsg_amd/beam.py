@@ -247,6 +247,83 @@ def ensemble_nbest(models, weights, mode, visual_feats, region_feats, n_best=Non
                          num_groups, diversity_penalty)
 
 
+def check_stochastic_options(n, L, V, temperature, min_len=0, no_repeat_ngram=0, return_threshold=False):
+    """ValueError for what `stochastic_nbest` cannot run; returns the number of beams: n, one more with the threshold"""
+    top = MAX_BEAM - 1 if return_threshold else MAX_BEAM
+    if not 1 <= n <= top:
+        raise ValueError('n %r: sampling without replacement draws 1 to %d captions per clip%s'
+                         % (n, top, ' with return_threshold (it runs one more beam)' if return_threshold else ''))
+    k = n + 1 if return_threshold else n
+    if not temperature > 0.0:                                          # (NaN fails the comparison)
+        raise ValueError('temperature (%r) must be positive' % (temperature,))
+    if L > MAX_WORDS:
+        raise ValueError('max_words %d: the search keeps at most %d tokens per beam' % (L, MAX_WORDS))
+    if no_repeat_ngram < 0 or min_len < 0:
+        raise ValueError('no_repeat_ngram (%d) and min_len (%d) must not be negative' % (no_repeat_ngram, min_len))
+    if min_len >= L:
+        raise ValueError('min_len %d leaves no room for <end> in max_words %d' % (min_len, L))
+    if V < k:
+        raise ValueError('vocabulary size (%d) too small for %d beams' % (V, k))
+    return k
+
+
+@torch.no_grad()
+def stochastic_nbest(model, visual_feats, region_feats, n=5, temperature=1.0, seed=None, min_len=0, no_repeat_ngram=0,
+                     return_threshold=False):
+    """Stochastic beam search (Kool, van Hoof & Welling 2019): n DISTINCT captions per clip that are an exact ordered sample without
+    replacement from softmax(logits / temperature), renormalised over the words min_len and no_repeat_ngram leave -- row 0 is
+    distributed as one ordinary sample, rows 0 .. m-1 as a without-replacement sample of size m.  Returns (ids (B, n, L) int64
+    padded with <end>, logp (B, n) float32 the captions' log-probabilities under that model, lens (B, n) int64 counting the first
+    <end>, else L).  return_threshold=True runs n + 1 beams and adds (gumbel (B, n) float64, the rows' perturbed log-probabilities,
+    descending; kappa (B,) float64, that of beam n + 1): `importance_weights(logp, kappa)` then weighs the n rows into an unbiased
+    estimator of any expectation under the model.
+    The search is `beam_nbest`'s -- eval-mode decode, state ping-pong, one select launch per word, all L steps launched, nothing read
+    back -- on `beam_select_gumbel`, whose noise is `sample`'s: with n = 1 the words are those of `model.eval().sample(n=1,
+    temperature, seed)`.  seed None draws the model's next seed; it may be a device word (a captured graph)."""
+    dec = model.decoder
+    L = dec.max_words
+    k = check_stochastic_options(n, L, dec.vocab_size, temperature, min_len, no_repeat_ngram, return_threshold)
+    if seed is None:
+        seed = model.next_seed()
+    mems, sv, enc_seed, _ = _encode(model, visual_feats, region_feats)
+    advance, B, R, _ = _beam_setup(model, mems, sv, enc_seed, k)
+    ops, end, dev = model.ops, dec.vocab('<end>'), mems[0].device
+    preds = torch.empty(2, R, dtype=torch.int64, device=dev)
+    hist = torch.empty(2, R, L, dtype=torch.int64, device=dev)     # filled by step 0
+    back = torch.empty(R, dtype=torch.int64, device=dev)
+    rows = torch.empty(R, dtype=torch.int64, device=dev)
+    lps = torch.zeros(2, R, dtype=torch.float32, device=dev)
+    G = torch.zeros(2, R, dtype=torch.float64, device=dev)
+    words = torch.full((R,), dec.vocab('<start>'), dtype=torch.int64, device=dev)
+    for t in range(L):
+        logits = advance(t, words, rows)
+        ops.beam_select_gumbel(logits, words, lps[t % 2], preds[t % 2], lps[(t + 1) % 2], back, rows, k, end, hist[t % 2],
+                               hist[(t + 1) % 2], t, G[t % 2], G[(t + 1) % 2], temperature=float(temperature), seed=seed,
+                               site_sample=E.SITE_SAMPLE, no_repeat_ngram=no_repeat_ngram, min_len=min_len)
+        words = preds[t % 2]
+    ids = hist[L % 2].view(B, k, L)
+    # words before the first <end>, plus that <end>: L for a row without one
+    lens = ((ids == end).cumsum(2) == 0).sum(2).add_(1).clamp_(max=L)
+    out = ids[:, :n].contiguous(), lps[L % 2].view(B, k)[:, :n].contiguous(), lens[:, :n].contiguous()
+    if return_threshold:
+        Gk = G[L % 2].view(B, k)
+        out += (Gk[:, :n].contiguous(), Gk[:, n].contiguous())
+    return out
+
+
+def importance_weights(logp, kappa):
+    """The weights that turn the n rows of `stochastic_nbest(..., return_threshold=True)` into an unbiased estimator: with phi =
+    logp (B, n) and kappa (B,) the perturbed value of beam n + 1, w = exp(phi) / q, q = 1 - exp(-exp(phi - kappa)) the probability
+    that the caption's perturbed value exceeds kappa; sum_i w_i f(y_i) estimates E_p[f].  float64 (B, n)."""
+    phi = logp.double()
+    return phi.exp() / -torch.expm1(-(phi - kappa.double().unsqueeze(1)).exp())
+
+
+def sample_without_replacement(model, visual_feats, region_feats, **options):
+    """`stochastic_nbest`, the function form of `model.sample_without_replacement`"""
+    return stochastic_nbest(model, visual_feats, region_feats, **options)
+
+
 def beam_search(model, visual_feats, region_feats, beam_size=None, **options):
     """`beam_nbest` with `beam_size` beams (default: the decoder's own, which is not changed)"""
     return beam_nbest(model, visual_feats, region_feats, beam_size=beam_size, **options)

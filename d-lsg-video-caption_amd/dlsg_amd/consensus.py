@@ -39,10 +39,25 @@ def consensus_rerank(reward, ids, scores=None, lens=None, weights='uniform', tem
 
 
 @torch.no_grad()
-def consensus_search(model_or_ensemble, frames, regions, reward, n_best=1, weights='uniform', temperature=1.0, **beam_options):
+def consensus_search(model_or_ensemble, frames, regions, reward, n_best=1, weights='uniform', temperature=1.0, stochastic=None,
+                     **beam_options):
     """`beam_search` of a model (CapGnnModel, the baselines) or an `ensemble.Ensemble` with every beam kept, then
     `consensus_rerank`: (ids (B, n_best, L), expected, lens, order).  beam_options: beam_size, length_penalty, no_repeat_ngram,
     min_len, num_groups, diversity_penalty -- diverse groups give the consensus something to choose from.  The search's launches
-    plus one."""
-    ids, scores, lens = model_or_ensemble.beam_search(frames, regions, **beam_options)
+    plus one.
+    stochastic=dict(n=..., temperature=..., seed=..., min_len=..., no_repeat_ngram=...): the candidates are the n distinct
+    captions of `model.sample_without_replacement` instead (a model, not an ensemble), their log-probabilities the scores: a
+    without-replacement sample of the model as the candidate list of the Monte Carlo estimate, with no row spent on a duplicate.
+    beam_options must then be empty."""
+    if stochastic is not None:
+        if beam_options:
+            raise ValueError('consensus_search(stochastic=...) takes no beam options (%s): the candidates come from '
+                             'sample_without_replacement' % ', '.join(sorted(beam_options)))
+        if 'return_threshold' in stochastic:
+            raise ValueError('consensus_search(stochastic=...) reranks the captions themselves: return_threshold has no use here')
+        if not hasattr(model_or_ensemble, 'sample_without_replacement'):
+            raise ValueError('consensus_search(stochastic=...) takes one model: an ensemble does not sample without replacement')
+        ids, scores, lens = model_or_ensemble.sample_without_replacement(frames, regions, **stochastic)
+    else:
+        ids, scores, lens = model_or_ensemble.beam_search(frames, regions, **beam_options)
     return consensus_rerank(reward, ids, scores, lens, weights, temperature, n_best)

@@ -1,7 +1,7 @@
 """hipGraph capture and replay, in one place: entering and leaving the process's capture stream, the eager warm-up, capturing one
 graph or a chain of segments, dropping a capture whose body raised, staging inputs into the static buffers a graph reads --
-and the captured forms of inference built on it (GreedyGraph, SampleGraph, BeamGraph, NBestBeamGraph, EnsembleBeamGraph,
-ConsensusBeamGraph).  The Trainer (model.py), the GanTrainer (gan.py) and the SCSTTrainer (scst.py) capture through `capture` /
+and the captured forms of inference built on it (GreedyGraph, SampleGraph, BeamGraph, NBestBeamGraph, StochasticBeamGraph,
+EnsembleBeamGraph, ConsensusBeamGraph).  The Trainer (model.py), the GanTrainer (gan.py) and the SCSTTrainer (scst.py) capture through `capture` /
 `capture_segments`."""
 import torch
 
@@ -171,6 +171,29 @@ class NBestBeamGraph(_InferenceGraph):
 
     def _run(self):
         return self.model.beam_search(self.frames, self.regions, **self.options)
+
+
+class StochasticBeamGraph(_InferenceGraph):
+    """hipGraph-captured `model.sample_without_replacement(frames, regions, n, temperature, **options)` for one batch shape: encoder
+    and all max_words steps of stochastic beam search.  The seed is read from a device word, like SampleGraph's, so every replay
+    draws afresh; a replay with seed s gives the bits of the eager call with seed=s.  options: min_len, no_repeat_ngram,
+    return_threshold, fixed at capture.  Outputs are static buffers, valid until the next replay; nothing synchronises."""
+
+    def __init__(self, model, frames, regions, n=5, temperature=1.0, **options):
+        self.n, self.temperature, self.options = n, temperature, options
+        self.seed = torch.zeros(1, dtype=torch.int64, device=frames.device)
+        super().__init__(model, frames, regions)
+
+    def _run(self):
+        return self.model.sample_without_replacement(self.frames, self.regions, self.n, self.temperature, self.seed, **self.options)
+
+    @torch.no_grad()
+    def __call__(self, frames, regions, seed):
+        from .hip import copy_to_device
+        self._stage(frames, regions)
+        copy_to_device(self.seed, [int(seed)])
+        self.graph.replay()
+        return self.out
 
 
 class EnsembleBeamGraph(_InferenceGraph):

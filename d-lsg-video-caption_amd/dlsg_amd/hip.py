@@ -562,6 +562,21 @@ class HipOps(object):
         self._check(self.lib.dlsg_beam_select_hist(C.byref(a), _p(hist_in), _p(hist_out), hist_out.shape[1], int(t), int(no_repeat_ngram),
                                                    int(min_len), self._stream()), 'dlsg_beam_select_hist')
 
+    def beam_select_gumbel(self, logits, last, last_lp, pred, new_lp, back, rows, k, end, hist_in, hist_out, t, G_in, G_out,
+                           temperature=1.0, seed=0, site_sample=0, no_repeat_ngram=0, min_len=0, ended_count=None):
+        """`beam_select_hist` for stochastic beam search: the k new beams of a clip are the k largest perturbed values G (float64,
+        (B*k), two buffers like last_lp / new_lp), rows in sampling order; last_lp / new_lp are log-probs under the tempered model
+        renormalised over the unbanned words; the noise is `sample_embed`'s, keyed (seed, site_sample, ((t+1) R + r) V + j); seed an
+        int or a device word (see include/dlsg.h)."""
+        R, V = logits.shape
+        for G in (G_in, G_out):
+            assert G.dtype == torch.float64 and G.is_contiguous() and G.numel() == R, (G.dtype, G.shape)
+        a = self._beam_args(R, V, last, last_lp, pred, new_lp, back, rows, k, end, t == 0, ended_count, logits, (hist_in, hist_out))
+        sd, sp = _seed(seed)
+        self._check(self.lib.dlsg_beam_select_gumbel(C.byref(a), _p(hist_in), _p(hist_out), hist_out.shape[1], int(t), int(no_repeat_ngram),
+                                                     int(min_len), f32(temperature), u64(sd), sp, u32(site_sample), _p(G_in), _p(G_out),
+                                                     self._stream()), 'dlsg_beam_select_gumbel')
+
     def beam_select_ens(self, logits_list, weights, mode, last, last_lp, pred, new_lp, back, rows, k, end, hist_in, hist_out, t,
                         no_repeat_ngram=0, min_len=0, ended_count=None):
         """`beam_select_hist` for an ensemble: the candidates of beam row r are combined from logits_list[m][r], one (R, V) float32

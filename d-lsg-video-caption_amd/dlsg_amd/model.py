@@ -273,6 +273,19 @@ class _HipModel(_ArenaModule):
         return beam_search(self, visual_feats, region_feats, beam_size, n_best=n_best, length_penalty=length_penalty,
                            no_repeat_ngram=no_repeat_ngram, min_len=min_len, num_groups=num_groups, diversity_penalty=diversity_penalty)
 
+    def sample_without_replacement(self, visual_feats, region_feats, n=5, temperature=1.0, seed=None, min_len=0, no_repeat_ngram=0,
+                                   return_threshold=False):
+        """n (at most 8) DISTINCT captions per clip, an exact ordered sample without replacement from softmax(logits /
+        temperature) by stochastic beam search, entirely on the device: (ids (B, n, L) int64 padded with <end>, logp (B, n) float32
+        the captions' log-probabilities, lens (B, n) int64 counting the <end>), rows in sampling order -- row 0 is distributed as
+        one ordinary sample.  min_len, no_repeat_ngram as in `sample`: the model is renormalised over the words they leave.
+        return_threshold=True (n at most 7) adds (gumbel (B, n) float64, kappa (B,) float64) for `dlsg_amd.importance_weights`.
+        seed None draws the model's next seed, a given seed reproduces the draw.  The decode runs in eval mode whatever
+        `self.training` is (`beam.stochastic_nbest`); nothing synchronises with the host."""
+        from .beam import stochastic_nbest
+        return stochastic_nbest(self, visual_feats, region_feats, n=n, temperature=temperature, seed=seed, min_len=min_len,
+                                no_repeat_ngram=no_repeat_ngram, return_threshold=return_threshold)
+
     def _draw_coins(self, L, infer, tf_ratio):
         # reference draws one coin per step only when not inferring (layer.py:432)
         if infer:

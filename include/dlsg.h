@@ -881,6 +881,29 @@ int dlsg_beam_select_ens(const dlsg_beam_select_args* a, const float* const* log
 int dlsg_beam_select_groups(const dlsg_beam_select_args* a, const float* const* logits, const int64_t* ld, const float* w,
                             const float* logw, int M, int mode, const int64_t* hist_in, int64_t* hist_out, int L, int t,
                             int no_repeat_ngram, int min_len, int groups, float diversity, void* stream);
+/* dlsg_beam_select_hist for stochastic beam search (Kool, van Hoof & Welling 2019): the step that makes the k beams of a clip an
+ * ordered sample WITHOUT replacement from the model.  a, hist_in / hist_out, L, t, no_repeat_ngram, min_len as dlsg_beam_select_hist
+ * takes them, but last_lp / new_lp carry phi, the float32 log-prob of the prefix under the tempered model renormalised over the
+ * unbanned classes, and G_in / G_out (B*k) float64, two buffers used ping-pong like them, carry the prefix's perturbed value.  A
+ * live row r with phi = last_lp[r], T = G_in[r] (step 0: only the clip's first row is read, phi = 0 and T = the root's own Gumbel(0)
+ * noise, in float64 from the hash keyed (seed, site_sample, r * V) -- a root pinned to 0 would draw the same captions but condition
+ * the largest perturbed value on being 0, and the threshold would no longer give unbiased importance weights): z_j = logits[r, j] *
+ * (1 / temperature) in float32; a banned class, a NaN and a -inf logit count as -inf; lse = the log-sum-exp of z over the others, in
+ * one pass with an online (max m, sum s); key_j = z_j - log(-log u_j), the float32 key of dlsg_sample_embed, u_j from the counter
+ * hash keyed (seed, site_sample, ((t+1) * B*k + r) * V + j) -- with k == 1 the key that call ranks by at row0 = (t+1) * B, so the
+ * one-beam search draws its word.  The row's k largest keys (ties to the lower class) are its children; for those only, in float64
+ * with the noise of the same 24 hash bits: g_j = phi + (z_j - lse) + noise_j, Z = their maximum, and
+ *   v = T - g_j + log1mexp(g_j - Z),  G_j = T - max(0, v) - log1p(exp(-|v|)),  log1mexp(a) = a > -ln 2 ? log(-expm1(a)) : log1p(-exp(a))
+ * -- the children's perturbed values given that their maximum is T; the largest child gets T exactly.  A child's phi is last_lp +
+ * ((z_j - m) - log s) in float32, the log-prob dlsg_sample_embed reports.  A row that has ended offers `end` with its phi and its T
+ * unchanged.  The clip's k new beams are the k largest G_j among the k*k candidates (row, then rank), larger first, ties to the
+ * lower candidate, so the output rows of a clip are in sampling order; with fewer than k finite candidates a slot takes phi = -inf
+ * and G = -inf.  Out: pred, new_lp, G_out, back, rows, hist_out, ended_count.  seed_ptr (optional, device) is added to seed at run
+ * time: a replayed graph draws afresh.  One workgroup per clip, one wave per row; no atomics but ended_count's; deterministic.
+ * EINVAL for what dlsg_beam_select_hist refuses, temperature <= 0 or NaN, G_out NULL, t > 0 with G_in NULL or G_in == G_out. */
+int dlsg_beam_select_gumbel(const dlsg_beam_select_args* a, const int64_t* hist_in, int64_t* hist_out, int L, int t,
+                            int no_repeat_ngram, int min_len, float temperature, uint64_t seed, const uint64_t* seed_ptr,
+                            uint32_t site_sample, const double* G_in, double* G_out, void* stream);
 /* After the last step: the n <= k best beams of every clip by score = lp / len^alpha (computed in double, stored as float),
  * descending, ties to the lower beam.  hist (B*k, L) the final history, lp (B*k) the final log-probs; len = tokens up to and
  * including the first `end`, L without one.  Out: ids (B, n, L) int64, scores (B, n), lens (B, n) int64.  One wave per clip. */
