@@ -8,20 +8,13 @@
 
 #include "common.hpp"
 #include "dlsg.h"
+#include "ngram.hpp"
+
+using namespace dlsg;
 
 namespace {
 
-constexpr int CIDER_THREADS = 256;      // wave k holds the n-grams of order k + 1: n <= 4
-constexpr int CIDER_MAXL = 64;          // lane i holds word position i
 constexpr int CIDER_STAGE = 2048;       // reference entries staged in LDS per pass (16 KiB keys + 16 KiB weights)
-constexpr uint32_t CIDER_NONE = 0xFFFFu;
-
-// every lane gets the same bits: a butterfly adds the same two partial sums in every lane (a + b == b + a)
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
 
 // index of `key` in keys[0, n) (sorted ascending), -1 if absent; reads only inside [0, n)
 __device__ __forceinline__ int64_t find_key(const uint64_t* keys, int64_t n, uint64_t key) {
@@ -34,11 +27,12 @@ __device__ __forceinline__ int64_t find_key(const uint64_t* keys, int64_t n, uin
     return lo < n && keys[lo] == key ? lo : -1;
 }
 
-// One workgroup per row.  Lane i of every wave holds word i; wave k builds the row's order-(k + 1) n-grams (position i = lane),
-// counts each one's occurrences, and keeps it at its first position only.  Per reference of the row's clip each kept n-gram
+// One workgroup per row.  The row front end (RowNgrams, ngram.hpp) gives lane i of wave k the order-(k + 1) n-gram at position
+// i, its count, and whether it is kept (its first position); every kept n-gram weighs in the norm, one with a word outside the
+// vocabulary is looked up nowhere.  Per reference of the row's clip each kept n-gram
 // looks itself up in the reference's sorted entries (staged in LDS) and adds min(w_h, w_r) w_r, divided by the two norms when
 // both are nonzero, times the length penalty.  The n per-order sums are added in order by one thread.
-__global__ __launch_bounds__(CIDER_THREADS) void cider_d_kernel(const int64_t* __restrict__ ids, int64_t ld, int L,
+__global__ __launch_bounds__(NGRAM_THREADS) void cider_d_kernel(const int64_t* __restrict__ ids, int64_t ld, int L,
                                                                 const int32_t* __restrict__ clip_idx, int64_t end_id,
                                                                 const dlsg_cider_tables t, double* __restrict__ scores) {
     __shared__ uint64_t skey[CIDER_STAGE];
@@ -54,37 +48,13 @@ __global__ __launch_bounds__(CIDER_THREADS) void cider_d_kernel(const int64_t* _
         if (threadIdx.x == 0) scores[row] = NAN;
         return;
     }
-    // the row's words (decode_tokens): those before the first end_id, all L without one
     const int64_t id = lane < L ? ids[(int64_t)row * ld + lane] : end_id;
-    const unsigned long long ends = __ballot(lane >= L || id == end_id);
-    const int len = ends ? __builtin_ctzll(ends) : CIDER_MAXL;
-    const bool bad = id < 0 || id >= t.vocab;                 // outside the vocabulary: matches nothing, never indexes a table
-    const uint32_t w = bad ? CIDER_NONE : (uint32_t)id;
-
-    uint64_t key = 0;
-    bool kbad = false;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const uint32_t wj = (uint32_t)__shfl((int)w, (lane + j) & 63, 64);
-        const int bj = __shfl((int)bad, (lane + j) & 63, 64);
-        const bool used = j <= k;
-        key |= (uint64_t)(used ? wj : CIDER_NONE) << (16 * j);
-        kbad |= used && bj;
-    }
+    const RowNgrams g(id, L, end_id, t.vocab, lane, k);
+    const int len = g.len, tf = g.tf;
+    const uint64_t key = g.key;
     const bool live = k < n;                                  // wave-uniform
-    const bool active = live && lane + k < len;
-    // term frequency, and whether this is the n-gram's first position (an n-gram with a word outside the vocabulary keeps the
-    // 0xFFFF of that word in a used slot: equal keys within one order still mean equal word sequences)
-    int tf = 0;
-    bool first = active;
-    for (int j = 0; j < CIDER_MAXL; ++j) {
-        const uint64_t kj = __shfl(key, j, 64);
-        if (j + k < len && kj == key) {
-            ++tf;
-            if (j < lane) first = false;
-        }
-    }
-    const bool look = first && !kbad;                         // a key with a bad word may alias a shorter n-gram's: no lookups
+    const bool first = live && g.first;
+    const bool look = first && !g.kbad;                       // a key with a bad word may alias a shorter n-gram's: no lookups
     double idf = t.log_n;                                     // not in the corpus: df = 0, max(1, df) = 1
     if (look && t.n_grams > 0) {
         const int64_t p = find_key(t.gram_keys, t.n_grams, key);
@@ -104,7 +74,7 @@ __global__ __launch_bounds__(CIDER_THREADS) void cider_d_kernel(const int64_t* _
         const int64_t cnt = t.ref_off[r1] - e0;
         const bool staged = cnt <= CIDER_STAGE;
         if (staged) {
-            for (int64_t i = threadIdx.x; i < cnt; i += CIDER_THREADS) {
+            for (int64_t i = threadIdx.x; i < cnt; i += NGRAM_THREADS) {
                 skey[i] = t.ent_keys[e0 + i];
                 sw[i] = t.ent_w[e0 + i];
             }
@@ -167,29 +137,12 @@ __global__ __launch_bounds__(256) void scst_advantage_kernel(const double* __res
         sb += base;
         sl += (double)lens[i];
     }
-    sr = wave_sum_f64(sr);
-    sb = wave_sum_f64(sb);
-    sl = wave_sum_f64(sl);
-    const int wv = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) {
-        red[0][wv] = sr;
-        red[1][wv] = sb;
-        red[2][wv] = sl;
-    }
+    block256_put(sr, red[0]);
+    block256_put(sb, red[1]);
+    block256_put(sl, red[2]);
     __syncthreads();
-    if (threadIdx.x < 3) {
-        const double* v = red[threadIdx.x];
-        stats[threadIdx.x] = ((v[0] + v[1]) + (v[2] + v[3])) / (double)N;
-    }
+    if (threadIdx.x < 3) stats[threadIdx.x] = block256_get(red[threadIdx.x]) / (double)N;
 }
-
-// lane `j`'s value of v, j wave-uniform: two v_readlane, no trip through the LDS crossbar (unlike __shfl with a register index)
-__device__ __forceinline__ uint64_t lane_u64(uint64_t v, int j) {
-    const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, j);
-    const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(v >> 32), j);
-    return (uint64_t)hi << 32 | lo;
-}
-__device__ __forceinline__ double lane_f64(double v, int j) { return __longlong_as_double((long long)lane_u64((uint64_t)__double_as_longlong(v), j)); }
 
 // find_key for NQ keys in lockstep (n >= 1): the halving lower bound probes at a sequence of lengths that is the same for every
 // key, so the NQ loads of a step do not depend on one another and are in flight together; reads only inside [0, n)
@@ -215,29 +168,27 @@ constexpr int CONS_MAXN = 32;           // candidates per clip: 32 x 4 orders x 
 
 // dynamic LDS of cider_consensus_kernel for n candidates: keys and weights [n][4][64], norms and per-order sums [n][4], weight,
 // utility row and expected utility [n], length [n]; every carve offset is a multiple of 8, the total of 16
-constexpr int cons_lds_bytes(int n) { return (n * (4 * CIDER_MAXL * 16 + 4 * 8 * 2 + 3 * 8 + 4) + 15) & ~15; }
+constexpr int cons_lds_bytes(int n) { return (n * (4 * NGRAM_MAXL * 16 + 4 * 8 * 2 + 3 * 8 + 4) + 15) & ~15; }
 
 // One workgroup per clip, its n candidates' tf-idf vectors staged in LDS.
-// Phase A, per candidate: cider_d_kernel's row front end -- lane i of wave k holds the order-(k + 1) n-gram at position i, its
-// count, whether this is its first position -- then the candidate's (key, count) entries, one per position (0 away from a first
-// position), and its length go to LDS; the counts become weights by a bisection for the idf in the corpus table, the entries
-// dealt over all threads; wave k sums the candidates' order-(k + 1) norms.  An id outside [0, vocab) is the word
-// 0xFFFF here as well, but it MATCHES itself (within the candidate and across candidates): only the corpus lookup is left out
-// for a key that holds it (a key with 0xFFFF in a used slot may equal a shorter n-gram's key, and keys are compared within one
-// order only).
+// Phase A, per candidate: the row front end (RowNgrams, ngram.hpp), then the candidate's (key, count) entries, one per position
+// (0 away from a first position), and its length go to LDS; the counts become weights by a bisection for the idf in the corpus
+// table, the entries dealt over all threads; wave k sums the candidates' order-(k + 1) norms.  A word outside the vocabulary
+// MATCHES itself here (within the candidate and across candidates, keys being compared within one order only): a `kbad` key
+// keeps its entry and only its corpus lookup is left out.
 // Phase B, per ordered pair (i, j): the lane holding position p of i scans j's entries of its order (one LDS read per lane, then
 // at most 64 lane reads) for its key; min(w_i, w_j) w_j is summed over the wave by a butterfly; thread j folds the orders
 // (norms, length penalty, x10 / n) into U[i][j]; thread 0 forms i's expected utility over j != i in index order.  Ranks are
 // counted at the end.
-__global__ __launch_bounds__(CIDER_THREADS) void cider_consensus_kernel(const int64_t* __restrict__ ids, int64_t ld, int n, int L,
+__global__ __launch_bounds__(NGRAM_THREADS) void cider_consensus_kernel(const int64_t* __restrict__ ids, int64_t ld, int n, int L,
                                                                         int64_t end_id, const dlsg_cider_tables t,
                                                                         const float* __restrict__ scores, double temperature,
                                                                         double* __restrict__ util, double* __restrict__ expected,
                                                                         int64_t* __restrict__ order) {
     extern __shared__ __attribute__((aligned(16))) char cons_smem[];
     uint64_t* skey = reinterpret_cast<uint64_t*>(cons_smem);
-    double* sw = reinterpret_cast<double*>(skey + n * 4 * CIDER_MAXL);
-    double* snorm = sw + n * 4 * CIDER_MAXL;
+    double* sw = reinterpret_cast<double*>(skey + n * 4 * NGRAM_MAXL);
+    double* snorm = sw + n * 4 * NGRAM_MAXL;
     double* stot = snorm + n * 4;
     double* sq = stot + n * 4;                                // weight of a candidate; -1: invalid
     double* surow = sq + n;
@@ -252,35 +203,12 @@ __global__ __launch_bounds__(CIDER_THREADS) void cider_consensus_kernel(const in
     for (int c = 0; c < n; ++c) {
         const int64_t id = next;                              // (the next candidate's words are on their way meanwhile)
         if (c + 1 < n && lane < L) next = ids[((int64_t)b * n + c + 1) * ld + lane];
-        const unsigned long long ends = __ballot(lane >= L || id == end_id);
-        const int len = ends ? __builtin_ctzll(ends) : CIDER_MAXL;
-        const bool bad = id < 0 || id >= t.vocab;             // one word outside the vocabulary: never indexes a table
-        const uint32_t w = bad ? CIDER_NONE : (uint32_t)id;
-        uint64_t key = 0;
-        bool kbad = false;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const uint32_t wj = (uint32_t)__shfl((int)w, (lane + j) & 63, 64);
-            const int bj = __shfl((int)bad, (lane + j) & 63, 64);
-            const bool used = j <= k;
-            key |= (uint64_t)(used ? wj : CIDER_NONE) << (16 * j);
-            kbad |= used && bj;
-        }
-        const bool active = live && lane + k < len;
-        int tf = 0;
-        bool first = active;
-        for (int j = 0; j < CIDER_MAXL; ++j) {
-            const uint64_t kj = lane_u64(key, j);
-            if (j + k < len && kj == key) {
-                ++tf;
-                if (j < lane) first = false;
-            }
-        }
+        const RowNgrams g(id, L, end_id, t.vocab, lane, k);
         if (live) {                                           // the count for now; negative: no corpus lookup for this key
-            skey[(c * 4 + k) * CIDER_MAXL + lane] = key;
-            sw[(c * 4 + k) * CIDER_MAXL + lane] = first ? (kbad ? -(double)tf : (double)tf) : 0.0;
+            skey[(c * 4 + k) * NGRAM_MAXL + lane] = g.key;
+            sw[(c * 4 + k) * NGRAM_MAXL + lane] = g.first ? (g.kbad ? -(double)g.tf : (double)g.tf) : 0.0;
         }
-        if (threadIdx.x == 0) slen[c] = len;
+        if (threadIdx.x == 0) slen[c] = g.len;
     }
     __syncthreads();
     // The idf lookups, dealt round-robin over the 256 threads, four to a thread at a time: captions are short, so a
@@ -289,19 +217,19 @@ __global__ __launch_bounds__(CIDER_THREADS) void cider_consensus_kernel(const in
     int maxlen = 0;
     for (int c = 0; c < n; ++c) maxlen = max(maxlen, slen[c]);
     const int total = n * no * maxlen;
-    for (int e0 = threadIdx.x; e0 < total; e0 += 4 * CIDER_THREADS) {
+    for (int e0 = threadIdx.x; e0 < total; e0 += 4 * NGRAM_THREADS) {
         int at[4];
         double tf[4];
         uint64_t key[4];
         int64_t pos[4];
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
-            const int e = e0 + q * CIDER_THREADS;
+            const int e = e0 + q * NGRAM_THREADS;
             at[q] = 0;
             tf[q] = 0.0;
             if (e < total) {
                 const int c = e / (no * maxlen), r = e - c * (no * maxlen);
-                at[q] = (c * 4 + r / maxlen) * CIDER_MAXL + r % maxlen;
+                at[q] = (c * 4 + r / maxlen) * NGRAM_MAXL + r % maxlen;
                 tf[q] = sw[at[q]];
             }
             key[q] = skey[at[q]];
@@ -319,7 +247,7 @@ __global__ __launch_bounds__(CIDER_THREADS) void cider_consensus_kernel(const in
     __syncthreads();
     if (live) {
         for (int c = 0; c < n; ++c) {
-            const double wh = sw[(c * 4 + k) * CIDER_MAXL + lane];
+            const double wh = sw[(c * 4 + k) * NGRAM_MAXL + lane];
             const double nh = sqrt(wave_sum_f64(wh * wh));
             if (lane == 0) snorm[c * 4 + k] = nh;
         }
@@ -343,12 +271,12 @@ __global__ __launch_bounds__(CIDER_THREADS) void cider_consensus_kernel(const in
     const double two_s2 = 2.0 * (t.sigma * t.sigma);
     for (int i = 0; i < n; ++i) {
         if (live) {
-            const uint64_t key = skey[(i * 4 + k) * CIDER_MAXL + lane];
-            const double wh = sw[(i * 4 + k) * CIDER_MAXL + lane];
+            const uint64_t key = skey[(i * 4 + k) * NGRAM_MAXL + lane];
+            const double wh = sw[(i * 4 + k) * NGRAM_MAXL + lane];
             for (int j = 0; j < n; ++j) {
                 const int m = __builtin_amdgcn_readfirstlane(slen[j]) - k;     // j's entries of this order: wave-uniform
-                const uint64_t kj = skey[(j * 4 + k) * CIDER_MAXL + lane];     // lane p holds j's entry p; those below m are read
-                const double wj = sw[(j * 4 + k) * CIDER_MAXL + lane];
+                const uint64_t kj = skey[(j * 4 + k) * NGRAM_MAXL + lane];     // lane p holds j's entry p; those below m are read
+                const double wj = sw[(j * 4 + k) * NGRAM_MAXL + lane];
                 double wr = 0.0;                              // at most one match has a nonzero weight: the sum is exact
                 for (int p = 0; p < m; ++p) {
                     const double wp = lane_f64(wj, p);
@@ -406,14 +334,20 @@ __global__ __launch_bounds__(CIDER_THREADS) void cider_consensus_kernel(const in
 
 #define ST(s) reinterpret_cast<hipStream_t>(s)
 
+// the tables every CIDEr-D kernel reads: the orders, the vocabulary and the corpus n-grams; need_refs: the references as well
+static bool cider_tables_ok(const dlsg_cider_tables* t, bool need_refs) {
+    if (!t || t->n < 1 || t->n > 4 || t->vocab < 1 || t->vocab > 65535 || t->n_grams < 0) return false;
+    if (t->n_grams > 0 && (!t->gram_keys || !t->gram_idf)) return false;
+    if (!need_refs) return true;
+    return t->n_clips >= 0 && !(t->n_clips > 0 && (!t->clip_off || !t->ref_off || !t->ref_norm || !t->ref_len));
+}
+
 extern "C" int dlsg_cider_d(const int64_t* ids, int64_t ld, int rows, int L, const int32_t* clip_idx, int64_t end_id,
                             const dlsg_cider_tables* t, double* scores, void* stream) {
     if (rows == 0) return DLSG_OK;
-    if (!t || !ids || !clip_idx || !scores || rows < 0 || L < 0 || L > CIDER_MAXL || (L > 0 && ld < L)) return DLSG_EINVAL;
-    if (t->n < 1 || t->n > 4 || t->vocab < 1 || t->vocab > 65535 || t->n_clips < 0 || t->n_grams < 0) return DLSG_EINVAL;
-    if (t->n_clips > 0 && (!t->clip_off || !t->ref_off || !t->ref_norm || !t->ref_len)) return DLSG_EINVAL;
-    if (t->n_grams > 0 && (!t->gram_keys || !t->gram_idf)) return DLSG_EINVAL;
-    hipLaunchKernelGGL(cider_d_kernel, dim3(rows), dim3(CIDER_THREADS), 0, ST(stream), ids, ld, L, clip_idx, end_id, *t, scores);
+    if (!ids || !clip_idx || !scores || rows < 0 || L < 0 || L > NGRAM_MAXL || (L > 0 && ld < L)) return DLSG_EINVAL;
+    if (!cider_tables_ok(t, true)) return DLSG_EINVAL;
+    hipLaunchKernelGGL(cider_d_kernel, dim3(rows), dim3(NGRAM_THREADS), 0, ST(stream), ids, ld, L, clip_idx, end_id, *t, scores);
     DLSG_CHECK_LAUNCH();
     return DLSG_OK;
 }
@@ -430,11 +364,9 @@ extern "C" int dlsg_scst_advantage(const double* rewards, const int64_t* lens, c
 extern "C" int dlsg_cider_consensus(const int64_t* ids, int64_t ld, int B, int n, int L, int64_t end_id, const dlsg_cider_tables* t,
                                     const float* scores, double temperature, double* util, double* expected, int64_t* order,
                                     void* stream) {
-    if (n < 1 || n > CONS_MAXN || L < 1 || L > CIDER_MAXL || B < 0) return DLSG_EINVAL;
+    if (n < 1 || n > CONS_MAXN || L < 1 || L > NGRAM_MAXL || B < 0) return DLSG_EINVAL;
     if (B == 0) return DLSG_OK;
-    if (!t || !ids || !expected || !order || ld < L || !(temperature > 0.0)) return DLSG_EINVAL;
-    if (t->n < 1 || t->n > 4 || t->vocab < 1 || t->vocab > 65535 || t->n_grams < 0) return DLSG_EINVAL;
-    if (t->n_grams > 0 && (!t->gram_keys || !t->gram_idf)) return DLSG_EINVAL;
+    if (!ids || !expected || !order || ld < L || !(temperature > 0.0) || !cider_tables_ok(t, false)) return DLSG_EINVAL;
     static std::once_flag once;
     static hipError_t attr = hipSuccess;
     std::call_once(once, [] {
@@ -442,7 +374,7 @@ extern "C" int dlsg_cider_consensus(const int64_t* ids, int64_t ld, int B, int n
                                    cons_lds_bytes(CONS_MAXN));
     });
     if (attr != hipSuccess) return DLSG_ELAUNCH;
-    hipLaunchKernelGGL(cider_consensus_kernel, dim3(B), dim3(CIDER_THREADS), cons_lds_bytes(n), ST(stream), ids, ld, n, L, end_id, *t,
+    hipLaunchKernelGGL(cider_consensus_kernel, dim3(B), dim3(NGRAM_THREADS), cons_lds_bytes(n), ST(stream), ids, ld, n, L, end_id, *t,
                        scores, temperature, util, expected, order);
     DLSG_CHECK_LAUNCH();
     return DLSG_OK;

@@ -75,6 +75,38 @@ __device__ __forceinline__ float block_max(float v, float* red) {
     return r;
 }
 
+// Fixed-order sums for the kernels that promise the same bits on every launch (no atomics).  The __shfl_xor butterfly adds the
+// same two partial sums in every lane (a + b == b + a), so every lane gets the same bits; T = double, int, long long.
+template <typename T>
+__device__ __forceinline__ T wave_sum_xor(T v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+__device__ __forceinline__ double wave_sum_f64(double v) { return wave_sum_xor(v); }
+// The sum over a workgroup of 256: the four waves' sums meet in `red` (one row of LDS per value) and fold as (r0 + r1) + (r2 + r3).
+// Several values share one barrier: block256_put each, __syncthreads(), block256_get in the threads that want a result.
+template <typename T>
+__device__ __forceinline__ void block256_put(T v, T (&red)[4]) {
+    v = wave_sum_xor(v);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+}
+template <typename T>
+__device__ __forceinline__ T block256_get(const T (&red)[4]) { return (red[0] + red[1]) + (red[2] + red[3]); }
+__device__ __forceinline__ double block256_sum_f64(double v, double (&red)[4]) {
+    block256_put(v, red);
+    __syncthreads();
+    return block256_get(red);
+}
+
+// lane `j`'s value of v, j wave-uniform: two v_readlane, no trip through the LDS crossbar (unlike __shfl with a register index)
+__device__ __forceinline__ uint64_t lane_u64(uint64_t v, int j) {
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, j);
+    const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(v >> 32), j);
+    return (uint64_t)hi << 32 | lo;
+}
+__device__ __forceinline__ double lane_f64(double v, int j) { return __longlong_as_double((long long)lane_u64((uint64_t)__double_as_longlong(v), j)); }
+
 __device__ __forceinline__ float sigmoidf_(float x) { return 1.f / (1.f + __expf(-x)); }
 
 // Counter-based dropout mask: keep iff hash(seed, site, idx) >= p.  Stateless, so the backward pass

@@ -8,53 +8,30 @@
 
 #include "common.hpp"
 #include "dlsg.h"
+#include "ngram.hpp"
+
+using namespace dlsg;
 
 namespace {
 
-constexpr int METRICS_THREADS = 256;            // wave k holds the n-grams of order k + 1
-constexpr int METRICS_MAXL = 64;                // lane i holds word position i
 constexpr int METRICS_STAGE = DLSG_METRICS_STAGE;   // reference words staged in LDS per pass
-constexpr uint32_t REF_OOV = 0xFFFFu;           // a reference word outside the vocabulary (no id reaches it: vocab <= 65535)
+constexpr uint32_t REF_OOV = NGRAM_NONE;        // a reference word outside the vocabulary (no id reaches it: vocab <= 65535)
 constexpr uint32_t HYP_BAD = 0x10000u;          // an id outside [0, vocab): no 16-bit reference word equals it
 
 struct mix_weights {
     double w[6];                                // base (CIDEr-D), BLEU-1..4, ROUGE_L
 };
 
-__device__ __forceinline__ int wave_sum_i32(int v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
-__device__ __forceinline__ long long wave_sum_i64(long long v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
-// lane `src` (wave-uniform) of a 64-bit value, to every lane
-__device__ __forceinline__ int64_t lane_i64(int64_t v, int src) {
-    const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, src);
-    const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)((uint64_t)v >> 32), src);
-    return (int64_t)(((uint64_t)hi << 32) | lo);
-}
-
-// One workgroup per row.  Lane i of every wave holds word i; wave k builds the row's order-(k + 1) n-grams (position i = lane),
-// counts each one's occurrences in the row and keeps it at its first position only.  The references of the row's clip pass
-// through LDS in pieces of whole references (at most 63, at most METRICS_STAGE words; one longer than that is read from HBM).
+// One workgroup per row.  The row front end (RowNgrams, ngram.hpp) gives lane i of wave k the order-(k + 1) n-gram at position
+// i and its count in the row; it is kept at its first position, and not at all with a word outside the vocabulary.  The
+// references of the row's clip pass through LDS in pieces of whole references (at most 63, at most METRICS_STAGE words; one
+// longer than that is read from HBM).
 // Per reference every wave takes the words 64 at a time into a register, slides its order's window over them and counts in
 // each lane the windows equal to the lane's n-gram; the count joins the clip (the maximum over the references) and the
 // reference's length joins the closest-length search.  Wave w also runs the bit-parallel LCS (Hyyro's form of
 // Allison-Dix: bit i of V is clear where the LCS grows at hypothesis word i) of references w, w + 4, ...  The four waves'
 // results meet in LDS and one thread does the float64 arithmetic of the host code.
-__global__ __launch_bounds__(METRICS_THREADS) void caption_metrics_kernel(
+__global__ __launch_bounds__(NGRAM_THREADS) void caption_metrics_kernel(
     const int64_t* __restrict__ ids, int64_t ld, int L, const int32_t* __restrict__ clip_idx, int64_t end_id,
     const int64_t* __restrict__ clip_off, const int64_t* __restrict__ ref_off, const uint16_t* __restrict__ ref_words, int n_clips,
     int vocab, const mix_weights mix, const double* __restrict__ base, double* __restrict__ scores, int32_t* __restrict__ stats,
@@ -75,36 +52,13 @@ __global__ __launch_bounds__(METRICS_THREADS) void caption_metrics_kernel(
         if (reward && threadIdx.x == 0) reward[row] = NAN;
         return;
     }
-    // the row's words (decode_tokens): those before the first end_id, all L without one
     const int64_t id = lane < L ? ids[(int64_t)row * ld + lane] : end_id;
-    const unsigned long long ends = __ballot(lane >= L || id == end_id);
-    const int len = ends ? __builtin_ctzll(ends) : METRICS_MAXL;
-    const bool bad = id < 0 || id >= vocab;                   // outside the vocabulary: matches nothing, never indexes a table
-    const uint32_t w = bad ? REF_OOV : (uint32_t)id;
-    const uint32_t hcode = (bad || lane >= len) ? HYP_BAD : (uint32_t)id;
-
-    uint64_t key = 0;
-    bool kbad = false;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const uint32_t wj = (uint32_t)__shfl((int)w, (lane + j) & 63, 64);
-        const int bj = __shfl((int)bad, (lane + j) & 63, 64);
-        const bool used = j <= k;
-        key |= (uint64_t)(used ? wj : REF_OOV) << (16 * j);
-        kbad |= used && bj;
-    }
+    const RowNgrams g(id, L, end_id, vocab, lane, k);
+    const int len = g.len, tf = g.tf;
+    const uint64_t key = g.key;
+    const bool first = g.first && !g.kbad;                    // an n-gram with a word outside the vocabulary matches no reference
+    const uint32_t hcode = (g.bad || lane >= len) ? HYP_BAD : (uint32_t)id;
     const uint64_t past = k < 3 ? ~0ull << (16 * (k + 1)) : 0ull;       // the key slots past the order, all ones
-    const int guess = len > k ? len - k : 0;
-    // the n-gram's count in the row, at its first position only; one with a word outside the vocabulary matches no reference
-    int tf = 0;
-    bool first = lane < guess && !kbad;
-    for (int j = 0; j < guess; ++j) {
-        const uint64_t kj = (uint64_t)lane_i64((int64_t)key, j);
-        if (kj == key) {
-            ++tf;
-            if (j < lane) first = false;
-        }
-    }
 
     int clip = 0;                                             // max over the references of the n-gram's count there
     int best_d = 0x7fffffff, best_len = 0;                    // closest reference length, shorter on ties (wave-uniform)
@@ -115,7 +69,7 @@ __global__ __launch_bounds__(METRICS_THREADS) void caption_metrics_kernel(
         // lane i holds the word offset of reference r + i: the piece is the run of whole references that fits the stage
         const int64_t qi = r + lane < re ? r + lane : re;
         const int64_t oi = ref_off[qi];
-        const int64_t e0 = lane_i64(oi, 0);
+        const int64_t e0 = (int64_t)lane_u64((uint64_t)oi, 0);
         const unsigned long long fits = __ballot(lane >= 1 && r + lane <= re && oi >= e0 && oi - e0 <= METRICS_STAGE) | 1ull;
         int nr = ~fits ? __builtin_ctzll(~fits) - 1 : 63;
         const bool staged = nr > 0;
@@ -124,7 +78,7 @@ __global__ __launch_bounds__(METRICS_THREADS) void caption_metrics_kernel(
         const int rel = di < 0 ? 0 : (di > 0x7fffffff ? 0x7fffffff : (int)di);    // where reference r + i starts in the piece
         const int cnt = __builtin_amdgcn_readlane(rel, nr);                       // the piece's words
         if (staged)
-            for (int i = threadIdx.x; i < cnt; i += METRICS_THREADS) sref[i] = ref_words[e0 + i];
+            for (int i = threadIdx.x; i < cnt; i += NGRAM_THREADS) sref[i] = ref_words[e0 + i];
         __syncthreads();
         // reference by reference, its words 64 at a time in a register: the window count in every wave, the LCS in one
         auto scan = [&](auto from_lds) {
@@ -182,7 +136,7 @@ __global__ __launch_bounds__(METRICS_THREADS) void caption_metrics_kernel(
     // the maximum of the quotients is the quotient of the maximal fraction: division rounds monotonically
     const double prec = len > 0 ? (double)prec_l / (double)len : 0.0;
     const double rec = (double)rec_l / (double)rec_m;
-    const int correct = wave_sum_i32(first ? (tf < clip ? tf : clip) : 0);
+    const int correct = wave_sum_xor(first ? (tf < clip ? tf : clip) : 0);
     if (lane == 0) {
         scorrect[k] = correct;
         sprec[k] = prec;
@@ -238,22 +192,14 @@ __global__ __launch_bounds__(256) void caption_corpus_kernel(const int32_t* __re
         sr += scores[(int64_t)i * 5 + 4];
         if (base) sb += base[i];
     }
-    const int wv = threadIdx.x >> 6;
 #pragma unroll
-    for (int j = 0; j < 10; ++j) {
-        const long long v = wave_sum_i64(s[j]);
-        if ((threadIdx.x & 63) == 0) ired[j][wv] = v;
-    }
-    sr = wave_sum_f64(sr);
-    sb = wave_sum_f64(sb);
-    if ((threadIdx.x & 63) == 0) {
-        fred[0][wv] = sr;
-        fred[1][wv] = sb;
-    }
+    for (int j = 0; j < 10; ++j) block256_put(s[j], ired[j]);
+    block256_put(sr, fred[0]);
+    block256_put(sb, fred[1]);
     __syncthreads();
     if (threadIdx.x == 0) {
         long long t[10];
-        for (int j = 0; j < 10; ++j) t[j] = (ired[j][0] + ired[j][1]) + (ired[j][2] + ired[j][3]);
+        for (int j = 0; j < 10; ++j) t[j] = block256_get(ired[j]);
         const double small = 1e-9, tiny = 1e-15;
         const double ratio = ((double)t[8] + tiny) / ((double)t[9] + small);
         double b = 1.0;
@@ -262,8 +208,8 @@ __global__ __launch_bounds__(256) void caption_corpus_kernel(const int32_t* __re
             const double sk = pow(b, 1.0 / (double)(kk + 1));
             out[kk] = ratio < 1.0 ? sk * exp(1.0 - 1.0 / ratio) : sk;
         }
-        out[4] = ((fred[0][0] + fred[0][1]) + (fred[0][2] + fred[0][3])) / (double)rows;
-        out[5] = base ? ((fred[1][0] + fred[1][1]) + (fred[1][2] + fred[1][3])) / (double)rows : NAN;
+        out[4] = block256_get(fred[0]) / (double)rows;
+        out[5] = base ? block256_get(fred[1]) / (double)rows : NAN;
     }
 }
 
@@ -276,14 +222,14 @@ extern "C" int dlsg_caption_metrics(const int64_t* ids, int64_t ld, int rows, in
                                     const double* weights, const double* base, double* scores, int32_t* stats, double* reward,
                                     void* stream) {
     if (rows == 0) return DLSG_OK;
-    if (!ids || !clip_idx || rows < 0 || L < 0 || L > METRICS_MAXL || (L > 0 && ld < L)) return DLSG_EINVAL;
+    if (!ids || !clip_idx || rows < 0 || L < 0 || L > NGRAM_MAXL || (L > 0 && ld < L)) return DLSG_EINVAL;
     if (vocab < 1 || vocab > 65535 || n_clips < 0) return DLSG_EINVAL;
     if (n_clips > 0 && (!clip_off || !ref_off || !ref_words)) return DLSG_EINVAL;
     if (reward && (!weights || (weights[0] != 0.0 && !base))) return DLSG_EINVAL;
     mix_weights mix = {{0.0, 0.0, 0.0, 0.0, 0.0, 0.0}};
     if (reward)
         for (int j = 0; j < 6; ++j) mix.w[j] = weights[j];
-    hipLaunchKernelGGL(caption_metrics_kernel, dim3(rows), dim3(METRICS_THREADS), 0, ST(stream), ids, ld, L, clip_idx, end_id, clip_off,
+    hipLaunchKernelGGL(caption_metrics_kernel, dim3(rows), dim3(NGRAM_THREADS), 0, ST(stream), ids, ld, L, clip_idx, end_id, clip_off,
                        ref_off, ref_words, n_clips, vocab, mix, base, scores, stats, reward);
     DLSG_CHECK_LAUNCH();
     return DLSG_OK;

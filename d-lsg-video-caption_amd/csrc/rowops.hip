@@ -793,19 +793,7 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const 
 }
 
 // ------------------------------------------------------------------------------------------------ gradient clipping
-// Wave- and block-wide float64 sums in a fixed order (no atomics): the same input gives the same bits on every launch.
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
-// blockDim.x == 256; `red` = 4 doubles of LDS; the result is valid in thread 0
-__device__ __forceinline__ double block256_sum_f64(double v, double* red) {
-    v = wave_sum_f64(v);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return (red[0] + red[1]) + (red[2] + red[3]);
-}
+// Wave- and block-wide float64 sums in a fixed order (no atomics, common.hpp): the same input gives the same bits on every launch.
 // slots[blockIdx.x] = this workgroup's share of sum g[i]^2 over g[0..n), squared and added in float64 (the square of a float is
 // exact there).  Grid = DLSG_GRAD_SUMSQ_SLOTS workgroups whatever n is; a workgroup without elements writes 0.  Ordinary loads:
 // the Adam launch behind it reads the same bytes.  16-byte loads over the aligned body, scalar head and tail, as adam_kernel.

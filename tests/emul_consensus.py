@@ -11,34 +11,22 @@ import torch
 
 from dlsg_amd import scoring as S
 from emul_groups import GroupsEmul
+from emul_ngram import find as _find, row_ngrams
 from test_scst_host import ScstEmul
-
-NONE = S.NGRAM_NONE
-
-
-def _find(keys, key):
-    p = int(np.searchsorted(keys, np.uint64(key)))
-    return p if p < len(keys) and keys[p] == np.uint64(key) else -1
 
 
 def candidate_vectors(tb, gram_keys, gram_idf, row, end_id):
     """phase A for one id row: ([per order {key: weight} in first-position order], [norm per order], bigram count)"""
-    n, V = tb.n, tb.V
-    hits = np.nonzero(row == end_id)[0]
-    ln = int(hits[0]) if len(hits) else len(row)
-    words = row[:ln]
-    bad = (words < 0) | (words >= V)
-    code = np.where(bad, NONE, words).astype(np.int64)
+    n, ln = tb.n, 0
     vecs, norms = [], []
     for k in range(n):
-        m = max(ln - k, 0)
-        keys = [S.pack_ngram([int(x) for x in code[i:i + k + 1]]) for i in range(m)]
+        ln, _, _, keys, kbad, first, tf = row_ngrams(row, end_id, tb.V, k)
         vec = {}
-        for i in range(m):
-            if keys.index(keys[i]) != i:
+        for i in range(len(keys)):
+            if not first[i]:
                 continue
-            p = -1 if bad[i:i + k + 1].any() else _find(gram_keys, keys[i])
-            vec[keys[i]] = keys.count(keys[i]) * (gram_idf[p] if p >= 0 else tb.log_n)
+            p = -1 if kbad[i] else _find(gram_keys, keys[i])
+            vec[keys[i]] = tf[i] * (gram_idf[p] if p >= 0 else tb.log_n)
         vecs.append(vec)
         norms.append(math.sqrt(sum(w * w for w in vec.values())))
     return vecs, norms, (max(ln - 1, 0) if n >= 2 else 0)

@@ -13,15 +13,12 @@ import torch
 
 import dlsg_amd
 from dlsg_amd import scoring as S
+from emul_ngram import np_tables, row_ngrams
 from test_cider_device_host import GOLD, OOV, CiderEmul, _spy, corpus_for, encode, host_words, random_corpus, vocab_of
 from test_scst_host import small_net
 
 HYP_BAD = 0x10000                       # the kernel's code of an id outside [0, V): no 16-bit reference word equals it
 M64 = (1 << 64) - 1
-
-
-def np_tables(tb):
-    return tb.clip_off.cpu().numpy(), tb.ref_off.cpu().numpy(), tb.ref_words.cpu().numpy().view(np.uint16).astype(np.int64)
 
 
 def lcs_bits(hyp, ref):
@@ -40,7 +37,7 @@ def emul_caption_metrics(tb, ids, clip_idx, end_id, weights=None, base=None):
     [0, V) dropped; per reference a window slides over its words and counts the windows equal to each kept n-gram, the clip is
     the maximum over the references; the closest reference length, shorter on ties; per reference the bit-parallel LCS against
     the row, best precision and best recall apart; then the float64 arithmetic of scoring.bleu / scoring.rouge_l."""
-    clip_off, ref_off, words = np_tables(tb)
+    clip_off, ref_off, words = (np_tables(tb)[k] for k in ('clip_off', 'ref_off', 'ref_words'))
     ids = ids.cpu().numpy()
     clip_idx = clip_idx.cpu().numpy()
     R, L = ids.shape
@@ -57,20 +54,16 @@ def emul_caption_metrics(tb, ids, clip_idx, end_id, weights=None, base=None):
                 reward[r] = float('nan')
             continue
         refs = [words[ref_off[q]:ref_off[q + 1]].tolist() for q in range(int(clip_off[c]), int(clip_off[c + 1]))]
-        row = ids[r]
-        hits = np.nonzero(row == end_id)[0]
-        ln = int(hits[0]) if len(hits) else L
-        code = [HYP_BAD if (x < 0 or x >= tb.V) else int(x) for x in row[:ln]]
         correct, guess = [0] * 4, [0] * 4
         for k in range(4):
-            g = guess[k] = max(0, ln - k)
-            grams = [tuple(code[i:i + k + 1]) for i in range(g)]
+            ln, bad, code, keys, kbad, first, tf = row_ngrams(ids[r], end_id, tb.V, k)
+            g = guess[k] = len(keys)
             for i in range(g):
-                if HYP_BAD in grams[i] or grams.index(grams[i]) != i:
+                if kbad[i] or not first[i]:
                     continue
-                tf = grams.count(grams[i])
-                clip = max(sum(1 for j in range(k, len(ref)) if tuple(ref[j - k:j + 1]) == grams[i]) for ref in refs)
-                correct[k] += min(tf, clip)
+                clip = max(sum(1 for j in range(k, len(ref)) if S.pack_ngram(ref[j - k:j + 1]) == keys[i]) for ref in refs)
+                correct[k] += min(tf[i], clip)
+        code = [HYP_BAD if b else int(x) for b, x in zip(bad, code)]
         best = min((abs(len(ref) - ln), len(ref)) for ref in refs)[1]
         stats[r] = correct + guess + [ln, best]
         b, ratio = 1.0, (ln + tiny) / (best + small)
@@ -336,7 +329,7 @@ def unk_case():
 def test_out_of_vocabulary_reference_word_does_not_match_a_sampled_unk():
     refs, vocab, vids, rows = unk_case()
     dm = emul_metrics(refs, vocab)
-    assert np_tables(dm)[2].tolist().count(S.REF_OOV) == 1
+    assert np_tables(dm)['ref_words'].tolist().count(S.REF_OOV) == 1
     got, stats, _ = check_rows(dm, vids, rows)
     cheat = dm.scores(['a'], ['a dog runs zebroid fast'])[0]
     assert stats[1, 0] == 4 and stats[1, 8] == 5 and got[1, 4] < cheat[4] - 1e-3 and got[1, 0] < cheat[0] - 1e-3
@@ -430,7 +423,7 @@ def test_table_invariants_and_index():
     refs['c2'] = refs['c2'][:1]
     vocab = vocab_of(words[:8])
     dm = S.DeviceCaptionMetrics(refs, vocab, device='cpu')
-    clip_off, ref_off, w = np_tables(dm)
+    clip_off, ref_off, w = (np_tables(dm)[k] for k in ('clip_off', 'ref_off', 'ref_words'))
     assert dm.clip_off.dtype == dm.ref_off.dtype == torch.int64 and dm.ref_words.dtype == torch.int16
     assert clip_off[0] == 0 and ref_off[0] == 0 and np.all(np.diff(clip_off) >= 1) and np.all(np.diff(ref_off) >= 1)
     assert clip_off[-1] == len(ref_off) - 1 == sum(len(r) for r in refs.values()) and ref_off[-1] == len(w) and dm.n_clips == 5

@@ -14,25 +14,11 @@ import torch
 import dlsg_amd
 from dlsg_amd import scoring as S
 from dlsg_amd.config import Vocabulary
+from emul_ngram import find as _find, np_tables, row_ngrams
 from test_scst_host import ScstEmul, small_net
 
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'scoring.json')
-NONE = S.NGRAM_NONE
 OOV = '<out-of-range-id>'               # the string an id outside [0, V) stands for in the host reference
-
-
-def np_tables(tb):
-    """the device tables as numpy arrays (keys as uint64)"""
-    a = {k: getattr(tb, k).cpu().numpy() for k in ('gram_keys', 'gram_idf', 'clip_off', 'ref_off', 'ref_norm', 'ref_len', 'ent_keys',
-                                                   'ent_w')}
-    a['gram_keys'] = a['gram_keys'].view(np.uint64)
-    a['ent_keys'] = a['ent_keys'].view(np.uint64)
-    return a
-
-
-def _find(keys, key):
-    p = int(np.searchsorted(keys, np.uint64(key)))
-    return p if p < len(keys) and keys[p] == np.uint64(key) else -1
 
 
 def emul_cider_d(tb, ids, clip_idx, end_id):
@@ -52,22 +38,13 @@ def emul_cider_d(tb, ids, clip_idx, end_id):
             out[r] = float('nan')
             continue
         rb, re = int(a['clip_off'][c]), int(a['clip_off'][c + 1])
-        row = ids[r]
-        hits = np.nonzero(row == end_id)[0]
-        ln = int(hits[0]) if len(hits) else L
-        words = row[:ln]
-        bad = (words < 0) | (words >= V)
-        code = np.where(bad, NONE, words).astype(np.int64)
-        lh = max(ln - 1, 0) if n >= 2 else 0
         tot = np.zeros(n)
         for k in range(n):
-            m = ln - k
-            if m <= 0:
+            ln, _, _, keys, kbad, first, tf = row_ngrams(ids[r], end_id, V, k)
+            lh = max(ln - 1, 0) if n >= 2 else 0
+            m = len(keys)
+            if m == 0:
                 continue
-            keys = [S.pack_ngram([int(x) for x in code[i:i + k + 1]]) for i in range(m)]
-            kbad = [bool(bad[i:i + k + 1].any()) for i in range(m)]
-            first = [keys.index(keys[i]) == i for i in range(m)]
-            tf = [keys.count(keys[i]) for i in range(m)]
             wh = np.zeros(m)
             for i in range(m):
                 if first[i]:
