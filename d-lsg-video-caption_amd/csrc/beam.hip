@@ -1,5 +1,5 @@
-// The beam-search step (gfx950): dlsg_beam_select and its variants with a token history, Gumbel-perturbed selection (stochastic
-// beam search), an ensemble of members and beam groups, and dlsg_beam_finalize.  One workgroup per batch item, one wave per live
+// The beam-search step (gfx950): dlsg_beam_select and its variants with a token history, lexical constraints (dynamic beam
+// allocation), Gumbel-perturbed selection (stochastic beam search), an ensemble of members and beam groups, and dlsg_beam_finalize.  One workgroup per batch item, one wave per live
 // beam (BeamSearch.search, allennlp_beamsearch.py:140-260 with per_node_beam_size == beam_size): log-softmax of the beam's logits
 // row, its top-k classes (a finished beam offers <end> at log-prob 0 and nothing else), then the top-k of the k*k summed
 // candidates, back-pointers and the row indices that reorder the recurrent state.  Ties resolve to the lower index.  The step kernels are compositions of the
@@ -110,6 +110,59 @@ __global__ __launch_bounds__(64 * K) void beam_select_gumbel_kernel(const dlsg_b
     }
     __syncthreads();
     if (w == 0) beam_flat_merge<K, true, double>(a, nbeam, lane, cand_g, cand_cls, hist_in, hist_out, L, t, cand_lp, G_out);
+}
+
+// Lexically constrained beam search (dlsg_beam_select_cons): beam_select_hist_kernel's step with dynamic beam allocation.  Phase 0
+// stages the clip's C * W set entries in LDS (an id outside [0, V) as -1).  Phase 1, wave w for row w: the constraints the row has
+// met, from its history (beam_row_met); the ban list with `end` added while a constraint is unmet (beam_ban_list bans `end` below a
+// minimum length: an unmet row's is t + 1); list A as beam_select_hist_kernel offers it, and list B, the best word of every unmet
+// constraint (beam_offer_constraints).  Phase 2, wave 0: beam_bank_merge.  C = 0 gives the bits of beam_select_hist_kernel.
+template <int K>
+__global__ __launch_bounds__(64 * K) void beam_select_cons_kernel(const dlsg_beam_select_args a, const int64_t* __restrict__ hist_in,
+                                                                    int64_t* __restrict__ hist_out, int L, int t, int g, int min_len,
+                                                                    const int64_t* __restrict__ cons, int C, int W,
+                                                                    int32_t* __restrict__ met_out) {
+    __shared__ float cand_lp[K * K];
+    __shared__ int cand_cls[K * K];
+    __shared__ float cons_lp[K * DLSG_CONS_MAX];
+    __shared__ int cons_cls[K * DLSG_CONS_MAX];
+    __shared__ int hist[K][BEAM_MAXL];
+    __shared__ int ban[K][BEAM_MAXL + 1];
+    __shared__ int nban[K];
+    __shared__ int cons_s[CONS_SLOTS];
+    __shared__ unsigned met_s[K];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    if ((int)threadIdx.x < C * W) {
+        const int64_t id = cons[(int64_t)blockIdx.x * (C * W) + threadIdx.x];
+        cons_s[threadIdx.x] = id >= 0 && id < a.V ? (int)id : -1;
+    }
+    __syncthreads();
+    const int nbeam = a.first ? 1 : K;
+    const int64_t row = (int64_t)blockIdx.x * K + w;
+    const bool ended = !a.first && a.last[row] == a.end;
+    const unsigned met = beam_row_met(hist_in, row, L, t, cons_s, C, W);
+    const unsigned unmet = beam_cons_present(cons_s, C, W) & ~met;
+    if (lane == 0) met_s[w] = met;
+    beam_row_bans(hist_in, row, L, t, g, unmet ? t + 1 : min_len, a.end, w < nbeam && !ended, hist, ban, nban);
+    if (w < nbeam) {
+        const float base = a.first ? 0.f : a.last_lp[row];
+        if (ended) {
+            beam_offer_ended<K>(a, lane, base, cand_lp + w * K, cand_cls + w * K);
+            if (lane < C) { cons_lp[w * C + lane] = -INFINITY; cons_cls[w * C + lane] = 0; }
+        } else {
+            float lse, bv[K];
+            int bi[K];
+            beam_row_topk<K, true>(a.logits + row * a.ld, a.V, lane, lse, bv, bi, ban[w], nban[w]);
+            beam_offer_constraints<K>(a.logits + row * a.ld, lane, cons_s, C, W, unmet, ban[w], nban[w], bi, lse, base, cons_lp + w * C,
+                                      cons_cls + w * C);
+#pragma unroll
+            for (int c = 0; c < K; ++c) bv[c] -= lse;
+            beam_offer_live<K>(lane, bv, bi, base, cand_lp + w * K, cand_cls + w * K);
+        }
+    }
+    __syncthreads();
+    if (w == 0)
+        beam_bank_merge<K>(a, nbeam, lane, cand_lp, cand_cls, cons_lp, cons_cls, met_s, cons_s, C, W, hist_in, hist_out, L, t, met_out);
 }
 
 // Phase 1 of the ensemble step and of the group step, wave w for row w: beam_select_hist_kernel's, but a live beam's candidates
@@ -294,6 +347,17 @@ extern "C" int dlsg_beam_select_hist(const dlsg_beam_select_args* a, const int64
     if (!beam_args_ok(a) || !beam_hist_ok(a, hist_in, hist_out, L, t, no_repeat_ngram, min_len)) return DLSG_EINVAL;
     if (a->B == 0) return DLSG_OK;
     BEAM_LAUNCH(beam_select_hist_kernel, hist_in, hist_out, L, t, no_repeat_ngram, min_len);
+    DLSG_CHECK_LAUNCH();
+    return DLSG_OK;
+}
+extern "C" int dlsg_beam_select_cons(const dlsg_beam_select_args* a, const int64_t* hist_in, int64_t* hist_out, int L, int t,
+                                     int no_repeat_ngram, int min_len, const int64_t* cons, int C, int W, int32_t* met_out, void* stream) {
+    if (!beam_args_ok(a) || !beam_hist_ok(a, hist_in, hist_out, L, t, no_repeat_ngram, min_len)) return DLSG_EINVAL;
+    if (C < 0 || C > DLSG_CONS_MAX || (C > 0 && (W < 1 || W > DLSG_CONS_ALT || !cons))) return DLSG_EINVAL;
+    if (a->B == 0) return DLSG_OK;
+    if (!cons) C = 0;
+    if (C == 0) W = 1;
+    BEAM_LAUNCH(beam_select_cons_kernel, hist_in, hist_out, L, t, no_repeat_ngram, min_len, cons, C, W, met_out);
     DLSG_CHECK_LAUNCH();
     return DLSG_OK;
 }

@@ -289,6 +289,72 @@ __device__ __forceinline__ void beam_offer_gumbel(const float* x, int V, int lan
     }
 }
 
+// ------------------------------------------------------------------------------------------------ lexical constraints
+// A clip's constraints are C sets of W word ids, staged in LDS as cons[c * W + w] with -1 for padding (C * W <= 64: one lane per
+// entry).  Bit c of a mask stands for constraint c.
+constexpr int CONS_SLOTS = DLSG_CONS_MAX * DLSG_CONS_ALT;
+
+// the constraints that hold `cls` as a valid entry (cls < 0: none).  Every lane reads the same entry: LDS broadcasts.
+__device__ __forceinline__ unsigned beam_cons_of(const int* cons, int C, int W, int cls) {
+    unsigned m = 0;
+    for (int c = 0; c < C; ++c)
+        for (int w = 0; w < W; ++w) m |= (cls >= 0 && cons[c * W + w] == cls) ? 1u << c : 0u;
+    return m;
+}
+// the constraints with a valid entry
+__device__ __forceinline__ unsigned beam_cons_present(const int* cons, int C, int W) {
+    unsigned m = 0;
+    for (int c = 0; c < C; ++c)
+        for (int w = 0; w < W; ++w) m |= cons[c * W + w] >= 0 ? 1u << c : 0u;
+    return m;
+}
+
+// The constraints a row has met, ONE wave, to every lane: lane i holds token i of the row's history (i < t), and per constraint a
+// ballot over "the token is an entry of the set".  A function of the history row alone, so the search carries no mask along.
+__device__ __forceinline__ unsigned beam_row_met(const int64_t* __restrict__ hist_in, int64_t row, int L, int t, const int* cons, int C,
+                                                 int W) {
+    const int lane = threadIdx.x & 63;
+    const unsigned mine = beam_cons_of(cons, C, W, lane < t ? (int)hist_in[row * L + lane] : -1);
+    unsigned met = 0;
+    for (int c = 0; c < C; ++c) met |= __ballot((mine >> c) & 1u) ? 1u << c : 0u;
+    return met;
+}
+
+// A live row's list B, ONE wave: per constraint c of `unmet` the best word of its set -- lane c * W + w reads the logit of entry w;
+// a padding entry, a banned word, a -inf and a NaN logit are out; larger logit first, ties to the lower class -- offered at
+// (x - lse) + base, the float32 operations of list A.  The slot is empty (-inf) for a constraint that is met or absent or has no
+// such word, and for a class that is already in the row's list A (bi) or in an earlier slot of the row: the clip would get the
+// same beam twice.  lp / cls: the row's C slots.
+template <int K>
+__device__ __forceinline__ void beam_offer_constraints(const float* x, int lane, const int* cons, int C, int W, unsigned unmet,
+                                                       const int* ban, int nban, const int (&bi)[K], float lse, float base, float* lp,
+                                                       int* cls) {
+    const int id = lane < C * W ? cons[lane] : -1;
+    const int mine = lane / W;
+    float v = -INFINITY;
+    if (id >= 0 && ((unmet >> mine) & 1u)) {
+        const float xv = x[id];
+        bool ok = xv > -INFINITY;                              // (NaN fails)
+        for (int q = 0; q < nban; ++q) ok &= ban[q] != id;
+        v = ok ? xv : -INFINITY;
+    }
+    int mypick = -1;                                           // lane c: the class in slot c
+    for (int c = 0; c < C; ++c) {
+        float bv = mine == c ? v : -INFINITY;
+        int bc = bv > -INFINITY ? id : 0x7fffffff;
+        wave_argmax(bv, bc);
+        bool have = bc != 0x7fffffff;
+#pragma unroll
+        for (int q = 0; q < K; ++q) have &= bi[q] != bc;
+        have &= __ballot(lane < c && mypick == bc) == 0ull;
+        if (lane == c) {
+            mypick = have ? bc : -1;
+            lp[c] = have ? (bv - lse) + base : -INFINITY;
+            cls[c] = have ? bc : 0;
+        }
+    }
+}
+
 // ------------------------------------------------------------------------------------------------ the clip's K best
 // Row o of hist_out (B*k, L): the parent's row of hist_in up to t, the chosen class at t, `end` behind it (step 0 writes whole
 // rows, so the search fills its own buffers).  One wave.
@@ -330,6 +396,77 @@ __device__ __forceinline__ void beam_flat_merge(const dlsg_beam_select_args& a, 
             a.rows[o] = (int64_t)b * k + bi / k;
         }
         if constexpr (HIST) beam_write_hist(hist_in, hist_out, o, (int64_t)b * k + bi / k, L, t, lane, cls, a.end);
+        n_end += cls == a.end;
+    }
+    if (lane == 0 && a.ended_count) atomicAdd(a.ended_count, n_end);
+}
+
+// Dynamic beam allocation (Post & Vilar 2018) over the clip's candidates, by wave 0.  Lane i holds two slots: candidate i of list A
+// (row, then rank; index i) and candidate i of list B (row, then constraint; index 64 + i).  A candidate is a value above -inf
+// (a NaN is none); its mask is its parent's met mask and the constraints of its class, its bank the mask's population count.
+// Rounds until K output slots are filled or no candidate is left: bank C down to 0, the best candidate left in the bank -- larger
+// value first, ties to the lower index -- takes the next output slot; an empty bank (seen by ballot) is skipped.  A slot q left
+// over takes candidate q of list A at log-prob -inf, as beam_flat_merge fills it.  With one bank the picks are beam_flat_merge's.
+template <int K>
+__device__ __forceinline__ void beam_bank_merge(const dlsg_beam_select_args& a, int nbeam, int lane, const float* a_lp, const int* a_cls,
+                                                const float* b_lp, const int* b_cls, const unsigned* met, const int* cons, int C, int W,
+                                                const int64_t* __restrict__ hist_in, int64_t* __restrict__ hist_out, int L, int t,
+                                                int32_t* __restrict__ met_out) {
+    const int b = blockIdx.x, Cd = C > 0 ? C : 1;
+    float v0 = lane < nbeam * K ? a_lp[lane] : -INFINITY;
+    float v1 = lane < nbeam * C ? b_lp[lane] : -INFINITY;
+    unsigned m0 = 0, m1 = 0;
+    int bank0 = -1, bank1 = -1;                               // -1: no candidate (never one, or taken)
+    if (v0 > -INFINITY) {
+        m0 = met[lane / K] | beam_cons_of(cons, C, W, a_cls[lane]);
+        bank0 = __popc(m0);
+    }
+    if (v1 > -INFINITY) {
+        m1 = met[lane / Cd] | beam_cons_of(cons, C, W, b_cls[lane]);
+        bank1 = __popc(m1);
+    }
+    int filled = 0, n_end = 0;
+    for (bool any = true; any && filled < K;) {
+        any = false;
+        for (int bank = C; bank >= 0 && filled < K; --bank) {
+            if ((__ballot(bank0 == bank) | __ballot(bank1 == bank)) == 0ull) continue;
+            float bv = -INFINITY;
+            int bi = 0x7fffffff;
+            if (bank0 == bank && (bank1 != bank || v0 >= v1)) { bv = v0; bi = lane; }
+            else if (bank1 == bank) { bv = v1; bi = 64 + lane; }
+            wave_argmax(bv, bi);
+            if (bi == lane) bank0 = -1;
+            if (bi == 64 + lane) bank1 = -1;
+            const bool listb = bi >= 64;
+            const int j = bi & 63;
+            const int cls = listb ? b_cls[j] : a_cls[j];
+            const int par = listb ? j / Cd : j / K;
+            const unsigned mask = __shfl(listb ? m1 : m0, j, 64);
+            const int64_t o = (int64_t)b * K + filled;
+            if (lane == 0) {
+                a.pred[o] = cls;
+                a.new_lp[o] = bv;
+                a.back[o] = par;
+                a.rows[o] = (int64_t)b * K + par;
+                if (met_out) met_out[o] = (int32_t)mask;
+            }
+            beam_write_hist(hist_in, hist_out, o, (int64_t)b * K + par, L, t, lane, cls, a.end);
+            n_end += cls == a.end;
+            ++filled;
+            any = true;
+        }
+    }
+    for (; filled < K; ++filled) {
+        const int cls = a_cls[filled];
+        const int64_t o = (int64_t)b * K + filled;
+        if (lane == 0) {
+            a.pred[o] = cls;
+            a.new_lp[o] = -INFINITY;
+            a.back[o] = 0;
+            a.rows[o] = (int64_t)b * K;
+            if (met_out) met_out[o] = 0;
+        }
+        beam_write_hist(hist_in, hist_out, o, (int64_t)b * K, L, t, lane, cls, a.end);
         n_end += cls == a.end;
     }
     if (lane == 0 && a.ended_count) atomicAdd(a.ended_count, n_end);

@@ -12,6 +12,8 @@ the host does not synchronise inside the loop except for the early-exit test eve
 blocking and a minimum length, with no host synchronisation at all (`beam_select_hist` carries every beam's tokens along, so
 there is no back-trace; `beam_finalize` ranks the beams).  `ensemble_nbest` is that search run by several models at once: each
 member steps its own state, `beam_select_ens` combines their logits and chooses the beams (`ensemble.Ensemble`).
+`constrained_nbest` is `beam_nbest` whose captions must contain given words: `beam_select_cons` shares the beams out over the
+banks "constraints met" (dynamic beam allocation) and recomputes what a beam has met from its token history.
 """
 import torch
 
@@ -317,6 +319,122 @@ def importance_weights(logp, kappa):
     that the caption's perturbed value exceeds kappa; sum_i w_i f(y_i) estimates E_p[f].  float64 (B, n)."""
     phi = logp.double()
     return phi.exp() / -torch.expm1(-(phi - kappa.double().unsqueeze(1)).exp())
+
+
+MAX_CONSTRAINTS, MAX_ALTERNATIVES = 8, 8          # DLSG_CONS_MAX, DLSG_CONS_ALT
+
+
+def pack_constraints(per_clip, vocab, device=None, skip_unknown=False):
+    """The constraint tensor of `constrained_nbest`: (B, C, W) int64 padded with -1.  per_clip: for every clip a list of
+    constraints, each a word, a word id or a list of alternatives (words or ids) of which the caption must contain one.
+    ValueError for more than 8 constraints per clip or 8 alternatives per constraint, for <end>, <start> or <pad> in a set, and
+    for a word outside the vocabulary -- unless skip_unknown: then the alternative is dropped, and a constraint left with none is
+    absent."""
+    special = {vocab(w) for w in ('<end>', '<start>', '<pad>') if w in vocab.word2idx}
+    packed = []
+    for b, clip in enumerate(per_clip):
+        if len(clip) > MAX_CONSTRAINTS:
+            raise ValueError('clip %d: %d constraints, at most %d per clip' % (b, len(clip), MAX_CONSTRAINTS))
+        sets = []
+        for con in clip:
+            alts = list(con) if isinstance(con, (list, tuple, set, frozenset)) else [con]
+            ids = []
+            for a in alts:
+                if isinstance(a, str):
+                    known = a in vocab.word2idx
+                    i = vocab.word2idx[a] if known else -1
+                else:
+                    i = int(a)
+                    known = 0 <= i < len(vocab)
+                if not known:
+                    if skip_unknown:
+                        continue
+                    raise ValueError('clip %d: %r is not in the vocabulary' % (b, a))
+                if i in special:
+                    raise ValueError('clip %d: %r cannot be required (<end>, <start> and <pad> are not words of a caption)' % (b, a))
+                if i not in ids:
+                    ids.append(i)
+            if len(ids) > MAX_ALTERNATIVES:
+                raise ValueError('clip %d: %d alternatives in one constraint, at most %d' % (b, len(ids), MAX_ALTERNATIVES))
+            sets.append(ids)
+        packed.append(sets)
+    C = max([len(s) for s in packed] + [0])
+    W = max([len(ids) for s in packed for ids in s] + [1])
+    out = torch.full((len(packed), C, W), -1, dtype=torch.int64)
+    for b, sets in enumerate(packed):
+        for c, ids in enumerate(sets):
+            out[b, c, :len(ids)] = torch.tensor(ids, dtype=torch.int64)
+    return out if device is None else out.to(device)
+
+
+def check_constrained_options(k, L, B, cons, device, n_best=None, length_penalty=0.0, no_repeat_ngram=0, min_len=0):
+    """ValueError for what `constrained_nbest` cannot run (what `check_nbest_options` refuses, and a constraint tensor of the wrong
+    shape, dtype or device, or with more constraints than words: a caption of max_words tokens holds max_words - 1 words and
+    <end>; the tensor's C counts, since nothing is read back); returns n"""
+    n = check_nbest_options(k, L, n_best, length_penalty, no_repeat_ngram, min_len)
+    if not torch.is_tensor(cons) or cons.dtype != torch.int64:
+        raise ValueError('constraints: an int64 tensor (B, C, W) (pack_constraints makes one), not %s'
+                         % (cons.dtype if torch.is_tensor(cons) else type(cons).__name__))
+    if cons.dim() != 3 or cons.shape[0] != B:
+        raise ValueError('constraints of shape %s: (B, C, W) with B = %d clips' % (tuple(cons.shape), B))
+    if cons.shape[1] > MAX_CONSTRAINTS or (cons.shape[1] > 0 and not 1 <= cons.shape[2] <= MAX_ALTERNATIVES):
+        raise ValueError('constraints of shape %s: at most %d constraints per clip of 1 to %d alternatives'
+                         % (tuple(cons.shape), MAX_CONSTRAINTS, MAX_ALTERNATIVES))
+    if cons.device != device:
+        raise ValueError('constraints on %s, the clips on %s' % (cons.device, device))
+    if cons.shape[1] + 1 > L:
+        raise ValueError('%d constraints and <end> do not fit into max_words %d' % (cons.shape[1], L))
+    return n
+
+
+@torch.no_grad()
+def constrained_nbest(model, visual_feats, region_feats, constraints, n_best=None, length_penalty=0.0, no_repeat_ngram=0, min_len=0,
+                      beam_size=None, return_met=False):
+    """Lexically constrained beam search (dynamic beam allocation, Post & Vilar 2018): `beam_nbest` whose captions must contain a
+    word of every constraint of their clip.  constraints: the (B, C, W) int64 tensor of `pack_constraints` on the clips' device
+    (C sets of W alternative word ids per clip, -1 or an id outside the vocabulary for padding), or the per-clip lists, which are
+    packed here.  Returns (ids, scores, lens) as `beam_nbest`, the rows of a clip ordered by the number of constraints they meet,
+    most first, and by score within a number; return_met=True adds met (B, n) int64, that number.  A beam cannot end before it has
+    met every constraint, and the beams are shared out over the banks "number of constraints met" at every word
+    (`beam_select_cons`, include/dlsg.h), so row 0 meets every constraint whose set holds a word the model gives a finite logit.
+    The loop is `beam_nbest`'s: the same buffers, all L steps launched, nothing read back -- the met masks are recomputed from the
+    token history, so there is no further state.  Without constraints the result is `beam_nbest`'s, bit for bit."""
+    dec = model.decoder
+    k, L = dec.beam_size if beam_size is None else beam_size, dec.max_words
+    B, dev = visual_feats.shape[0], visual_feats.device
+    cons = constraints if torch.is_tensor(constraints) else pack_constraints(constraints, dec.vocab, dev)
+    n = check_constrained_options(k, L, B, cons, dev, n_best, length_penalty, no_repeat_ngram, min_len)
+    cons = cons.contiguous()
+    mems, sv, seed, _ = _encode(model, visual_feats, region_feats)
+    advance, B, R, _ = _beam_setup(model, mems, sv, seed, k)
+    ops, end = model.ops, dec.vocab('<end>')
+    preds = torch.empty(2, R, dtype=torch.int64, device=dev)
+    hist = torch.empty(2, R, L, dtype=torch.int64, device=dev)     # filled by step 0
+    back = torch.empty(R, dtype=torch.int64, device=dev)
+    rows = torch.empty(R, dtype=torch.int64, device=dev)
+    lps = torch.zeros(2, R, dtype=torch.float32, device=dev)
+    words = torch.full((R,), dec.vocab('<start>'), dtype=torch.int64, device=dev)
+    for t in range(L):
+        logits = advance(t, words, rows)
+        ops.beam_select_cons(logits, words, lps[t % 2], preds[t % 2], lps[(t + 1) % 2], back, rows, k, end, hist[t % 2],
+                             hist[(t + 1) % 2], t, cons, no_repeat_ngram, min_len)
+        words = preds[t % 2]
+    ids = torch.empty(B, k, L, dtype=torch.int64, device=dev)
+    scores = torch.empty(B, k, dtype=torch.float32, device=dev)
+    lens = torch.empty(B, k, dtype=torch.int64, device=dev)
+    ops.beam_finalize(hist[L % 2], lps[L % 2], k, end, float(length_penalty), ids, scores, lens)
+    # constraints met per row: a broadcast compare of the final ids with the valid entries (padding never matches)
+    valid = (cons >= 0) & (cons < dec.vocab_size)
+    hit = (ids.view(B, k, L, 1, 1) == cons.view(B, 1, 1, *cons.shape[1:])) & valid.view(B, 1, 1, *cons.shape[1:])
+    met = hit.any(4).any(2).sum(2)                                 # (B, k)
+    order = met.sort(dim=1, descending=True, stable=True)[1][:, :n]
+    out = (ids.gather(1, order.unsqueeze(2).expand(B, n, L)), scores.gather(1, order), lens.gather(1, order))
+    return out + (met.gather(1, order),) if return_met else out
+
+
+def constrained_beam_search(model, visual_feats, region_feats, constraints, **options):
+    """`constrained_nbest`, the function form of `model.constrained_beam_search`"""
+    return constrained_nbest(model, visual_feats, region_feats, constraints, **options)
 
 
 def sample_without_replacement(model, visual_feats, region_feats, **options):

@@ -1,7 +1,7 @@
 """hipGraph capture and replay, in one place: entering and leaving the process's capture stream, the eager warm-up, capturing one
 graph or a chain of segments, dropping a capture whose body raised, staging inputs into the static buffers a graph reads --
 and the captured forms of inference built on it (GreedyGraph, SampleGraph, BeamGraph, NBestBeamGraph, StochasticBeamGraph,
-EnsembleBeamGraph, ConsensusBeamGraph).  The Trainer (model.py), the GanTrainer (gan.py) and the SCSTTrainer (scst.py) capture through `capture` /
+ConstrainedBeamGraph, EnsembleBeamGraph, ConsensusBeamGraph).  The Trainer (model.py), the GanTrainer (gan.py) and the SCSTTrainer (scst.py) capture through `capture` /
 `capture_segments`."""
 import torch
 
@@ -192,6 +192,49 @@ class StochasticBeamGraph(_InferenceGraph):
         from .hip import copy_to_device
         self._stage(frames, regions)
         copy_to_device(self.seed, [int(seed)])
+        self.graph.replay()
+        return self.out
+
+
+class ConstrainedBeamGraph(_InferenceGraph):
+    """hipGraph-captured `model.constrained_beam_search(frames, regions, constraints, **options)` for one batch shape and one shape
+    (B, C, W) of the constraint tensor, which is a static buffer like the inputs: `graph(frames, regions, constraints)` stages all
+    three and replays; constraints are the packed int64 tensor or the per-clip lists (packed to the captured shape; ValueError for
+    another shape).  A replay returns the eager call's (ids, scores, lens[, met]), static buffers, and synchronises nothing."""
+
+    def __init__(self, model, frames, regions, constraints, **options):
+        self.options = options
+        self.cons = self._packed(model, constraints, frames.device).clone()
+        super().__init__(model, frames, regions)
+
+    @staticmethod
+    def _packed(model, constraints, device):
+        from .beam import pack_constraints
+        if torch.is_tensor(constraints):
+            return constraints
+        return pack_constraints(constraints, model.decoder.vocab, device)
+
+    def _run(self):
+        return self.model.constrained_beam_search(self.frames, self.regions, self.cons, **self.options)
+
+    def _fitted(self, constraints):
+        """the constraints as a tensor of the captured shape: per-clip lists are packed and padded to it; ValueError otherwise"""
+        cons = self._packed(self.model, constraints, self.cons.device)
+        if not torch.is_tensor(constraints) and cons.dim() == 3 and cons.shape[0] == self.cons.shape[0] and \
+                cons.shape[1] <= self.cons.shape[1] and cons.shape[2] <= self.cons.shape[2]:
+            wide = torch.full_like(self.cons, -1)
+            wide[:, :cons.shape[1], :cons.shape[2]] = cons
+            cons = wide
+        if cons.shape != self.cons.shape or cons.dtype != self.cons.dtype or cons.device != self.cons.device:
+            raise ValueError('ConstrainedBeamGraph: constraints of shape %s %s on %s, captured with %s int64 on %s -- build a new graph'
+                             % (tuple(cons.shape), cons.dtype, cons.device, tuple(self.cons.shape), self.cons.device))
+        return cons
+
+    @torch.no_grad()
+    def __call__(self, frames, regions, constraints):
+        cons = self._fitted(constraints)
+        self._stage(frames, regions)
+        stage(self.cons, cons)
         self.graph.replay()
         return self.out
 

@@ -562,6 +562,25 @@ class HipOps(object):
         self._check(self.lib.dlsg_beam_select_hist(C.byref(a), _p(hist_in), _p(hist_out), hist_out.shape[1], int(t), int(no_repeat_ngram),
                                                    int(min_len), self._stream()), 'dlsg_beam_select_hist')
 
+    def beam_select_cons(self, logits, last, last_lp, pred, new_lp, back, rows, k, end, hist_in, hist_out, t, cons,
+                         no_repeat_ngram=0, min_len=0, ended_count=None, met_out=None):
+        """`beam_select_hist` for lexically constrained beam search: cons (B, C, W) int64 holds C sets of alternative word ids per
+        clip (an id outside [0, V) is padding), a beam may end only once its history holds a word of every set, and the k new beams
+        are allocated over the banks "number of constraints met", most first (see include/dlsg.h).  cons None, or C == 0: the bits
+        of `beam_select_hist`.  met_out (B*k) int32, optional: the new beams' met masks."""
+        R, V = logits.shape
+        a = self._beam_args(R, V, last, last_lp, pred, new_lp, back, rows, k, end, t == 0, ended_count, logits, (hist_in, hist_out))
+        Cn, W = 0, 1
+        if cons is not None:
+            assert cons.dtype == torch.int64 and cons.is_contiguous() and cons.dim() == 3 and cons.shape[0] == R // k, (cons.dtype, cons.shape)
+            assert cons.device == logits.device, (cons.device, logits.device)
+            Cn, W = cons.shape[1], cons.shape[2]
+        if met_out is not None:
+            assert met_out.dtype == torch.int32 and met_out.is_contiguous() and met_out.numel() == R, (met_out.dtype, met_out.shape)
+        self._check(self.lib.dlsg_beam_select_cons(C.byref(a), _p(hist_in), _p(hist_out), hist_out.shape[1], int(t), int(no_repeat_ngram),
+                                                   int(min_len), _p(cons) if Cn else None, Cn, W, _p(met_out), self._stream()),
+                    'dlsg_beam_select_cons')
+
     def beam_select_gumbel(self, logits, last, last_lp, pred, new_lp, back, rows, k, end, hist_in, hist_out, t, G_in, G_out,
                            temperature=1.0, seed=0, site_sample=0, no_repeat_ngram=0, min_len=0, ended_count=None):
         """`beam_select_hist` for stochastic beam search: the k new beams of a clip are the k largest perturbed values G (float64,

@@ -286,6 +286,18 @@ class _HipModel(_ArenaModule):
         return stochastic_nbest(self, visual_feats, region_feats, n=n, temperature=temperature, seed=seed, min_len=min_len,
                                 no_repeat_ngram=no_repeat_ngram, return_threshold=return_threshold)
 
+    def constrained_beam_search(self, visual_feats, region_feats, constraints, beam_size=None, n_best=None, length_penalty=0.0,
+                                no_repeat_ngram=0, min_len=0, return_met=False):
+        """`beam_search` whose captions must contain given words (lexically constrained beam search by dynamic beam allocation).
+        constraints: per clip a list of constraints, each a word, a word id or a list of alternatives of which one must appear
+        (at most 8 constraints of 8 alternatives), or the (B, C, W) int64 device tensor `dlsg_amd.pack_constraints` makes of them.
+        Returns (ids, scores, lens) as `beam_search`, a clip's rows ordered by the number of constraints met, most first, then by
+        score; return_met=True adds that number (B, n) int64.  Row 0 meets every constraint that has a word the model can emit; a
+        caption ends only with all of them met (`beam.constrained_nbest`).  Nothing synchronises with the host."""
+        from .beam import constrained_nbest
+        return constrained_nbest(self, visual_feats, region_feats, constraints, n_best=n_best, length_penalty=length_penalty,
+                                 no_repeat_ngram=no_repeat_ngram, min_len=min_len, beam_size=beam_size, return_met=return_met)
+
     def _draw_coins(self, L, infer, tf_ratio):
         # reference draws one coin per step only when not inferring (layer.py:432)
         if infer:

@@ -658,11 +658,18 @@ def gather_results(net, eval_loader, decode=None):
     `decode`: a dict of `beam_search` options (beam_size, length_penalty, no_repeat_ngram, min_len, num_groups,
     diversity_penalty); the captions are then the best beam of that search.  With the key consensus=reward (a `DeviceCiderD`;
     optionally consensus_weights, consensus_temperature) every beam of that search is kept and the caption is the one the
-    others agree with most: row 0 of `consensus.consensus_search`."""
+    others agree with most: row 0 of `consensus.consensus_search`.  With the key constraints=fn, fn(video_ids) -> the batch's
+    per-clip constraint lists or packed tensor (`beam.pack_constraints`), the caption is row 0 of
+    `constrained_beam_search` with the other options: it contains a word of every constraint (not together with consensus)."""
     import torch
     result = collections.OrderedDict()
     dec = (net.module if hasattr(net, 'module') else net).decoder
-    consensus = None
+    consensus, constraints = None, None
+    if decode is not None and 'constraints' in decode:
+        decode = dict(decode)
+        constraints = decode.pop('constraints')
+        if 'consensus' in decode:
+            raise ValueError('decode: constraints and consensus cannot be combined')
     if decode is not None and 'consensus' in decode:
         decode = dict(decode)
         consensus = dict(reward=decode.pop('consensus'), weights=decode.pop('consensus_weights', 'uniform'),
@@ -675,6 +682,12 @@ def gather_results(net, eval_loader, decode=None):
                 from .consensus import consensus_search
                 outputs = consensus_search(net.module if hasattr(net, 'module') else net, frames, regions,
                                            **dict(decode, n_best=1, **consensus))[0][:, 0]
+            elif constraints is not None:
+                cons = constraints(video_ids)
+                if torch.is_tensor(cons):
+                    cons = cons.to(frames.device)
+                outputs = (net.module if hasattr(net, 'module') else net).constrained_beam_search(
+                    frames, regions, cons, **dict(decode, n_best=1))[0][:, 0]
             else:
                 outputs = (net.module if hasattr(net, 'module') else net).beam_search(frames, regions, **dict(decode, n_best=1))[0][:, 0]
             ids = outputs.cpu()                                    # host synchronisation: the time-out word is final too

@@ -904,6 +904,36 @@ int dlsg_beam_select_groups(const dlsg_beam_select_args* a, const float* const* 
 int dlsg_beam_select_gumbel(const dlsg_beam_select_args* a, const int64_t* hist_in, int64_t* hist_out, int L, int t,
                             int no_repeat_ngram, int min_len, float temperature, uint64_t seed, const uint64_t* seed_ptr,
                             uint32_t site_sample, const double* G_in, double* G_out, void* stream);
+/* dlsg_beam_select_hist for lexically constrained beam search (dynamic beam allocation, Post & Vilar 2018; Anderson et al. 2017): a
+ * caption must contain a word of every constraint of its clip.  cons (B, C, W) int64, device: cons[b, c] is one constraint of clip b,
+ * a set of alternative class ids (disjunctive); an entry outside [0, V) is padding and matches nothing, a constraint without a
+ * valid entry is absent; clips may differ in their number C_b of present constraints.  A beam with history h[0..t-1] has MET
+ * constraint c iff some h[i], i < t, is a valid entry of cons[b, c]: the mask `met` (bit c) is recomputed from the row of hist_in
+ * at every step -- no state beside the history --, one word may meet several constraints, step 0 starts empty, unmet = present & ~met.
+ * a, hist_in / hist_out, L, t, no_repeat_ngram, min_len, the log-softmax, the (value, index) order and step 0 reading only the
+ * clip's first row are dlsg_beam_select_hist's.  A live row's ban list is that call's, and `end` too while unmet != 0: a beam ends
+ * only with every constraint met.  A live row offers two lists.  A: its k best unbanned classes at (x - lse) + last_lp, as
+ * dlsg_beam_select_hist offers them.  B: one slot per constraint c < C; for an unmet c the best valid entry of cons[b, c] that is
+ * not banned and whose logit is > -inf (a NaN fails), larger logit first, ties to the lower class id, at the same float32
+ * (x - lse) + last_lp with the whole row's lse; the slot is empty (-inf, no candidate) if c is met or absent, if no word qualifies,
+ * or if the class already is in the row's list A or in an earlier slot c' < c of the row (the clip would get one beam twice).  An
+ * ended row offers `end` at its own log-prob in A and nothing in B.  Every candidate above -inf (a NaN is none) has a bank:
+ * popcount(parent's met | {c: its class is a valid entry of cons[b, c]}), by one rule for both lists.  Allocation: candidate index =
+ * list A (row, then rank), then list B (row, then constraint); repeat until k output slots are filled or no candidate is left: for
+ * bank = C down to 0 the best candidate left in the bank (larger value, ties to the lower candidate index) takes the next output
+ * slot, an empty bank is skipped.  A slot q left over takes candidate q of list A with new_lp = -inf.  Out, in pick order: pred,
+ * new_lp (the candidate's log-prob, nothing added for the bank), back, rows, hist_out, ended_count as dlsg_beam_select_hist;
+ * met_out (B*k) int32, optional: the new beam's mask with the chosen word, 0 for a left-over slot.  While a beam of the clip has an
+ * unmet constraint with a finite-logit word, the highest bank among the clip's beams rises by one per step, and the top bank is
+ * served first, so from step C_b on a beam with every constraint met exists and stays.  With C == 0, cons NULL or every constraint
+ * of a clip absent there is one bank and the clip's outputs are the bits of dlsg_beam_select_hist.  Not covered: multi-word
+ * phrases, ordered constraints, the same word twice.  One workgroup per clip, one wave per row, the allocation in one wave; no
+ * atomics but ended_count's; deterministic.  EINVAL for what dlsg_beam_select_hist refuses, C < 0, C > DLSG_CONS_MAX, and with
+ * C > 0: W < 1, W > DLSG_CONS_ALT, cons NULL. */
+#define DLSG_CONS_MAX 8   /* constraints per clip */
+#define DLSG_CONS_ALT 8   /* alternative words per constraint */
+int dlsg_beam_select_cons(const dlsg_beam_select_args* a, const int64_t* hist_in, int64_t* hist_out, int L, int t,
+                          int no_repeat_ngram, int min_len, const int64_t* cons, int C, int W, int32_t* met_out, void* stream);
 /* After the last step: the n <= k best beams of every clip by score = lp / len^alpha (computed in double, stored as float),
  * descending, ties to the lower beam.  hist (B*k, L) the final history, lp (B*k) the final log-probs; len = tokens up to and
  * including the first `end`, L without one.  Out: ids (B, n, L) int64, scores (B, n), lens (B, n) int64.  One wave per clip. */
