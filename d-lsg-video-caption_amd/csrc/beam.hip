@@ -298,8 +298,9 @@ __global__ __launch_bounds__(64) void beam_finalize_kernel(const int64_t* __rest
 
 // ---- what the launchers share: the three argument checks and the dispatch over K
 bool beam_args_ok(const dlsg_beam_select_args* a) { return a && a->k >= 1 && a->k <= BEAM_MAXK && a->V >= a->k; }
+// what every history launcher checks first: the argument block and the history step
 bool beam_hist_ok(const dlsg_beam_select_args* a, const int64_t* hist_in, const int64_t* hist_out, int L, int t, int g, int min_len) {
-    if (!hist_out || L < 1 || L > BEAM_MAXL || t < 0 || t >= L || g < 0 || min_len < 0) return false;
+    if (!beam_args_ok(a) || !hist_out || L < 1 || L > BEAM_MAXL || t < 0 || t >= L || g < 0 || min_len < 0) return false;
     return (a->first != 0) == (t == 0) && (t == 0 || (hist_in && hist_in != hist_out));
 }
 bool beam_ens_pack(const float* const* logits, const int64_t* ld, const float* w, const float* logw, int M, int mode, EnsPack& e) {
@@ -344,7 +345,7 @@ extern "C" int dlsg_beam_select(const dlsg_beam_select_args* a, void* stream) {
 }
 extern "C" int dlsg_beam_select_hist(const dlsg_beam_select_args* a, const int64_t* hist_in, int64_t* hist_out, int L, int t,
                                      int no_repeat_ngram, int min_len, void* stream) {
-    if (!beam_args_ok(a) || !beam_hist_ok(a, hist_in, hist_out, L, t, no_repeat_ngram, min_len)) return DLSG_EINVAL;
+    if (!beam_hist_ok(a, hist_in, hist_out, L, t, no_repeat_ngram, min_len)) return DLSG_EINVAL;
     if (a->B == 0) return DLSG_OK;
     BEAM_LAUNCH(beam_select_hist_kernel, hist_in, hist_out, L, t, no_repeat_ngram, min_len);
     DLSG_CHECK_LAUNCH();
@@ -352,7 +353,7 @@ extern "C" int dlsg_beam_select_hist(const dlsg_beam_select_args* a, const int64
 }
 extern "C" int dlsg_beam_select_cons(const dlsg_beam_select_args* a, const int64_t* hist_in, int64_t* hist_out, int L, int t,
                                      int no_repeat_ngram, int min_len, const int64_t* cons, int C, int W, int32_t* met_out, void* stream) {
-    if (!beam_args_ok(a) || !beam_hist_ok(a, hist_in, hist_out, L, t, no_repeat_ngram, min_len)) return DLSG_EINVAL;
+    if (!beam_hist_ok(a, hist_in, hist_out, L, t, no_repeat_ngram, min_len)) return DLSG_EINVAL;
     if (C < 0 || C > DLSG_CONS_MAX || (C > 0 && (W < 1 || W > DLSG_CONS_ALT || !cons))) return DLSG_EINVAL;
     if (a->B == 0) return DLSG_OK;
     if (!cons) C = 0;
@@ -364,7 +365,7 @@ extern "C" int dlsg_beam_select_cons(const dlsg_beam_select_args* a, const int64
 extern "C" int dlsg_beam_select_gumbel(const dlsg_beam_select_args* a, const int64_t* hist_in, int64_t* hist_out, int L, int t,
                                        int no_repeat_ngram, int min_len, float temperature, uint64_t seed, const uint64_t* seed_ptr,
                                        uint32_t site_sample, const double* G_in, double* G_out, void* stream) {
-    if (!beam_args_ok(a) || !beam_hist_ok(a, hist_in, hist_out, L, t, no_repeat_ngram, min_len)) return DLSG_EINVAL;
+    if (!beam_hist_ok(a, hist_in, hist_out, L, t, no_repeat_ngram, min_len)) return DLSG_EINVAL;
     if (!(temperature > 0.f) || !G_out || (t > 0 && (!G_in || G_in == G_out))) return DLSG_EINVAL;     // (NaN fails the comparison)
     if (a->B == 0) return DLSG_OK;
     BEAM_LAUNCH(beam_select_gumbel_kernel, hist_in, hist_out, L, t, no_repeat_ngram, min_len, temperature, seed, seed_ptr, site_sample,
@@ -376,7 +377,7 @@ extern "C" int dlsg_beam_select_ens(const dlsg_beam_select_args* a, const float*
                                     const float* logw, int M, int mode, const int64_t* hist_in, int64_t* hist_out, int L, int t,
                                     int no_repeat_ngram, int min_len, void* stream) {
     EnsPack e;
-    if (!beam_args_ok(a) || !beam_hist_ok(a, hist_in, hist_out, L, t, no_repeat_ngram, min_len) ||
+    if (!beam_hist_ok(a, hist_in, hist_out, L, t, no_repeat_ngram, min_len) ||
         !beam_ens_pack(logits, ld, w, logw, M, mode, e))
         return DLSG_EINVAL;
     if (a->B == 0) return DLSG_OK;
@@ -388,7 +389,7 @@ extern "C" int dlsg_beam_select_groups(const dlsg_beam_select_args* a, const flo
                                        const float* logw, int M, int mode, const int64_t* hist_in, int64_t* hist_out, int L, int t,
                                        int no_repeat_ngram, int min_len, int groups, float diversity, void* stream) {
     EnsPack e;
-    if (!beam_args_ok(a) || !beam_hist_ok(a, hist_in, hist_out, L, t, no_repeat_ngram, min_len) ||
+    if (!beam_hist_ok(a, hist_in, hist_out, L, t, no_repeat_ngram, min_len) ||
         !beam_ens_pack(logits, ld, w, logw, M, mode, e))
         return DLSG_EINVAL;
     if (groups < 1 || a->k % groups != 0 || !(diversity >= 0.f)) return DLSG_EINVAL;     // (NaN fails the comparison)

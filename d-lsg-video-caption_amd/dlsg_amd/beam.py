@@ -155,19 +155,29 @@ def beam_finish(model, preds, backs, lps, ended, done, B, k, R, L, extras):
 MAX_BEAM, MAX_WORDS = 8, 64          # limits of dlsg_beam_select_hist / dlsg_beam_finalize
 
 
+def _check_max_words(L, what):
+    """ValueError for a history longer than the step kernels keep"""
+    if L > MAX_WORDS:
+        raise ValueError('max_words %d: %s keeps at most %d tokens per beam' % (L, what, MAX_WORDS))
+
+
+def _check_bans(L, no_repeat_ngram, min_len):
+    """ValueError for an n-gram ban or a minimum length no history step can apply"""
+    if no_repeat_ngram < 0 or min_len < 0:
+        raise ValueError('no_repeat_ngram (%d) and min_len (%d) must not be negative' % (no_repeat_ngram, min_len))
+    if min_len >= L:
+        raise ValueError('min_len %d leaves no room for <end> in max_words %d' % (min_len, L))
+
+
 def check_nbest_options(k, L, n_best=None, length_penalty=0.0, no_repeat_ngram=0, min_len=0, num_groups=1, diversity_penalty=0.0):
     """ValueError for what `beam_nbest` cannot run; returns n"""
     n = k if n_best is None else n_best
     if not 1 <= k <= MAX_BEAM:
         raise ValueError('beam size %d: the n-best search takes 1 to %d beams' % (k, MAX_BEAM))
-    if L > MAX_WORDS:
-        raise ValueError('max_words %d: the n-best search keeps at most %d tokens per beam' % (L, MAX_WORDS))
+    _check_max_words(L, 'the n-best search')
     if not 1 <= n <= k:
         raise ValueError('n_best %d outside 1 .. beam size %d' % (n, k))
-    if no_repeat_ngram < 0 or min_len < 0:
-        raise ValueError('no_repeat_ngram (%d) and min_len (%d) must not be negative' % (no_repeat_ngram, min_len))
-    if min_len >= L:
-        raise ValueError('min_len %d leaves no room for <end> in max_words %d' % (min_len, L))
+    _check_bans(L, no_repeat_ngram, min_len)
     if not 1 <= num_groups <= k or k % num_groups:
         raise ValueError('num_groups %r: diverse beam search splits the %d beams into 1 .. %d groups of equal size' % (num_groups, k, k))
     if not diversity_penalty >= 0.0:                                   # (NaN fails the comparison)
@@ -177,21 +187,18 @@ def check_nbest_options(k, L, n_best=None, length_penalty=0.0, no_repeat_ngram=0
     return n
 
 
-def _nbest_search(models, weights, mode, visual_feats, region_feats, n_best, length_penalty, no_repeat_ngram, min_len, beam_size,
-                  num_groups, diversity_penalty):
-    """The search of `beam_nbest` (weights None: one model) and `ensemble_nbest`: every model steps its own state on the shared
-    words and back-pointer rows, one select launch per step chooses the beams, `beam_finalize` ranks them."""
-    dec = models[0].decoder
-    k, L = dec.beam_size if beam_size is None else beam_size, dec.max_words
-    n = check_nbest_options(k, L, n_best, length_penalty, no_repeat_ngram, min_len, num_groups, diversity_penalty)
+def _hist_search(models, k, visual_feats, region_feats, select):
+    """The search every history step kernel runs in: each model encodes its clips and steps its own state on the shared words and
+    back-pointer rows; at every word `select(t, logits, step)` makes the one launch that chooses the beams -- `logits` the models'
+    (R, V) rows, `step` the arguments every history step takes after the logits (words, the log-prob and pred ping-pong, back, rows,
+    k, <end>, the history ping-pong, t).  All L steps are launched, nothing is read back.  -> the last step's (hist (R, L), lps (R,))"""
     steps = []
     for model in models:
         mems, sv, seed, _ = _encode(model, visual_feats, region_feats)
-        advance, B, R, _ = _beam_setup(model, mems, sv, seed, k)
+        advance, B, R, L = _beam_setup(model, mems, sv, seed, k)
         steps.append(advance)
-    ops = models[0].ops
+    dec, dev = models[0].decoder, mems[0].device
     end = dec.vocab('<end>')
-    dev = mems[0].device
     preds = torch.empty(2, R, dtype=torch.int64, device=dev)       # ping-pong: the history keeps the tokens
     hist = torch.empty(2, R, L, dtype=torch.int64, device=dev)     # filled by step 0
     back = torch.empty(R, dtype=torch.int64, device=dev)
@@ -200,21 +207,38 @@ def _nbest_search(models, weights, mode, visual_feats, region_feats, n_best, len
     words = torch.full((R,), dec.vocab('<start>'), dtype=torch.int64, device=dev)
     for t in range(L):
         logits = [advance(t, words, rows) for advance in steps]
-        step = (words, lps[t % 2], preds[t % 2], lps[(t + 1) % 2], back, rows, k, end, hist[t % 2], hist[(t + 1) % 2], t,
-                no_repeat_ngram, min_len)
-        if num_groups > 1:                                             # (a single model: one member of weight 1)
-            ops.beam_select_groups(logits, [1.0] if weights is None else weights, mode, *step, num_groups,
-                                   float(diversity_penalty))
-        elif weights is None:
-            ops.beam_select_hist(logits[0], *step)                     # (reads a logit row twice, the ensemble step three times)
-        else:
-            ops.beam_select_ens(logits, weights, mode, *step)
+        select(t, logits, (words, lps[t % 2], preds[t % 2], lps[(t + 1) % 2], back, rows, k, end, hist[t % 2], hist[(t + 1) % 2], t))
         words = preds[t % 2]
+    return hist[L % 2], lps[L % 2]
+
+
+def _finalize(model, hist, lps, k, n, length_penalty):
+    """`beam_finalize` on a search's last history: the n best of every clip's k beams -> (ids (B, n, L), scores (B, n), lens (B, n))"""
+    dev, B, L = hist.device, hist.shape[0] // k, hist.shape[1]
     ids = torch.empty(B, n, L, dtype=torch.int64, device=dev)
     scores = torch.empty(B, n, dtype=torch.float32, device=dev)
     lens = torch.empty(B, n, dtype=torch.int64, device=dev)
-    ops.beam_finalize(hist[L % 2], lps[L % 2], k, end, float(length_penalty), ids, scores, lens)
+    model.ops.beam_finalize(hist, lps, k, model.decoder.vocab('<end>'), float(length_penalty), ids, scores, lens)
     return ids, scores, lens
+
+
+def _nbest_search(models, weights, mode, visual_feats, region_feats, n_best, length_penalty, no_repeat_ngram, min_len, beam_size,
+                  num_groups, diversity_penalty):
+    """The search of `beam_nbest` (weights None: one model) and `ensemble_nbest`: `_hist_search` on the step kernel the options
+    ask for, `beam_finalize` ranks the beams."""
+    dec, ops = models[0].decoder, models[0].ops
+    k = dec.beam_size if beam_size is None else beam_size
+    n = check_nbest_options(k, dec.max_words, n_best, length_penalty, no_repeat_ngram, min_len, num_groups, diversity_penalty)
+
+    def select(t, logits, step):
+        if num_groups > 1:                                             # (a single model: one member of weight 1)
+            ops.beam_select_groups(logits, [1.0] if weights is None else weights, mode, *step, no_repeat_ngram, min_len, num_groups,
+                                   float(diversity_penalty))
+        elif weights is None:
+            ops.beam_select_hist(logits[0], *step, no_repeat_ngram, min_len)   # (reads a logit row twice, the ensemble step three times)
+        else:
+            ops.beam_select_ens(logits, weights, mode, *step, no_repeat_ngram, min_len)
+    return _finalize(models[0], *_hist_search(models, k, visual_feats, region_feats, select), k, n, length_penalty)
 
 
 @torch.no_grad()
@@ -258,12 +282,8 @@ def check_stochastic_options(n, L, V, temperature, min_len=0, no_repeat_ngram=0,
     k = n + 1 if return_threshold else n
     if not temperature > 0.0:                                          # (NaN fails the comparison)
         raise ValueError('temperature (%r) must be positive' % (temperature,))
-    if L > MAX_WORDS:
-        raise ValueError('max_words %d: the search keeps at most %d tokens per beam' % (L, MAX_WORDS))
-    if no_repeat_ngram < 0 or min_len < 0:
-        raise ValueError('no_repeat_ngram (%d) and min_len (%d) must not be negative' % (no_repeat_ngram, min_len))
-    if min_len >= L:
-        raise ValueError('min_len %d leaves no room for <end> in max_words %d' % (min_len, L))
+    _check_max_words(L, 'the search')
+    _check_bans(L, no_repeat_ngram, min_len)
     if V < k:
         raise ValueError('vocabulary size (%d) too small for %d beams' % (V, k))
     return k
@@ -286,29 +306,22 @@ def stochastic_nbest(model, visual_feats, region_feats, n=5, temperature=1.0, se
     L = dec.max_words
     k = check_stochastic_options(n, L, dec.vocab_size, temperature, min_len, no_repeat_ngram, return_threshold)
     if seed is None:
-        seed = model.next_seed()
-    mems, sv, enc_seed, _ = _encode(model, visual_feats, region_feats)
-    advance, B, R, _ = _beam_setup(model, mems, sv, enc_seed, k)
-    ops, end, dev = model.ops, dec.vocab('<end>'), mems[0].device
-    preds = torch.empty(2, R, dtype=torch.int64, device=dev)
-    hist = torch.empty(2, R, L, dtype=torch.int64, device=dev)     # filled by step 0
-    back = torch.empty(R, dtype=torch.int64, device=dev)
-    rows = torch.empty(R, dtype=torch.int64, device=dev)
-    lps = torch.zeros(2, R, dtype=torch.float32, device=dev)
-    G = torch.zeros(2, R, dtype=torch.float64, device=dev)
-    words = torch.full((R,), dec.vocab('<start>'), dtype=torch.int64, device=dev)
-    for t in range(L):
-        logits = advance(t, words, rows)
-        ops.beam_select_gumbel(logits, words, lps[t % 2], preds[t % 2], lps[(t + 1) % 2], back, rows, k, end, hist[t % 2],
-                               hist[(t + 1) % 2], t, G[t % 2], G[(t + 1) % 2], temperature=float(temperature), seed=seed,
-                               site_sample=E.SITE_SAMPLE, no_repeat_ngram=no_repeat_ngram, min_len=min_len)
-        words = preds[t % 2]
-    ids = hist[L % 2].view(B, k, L)
+        seed = model.next_seed()                                       # (before the encoder draws its own)
+    G = []                                                             # the beams' perturbed values (2, R), ping-pong
+
+    def select(t, logits, step):
+        if t == 0:                                                     # (beside the search's buffers, behind the encoder)
+            G.append(torch.zeros(2, step[0].shape[0], dtype=torch.float64, device=step[0].device))
+        model.ops.beam_select_gumbel(logits[0], *step, G[0][t % 2], G[0][(t + 1) % 2], temperature=float(temperature), seed=seed,
+                                     site_sample=E.SITE_SAMPLE, no_repeat_ngram=no_repeat_ngram, min_len=min_len)
+    hist, lps = _hist_search([model], k, visual_feats, region_feats, select)
+    ids = hist.view(-1, k, L)
+    B = ids.shape[0]
     # words before the first <end>, plus that <end>: L for a row without one
-    lens = ((ids == end).cumsum(2) == 0).sum(2).add_(1).clamp_(max=L)
-    out = ids[:, :n].contiguous(), lps[L % 2].view(B, k)[:, :n].contiguous(), lens[:, :n].contiguous()
+    lens = ((ids == dec.vocab('<end>')).cumsum(2) == 0).sum(2).add_(1).clamp_(max=L)
+    out = ids[:, :n].contiguous(), lps.view(B, k)[:, :n].contiguous(), lens[:, :n].contiguous()
     if return_threshold:
-        Gk = G[L % 2].view(B, k)
+        Gk = G[0][L % 2].view(B, k)
         out += (Gk[:, :n].contiguous(), Gk[:, n].contiguous())
     return out
 
@@ -405,24 +418,10 @@ def constrained_nbest(model, visual_feats, region_feats, constraints, n_best=Non
     cons = constraints if torch.is_tensor(constraints) else pack_constraints(constraints, dec.vocab, dev)
     n = check_constrained_options(k, L, B, cons, dev, n_best, length_penalty, no_repeat_ngram, min_len)
     cons = cons.contiguous()
-    mems, sv, seed, _ = _encode(model, visual_feats, region_feats)
-    advance, B, R, _ = _beam_setup(model, mems, sv, seed, k)
-    ops, end = model.ops, dec.vocab('<end>')
-    preds = torch.empty(2, R, dtype=torch.int64, device=dev)
-    hist = torch.empty(2, R, L, dtype=torch.int64, device=dev)     # filled by step 0
-    back = torch.empty(R, dtype=torch.int64, device=dev)
-    rows = torch.empty(R, dtype=torch.int64, device=dev)
-    lps = torch.zeros(2, R, dtype=torch.float32, device=dev)
-    words = torch.full((R,), dec.vocab('<start>'), dtype=torch.int64, device=dev)
-    for t in range(L):
-        logits = advance(t, words, rows)
-        ops.beam_select_cons(logits, words, lps[t % 2], preds[t % 2], lps[(t + 1) % 2], back, rows, k, end, hist[t % 2],
-                             hist[(t + 1) % 2], t, cons, no_repeat_ngram, min_len)
-        words = preds[t % 2]
-    ids = torch.empty(B, k, L, dtype=torch.int64, device=dev)
-    scores = torch.empty(B, k, dtype=torch.float32, device=dev)
-    lens = torch.empty(B, k, dtype=torch.int64, device=dev)
-    ops.beam_finalize(hist[L % 2], lps[L % 2], k, end, float(length_penalty), ids, scores, lens)
+
+    def select(t, logits, step):
+        model.ops.beam_select_cons(logits[0], *step, cons, no_repeat_ngram, min_len)
+    ids, scores, lens = _finalize(model, *_hist_search([model], k, visual_feats, region_feats, select), k, k, length_penalty)
     # constraints met per row: a broadcast compare of the final ids with the valid entries (padding never matches)
     valid = (cons >= 0) & (cons < dec.vocab_size)
     hit = (ids.view(B, k, L, 1, 1) == cons.view(B, 1, 1, *cons.shape[1:])) & valid.view(B, 1, 1, *cons.shape[1:])

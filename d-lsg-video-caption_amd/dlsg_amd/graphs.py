@@ -77,33 +77,55 @@ def expand_rows(x, n):
 class _InferenceGraph(object):
     """A no-grad pass of `model` over (frames, regions), captured once for a batch shape and replayed: a subclass says what to
     run (`_run`, on the static inputs self.frames / self.regions; its return value becomes self.out).  A captured graph holds raw
-    addresses into the model's parameter arena and the model's train / eval mode at construction: `valid_for` tells whether it
-    still fits, and a replay after the model re-packed its parameters (load_encoder, load_state_dict into a copy, .to()) raises
-    instead of computing from the old arena."""
+    addresses into the parameter arena of every model it runs and their train / eval modes at construction -- `models` lists
+    them where there are several (an ensemble's members; self.model is the first): `valid_for` tells whether the graph still
+    fits, and a replay after a model re-packed its parameters (load_encoder, load_state_dict into a copy, .to()) raises instead
+    of computing from the old arena."""
 
-    def __init__(self, model, frames, regions):
-        model.flatten_parameters_()
-        self.model, self.arena, self.training = model, model._flat, model.training
+    def __init__(self, model, frames, regions, models=None):
+        models = [model] if models is None else list(models)
+        for m in models:
+            m.flatten_parameters_()
+        self.held = [(m, m._flat, m.training) for m in models]
+        self.model, self.arena, self.training = self.held[0]
         self.frames, self.regions = frames.clone(), regions.clone()
         with torch.no_grad():
             self.graph, self.out = capture(frames.device, self._run)
 
     def valid_for(self, frames, regions):
-        """this graph may be replayed on these inputs: same shapes, the arena it was captured on, the same train / eval mode"""
+        """this graph may be replayed on these inputs: same shapes, the arenas it was captured on, the same train / eval modes"""
         return self.frames.shape == frames.shape and self.regions.shape == regions.shape and \
-            self.arena is self.model._flat and self.training == self.model.training
+            all(arena is m._flat and training == m.training for m, arena, training in self.held)
 
     def _stage(self, frames, regions):
-        if self.arena is not self.model._flat:
-            raise RuntimeError('%s: the model re-packed its parameter arena after this graph was captured (flatten_parameters_ after '
-                               'load_encoder / load_state_dict / .to()); the graph holds addresses into the old arena -- build a '
-                               'new one' % type(self).__name__)
+        for i, (m, arena, _) in enumerate(self.held):
+            if arena is not m._flat:
+                raise RuntimeError('%s: %s re-packed its parameter arena after this graph was captured (flatten_parameters_ after '
+                                   'load_encoder / load_state_dict / .to()); the graph holds addresses into the old arena -- build a '
+                                   'new one' % (type(self).__name__, 'the model' if len(self.held) == 1 else 'member %d' % i))
         stage(self.frames, frames)
         stage(self.regions, regions)
 
     @torch.no_grad()
     def __call__(self, frames, regions):
         self._stage(frames, regions)
+        self.graph.replay()
+        return self.out
+
+
+class _SeededGraph(_InferenceGraph):
+    """An inference graph that draws: the seed is read from a device word, so every replay draws afresh, and a replay with seed s
+    gives the bits of the eager call with seed=s"""
+
+    def __init__(self, model, frames, regions):
+        self.seed = torch.zeros(1, dtype=torch.int64, device=frames.device)
+        super().__init__(model, frames, regions)
+
+    @torch.no_grad()
+    def __call__(self, frames, regions, seed):
+        from .hip import copy_to_device
+        self._stage(frames, regions)
+        copy_to_device(self.seed, [int(seed)])
         self.graph.replay()
         return self.out
 
@@ -117,7 +139,7 @@ class GreedyGraph(_InferenceGraph):
         return self.model._greedy_ids(self.frames, self.regions, 0)[0]
 
 
-class SampleGraph(_InferenceGraph):
+class SampleGraph(_SeededGraph):
     """hipGraph-captured `CapGnnModel.sample`: the n-fold expansion of the batch, the encoder on B*n rows and the sampled decode
     steps, captured once for a batch shape (and for the model's train / eval mode at construction) and replayed.  The seed is
     read from a device word, so every replay draws fresh samples; a replay with seed s gives the bits of
@@ -130,19 +152,10 @@ class SampleGraph(_InferenceGraph):
                  no_repeat_ngram=0, return_kept=False):
         self.n, self.temperature, self.share_encoder = n, temperature, bool(share_encoder)
         self.options = dict(top_k=top_k, top_p=top_p, min_len=min_len, no_repeat_ngram=no_repeat_ngram, return_kept=return_kept)
-        self.seed = torch.zeros(1, dtype=torch.int64, device=frames.device)
         super().__init__(model, frames, regions)
 
     def _run(self):
         return self.model.sample(self.frames, self.regions, self.n, self.temperature, self.seed, self.share_encoder, **self.options)
-
-    @torch.no_grad()
-    def __call__(self, frames, regions, seed):
-        from .hip import copy_to_device
-        self._stage(frames, regions)
-        copy_to_device(self.seed, [int(seed)])
-        self.graph.replay()
-        return self.out
 
 
 class BeamGraph(_InferenceGraph):
@@ -173,7 +186,7 @@ class NBestBeamGraph(_InferenceGraph):
         return self.model.beam_search(self.frames, self.regions, **self.options)
 
 
-class StochasticBeamGraph(_InferenceGraph):
+class StochasticBeamGraph(_SeededGraph):
     """hipGraph-captured `model.sample_without_replacement(frames, regions, n, temperature, **options)` for one batch shape: encoder
     and all max_words steps of stochastic beam search.  The seed is read from a device word, like SampleGraph's, so every replay
     draws afresh; a replay with seed s gives the bits of the eager call with seed=s.  options: min_len, no_repeat_ngram,
@@ -181,19 +194,10 @@ class StochasticBeamGraph(_InferenceGraph):
 
     def __init__(self, model, frames, regions, n=5, temperature=1.0, **options):
         self.n, self.temperature, self.options = n, temperature, options
-        self.seed = torch.zeros(1, dtype=torch.int64, device=frames.device)
         super().__init__(model, frames, regions)
 
     def _run(self):
         return self.model.sample_without_replacement(self.frames, self.regions, self.n, self.temperature, self.seed, **self.options)
-
-    @torch.no_grad()
-    def __call__(self, frames, regions, seed):
-        from .hip import copy_to_device
-        self._stage(frames, regions)
-        copy_to_device(self.seed, [int(seed)])
-        self.graph.replay()
-        return self.out
 
 
 class ConstrainedBeamGraph(_InferenceGraph):
@@ -247,24 +251,10 @@ class EnsembleBeamGraph(_InferenceGraph):
 
     def __init__(self, ensemble, frames, regions, **options):
         self.ensemble, self.options = ensemble, options
-        for m in ensemble.members:
-            m.flatten_parameters_()
-        self.held = [(m, m._flat, m.training) for m in ensemble.members]
-        super().__init__(ensemble.members[0], frames, regions)
+        super().__init__(ensemble.members[0], frames, regions, ensemble.members)
 
     def _run(self):
         return self.ensemble.beam_search(self.frames, self.regions, **self.options)
-
-    def valid_for(self, frames, regions):
-        return super().valid_for(frames, regions) and all(a is m._flat and tr == m.training for m, a, tr in self.held)
-
-    def _stage(self, frames, regions):
-        for i, (m, arena, _) in enumerate(self.held):
-            if arena is not m._flat:
-                raise RuntimeError('EnsembleBeamGraph: member %d re-packed its parameter arena after this graph was captured '
-                                   '(flatten_parameters_ after load_encoder / load_state_dict / .to()); the graph holds addresses '
-                                   'into the old arena -- build a new one' % i)
-        super()._stage(frames, regions)
 
 
 class ConsensusBeamGraph(_InferenceGraph):
@@ -276,22 +266,8 @@ class ConsensusBeamGraph(_InferenceGraph):
     def __init__(self, model_or_ensemble, frames, regions, reward, **options):
         self.search, self.reward, self.options = model_or_ensemble, reward, options
         members = list(getattr(model_or_ensemble, 'members', [model_or_ensemble]))
-        for m in members:
-            m.flatten_parameters_()
-        self.held = [(m, m._flat, m.training) for m in members]
-        super().__init__(members[0], frames, regions)
+        super().__init__(members[0], frames, regions, members)
 
     def _run(self):
         from .consensus import consensus_search
         return consensus_search(self.search, self.frames, self.regions, self.reward, **self.options)
-
-    def valid_for(self, frames, regions):
-        return super().valid_for(frames, regions) and all(a is m._flat and tr == m.training for m, a, tr in self.held)
-
-    def _stage(self, frames, regions):
-        for i, (m, arena, _) in enumerate(self.held):
-            if arena is not m._flat:
-                raise RuntimeError('ConsensusBeamGraph: model %d re-packed its parameter arena after this graph was captured '
-                                   '(flatten_parameters_ after load_encoder / load_state_dict / .to()); the graph holds addresses '
-                                   'into the old arena -- build a new one' % i)
-        _InferenceGraph._stage(self, frames, regions)

@@ -521,11 +521,8 @@ class HipOps(object):
 
     # ------------------------------------------------------------------ beam search
     @staticmethod
-    def _beam_args(R, V, last, last_lp, pred, new_lp, back, rows, k, end, first, ended_count, logits=None, hist=()):
-        """dlsg_beam_select_args of one step on R = B*k rows; logits: the one model's (R, V) rows (an ensemble passes its own);
-        hist: the step's two (R, L) history buffers, which are checked"""
-        for h in hist:
-            assert h.dtype == torch.int64 and h.is_contiguous() and h.shape == (R, hist[1].shape[1]), (h.dtype, h.shape)
+    def _beam_args(R, V, last, last_lp, pred, new_lp, back, rows, k, end, first, ended_count, logits=None):
+        """dlsg_beam_select_args of one step on R = B*k rows; logits: the one model's (R, V) rows (an ensemble passes its own)"""
         a = abi.dlsg_beam_select_args()
         if logits is not None:
             a.logits, a.ld = _p(logits), logits.stride(0)
@@ -533,6 +530,16 @@ class HipOps(object):
         a.pred, a.new_lp, a.back, a.rows, a.ended_count = _p(pred), _p(new_lp), _p(back), _p(rows), _p(ended_count)
         a.B, a.k, a.V, a.end, a.first = R // k, k, V, end, int(first)
         return a
+
+    @staticmethod
+    def _hist_step(R, V, last, last_lp, pred, new_lp, back, rows, k, end, hist_in, hist_out, t, no_repeat_ngram, min_len, ended_count,
+                   logits=None):
+        """a history step at t (t == 0 is the first step) -> its dlsg_beam_select_args, and the arguments every history entry point
+        takes alike: the two (R, L) history buffers, which are checked, L, t, no_repeat_ngram, min_len"""
+        for h in (hist_in, hist_out):
+            assert h.dtype == torch.int64 and h.is_contiguous() and h.shape == (R, hist_out.shape[1]), (h.dtype, h.shape)
+        a = HipOps._beam_args(R, V, last, last_lp, pred, new_lp, back, rows, k, end, t == 0, ended_count, logits)
+        return a, (_p(hist_in), _p(hist_out), hist_out.shape[1], int(t), int(no_repeat_ngram), int(min_len))
 
     @staticmethod
     def _beam_members(logits_list, weights, device):
@@ -557,10 +564,9 @@ class HipOps(object):
         """`beam_select` at step t (t == 0 is the first step) with the beams' token history: hist_out[c] = hist_in[parent of c]
         with hist[t] = pred and `end` behind it ((B*k, L) int64, two buffers), a repeated-n-gram ban and a minimum length (see
         include/dlsg.h)."""
-        R, V = logits.shape
-        a = self._beam_args(R, V, last, last_lp, pred, new_lp, back, rows, k, end, t == 0, ended_count, logits, (hist_in, hist_out))
-        self._check(self.lib.dlsg_beam_select_hist(C.byref(a), _p(hist_in), _p(hist_out), hist_out.shape[1], int(t), int(no_repeat_ngram),
-                                                   int(min_len), self._stream()), 'dlsg_beam_select_hist')
+        a, hist = self._hist_step(*logits.shape, last, last_lp, pred, new_lp, back, rows, k, end, hist_in, hist_out, t, no_repeat_ngram,
+                                  min_len, ended_count, logits)
+        self._check(self.lib.dlsg_beam_select_hist(C.byref(a), *hist, self._stream()), 'dlsg_beam_select_hist')
 
     def beam_select_cons(self, logits, last, last_lp, pred, new_lp, back, rows, k, end, hist_in, hist_out, t, cons,
                          no_repeat_ngram=0, min_len=0, ended_count=None, met_out=None):
@@ -569,7 +575,8 @@ class HipOps(object):
         are allocated over the banks "number of constraints met", most first (see include/dlsg.h).  cons None, or C == 0: the bits
         of `beam_select_hist`.  met_out (B*k) int32, optional: the new beams' met masks."""
         R, V = logits.shape
-        a = self._beam_args(R, V, last, last_lp, pred, new_lp, back, rows, k, end, t == 0, ended_count, logits, (hist_in, hist_out))
+        a, hist = self._hist_step(R, V, last, last_lp, pred, new_lp, back, rows, k, end, hist_in, hist_out, t, no_repeat_ngram, min_len,
+                                  ended_count, logits)
         Cn, W = 0, 1
         if cons is not None:
             assert cons.dtype == torch.int64 and cons.is_contiguous() and cons.dim() == 3 and cons.shape[0] == R // k, (cons.dtype, cons.shape)
@@ -577,8 +584,7 @@ class HipOps(object):
             Cn, W = cons.shape[1], cons.shape[2]
         if met_out is not None:
             assert met_out.dtype == torch.int32 and met_out.is_contiguous() and met_out.numel() == R, (met_out.dtype, met_out.shape)
-        self._check(self.lib.dlsg_beam_select_cons(C.byref(a), _p(hist_in), _p(hist_out), hist_out.shape[1], int(t), int(no_repeat_ngram),
-                                                   int(min_len), _p(cons) if Cn else None, Cn, W, _p(met_out), self._stream()),
+        self._check(self.lib.dlsg_beam_select_cons(C.byref(a), *hist, _p(cons) if Cn else None, Cn, W, _p(met_out), self._stream()),
                     'dlsg_beam_select_cons')
 
     def beam_select_gumbel(self, logits, last, last_lp, pred, new_lp, back, rows, k, end, hist_in, hist_out, t, G_in, G_out,
@@ -590,11 +596,11 @@ class HipOps(object):
         R, V = logits.shape
         for G in (G_in, G_out):
             assert G.dtype == torch.float64 and G.is_contiguous() and G.numel() == R, (G.dtype, G.shape)
-        a = self._beam_args(R, V, last, last_lp, pred, new_lp, back, rows, k, end, t == 0, ended_count, logits, (hist_in, hist_out))
+        a, hist = self._hist_step(R, V, last, last_lp, pred, new_lp, back, rows, k, end, hist_in, hist_out, t, no_repeat_ngram, min_len,
+                                  ended_count, logits)
         sd, sp = _seed(seed)
-        self._check(self.lib.dlsg_beam_select_gumbel(C.byref(a), _p(hist_in), _p(hist_out), hist_out.shape[1], int(t), int(no_repeat_ngram),
-                                                     int(min_len), f32(temperature), u64(sd), sp, u32(site_sample), _p(G_in), _p(G_out),
-                                                     self._stream()), 'dlsg_beam_select_gumbel')
+        self._check(self.lib.dlsg_beam_select_gumbel(C.byref(a), *hist, f32(temperature), u64(sd), sp, u32(site_sample), _p(G_in),
+                                                     _p(G_out), self._stream()), 'dlsg_beam_select_gumbel')
 
     def beam_select_ens(self, logits_list, weights, mode, last, last_lp, pred, new_lp, back, rows, k, end, hist_in, hist_out, t,
                         no_repeat_ngram=0, min_len=0, ended_count=None):
@@ -602,9 +608,9 @@ class HipOps(object):
         array per member, with `weights` (positive, normalised here in float64) -- mode 0: log of the weighted mean probability,
         mode 1: weighted mean log-probability (see include/dlsg.h)."""
         R, V, members = self._beam_members(logits_list, weights, hist_out.device)
-        a = self._beam_args(R, V, last, last_lp, pred, new_lp, back, rows, k, end, t == 0, ended_count, hist=(hist_in, hist_out))
-        self._check(self.lib.dlsg_beam_select_ens(C.byref(a), *members, int(mode), _p(hist_in), _p(hist_out), hist_out.shape[1], int(t),
-                                                  int(no_repeat_ngram), int(min_len), self._stream()), 'dlsg_beam_select_ens')
+        a, hist = self._hist_step(R, V, last, last_lp, pred, new_lp, back, rows, k, end, hist_in, hist_out, t, no_repeat_ngram, min_len,
+                                  ended_count)
+        self._check(self.lib.dlsg_beam_select_ens(C.byref(a), *members, int(mode), *hist, self._stream()), 'dlsg_beam_select_ens')
 
     def beam_select_groups(self, logits_list, weights, mode, last, last_lp, pred, new_lp, back, rows, k, end, hist_in, hist_out, t,
                            no_repeat_ngram=0, min_len=0, num_groups=1, diversity_penalty=0.0, ended_count=None):
@@ -613,9 +619,9 @@ class HipOps(object):
         `diversity_penalty` per choice (inf: it is excluded).  new_lp stays the log-prob without the penalty (see include/dlsg.h).
         A single model passes one logits array and weights [1.0]."""
         R, V, members = self._beam_members(logits_list, weights, hist_out.device)
-        a = self._beam_args(R, V, last, last_lp, pred, new_lp, back, rows, k, end, t == 0, ended_count, hist=(hist_in, hist_out))
-        self._check(self.lib.dlsg_beam_select_groups(C.byref(a), *members, int(mode), _p(hist_in), _p(hist_out), hist_out.shape[1],
-                                                     int(t), int(no_repeat_ngram), int(min_len), int(num_groups),
+        a, hist = self._hist_step(R, V, last, last_lp, pred, new_lp, back, rows, k, end, hist_in, hist_out, t, no_repeat_ngram, min_len,
+                                  ended_count)
+        self._check(self.lib.dlsg_beam_select_groups(C.byref(a), *members, int(mode), *hist, int(num_groups),
                                                      C.c_float(diversity_penalty), self._stream()), 'dlsg_beam_select_groups')
 
     def beam_finalize(self, hist, lp, k, end, alpha, ids, scores, lens):

@@ -15,7 +15,8 @@ import torch
 
 import dlsg_amd
 from dlsg_amd.synth import synth_batch, synth_state_dict
-from emul_beam import BeamEmul
+from emul_constrained import ConsEmul
+from emul_sbs import SbsEmul
 from helpers import load_case
 from test_scst_host import LengthReward
 from test_seq_per_clip_host import SeqEmul, captions_for
@@ -34,8 +35,9 @@ def describe(x):
     return type(x).__name__
 
 
-class TraceEmul(SeqEmul, BeamEmul):
-    """every emulated op (train step, sampling, seq_per_clip, both beam searches); `trace` (a list) collects the calls"""
+class TraceEmul(SeqEmul, SbsEmul, ConsEmul):
+    """every emulated op (train step, sampling, seq_per_clip, the beam searches: SbsEmul brings the ensemble, group and consensus
+    ops with the stochastic step, ConsEmul the constrained one); `trace` (a list) collects the calls"""
 
     trace = None
 
@@ -136,6 +138,32 @@ def _nbest(options):
     return traced(net, lambda: net.beam_search(frames, regions, beam_size=3, **kw))
 
 
+def _sbs(threshold):
+    net, args, vocab, frames, regions, caps, lens = fresh('capgnn')
+    kw = dict(temperature=0.7, min_len=2, no_repeat_ngram=2, return_threshold=True) if threshold else {}
+    return traced(net, lambda: net.sample_without_replacement(frames, regions, n=3, seed=9, **kw))
+
+
+def _constrained(options):
+    net, args, vocab, frames, regions, caps, lens = fresh('capgnn')
+    kw = dict(n_best=2, length_penalty=0.7, no_repeat_ngram=2, min_len=2, return_met=True) if options else {}
+    per_clip = [[[5, 6], 7], [], [8]]
+    return traced(net, lambda: net.constrained_beam_search(frames, regions, per_clip, beam_size=3, **kw))
+
+
+def _ensemble(groups):
+    """the three model classes as one ensemble on one traced op set"""
+    nets = [fresh(kind) for kind in MODELS]
+    frames, regions = nets[0][3:5]
+    for member in nets[1:]:
+        member[0].set_ops(nets[0][0].ops)
+        member[0].flatten_parameters_()
+    ens = dlsg_amd.Ensemble([member[0] for member in nets], weights=[0.5, 0.3, 0.2], mode='logprob' if groups else 'prob')
+    kw = dict(num_groups=2, diversity_penalty=0.5) if groups else {}
+    return traced(nets[0][0], lambda: ens.beam_search(frames, regions, beam_size=4, n_best=2, length_penalty=0.7, no_repeat_ngram=2,
+                                                      min_len=2, **kw))
+
+
 def _decoder(kind, mode, feats2, step):
     """Decoder.forward on its own: mode 'tf' (train mode, scheduled sampling), 'greedy' or 'beam'"""
     net, args, vocab, frames, regions, caps, lens = fresh(kind, train=mode == 'tf', beam=3 if mode == 'beam' else 1)
@@ -173,6 +201,10 @@ def _paths():
         P['capgnn/sample_n3%s' % ('_shared' if share else '')] = lambda share=share: _sample(share)
     for opt in (True, False):
         P['capgnn/beam_search_%s' % ('options' if opt else 'plain')] = lambda opt=opt: _nbest(opt)
+    for flag in (False, True):
+        P['capgnn/sample_without_replacement%s' % ('_threshold' if flag else '')] = lambda flag=flag: _sbs(flag)
+        P['capgnn/constrained_beam_search_%s' % ('options' if flag else 'plain')] = lambda flag=flag: _constrained(flag)
+        P['ensemble/beam_search%s' % ('_groups' if flag else '')] = lambda flag=flag: _ensemble(flag)
     for kind, feats2 in (('capgnn', True), ('baseline1', False)):
         for step in (False, True):
             for mode in ('tf', 'greedy', 'beam'):
