@@ -1,0 +1,177 @@
+// Scoring GIVEN captions (gfx950): dlsg_seq_logprob, the log-probability of every word of a caption under one model or an
+// ensemble, the caption's sum and length-normalised score, and optionally each word's rank in its row.  One workgroup per
+// caption, one wave per position (SEQ_WAVES = 8 positions at a time): only the logit rows of a caption's live positions are
+// read.  A row's log-sum-exp and the members' combination take the float32 operations of the beam steps in their order, so a
+// word's value has the bits the searches add to a beam's log-prob; the length and the score are dlsg_beam_finalize's.  No
+// atomics, every reduction in a fixed order.  (16 waves per caption measured slower: DESIGN.md section 27.)
+#include <math.h>
+
+#include "beam.hpp"
+
+using namespace dlsg;
+
+namespace {
+
+constexpr int SEQ_WAVES = 8;
+
+// the M members' bases, time and row strides and weights: by value in the argument block (a captured launch keeps them)
+struct SeqPack {
+    const float* x[DLSG_ENS_MAX];
+    int64_t ld_t[DLSG_ENS_MAX], ld_r[DLSG_ENS_MAX];
+    float w[DLSG_ENS_MAX], logw[DLSG_ENS_MAX];
+    int M, mode;
+};
+
+// beam_ens_row_topk's two steps (beam.hpp), RESTATED here operation for operation: taking them out of that function as shared
+// helpers changed the code the compiler emits for the ensemble and group step kernels, and those stay as they are.
+// tests/test_gpu_rescore.py holds the two statements together: a word's value here equals the new_lp of dlsg_beam_select_hist /
+// dlsg_beam_select_ens bit for bit.
+// a member's row: its log-sum-exp, ONE wave, to every lane
+__device__ __forceinline__ float beam_row_lse(const float* x, int V, int lane) {
+    float mx = -INFINITY;
+    for (int j = lane; j < V; j += 64) mx = fmaxf(mx, x[j]);
+    mx = dlsg::wave_max(mx);
+    float sum = 0.f;
+    for (int j = lane; j < V; j += 64) sum += expf(x[j] - mx);
+    sum = dlsg::wave_sum(sum);
+    return logf(sum) + mx;
+}
+// class j's combined value from the members' rows x and their log-sum-exps
+__device__ __forceinline__ float beam_ens_combine(const float* const (&x)[DLSG_ENS_MAX], const float (&lse)[DLSG_ENS_MAX],
+                                                  const float (&w)[DLSG_ENS_MAX], const float (&logw)[DLSG_ENS_MAX], int M, int mode,
+                                                  int j) {
+    float c;
+    if (mode == 0) {
+        float v[DLSG_ENS_MAX], mx = -INFINITY, sum = 0.f;
+#pragma unroll
+        for (int m = 0; m < DLSG_ENS_MAX; ++m)
+            if (m < M) { v[m] = (x[m][j] - lse[m]) + logw[m]; mx = fmaxf(mx, v[m]); }
+#pragma unroll
+        for (int m = 0; m < DLSG_ENS_MAX; ++m)
+            if (m < M) sum += expf(v[m] - mx);
+        c = mx == -INFINITY ? -INFINITY : mx + logf(sum);
+    } else {
+        c = 0.f;
+#pragma unroll
+        for (int m = 0; m < DLSG_ENS_MAX; ++m)
+            if (m < M) c += w[m] * (x[m][j] - lse[m]);
+    }
+    return c;
+}
+
+// RANK: tok_rank is wanted.  With one member the count rides on the maximum pass over the raw logits (the row is read twice, as
+// without it); with several it is a third pass per member over the combined values.
+template <bool RANK>
+__global__ __launch_bounds__(64 * SEQ_WAVES) void seq_logprob_kernel(const SeqPack e, const int64_t* __restrict__ ids, int64_t ids_ld,
+                                                                      const int64_t* __restrict__ lens_in, int L, int V, int64_t end,
+                                                                      double alpha, float* __restrict__ tok_lp,
+                                                                      int32_t* __restrict__ tok_rank, float* __restrict__ lp,
+                                                                      float* __restrict__ scores, int64_t* __restrict__ lens_out) {
+    __shared__ float tl_s[BEAM_MAXL];
+    __shared__ float lse_s[SEQ_WAVES][DLSG_ENS_MAX];
+    const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int64_t r = blockIdx.x;
+    // every wave holds the caption: lane t word t (no barrier before the rows are read)
+    const int64_t myid = lane < L ? ids[r * ids_ld + lane] : end;
+    int len;
+    if (lens_in) {
+        const int64_t l = lens_in[r];
+        len = l < 0 ? 0 : l > L ? L : (int)l;
+    } else {
+        const unsigned long long m = __ballot(lane < L && myid == end);
+        len = m ? __ffsll((long long)m) : L;
+    }
+    for (int t = w; t < len; t += SEQ_WAVES) {
+        const int64_t tgt64 = (int64_t)lane_u64((uint64_t)myid, t);
+        float val = NAN;
+        int cnt = -1;
+        if (tgt64 >= 0 && tgt64 < V) {                        // a target outside [0, V) reads nothing: NaN, rank -1
+            const int tgt = (int)tgt64;
+            if (e.M == 1) {
+                const float* x = e.x[0] + t * e.ld_t[0] + r * e.ld_r[0];
+                const float xt = x[tgt];
+                float lse;
+                if constexpr (RANK) {                         // beam_row_lse with the count in its first pass
+                    float mx = -INFINITY;
+                    cnt = 0;
+                    for (int j = lane; j < V; j += 64) {
+                        const float v = x[j];
+                        mx = fmaxf(mx, v);
+                        cnt += beam_better(v, j, xt, tgt);
+                    }
+                    mx = dlsg::wave_max(mx);
+                    float sum = 0.f;
+                    for (int j = lane; j < V; j += 64) sum += expf(x[j] - mx);
+                    sum = dlsg::wave_sum(sum);
+                    lse = logf(sum) + mx;
+                } else {
+                    lse = beam_row_lse(x, V, lane);
+                }
+                val = xt - lse;
+            } else {
+                for (int m = 0; m < e.M; ++m)                 // (not unrolled; every lane reads back its own store)
+                    lse_s[w][m] = beam_row_lse(e.x[m] + t * e.ld_t[m] + r * e.ld_r[m], V, lane);
+                const float* x[DLSG_ENS_MAX];
+                float lse[DLSG_ENS_MAX];
+#pragma unroll
+                for (int m = 0; m < DLSG_ENS_MAX; ++m) {
+                    x[m] = m < e.M ? e.x[m] + t * e.ld_t[m] + r * e.ld_r[m] : nullptr;
+                    lse[m] = m < e.M ? lse_s[w][m] : 0.f;
+                }
+                val = beam_ens_combine(x, lse, e.w, e.logw, e.M, e.mode, tgt);
+                if constexpr (RANK) {
+                    cnt = 0;
+                    for (int j = lane; j < V; j += 64)
+                        cnt += j != tgt && beam_better(beam_ens_combine(x, lse, e.w, e.logw, e.M, e.mode, j), j, val, tgt);
+                }
+            }
+            if constexpr (RANK) cnt = wave_sum_xor(cnt);
+        }
+        if (lane == 0) {
+            tl_s[t] = val;
+            if (tok_lp) tok_lp[r * L + t] = val;
+            if constexpr (RANK) tok_rank[r * L + t] = cnt;
+        }
+    }
+    __syncthreads();
+    const int t = threadIdx.x;
+    if (t >= len && t < L) {                                  // padding
+        if (tok_lp) tok_lp[r * L + t] = 0.f;
+        if constexpr (RANK) tok_rank[r * L + t] = -1;
+    }
+    if (t == 0) {
+        float acc = 0.f;                                      // the searches' order: new_lp = word + last_lp
+        for (int i = 0; i < len; ++i) acc = tl_s[i] + acc;
+        if (lp) lp[r] = acc;
+        if (scores) scores[r] = len ? (float)((double)acc / pow((double)len, alpha)) : 0.f;
+        if (lens_out) lens_out[r] = len;
+    }
+}
+
+}  // namespace
+
+#define ST(s) reinterpret_cast<hipStream_t>(s)
+
+extern "C" int dlsg_seq_logprob(const float* const* logits, const int64_t* ld_t, const int64_t* ld_r, const float* w, const float* logw,
+                                int M, int mode, const int64_t* ids, int64_t ids_ld, const int64_t* lens_in, int R, int L, int V,
+                                int64_t end, double alpha, float* tok_lp, int32_t* tok_rank, float* lp, float* scores, int64_t* lens_out,
+                                void* stream) {
+    if (!logits || !ld_t || !ld_r || !w || !logw || M < 1 || M > DLSG_ENS_MAX || (mode != 0 && mode != 1)) return DLSG_EINVAL;
+    if (L < 1 || L > BEAM_MAXL || V < 1 || R < 0 || !(alpha >= 0.0)) return DLSG_EINVAL;     // (NaN fails the comparison)
+    SeqPack e = {};
+    for (int m = 0; m < M; ++m) {
+        if (!logits[m]) return DLSG_EINVAL;
+        e.x[m] = logits[m]; e.ld_t[m] = ld_t[m]; e.ld_r[m] = ld_r[m]; e.w[m] = w[m]; e.logw[m] = logw[m];
+    }
+    e.M = M; e.mode = mode;
+    if (R == 0) return DLSG_OK;
+    if (!ids || ids_ld < L) return DLSG_EINVAL;
+    if (tok_rank)
+        hipLaunchKernelGGL(seq_logprob_kernel<true>, dim3(R), dim3(64 * SEQ_WAVES), 0, ST(stream), e, ids, ids_ld, lens_in, L, V, end,
+                           alpha, tok_lp, tok_rank, lp, scores, lens_out);
+    else
+        hipLaunchKernelGGL(seq_logprob_kernel<false>, dim3(R), dim3(64 * SEQ_WAVES), 0, ST(stream), e, ids, ids_ld, lens_in, L, V, end,
+                           alpha, tok_lp, tok_rank, lp, scores, lens_out);
+    DLSG_CHECK_LAUNCH();
+    return DLSG_OK;
+}

@@ -10,5 +10,7 @@ from .beam import constrained_beam_search, constrained_nbest, pack_constraints  
 from .ensemble import Ensemble  # noqa: F401
 from .graphs import EnsembleBeamGraph, ConsensusBeamGraph, StochasticBeamGraph, ConstrainedBeamGraph  # noqa: F401
 from .consensus import consensus_rerank, consensus_search  # noqa: F401
+from .rescore import score_captions, rescore, rescore_search  # noqa: F401
+from .graphs import ScoreGraph, RescoreBeamGraph  # noqa: F401
 from .scoring import DeviceCaptionMetrics, MixedReward, DeviceMixedReward  # noqa: F401
-from .scoring import CiderD, DeviceCiderD, CaptionScorer, convert_data_to_coco_scorer_format, convert_prediction, evaluate  # noqa: F401
+from .scoring import CiderD, DeviceCiderD, CaptionScorer, convert_data_to_coco_scorer_format, convert_prediction, evaluate, perplexity  # noqa: F401

@@ -86,6 +86,13 @@ class Ensemble(object):
             out.append(sv['dec']['LOGITS'])
         return out
 
+    def score(self, visual_feats, region_feats, ids, **options):
+        """The log-probability of GIVEN captions under the ensemble, combined per word as its beam search combines them:
+        `rescore.score_captions(self, ...)` -> (scores, lens[, tok_lp][, tok_rank]).  One teacher-forced pass per member and one
+        `seq_logprob` launch."""
+        from .rescore import score_captions
+        return score_captions(self, visual_feats, region_feats, ids, **options)
+
     def __call__(self, visual_feats, region_feats, captions=None):
         """inference as `model(frames, regions, None)` returns it: (ids (B, L) of the best beam at the first member's beam size,
         <end>-padded, 0, 0, 0)"""

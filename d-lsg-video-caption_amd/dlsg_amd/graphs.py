@@ -1,7 +1,7 @@
 """hipGraph capture and replay, in one place: entering and leaving the process's capture stream, the eager warm-up, capturing one
 graph or a chain of segments, dropping a capture whose body raised, staging inputs into the static buffers a graph reads --
 and the captured forms of inference built on it (GreedyGraph, SampleGraph, BeamGraph, NBestBeamGraph, StochasticBeamGraph,
-ConstrainedBeamGraph, EnsembleBeamGraph, ConsensusBeamGraph).  The Trainer (model.py), the GanTrainer (gan.py) and the SCSTTrainer (scst.py) capture through `capture` /
+ConstrainedBeamGraph, EnsembleBeamGraph, ConsensusBeamGraph, ScoreGraph, RescoreBeamGraph).  The Trainer (model.py), the GanTrainer (gan.py) and the SCSTTrainer (scst.py) capture through `capture` /
 `capture_segments`."""
 import torch
 
@@ -271,3 +271,55 @@ class ConsensusBeamGraph(_InferenceGraph):
     def _run(self):
         from .consensus import consensus_search
         return consensus_search(self.search, self.frames, self.regions, self.reward, **self.options)
+
+
+def _members(model_or_ensemble):
+    return list(getattr(model_or_ensemble, 'members', [model_or_ensemble]))
+
+
+class ScoreGraph(_InferenceGraph):
+    """hipGraph-captured `rescore.score_captions(scorer, frames, regions, ids, **options)` for one batch shape and one shape of
+    `ids`, which is a static buffer like the inputs: `graph(frames, regions, ids)` stages all three and replays.  options:
+    length_penalty, return_tokens, return_ranks, fixed at capture (lens are always counted from <end>).  A replay returns the eager
+    call's tuple, static buffers, and synchronises nothing.  It holds the arena and train / eval mode of every member of the
+    scorer."""
+
+    def __init__(self, scorer, frames, regions, ids, **options):
+        if 'lens' in options:
+            raise ValueError('ScoreGraph counts the captions\' lengths from <end>: it takes no lens')
+        self.scorer, self.options = scorer, options
+        self.ids = ids.clone()
+        members = _members(scorer)
+        super().__init__(members[0], frames, regions, members)
+
+    def _run(self):
+        from .rescore import score_captions
+        return score_captions(self.scorer, self.frames, self.regions, self.ids, **self.options)
+
+    @torch.no_grad()
+    def __call__(self, frames, regions, ids):
+        if ids.shape != self.ids.shape or ids.dtype != self.ids.dtype or ids.device != self.ids.device:
+            raise ValueError('ScoreGraph: ids of shape %s %s on %s, captured with %s int64 on %s -- build a new graph'
+                             % (tuple(ids.shape), ids.dtype, ids.device, tuple(self.ids.shape), self.ids.device))
+        self._stage(frames, regions)
+        stage(self.ids, ids)
+        self.graph.replay()
+        return self.out
+
+
+class RescoreBeamGraph(_InferenceGraph):
+    """hipGraph-captured `rescore.rescore_search(model_or_ensemble, scorer, frames, regions, **options)` for one batch shape: the
+    beam search of a model or an `Ensemble` with every beam kept, the scorer's teacher-forced passes over the beams, the
+    `dlsg_seq_logprob` launch and the gathers that reorder the beams.  A replay returns (ids, scores, lens, order) -- static
+    buffers, valid until the next replay -- and synchronises nothing.  It holds the arena and train / eval mode of every model
+    involved, the searcher's and the scorer's."""
+
+    def __init__(self, model_or_ensemble, scorer, frames, regions, **options):
+        self.search, self.scorer, self.options = model_or_ensemble, scorer, options
+        models = _members(model_or_ensemble)
+        models += [m for m in _members(scorer) if not any(m is x for x in models)]
+        super().__init__(models[0], frames, regions, models)
+
+    def _run(self):
+        from .rescore import rescore_search
+        return rescore_search(self.search, self.scorer, self.frames, self.regions, **self.options)

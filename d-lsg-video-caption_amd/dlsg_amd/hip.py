@@ -635,6 +635,36 @@ class HipOps(object):
         self._check(self.lib.dlsg_beam_finalize(_p(hist), _p(lp), B, k, L, i64(end), C.c_double(alpha), n, _p(ids), _p(scores), _p(lens),
                                                 self._stream()), 'dlsg_beam_finalize')
 
+    def seq_logprob(self, logits_list, weights, mode, ids, lens=None, length_penalty=0.0, want_tokens=False, want_ranks=False,
+                    end=-1):
+        """The log-probability of GIVEN captions (see include/dlsg.h, dlsg_seq_logprob): logits_list holds one float32 (L, R, V)
+        view per member, row (t, r) what the member predicts for word t of caption r -- the decoder's time-major logits as they
+        stand, an (R, L, V) tensor as `.transpose(0, 1)`; any time and row strides, unit stride along V.  weights, mode: as
+        `beam_select_ens` takes them (one model: [1.0], 0).  ids (R, L) int64, rows any stride apart; lens (R) int64 or None: then
+        a caption runs up to and including its first `end` (default -1: no such id, every caption is L words).  Returns (scores
+        (R) float32 = lp / len^length_penalty, lens (R) int64, lp (R) float32, tok_lp (R, L) float32 or None, tok_rank (R, L) int32
+        or None): only the rows of a caption's own words are read.  One launch; nothing is read back."""
+        R, L = ids.shape
+        dev = ids.device
+        for x in logits_list:
+            assert x.dim() == 3 and x.shape[0] >= L, (x.shape, L)
+        _, V, members = self._beam_members([x[0] for x in logits_list], weights, dev)
+        assert logits_list[0].shape[1] == R, (logits_list[0].shape, R)
+        ld_t = (C.c_int64 * len(logits_list))(*[x.stride(0) for x in logits_list])
+        assert ids.dtype == torch.int64 and (ids.stride(1) == 1 or L == 1) and (R <= 1 or ids.stride(0) >= L), (ids.dtype, ids.stride())
+        if lens is not None:
+            assert lens.dtype == torch.int64 and lens.is_contiguous() and lens.numel() == R and lens.device == dev, (lens.dtype, lens.shape)
+        scores = torch.empty(R, dtype=torch.float32, device=dev)
+        lens_out = torch.empty(R, dtype=torch.int64, device=dev)
+        lp = torch.empty(R, dtype=torch.float32, device=dev)
+        tok_lp = torch.empty(R, L, dtype=torch.float32, device=dev) if want_tokens else None
+        tok_rank = torch.empty(R, L, dtype=torch.int32, device=dev) if want_ranks else None
+        ptrs, ld_r, w, logw, M = members
+        self._check(self.lib.dlsg_seq_logprob(ptrs, ld_t, ld_r, w, logw, M, int(mode), _p(ids), ids.stride(0) if R > 1 else L, _p(lens),
+                                              R, L, V, i64(end), C.c_double(length_penalty), _p(tok_lp), _p(tok_rank), _p(lp),
+                                              _p(scores), _p(lens_out), self._stream()), 'dlsg_seq_logprob')
+        return scores, lens_out, lp, tok_lp, tok_rank
+
     def gather_rows_multi(self, srcs, rows, dsts):
         """dsts[i][r] = srcs[i][rows[r]] for up to 4 dense (R, n_i) arrays in one launch."""
         a = abi.dlsg_gather_multi_args()

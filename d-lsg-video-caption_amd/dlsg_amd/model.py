@@ -298,6 +298,14 @@ class _HipModel(_ArenaModule):
         return constrained_nbest(self, visual_feats, region_feats, constraints, n_best=n_best, length_penalty=length_penalty,
                                  no_repeat_ngram=no_repeat_ngram, min_len=min_len, beam_size=beam_size, return_met=return_met)
 
+    def score(self, visual_feats, region_feats, ids, **options):
+        """The log-probability of GIVEN captions under this model: `rescore.score_captions(self, ...)` -- ids (B, L) or (B, n, L)
+        int64, <end>-padded; options lens, length_penalty, return_tokens, return_ranks.  -> (scores, lens[, tok_lp][, tok_rank]).
+        One teacher-forced pass without dropout and one `seq_logprob` launch; rescoring the model's own `beam_search` output
+        gives that search's scores and lens."""
+        from .rescore import score_captions
+        return score_captions(self, visual_feats, region_feats, ids, **options)
+
     def _draw_coins(self, L, infer, tf_ratio):
         # reference draws one coin per step only when not inferring (layer.py:432)
         if infer:

@@ -660,11 +660,19 @@ def gather_results(net, eval_loader, decode=None):
     optionally consensus_weights, consensus_temperature) every beam of that search is kept and the caption is the one the
     others agree with most: row 0 of `consensus.consensus_search`.  With the key constraints=fn, fn(video_ids) -> the batch's
     per-clip constraint lists or packed tensor (`beam.pack_constraints`), the caption is row 0 of
-    `constrained_beam_search` with the other options: it contains a word of every constraint (not together with consensus)."""
+    `constrained_beam_search` with the other options: it contains a word of every constraint (not together with consensus).
+    With the key rescore=scorer (a model or an `Ensemble`; optionally rescore_mix) every beam of that search is kept and the
+    caption is the one the scorer ranks first: row 0 of `rescore.rescore_search` (not together with consensus or constraints)."""
     import torch
     result = collections.OrderedDict()
     dec = (net.module if hasattr(net, 'module') else net).decoder
-    consensus, constraints = None, None
+    consensus, constraints, rescorer = None, None, None
+    if decode is not None and 'rescore' in decode:
+        decode = dict(decode)
+        rescorer = dict(scorer=decode.pop('rescore'), mix=decode.pop('rescore_mix', 1.0))
+        for other in ('consensus', 'constraints'):
+            if other in decode:
+                raise ValueError('decode: rescore and %s cannot be combined' % other)
     if decode is not None and 'constraints' in decode:
         decode = dict(decode)
         constraints = decode.pop('constraints')
@@ -682,6 +690,10 @@ def gather_results(net, eval_loader, decode=None):
                 from .consensus import consensus_search
                 outputs = consensus_search(net.module if hasattr(net, 'module') else net, frames, regions,
                                            **dict(decode, n_best=1, **consensus))[0][:, 0]
+            elif rescorer is not None:
+                from .rescore import rescore_search
+                outputs = rescore_search(net.module if hasattr(net, 'module') else net, rescorer['scorer'], frames, regions,
+                                         n_best=1, mix=rescorer['mix'], **decode)[0][:, 0]
             elif constraints is not None:
                 cons = constraints(video_ids)
                 if torch.is_tensor(cons):
@@ -726,3 +738,38 @@ def evaluate(net, eval_loader, reference, process_group=None, gather=True, decod
     pred = convert_prediction(result)
     scores, _ = CaptionScorer().score(reference, pred, list(pred.keys()))
     return scores, result
+
+
+def perplexity(scorer, loader):
+    """Held-out likelihood of the reference captions a `data.TrainLoader` yields (captions_per_clip = n included: the encoder then
+    runs once per clip) under `scorer`, a model or an `Ensemble`: the cheap validation signal between two full evaluations.
+    Returns dict(nll, ppl, words, top1, top5): the mean negative log-probability per counted word, its exponential, the number of
+    counted words, and the fraction of them the scorer ranks first / among its five best, teacher-forced.  The counted positions
+    are those `dlsg_ce_ragged` counts for the same batch in the train step: t < min(cap_len, L).  Per batch one teacher-forced
+    pass per member without dropout and one `seq_logprob` launch; the sums are kept on the device in float64 and read once at
+    the end."""
+    import torch
+    from .hip import host_to_device
+    from .ensemble import MODES
+    from .rescore import as_ensemble
+    ens = as_ensemble(scorer)
+    acc = None
+    with torch.no_grad():
+        for frames, regions, _, captions, _, cap_lens, _ in loader:
+            lens = cap_lens if torch.is_tensor(cap_lens) else host_to_device(list(cap_lens), torch.int64, captions.device)
+            logits = ens.teacher_logits(frames, regions, captions, seq_per_clip=captions.shape[0] // frames.shape[0])
+            _, counted, lp, _, rank = ens.ops.seq_logprob(logits, ens.weights, MODES[ens.mode], captions.contiguous(), lens.contiguous(),
+                                                          want_ranks=True)
+            live = rank >= 0
+            part = torch.stack([-lp.double().sum(), counted.sum().double(), (rank == 0).sum().double(),
+                                (live & (rank < 5)).sum().double()])
+            acc = part if acc is None else acc + part
+    if acc is None:
+        raise ValueError('perplexity: the loader yielded no batch')
+    nll, words, top1, top5 = acc.tolist()                              # the one host read
+    chk = getattr(ens.ops, 'check_persistent', None)
+    if chk is not None:
+        chk()
+    if words == 0:
+        raise ValueError('perplexity: no counted word')
+    return dict(nll=nll / words, ppl=math.exp(nll / words), words=int(words), top1=top1 / words, top5=top5 / words)

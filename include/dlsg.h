@@ -939,6 +939,34 @@ int dlsg_beam_select_cons(const dlsg_beam_select_args* a, const int64_t* hist_in
  * including the first `end`, L without one.  Out: ids (B, n, L) int64, scores (B, n), lens (B, n) int64.  One wave per clip. */
 int dlsg_beam_finalize(const int64_t* hist, const float* lp, int B, int k, int L, int64_t end, double alpha, int n,
                        int64_t* ids, float* scores, int64_t* lens, void* stream);
+/* The log-probability of GIVEN captions under one model or an ensemble of M members, from teacher-forced logits: what the
+ * searches report for captions of their own, for any caption.  Row (t, r) of member m is logits[m] + t * ld_t[m] + r * ld_r[m], V
+ * floats (time-major (L, R, V) and (R, L, V) alike); ids holds R rows of L int64, ids_ld apart, word t of row r being what position
+ * t should predict.  logits, ld_t, ld_r, w (normalised to sum 1), logw = log(w): HOST arrays of M entries, read during the call and
+ * passed to the kernel by value (a captured launch keeps them), as dlsg_beam_select_ens takes them.
+ *   len_r          lens_in == NULL: the tokens up to and including the first `end`, L without one (dlsg_beam_finalize's rule);
+ *                  else lens_in[r] clamped to [0, L].  lens_out[r] = len_r.
+ *   tok_lp[r, t]   t < len_r: the combined log-probability c of class ids[r, t], in the float32 operations and order of
+ *                  dlsg_beam_select_ens: per member lse_m (strided maximum, wave maximum, strided exponential sum, wave sum,
+ *                  logf(sum) + max), then mode 0 or mode 1 over the members in member order.  With M == 1 it is x - lse, the bits
+ *                  dlsg_beam_select_hist adds to last_lp for that class.  t >= len_r: 0.  Only the rows t < len_r are read.
+ *   lp[r]          the float32 sum in step order, acc = tok_lp[t] + acc from 0 at t = 0 (how the searches accumulate new_lp);
+ *   scores[r]      lp / len_r^alpha, computed in double, stored as float (dlsg_beam_finalize's); len_r == 0: lp = scores = 0.
+ *   tok_rank[r, t] t < len_r: the number of classes j with c_j > c_tgt, or c_j == c_tgt and j < tgt (the searches' order: 0 is
+ *                  the word a greedy decode chooses here).  With M == 1 the comparison is on the raw logits, as the one-model step
+ *                  ranks: exact, whatever the rounding of lse.  A class whose c is NaN is not counted (a NaN target has rank 0).
+ *                  t >= len_r: -1.  NULL skips its work: with M == 1 the count rides on the maximum pass, with M > 1 it reads
+ *                  every member row a third time.
+ * A target outside [0, V) indexes nothing: tok_lp NaN, tok_rank -1, so lp and scores are NaN (dlsg_ce_ragged_soft's rule).  A
+ * target whose logit is -inf has tok_lp -inf.  A member row that is all -inf or holds a NaN has lse_m = NaN, as in
+ * dlsg_beam_select_ens, so every l_m of the row is NaN: with M == 1 and in mode 1 tok_lp is NaN; in mode 0 the maximum over the
+ * members skips a NaN, so tok_lp is NaN where another member gives the class a finite value and -inf where none does.
+ * tok_lp, tok_rank ((R, L) dense), lp, scores, lens_out ((R)) are each optional (NULL).  One launch, one workgroup per caption, one
+ * wave per position, no atomics, fixed-order reductions: two launches give equal bits.  EINVAL and no launch for M outside
+ * 1..DLSG_ENS_MAX, mode outside {0, 1}, L outside 1..64, V < 1, alpha negative or NaN, ids_ld < L.  R == 0 launches nothing. */
+int dlsg_seq_logprob(const float* const* logits, const int64_t* ld_t, const int64_t* ld_r, const float* w, const float* logw, int M,
+                     int mode, const int64_t* ids, int64_t ids_ld, const int64_t* lens_in, int R, int L, int V, int64_t end,
+                     double alpha, float* tok_lp, int32_t* tok_rank, float* lp, float* scores, int64_t* lens_out, void* stream);
 /* dst_i[r,:] = src_i[rows[r],:] (dense rows of n[i] floats) for count <= 4 arrays in one launch */
 typedef struct {
     const float* src[4]; float* dst[4]; int32_t n[4];
