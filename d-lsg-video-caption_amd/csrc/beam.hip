@@ -165,6 +165,67 @@ __global__ __launch_bounds__(64 * K) void beam_select_cons_kernel(const dlsg_bea
         beam_bank_merge<K>(a, nbeam, lane, cand_lp, cand_cls, cons_lp, cons_cls, met_s, cons_s, C, W, hist_in, hist_out, L, t, met_out);
 }
 
+// Constrained beam search with multi-word phrases (dlsg_beam_select_phrases): beam_select_cons_kernel's step, a constraint being a
+// set of alternative phrases.  Phase 0 stages the clip's C * W alternatives in LDS, cut to their valid leading run
+// (beam_stage_phrases).  Phase 1, wave w for row w: the row's history into LDS, whatever g is; from it the constraints met, the
+// border masks of all alternatives -- kept in LDS for the merge -- and the row's progress (beam_row_phrases); the ban list with
+// `end` added while a constraint is unmet; list A, and list B, the next word of the most advanced phrase of every unmet constraint
+// (beam_offer_phrases).  Phase 2, wave 0: beam_phrase_merge over the banks (constraints met, progress), which it works out per
+// candidate from the parent's masks and the class.  P = 1 gives the bits of beam_select_cons_kernel, C = 0 those of
+// beam_select_hist_kernel.
+template <int K>
+__global__ __launch_bounds__(64 * K) void beam_select_phrases_kernel(const dlsg_beam_select_args a, const int64_t* __restrict__ hist_in,
+                                                                       int64_t* __restrict__ hist_out, int L, int t, int g, int min_len,
+                                                                       const int64_t* __restrict__ phr, int C, int W, int P,
+                                                                       int32_t* __restrict__ met_out, int32_t* __restrict__ bank_out) {
+    __shared__ float cand_lp[K * K];
+    __shared__ int cand_cls[K * K];
+    __shared__ float cons_lp[K * DLSG_CONS_MAX];
+    __shared__ int cons_cls[K * DLSG_CONS_MAX];
+    __shared__ int hist[K][BEAM_MAXL];
+    __shared__ int ban[K][BEAM_MAXL + 1];
+    __shared__ int nban[K];
+    __shared__ int phr_s[PHRASE_SLOTS];
+    __shared__ int n_s[CONS_SLOTS];
+    __shared__ unsigned char border_s[K][CONS_SLOTS];
+    __shared__ unsigned met_s[K];
+    __shared__ int q_s[K];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const int nbeam = a.first ? 1 : K;
+    const int64_t row = (int64_t)blockIdx.x * K + w;
+    const bool ended = !a.first && a.last[row] == a.end;
+    beam_stage_phrases(phr + (int64_t)blockIdx.x * (C * W * P), C * W, P, a.V, phr_s, n_s);
+    hist[w][lane] = lane < t ? (int)hist_in[row * L + lane] : -1;
+    __syncthreads();
+    unsigned present, border;
+    int q;
+    const unsigned met = beam_row_phrases(hist[w], t, phr_s, n_s, C, W, P, border_s[w], present, q, border);
+    const unsigned unmet = present & ~met;
+    if (lane == 0) { met_s[w] = met; q_s[w] = q; }
+    if (w < nbeam && !ended) beam_ban_list(hist[w], t, g, unmet ? t + 1 : min_len, a.end, ban[w], &nban[w]);
+    __syncthreads();
+    if (w < nbeam) {
+        const float base = a.first ? 0.f : a.last_lp[row];
+        if (ended) {
+            beam_offer_ended<K>(a, lane, base, cand_lp + w * K, cand_cls + w * K);
+            if (lane < C) { cons_lp[w * C + lane] = -INFINITY; cons_cls[w * C + lane] = 0; }
+        } else {
+            float lse, bv[K];
+            int bi[K];
+            beam_row_topk<K, true>(a.logits + row * a.ld, a.V, lane, lse, bv, bi, ban[w], nban[w]);
+            beam_offer_phrases<K>(a.logits + row * a.ld, lane, phr_s, n_s, C, W, P, unmet, border, ban[w], nban[w], bi, lse, base,
+                                  cons_lp + w * C, cons_cls + w * C);
+#pragma unroll
+            for (int c = 0; c < K; ++c) bv[c] -= lse;
+            beam_offer_live<K>(lane, bv, bi, base, cand_lp + w * K, cand_cls + w * K);
+        }
+    }
+    __syncthreads();
+    if (w == 0)
+        beam_phrase_merge<K>(a, nbeam, lane, cand_lp, cand_cls, cons_lp, cons_cls, met_s, q_s, border_s, phr_s, n_s, C, W, P, hist_in,
+                             hist_out, L, t, met_out, bank_out);
+}
+
 // Phase 1 of the ensemble step and of the group step, wave w for row w: beam_select_hist_kernel's, but a live beam's candidates
 // are the K best combined values of the members' rows (beam_ens_row_topk).  Every row's K (c + last_lp, class) end up in LDS.
 template <int K>
@@ -359,6 +420,18 @@ extern "C" int dlsg_beam_select_cons(const dlsg_beam_select_args* a, const int64
     if (!cons) C = 0;
     if (C == 0) W = 1;
     BEAM_LAUNCH(beam_select_cons_kernel, hist_in, hist_out, L, t, no_repeat_ngram, min_len, cons, C, W, met_out);
+    DLSG_CHECK_LAUNCH();
+    return DLSG_OK;
+}
+extern "C" int dlsg_beam_select_phrases(const dlsg_beam_select_args* a, const int64_t* hist_in, int64_t* hist_out, int L, int t,
+                                        int no_repeat_ngram, int min_len, const int64_t* phr, int C, int W, int P, int32_t* met_out,
+                                        int32_t* bank_out, void* stream) {
+    if (!beam_hist_ok(a, hist_in, hist_out, L, t, no_repeat_ngram, min_len)) return DLSG_EINVAL;
+    if (C < 0 || C > DLSG_CONS_MAX || (C > 0 && (W < 1 || W > DLSG_CONS_ALT || P < 1 || P > DLSG_PHRASE_MAX || !phr))) return DLSG_EINVAL;
+    if (a->B == 0) return DLSG_OK;
+    if (!phr) C = 0;
+    if (C == 0) W = P = 1;
+    BEAM_LAUNCH(beam_select_phrases_kernel, hist_in, hist_out, L, t, no_repeat_ngram, min_len, phr, C, W, P, met_out, bank_out);
     DLSG_CHECK_LAUNCH();
     return DLSG_OK;
 }

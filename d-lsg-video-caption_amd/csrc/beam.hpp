@@ -472,4 +472,202 @@ __device__ __forceinline__ void beam_bank_merge(const dlsg_beam_select_args& a, 
     if (lane == 0 && a.ended_count) atomicAdd(a.ended_count, n_end);
 }
 
+// ------------------------------------------------------------------------------------------------ phrase constraints
+// A clip's constraints are C sets of W alternative phrases of up to P <= DLSG_PHRASE_MAX words: alternative a = c * W + w lies in LDS
+// as phr[a * P + j], cut behind its leading run of ids in [0, V) (-1 from there on), with its length in n[a] (0: absent).
+constexpr int PHRASE_SLOTS = CONS_SLOTS * DLSG_PHRASE_MAX;
+
+// Phase 0, thread a < CW of the workgroup: alternative a of the clip from global memory (phr: the clip's CW * P entries)
+__device__ __forceinline__ void beam_stage_phrases(const int64_t* __restrict__ phr, int CW, int P, int V, int* phr_s, int* n_s) {
+    const int a = threadIdx.x;
+    if (a < CW) {
+        int n = 0;
+        bool run = true;
+        for (int j = 0; j < P; ++j) {
+            const int64_t id = phr[(int64_t)a * P + j];
+            run = run && id >= 0 && id < V;
+            phr_s[a * P + j] = run ? (int)id : -1;
+            n += run;
+        }
+        n_s[a] = n;
+    }
+}
+
+// What a row's history (hist[i] = token i for i < t, in LDS) says about the clip's phrases, ONE wave.  To every lane: the mask of
+// the constraints that are met (lane i tests "alternative a starts at token i", one ballot per constraint), `present`, and q, the
+// largest progress among the valid alternatives of the unmet constraints.  Lane a < C * W: the border mask of alternative a -- bit
+// j: j <= t, j < n[a] and the last j tokens equal its first j words (bit 0 of a valid alternative is set) -- in border[a] and
+// `mine`; its progress is the highest bit.  border[a] is 0 for every other lane below CONS_SLOTS.
+__device__ __forceinline__ unsigned beam_row_phrases(const int* hist, int t, const int* phr, const int* n_s, int C, int W, int P,
+                                                     unsigned char* border, unsigned& present, int& q, unsigned& mine) {
+    const int lane = threadIdx.x & 63;
+    unsigned met = 0;
+    present = 0;
+    for (int c = 0; c < C; ++c) {
+        bool hit = false;
+        for (int w = 0; w < W; ++w) {
+            const int a = c * W + w, n = n_s[a];                 // (every lane reads the same entry: LDS broadcasts)
+            present |= n > 0 ? 1u << c : 0u;
+            bool m = n > 0 && lane + n <= t;
+            for (int j = 0; j < P; ++j) m = m && (j >= n || hist[lane + j] == phr[a * P + j]);
+            hit |= m;
+        }
+        met |= __ballot(hit) ? 1u << c : 0u;
+    }
+    const int n = lane < C * W ? n_s[lane] : 0;
+    mine = n > 0 ? 1u : 0u;
+    for (int j = 1; j < P; ++j) {
+        bool ok = j < n && j <= t;
+        for (int i = 0; ok && i < j; ++i) ok = hist[t - j + i] == phr[lane * P + i];
+        mine |= ok ? 1u << j : 0u;
+    }
+    border[lane] = (unsigned char)mine;
+    const bool open = n > 0 && (((present & ~met) >> (lane / W)) & 1u);
+    q = 0;
+    for (int j = 1; j < P; ++j) q = __ballot(open && (mine >> j)) ? j : q;
+    return met;
+}
+
+// A live row's list B with phrases, ONE wave: lane a proposes the next word of alternative a, phr[a * P + p] behind a progress of p
+// (`border`: the lane's mask from beam_row_phrases), with a gain of DLSG_PHRASE_MAX if the word completes the phrase, else p + 1.  A
+// proposal is out as an entry of beam_offer_constraints is; the slot of an unmet constraint takes its proposal of the largest gain,
+// then the larger logit, then the lower class, and is offered, or left empty, by that function's rules.  With one-word phrases
+// every gain is equal and the slots are beam_offer_constraints' bit for bit.
+template <int K>
+__device__ __forceinline__ void beam_offer_phrases(const float* x, int lane, const int* phr, const int* n_s, int C, int W, int P,
+                                                   unsigned unmet, unsigned border, const int* ban, int nban, const int (&bi)[K], float lse,
+                                                   float base, float* lp, int* cls) {
+    const int n = lane < C * W ? n_s[lane] : 0;
+    const int mine = lane / W;
+    float v = -INFINITY, gain = 0.f;
+    int id = -1;
+    if (n > 0 && ((unmet >> mine) & 1u)) {
+        const int p = 31 - __clz((int)border);
+        id = phr[lane * P + p];
+        const float xv = x[id];
+        bool ok = xv > -INFINITY;                              // (NaN fails)
+        for (int q = 0; q < nban; ++q) ok &= ban[q] != id;
+        v = ok ? xv : -INFINITY;
+        gain = p + 1 == n ? (float)DLSG_PHRASE_MAX : (float)(p + 1);
+    }
+    int mypick = -1;                                           // lane c: the class in slot c
+    for (int c = 0; c < C; ++c) {
+        const bool in = mine == c && v > -INFINITY;
+        const float top = dlsg::wave_max(in ? gain : 0.f);
+        float bv = in && gain == top ? v : -INFINITY;
+        int bc = bv > -INFINITY ? id : 0x7fffffff;
+        wave_argmax(bv, bc);
+        bool have = bc != 0x7fffffff;
+#pragma unroll
+        for (int q = 0; q < K; ++q) have &= bi[q] != bc;
+        have &= __ballot(lane < c && mypick == bc) == 0ull;
+        if (lane == c) {
+            mypick = have ? bc : -1;
+            lp[c] = have ? (bv - lse) + base : -INFINITY;
+            cls[c] = have ? bc : 0;
+        }
+    }
+}
+
+// The bank of the history "parent + [cls]" from the parent's state alone: its met mask, its progress qpar and its border masks
+// (border[a], LDS).  cls completes alternative a iff bit n - 1 of the mask is set and the phrase's last word is cls; behind it the
+// progress of a is the largest j < n with bit j - 1 set and word j - 1 equal to cls, and that of the row the largest over the
+// alternatives of the constraints still unmet.  `end` changes neither.  -> popcount(mask) * DLSG_PHRASE_MAX + progress
+__device__ __forceinline__ int beam_phrase_bank(const int* phr, const int* n_s, int C, int W, int P, const unsigned char* border,
+                                                unsigned met, int qpar, int cls, int end, unsigned& mask) {
+    mask = met;
+    if (cls == end) return __popc(met) * DLSG_PHRASE_MAX + qpar;
+    for (int c = 0; c < C; ++c)
+        for (int w = 0; w < W; ++w) {
+            const int a = c * W + w, n = n_s[a];
+            if (n > 0 && ((border[a] >> (n - 1)) & 1) && phr[a * P + n - 1] == cls) mask |= 1u << c;
+        }
+    int q = 0;
+    for (int c = 0; c < C; ++c) {
+        if ((mask >> c) & 1u) continue;
+        for (int w = 0; w < W; ++w) {
+            const int a = c * W + w, n = n_s[a];
+            for (int j = 1; j < n; ++j)
+                if (((border[a] >> (j - 1)) & 1) && phr[a * P + j - 1] == cls) q = max(q, j);
+        }
+    }
+    return __popc(mask) * DLSG_PHRASE_MAX + q;
+}
+
+// beam_bank_merge over the banks (constraints met, progress) of beam_phrase_bank, by wave 0; the candidates, their indices and the
+// rules for ties and left-over slots are that function's.  Every pick takes the best candidate left in the highest non-empty bank
+// below the one served before it; when none is below, the round starts again from the top.  bank_out (optional): the new beam's
+// bank, 0 for a left-over slot.
+template <int K>
+__device__ __forceinline__ void beam_phrase_merge(const dlsg_beam_select_args& a, int nbeam, int lane, const float* a_lp, const int* a_cls,
+                                                  const float* b_lp, const int* b_cls, const unsigned* met, const int* qrow,
+                                                  const unsigned char (&border)[K][CONS_SLOTS], const int* phr, const int* n_s, int C,
+                                                  int W, int P, const int64_t* __restrict__ hist_in, int64_t* __restrict__ hist_out,
+                                                  int L, int t, int32_t* __restrict__ met_out, int32_t* __restrict__ bank_out) {
+    const int b = blockIdx.x, Cd = C > 0 ? C : 1;
+    float v0 = lane < nbeam * K ? a_lp[lane] : -INFINITY;
+    float v1 = lane < nbeam * C ? b_lp[lane] : -INFINITY;
+    unsigned m0 = 0, m1 = 0;
+    int bank0 = -1, bank1 = -1;                               // -1: no candidate (never one, or taken)
+    if (v0 > -INFINITY) {
+        const int par = lane / K;
+        bank0 = beam_phrase_bank(phr, n_s, C, W, P, border[par], met[par], qrow[par], a_cls[lane], a.end, m0);
+    }
+    if (v1 > -INFINITY) {
+        const int par = lane / Cd;
+        bank1 = beam_phrase_bank(phr, n_s, C, W, P, border[par], met[par], qrow[par], b_cls[lane], a.end, m1);
+    }
+    constexpr int TOP = (DLSG_CONS_MAX + 1) * DLSG_PHRASE_MAX;  // above every bank
+    int filled = 0, n_end = 0, cur = TOP;
+    while (filled < K) {
+        const int below = max(bank0 < cur ? bank0 : -1, bank1 < cur ? bank1 : -1);
+        const int bank = -wave_min_i32(-below);                // the highest bank below cur that has a candidate
+        if (bank < 0) {
+            if (cur == TOP) break;                            // no candidate is left
+            cur = TOP;
+            continue;
+        }
+        cur = bank;
+        float bv = -INFINITY;
+        int bi = 0x7fffffff;
+        if (bank0 == bank && (bank1 != bank || v0 >= v1)) { bv = v0; bi = lane; }
+        else if (bank1 == bank) { bv = v1; bi = 64 + lane; }
+        wave_argmax(bv, bi);
+        if (bi == lane) bank0 = -1;
+        if (bi == 64 + lane) bank1 = -1;
+        const bool listb = bi >= 64;
+        const int j = bi & 63;
+        const int cls = listb ? b_cls[j] : a_cls[j];
+        const int par = listb ? j / Cd : j / K;
+        const unsigned mask = __shfl(listb ? m1 : m0, j, 64);
+        const int64_t o = (int64_t)b * K + filled;
+        if (lane == 0) {
+            a.pred[o] = cls;
+            a.new_lp[o] = bv;
+            a.back[o] = par;
+            a.rows[o] = (int64_t)b * K + par;
+            if (met_out) met_out[o] = (int32_t)mask;
+            if (bank_out) bank_out[o] = bank;
+        }
+        beam_write_hist(hist_in, hist_out, o, (int64_t)b * K + par, L, t, lane, cls, a.end);
+        n_end += cls == a.end;
+        ++filled;
+    }
+    for (; filled < K; ++filled) {
+        const int cls = a_cls[filled];
+        const int64_t o = (int64_t)b * K + filled;
+        if (lane == 0) {
+            a.pred[o] = cls;
+            a.new_lp[o] = -INFINITY;
+            a.back[o] = 0;
+            a.rows[o] = (int64_t)b * K;
+            if (met_out) met_out[o] = 0;
+            if (bank_out) bank_out[o] = 0;
+        }
+        beam_write_hist(hist_in, hist_out, o, (int64_t)b * K, L, t, lane, cls, a.end);
+        n_end += cls == a.end;
+    }
+    if (lane == 0 && a.ended_count) atomicAdd(a.ended_count, n_end);
+}
+
 }  // namespace dlsg

@@ -13,7 +13,8 @@ blocking and a minimum length, with no host synchronisation at all (`beam_select
 there is no back-trace; `beam_finalize` ranks the beams).  `ensemble_nbest` is that search run by several models at once: each
 member steps its own state, `beam_select_ens` combines their logits and chooses the beams (`ensemble.Ensemble`).
 `constrained_nbest` is `beam_nbest` whose captions must contain given words: `beam_select_cons` shares the beams out over the
-banks "constraints met" (dynamic beam allocation) and recomputes what a beam has met from its token history.
+banks "constraints met" (dynamic beam allocation) and recomputes what a beam has met from its token history; with phrases
+(`pack_phrases`) the same loop runs on `beam_select_phrases`, whose banks are (constraints met, progress into a phrase).
 """
 import torch
 
@@ -400,6 +401,127 @@ def check_constrained_options(k, L, B, cons, device, n_best=None, length_penalty
     return n
 
 
+MAX_PHRASE = 4                                     # DLSG_PHRASE_MAX
+
+
+def _is_phrase_string(x):
+    """a string that is more than one word"""
+    return isinstance(x, str) and x.split() != [x]
+
+
+def has_phrases(per_clip):
+    """whether per-clip constraint lists hold a string with whitespace in it: then they are phrases (`pack_phrases`), else the
+    words and sets of words of `pack_constraints`"""
+    for clip in per_clip:
+        for con in clip:
+            if any(_is_phrase_string(a) for a in (con if isinstance(con, (list, tuple, set, frozenset)) else [con])):
+                return True
+    return False
+
+
+def pack_phrases(per_clip, vocab, device=None, skip_unknown=False):
+    """The phrase tensor of `constrained_nbest`: (B, C, W, P) int64 padded with -1.  per_clip: for every clip a list of
+    constraints, each a phrase or a list (or set) of alternative phrases of which the caption must contain one as contiguous
+    words; a phrase is a string, split on whitespace, a tuple of words or word ids, or a single word or id.  ValueError for more
+    than 8 constraints per clip, 8 alternatives per constraint or 4 words per phrase, for an empty phrase, for <end>, <start> or
+    <pad> inside a phrase, and for a word outside the vocabulary -- unless skip_unknown: then the whole alternative is dropped, and
+    a constraint left with none is absent.  Alternatives that are equal are folded."""
+    special = {vocab(w) for w in ('<end>', '<start>', '<pad>') if w in vocab.word2idx}
+    packed = []
+    for b, clip in enumerate(per_clip):
+        if len(clip) > MAX_CONSTRAINTS:
+            raise ValueError('clip %d: %d constraints, at most %d per clip' % (b, len(clip), MAX_CONSTRAINTS))
+        sets = []
+        for con in clip:
+            alts = []
+            for a in (list(con) if isinstance(con, (list, set, frozenset)) else [con]):
+                words = a.split() if isinstance(a, str) else list(a) if isinstance(a, tuple) else [a]
+                if not words:
+                    raise ValueError('clip %d: an empty phrase %r' % (b, a))
+                if len(words) > MAX_PHRASE:
+                    raise ValueError('clip %d: %r has %d words, at most %d per phrase' % (b, a, len(words), MAX_PHRASE))
+                ids = []
+                for wd in words:
+                    if isinstance(wd, str):
+                        i = vocab.word2idx.get(wd, -1)
+                    else:
+                        i = int(wd) if 0 <= int(wd) < len(vocab) else -1
+                    if i < 0:
+                        if skip_unknown:
+                            break
+                        raise ValueError('clip %d: %r is not in the vocabulary' % (b, wd))
+                    if i in special:
+                        raise ValueError('clip %d: %r cannot be required (<end>, <start> and <pad> are not words of a caption)' % (b, wd))
+                    ids.append(i)
+                if len(ids) == len(words) and ids not in alts:
+                    alts.append(ids)
+            if len(alts) > MAX_ALTERNATIVES:
+                raise ValueError('clip %d: %d alternatives in one constraint, at most %d' % (b, len(alts), MAX_ALTERNATIVES))
+            sets.append(alts)
+        packed.append(sets)
+    C = max([len(s) for s in packed] + [0])
+    W = max([len(alts) for s in packed for alts in s] + [1])
+    P = max([len(ids) for s in packed for alts in s for ids in alts] + [1])
+    out = torch.full((len(packed), C, W, P), -1, dtype=torch.int64)
+    for b, sets in enumerate(packed):
+        for c, alts in enumerate(sets):
+            for w, ids in enumerate(alts):
+                out[b, c, w, :len(ids)] = torch.tensor(ids, dtype=torch.int64)
+    return out if device is None else out.to(device)
+
+
+def check_phrase_options(k, L, B, phr, device, n_best=None, length_penalty=0.0, no_repeat_ngram=0, min_len=0):
+    """ValueError for what `constrained_nbest` cannot run on a phrase tensor: what `check_nbest_options` refuses, a tensor of the
+    wrong shape, dtype or device, or with more constraints than words (C + 1 > max_words: the tensor's C counts, since nothing is
+    read back); returns n"""
+    n = check_nbest_options(k, L, n_best, length_penalty, no_repeat_ngram, min_len)
+    if not torch.is_tensor(phr) or phr.dtype != torch.int64:
+        raise ValueError('constraints: an int64 tensor (B, C, W, P) (pack_phrases makes one), not %s'
+                         % (phr.dtype if torch.is_tensor(phr) else type(phr).__name__))
+    if phr.dim() != 4 or phr.shape[0] != B:
+        raise ValueError('constraints of shape %s: (B, C, W, P) with B = %d clips' % (tuple(phr.shape), B))
+    if phr.shape[1] > MAX_CONSTRAINTS or (phr.shape[1] > 0 and not (1 <= phr.shape[2] <= MAX_ALTERNATIVES and 1 <= phr.shape[3] <= MAX_PHRASE)):
+        raise ValueError('constraints of shape %s: at most %d constraints per clip of 1 to %d alternative phrases of 1 to %d words'
+                         % (tuple(phr.shape), MAX_CONSTRAINTS, MAX_ALTERNATIVES, MAX_PHRASE))
+    if phr.device != device:
+        raise ValueError('constraints on %s, the clips on %s' % (phr.device, device))
+    if phr.shape[1] + 1 > L:
+        raise ValueError('%d constraints and <end> do not fit into max_words %d' % (phr.shape[1], L))
+    return n
+
+
+def check_phrases_fit(phr, L):
+    """ValueError if a clip of a host tensor of `pack_phrases` needs more than max_words for the search's guarantee: C_b constraints
+    of at most n_max_b words, and <end>"""
+    if phr.numel():
+        lens = (phr >= 0).sum(3)                                       # (pack_phrases pads behind the words only)
+        need = (lens > 0).any(2).sum(1) * lens.amax((1, 2)) + 1
+        if int(need.max()) > L:
+            b = int(need.argmax())
+            raise ValueError('clip %d: %d phrase constraints of up to %d words and <end> do not fit into max_words %d'
+                             % (b, int((lens[b] > 0).any(1).sum()), int(lens[b].max()), L))
+
+
+def phrases_met(ids, phrases, vocab_size=None):
+    """How many of its clip's phrase constraints every caption contains: ids (B, n, L) or (B, L) int64, phrases (B, C, W, P) int64 as
+    `pack_phrases` makes them (a phrase: the leading run of ids in [0, vocab_size), any id >= 0 without vocab_size) -> (B, n) or
+    (B,) int64, the number of constraints with an alternative that stands in the caption as contiguous tokens.  Device tensors in,
+    a device tensor out, nothing is read back; any captions, not only a search's."""
+    if ids.dim() not in (2, 3) or phrases.dim() != 4 or ids.shape[0] != phrases.shape[0]:
+        raise ValueError('phrases_met: ids (B, n, L) or (B, L) and phrases (B, C, W, P), not %s and %s' % (tuple(ids.shape), tuple(phrases.shape)))
+    rows = ids if ids.dim() == 3 else ids.unsqueeze(1)
+    B, n, L = rows.shape
+    _, C, W, P = phrases.shape
+    valid = phrases >= 0 if vocab_size is None else (phrases >= 0) & (phrases < vocab_size)
+    run = valid.long().cumprod(3).bool()                               # (B, C, W, P): word j belongs to the phrase
+    # the P tokens from every position on, -2 behind the caption's end
+    win = torch.cat([rows, rows.new_full((B, n, max(P - 1, 0)), -2)], 2).unfold(2, P, 1) if P else rows.new_zeros(B, n, L, 0)
+    same = (win.view(B, n, L, 1, 1, P) == phrases.view(B, 1, 1, C, W, P)) | ~run.view(B, 1, 1, C, W, P)
+    occurs = same.all(5) & run[..., :1].reshape(B, 1, 1, C, W)         # an absent alternative occurs nowhere
+    met = occurs.any(2).any(3).sum(2)                                  # (B, n)
+    return met if ids.dim() == 3 else met[:, 0]
+
+
 @torch.no_grad()
 def constrained_nbest(model, visual_feats, region_feats, constraints, n_best=None, length_penalty=0.0, no_repeat_ngram=0, min_len=0,
                       beam_size=None, return_met=False):
@@ -411,7 +533,13 @@ def constrained_nbest(model, visual_feats, region_feats, constraints, n_best=Non
     met every constraint, and the beams are shared out over the banks "number of constraints met" at every word
     (`beam_select_cons`, include/dlsg.h), so row 0 meets every constraint whose set holds a word the model gives a finite logit.
     The loop is `beam_nbest`'s: the same buffers, all L steps launched, nothing read back -- the met masks are recomputed from the
-    token history, so there is no further state.  Without constraints the result is `beam_nbest`'s, bit for bit."""
+    token history, so there is no further state.  Without constraints the result is `beam_nbest`'s, bit for bit.
+    Phrases: a (B, C, W, P) int64 tensor of `pack_phrases`, or per-clip lists in which some string holds whitespace ("hot dog"),
+    which are packed by it, require phrases as contiguous words (`_phrase_nbest`: one `beam_select_phrases` launch per word).  A
+    3-D tensor and lists without such a string run what they always ran."""
+    if (torch.is_tensor(constraints) and constraints.dim() == 4) or (not torch.is_tensor(constraints) and has_phrases(constraints)):
+        return _phrase_nbest(model, visual_feats, region_feats, constraints, n_best, length_penalty, no_repeat_ngram, min_len,
+                             beam_size, return_met)
     dec = model.decoder
     k, L = dec.beam_size if beam_size is None else beam_size, dec.max_words
     B, dev = visual_feats.shape[0], visual_feats.device
@@ -426,6 +554,36 @@ def constrained_nbest(model, visual_feats, region_feats, constraints, n_best=Non
     valid = (cons >= 0) & (cons < dec.vocab_size)
     hit = (ids.view(B, k, L, 1, 1) == cons.view(B, 1, 1, *cons.shape[1:])) & valid.view(B, 1, 1, *cons.shape[1:])
     met = hit.any(4).any(2).sum(2)                                 # (B, k)
+    order = met.sort(dim=1, descending=True, stable=True)[1][:, :n]
+    out = (ids.gather(1, order.unsqueeze(2).expand(B, n, L)), scores.gather(1, order), lens.gather(1, order))
+    return out + (met.gather(1, order),) if return_met else out
+
+
+def _phrase_nbest(model, visual_feats, region_feats, constraints, n_best, length_penalty, no_repeat_ngram, min_len, beam_size,
+                  return_met):
+    """`constrained_nbest` with phrases: the same loop on `beam_select_phrases`, whose banks are (constraints met, progress into a
+    phrase); what a beam has met and how far into a phrase it is are recomputed from its history row, so there is still no state
+    beside `_hist_search`'s and nothing is read back.  Lists are packed on the host, where the bound of the guarantee is checked:
+    C_b constraints of up to n_max_b words meet within C_b * n_max_b words (no_repeat_ngram = 0, finite logits), which with <end>
+    must fit into max_words.  With an n-gram ban the next word of a phrase can be banned although the phrase has not occurred: the
+    search is then best effort, and a beam that cannot finish runs to max_words without <end>.  The rows of a clip are ordered by
+    `phrases_met` of the final ids, most first, then by score."""
+    dec = model.decoder
+    k, L = dec.beam_size if beam_size is None else beam_size, dec.max_words
+    B, dev = visual_feats.shape[0], visual_feats.device
+    if torch.is_tensor(constraints):
+        phr = constraints
+    else:
+        phr = pack_phrases(constraints, dec.vocab)
+        check_phrases_fit(phr, L)
+        phr = phr.to(dev)
+    n = check_phrase_options(k, L, B, phr, dev, n_best, length_penalty, no_repeat_ngram, min_len)
+    phr = phr.contiguous()
+
+    def select(t, logits, step):
+        model.ops.beam_select_phrases(logits[0], *step, phr, no_repeat_ngram, min_len)
+    ids, scores, lens = _finalize(model, *_hist_search([model], k, visual_feats, region_feats, select), k, k, length_penalty)
+    met = phrases_met(ids, phr, dec.vocab_size)
     order = met.sort(dim=1, descending=True, stable=True)[1][:, :n]
     out = (ids.gather(1, order.unsqueeze(2).expand(B, n, L)), scores.gather(1, order), lens.gather(1, order))
     return out + (met.gather(1, order),) if return_met else out

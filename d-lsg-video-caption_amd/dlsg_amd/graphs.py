@@ -202,9 +202,10 @@ class StochasticBeamGraph(_SeededGraph):
 
 class ConstrainedBeamGraph(_InferenceGraph):
     """hipGraph-captured `model.constrained_beam_search(frames, regions, constraints, **options)` for one batch shape and one shape
-    (B, C, W) of the constraint tensor, which is a static buffer like the inputs: `graph(frames, regions, constraints)` stages all
-    three and replays; constraints are the packed int64 tensor or the per-clip lists (packed to the captured shape; ValueError for
-    another shape).  A replay returns the eager call's (ids, scores, lens[, met]), static buffers, and synchronises nothing."""
+    of the constraint tensor -- (B, C, W) words or (B, C, W, P) phrases --, which is a static buffer like the inputs:
+    `graph(frames, regions, constraints)` stages all three and replays; constraints are the packed int64 tensor or the per-clip lists
+    (packed to the captured shape, by `pack_phrases` where that is 4-D; ValueError for another shape).  A replay returns the eager
+    call's (ids, scores, lens[, met]), static buffers, and synchronises nothing."""
 
     def __init__(self, model, frames, regions, constraints, **options):
         self.options = options
@@ -212,10 +213,13 @@ class ConstrainedBeamGraph(_InferenceGraph):
         super().__init__(model, frames, regions)
 
     @staticmethod
-    def _packed(model, constraints, device):
-        from .beam import pack_constraints
+    def _packed(model, constraints, device, phrases=None):
+        """constraints as a tensor; phrases: whether lists are phrases (None: as `constrained_nbest` decides)"""
+        from .beam import has_phrases, pack_constraints, pack_phrases
         if torch.is_tensor(constraints):
             return constraints
+        if has_phrases(constraints) if phrases is None else phrases:
+            return pack_phrases(constraints, model.decoder.vocab, device)
         return pack_constraints(constraints, model.decoder.vocab, device)
 
     def _run(self):
@@ -223,11 +227,11 @@ class ConstrainedBeamGraph(_InferenceGraph):
 
     def _fitted(self, constraints):
         """the constraints as a tensor of the captured shape: per-clip lists are packed and padded to it; ValueError otherwise"""
-        cons = self._packed(self.model, constraints, self.cons.device)
-        if not torch.is_tensor(constraints) and cons.dim() == 3 and cons.shape[0] == self.cons.shape[0] and \
-                cons.shape[1] <= self.cons.shape[1] and cons.shape[2] <= self.cons.shape[2]:
+        cons = self._packed(self.model, constraints, self.cons.device, self.cons.dim() == 4)
+        if not torch.is_tensor(constraints) and cons.dim() == self.cons.dim() and cons.shape[0] == self.cons.shape[0] and \
+                all(a <= b for a, b in zip(cons.shape, self.cons.shape)):
             wide = torch.full_like(self.cons, -1)
-            wide[:, :cons.shape[1], :cons.shape[2]] = cons
+            wide[tuple(slice(0, a) for a in cons.shape)] = cons
             cons = wide
         if cons.shape != self.cons.shape or cons.dtype != self.cons.dtype or cons.device != self.cons.device:
             raise ValueError('ConstrainedBeamGraph: constraints of shape %s %s on %s, captured with %s int64 on %s -- build a new graph'

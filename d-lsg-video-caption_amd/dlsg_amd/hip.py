@@ -587,6 +587,27 @@ class HipOps(object):
         self._check(self.lib.dlsg_beam_select_cons(C.byref(a), *hist, _p(cons) if Cn else None, Cn, W, _p(met_out), self._stream()),
                     'dlsg_beam_select_cons')
 
+    def beam_select_phrases(self, logits, last, last_lp, pred, new_lp, back, rows, k, end, hist_in, hist_out, t, phr,
+                            no_repeat_ngram=0, min_len=0, ended_count=None, met_out=None, bank_out=None):
+        """`beam_select_cons` whose constraints are sets of alternative phrases: phr (B, C, W, P) int64 holds per clip C sets of W
+        phrases of up to P <= 4 word ids (a phrase is the leading run of ids in [0, V)); a constraint is met once a phrase of its
+        set stands in the beam's history as contiguous tokens, and the banks are (constraints met, progress into a phrase) (see
+        include/dlsg.h).  P == 1: the bits of `beam_select_cons`; phr None, or C == 0: those of `beam_select_hist`.  met_out,
+        bank_out (B*k) int32, optional: the new beams' met masks and banks."""
+        R, V = logits.shape
+        a, hist = self._hist_step(R, V, last, last_lp, pred, new_lp, back, rows, k, end, hist_in, hist_out, t, no_repeat_ngram, min_len,
+                                  ended_count, logits)
+        Cn, W, P = 0, 1, 1
+        if phr is not None:
+            assert phr.dtype == torch.int64 and phr.is_contiguous() and phr.dim() == 4 and phr.shape[0] == R // k, (phr.dtype, phr.shape)
+            assert phr.device == logits.device, (phr.device, logits.device)
+            Cn, W, P = phr.shape[1:]
+        for o in (met_out, bank_out):
+            if o is not None:
+                assert o.dtype == torch.int32 and o.is_contiguous() and o.numel() == R, (o.dtype, o.shape)
+        self._check(self.lib.dlsg_beam_select_phrases(C.byref(a), *hist, _p(phr) if Cn else None, Cn, W, P, _p(met_out), _p(bank_out),
+                                                      self._stream()), 'dlsg_beam_select_phrases')
+
     def beam_select_gumbel(self, logits, last, last_lp, pred, new_lp, back, rows, k, end, hist_in, hist_out, t, G_in, G_out,
                            temperature=1.0, seed=0, site_sample=0, no_repeat_ngram=0, min_len=0, ended_count=None):
         """`beam_select_hist` for stochastic beam search: the k new beams of a clip are the k largest perturbed values G (float64,

@@ -293,7 +293,12 @@ class _HipModel(_ArenaModule):
         (at most 8 constraints of 8 alternatives), or the (B, C, W) int64 device tensor `dlsg_amd.pack_constraints` makes of them.
         Returns (ids, scores, lens) as `beam_search`, a clip's rows ordered by the number of constraints met, most first, then by
         score; return_met=True adds that number (B, n) int64.  Row 0 meets every constraint that has a word the model can emit; a
-        caption ends only with all of them met (`beam.constrained_nbest`).  Nothing synchronises with the host."""
+        caption ends only with all of them met (`beam.constrained_nbest`).  Nothing synchronises with the host.
+        Multi-word phrases: lists in which a string holds whitespace ("hot dog"; a constraint is then a phrase or a list of
+        alternative phrases, a phrase a string, a tuple of words or ids, or one word, at most 4 words), or the (B, C, W, P) tensor
+        `dlsg_amd.pack_phrases` makes, require phrases as contiguous words; met then counts the constraints with a phrase in the row
+        (`dlsg_amd.phrases_met`).  C_b phrase constraints of up to n words need C_b * n + 1 <= max_words; with no_repeat_ngram the
+        next word of a phrase can be banned, the search is then best effort and a beam that cannot finish runs to max_words."""
         from .beam import constrained_nbest
         return constrained_nbest(self, visual_feats, region_feats, constraints, n_best=n_best, length_penalty=length_penalty,
                                  no_repeat_ngram=no_repeat_ngram, min_len=min_len, beam_size=beam_size, return_met=return_met)

@@ -660,7 +660,8 @@ def gather_results(net, eval_loader, decode=None):
     optionally consensus_weights, consensus_temperature) every beam of that search is kept and the caption is the one the
     others agree with most: row 0 of `consensus.consensus_search`.  With the key constraints=fn, fn(video_ids) -> the batch's
     per-clip constraint lists or packed tensor (`beam.pack_constraints`), the caption is row 0 of
-    `constrained_beam_search` with the other options: it contains a word of every constraint (not together with consensus).
+    `constrained_beam_search` with the other options: it contains a word of every constraint (not together with consensus); fn may
+    as well return phrases -- lists with strings such as "hot dog", or the tensor of `beam.pack_phrases` --, which that call dispatches.
     With the key rescore=scorer (a model or an `Ensemble`; optionally rescore_mix) every beam of that search is kept and the
     caption is the one the scorer ranks first: row 0 of `rescore.rescore_search` (not together with consensus or constraints)."""
     import torch

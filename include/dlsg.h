@@ -926,14 +926,54 @@ int dlsg_beam_select_gumbel(const dlsg_beam_select_args* a, const int64_t* hist_
  * met_out (B*k) int32, optional: the new beam's mask with the chosen word, 0 for a left-over slot.  While a beam of the clip has an
  * unmet constraint with a finite-logit word, the highest bank among the clip's beams rises by one per step, and the top bank is
  * served first, so from step C_b on a beam with every constraint met exists and stays.  With C == 0, cons NULL or every constraint
- * of a clip absent there is one bank and the clip's outputs are the bits of dlsg_beam_select_hist.  Not covered: multi-word
- * phrases, ordered constraints, the same word twice.  One workgroup per clip, one wave per row, the allocation in one wave; no
+ * of a clip absent there is one bank and the clip's outputs are the bits of dlsg_beam_select_hist.  Not covered: ordered
+ * constraints, the same word twice; multi-word phrases are dlsg_beam_select_phrases'.  One workgroup per clip, one wave per row, the allocation in one wave; no
  * atomics but ended_count's; deterministic.  EINVAL for what dlsg_beam_select_hist refuses, C < 0, C > DLSG_CONS_MAX, and with
  * C > 0: W < 1, W > DLSG_CONS_ALT, cons NULL. */
 #define DLSG_CONS_MAX 8   /* constraints per clip */
 #define DLSG_CONS_ALT 8   /* alternative words per constraint */
 int dlsg_beam_select_cons(const dlsg_beam_select_args* a, const int64_t* hist_in, int64_t* hist_out, int L, int t,
                           int no_repeat_ngram, int min_len, const int64_t* cons, int C, int W, int32_t* met_out, void* stream);
+/* dlsg_beam_select_cons whose constraints are sets of alternative PHRASES: a caption must contain, as contiguous words, a phrase of
+ * every constraint of its clip.  phr (B, C, W, P) int64, device: C <= DLSG_CONS_MAX constraints per clip, W <= DLSG_CONS_ALT
+ * alternatives per constraint, 1 <= P <= DLSG_PHRASE_MAX words per alternative.  Alternative a is the leading run of entries in
+ * [0, V): its length n(a) is the number of such entries before the first entry outside that range, whatever follows is ignored,
+ * n(a) = 0 means absent; a constraint is present iff it has a valid alternative; clips may differ in all of this.
+ * The state of a row is recomputed from its history h[0..t) at every step, nothing is carried:
+ *   a OCCURS if h[i..i+n) == a for some i; constraint c is MET if a valid alternative of c occurs (`met`: the bit mask);
+ *   unmet = present & ~met;
+ *   the PROGRESS p(a) of a is the largest j <= min(n(a) - 1, t) such that the last j tokens of h equal a[0..j) -- the longest
+ *   border: for "x x y" behind "... x x x" it is 2, not 0;
+ *   the progress q of a row is the maximum of p(a) over the valid alternatives of its unmet constraints, 0 without any;
+ *   the BANK of a row is the pair (popcount(met), q), ordered lexicographically.
+ * The step is dlsg_beam_select_hist's (log-softmax, (value, index) order, bans, step 0 reading the clip's first row) with the three
+ * additions of dlsg_beam_select_cons, generalised.  (1) `end` is banned for a live row while unmet != 0.  (2) List B: a live row
+ * offers, beside list A, one slot per unmet constraint.  Every valid alternative a of the constraint proposes the word
+ * u = a[p(a)], with the gain s(a) = P if p(a) + 1 == n(a) (the word completes the phrase), else p(a) + 1; a proposal is out if u is
+ * banned or its logit is -inf or NaN; the slot takes the proposal with the largest gain, then the larger logit, then the lower
+ * class, at (x - lse) + last_lp in the float32 operations of list A; it is empty if that class already is in the row's list A or
+ * in an earlier slot of the row (no fall-through to the next proposal).  (3) Merge: every candidate (parent row, class u) above
+ * -inf, of either list, has the bank of the history h_parent + [u] by the definitions above; a candidate `end` changes neither
+ * met nor progress.  The k output slots are filled round-robin over the non-empty banks from the highest bank down, each time with
+ * the best candidate left in the bank: larger value first, ties to the lower candidate index (list A before list B, list B indexed
+ * by row, then constraint); left-over slots as dlsg_beam_select_cons fills them.  new_lp is the plain log-prob.  met_out (B*k)
+ * int32, optional: the new beam's mask; bank_out (B*k) int32, optional: popcount(met) * DLSG_PHRASE_MAX + q; both 0 for a
+ * left-over slot.
+ * One word may serve several constraints ("hot dog house" meets "hot dog" and "dog house").  Widening C, W or P with entries of -1
+ * changes no output bit.  With P == 1 the launch returns the bits of dlsg_beam_select_cons; with C == 0, phr NULL or only absent
+ * constraints those of dlsg_beam_select_hist.  A row of the clip's highest bank whose deciding constraint has a proposal that is
+ * not out offers a candidate of a strictly higher bank, and the highest bank is served first: with no_repeat_ngram == 0 and finite
+ * logits some beam meets every present constraint within C_b * n_max_b words (n_max_b: the clip's longest phrase) and is never
+ * dropped.  Progress can be thrown away -- completing a one-word constraint mid-phrase outranks continuing the phrase --, hence not
+ * the sum of the lengths.  With an n-gram ban the next word of a phrase can be banned without the phrase having occurred
+ * (g = 2, "a b c" behind "b c ... a b"): best effort, a beam that cannot finish runs on without `end`.  Not covered: ordered
+ * constraints, the same phrase twice, phrases of more than DLSG_PHRASE_MAX words.  One workgroup per clip, one wave per row, the
+ * merge in one wave; no atomics but ended_count's, a fixed reduction order: two launches give equal bits.  EINVAL for what
+ * dlsg_beam_select_cons refuses, and with C > 0 for P < 1 or P > DLSG_PHRASE_MAX. */
+#define DLSG_PHRASE_MAX 4   /* words per phrase */
+int dlsg_beam_select_phrases(const dlsg_beam_select_args* a, const int64_t* hist_in, int64_t* hist_out, int L, int t,
+                             int no_repeat_ngram, int min_len, const int64_t* phr, int C, int W, int P, int32_t* met_out,
+                             int32_t* bank_out, void* stream);
 /* After the last step: the n <= k best beams of every clip by score = lp / len^alpha (computed in double, stored as float),
  * descending, ties to the lower beam.  hist (B*k, L) the final history, lp (B*k) the final log-probs; len = tokens up to and
  * including the first `end`, L without one.  Out: ids (B, n, L) int64, scores (B, n), lens (B, n) int64.  One wave per clip. */
