@@ -15,7 +15,7 @@ import os
 
 import torch
 
-from . import abi
+from . import abi, limits
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, 'libdlsg_hip.so')
@@ -451,7 +451,7 @@ class HipOps(object):
 
     # ------------------------------------------------------------------ o2v graph
     def o2v_supported(self, T, H):
-        return T <= 32 and H in (64, 512, 1024)
+        return limits.o2v(T, H)
 
     def o2v_fwd(self, y, v, g_obj, b_obj, z, ml, ostats, S, scale, nsplit, eps=1e-5):
         self.o2v_fwd_multi([dict(y=y, v=v, g_obj=g_obj, b_obj=b_obj, z=z, ml=ml, ostats=ostats, S=S)], scale, nsplit, eps)
@@ -697,7 +697,7 @@ class HipOps(object):
 
     # ------------------------------------------------------------------ small per-clip graphs of the encoder
     def latent_psl_supported(self, T, P, H):
-        return T <= 32 and P <= 32 and H % 4 == 0 and H <= 2048 and T * H * 4 <= 140 * 1024
+        return limits.latent_psl(T, P, H)
 
     def _psl_args(self, a, ov, theta, gamma, beta, adj, u, out, stats, p=0.0, site=0, seed=0, eps=1e-5):
         B, T, H = ov.shape
@@ -724,7 +724,7 @@ class HipOps(object):
         self._check(self.lib.dlsg_latent_psl_fwd_multi(arr, n, self._stream()), 'dlsg_latent_psl_fwd_multi')
 
     def latent_psl_bwd_supported(self, T, P, H):
-        return T <= 32 and P <= 8 and H % 4 == 0 and H <= 2048 and (T + 8) * H * 4 <= 150 * 1024
+        return limits.latent_psl_bwd(T, P, H)
 
     def _psl_bwd_args(self, a, dout, u, stats, gamma, adj, ov, theta, dov, dtheta_part, part, p=0.0, site=0, seed=0):
         B, T, H = ov.shape
@@ -751,7 +751,7 @@ class HipOps(object):
         self._check(self.lib.dlsg_latent_psl_bwd_multi(arr, n, self._stream()), 'dlsg_latent_psl_bwd_multi')
 
     def sa_core_supported(self, T, D):
-        return T <= 32 and D % 64 == 0
+        return limits.sa_core(T, D)
 
     def sa_core_fwd(self, K, Q, V, w, out, scale, mask=None):
         """K, Q, V (B,T,D) -> w (B,T,T) = softmax_j(K_i.Q_j*scale), out (B,T,D) = w V; one launch."""
@@ -838,10 +838,10 @@ class HipOps(object):
     # sampled word may differ from argmax(logits).  The reference itself is not bit-stable there (its GEMM's order is the
     # library's); every fixture with sampled steps -- reference-generated, both sides of this threshold -- gives identical ids
     # (tests/test_gpu_parity.py, test_gpu_bench_parity.py: MSVD below, MSR-VTT above).
-    DEC_TAIL_SAMPLE_MAX_WEIGHTS = 1 << 21
+    DEC_TAIL_SAMPLE_MAX_WEIGHTS = limits.DEC_TAIL_SAMPLE_MAX_WEIGHTS
 
     def dec_tail_sample_supported(self, V, D):
-        return V * D <= self.DEC_TAIL_SAMPLE_MAX_WEIGHTS
+        return limits.dec_tail_sample(V, D)
 
     # s_split of every dec_tail_fwd(sample=...) launch: 0 the library's choice (dlsg_dec_tail_split), 1 unsplit, 2 ..
     # DLSG_DEC_TAIL_MAX_SPLIT forced (tests).  The outputs do not depend on it.

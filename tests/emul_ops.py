@@ -10,6 +10,7 @@ import math
 import numpy as np
 import torch
 
+from dlsg_amd import limits
 from emul_critic import CriticEmul
 
 GEMM_NT, GEMM_NN, GEMM_TN = 0, 1, 2
@@ -207,7 +208,7 @@ class EmulOps(CriticEmul):
 
     # ------------------------------------------------------------------ o2v
     def o2v_supported(self, T, H):
-        return self.fused_supported and T <= 32
+        return self.fused_supported and limits.o2v(T, H)
 
     def o2v_fwd(self, y, v, g_obj, b_obj, z, ml, ostats, S, scale, nsplit, eps=1e-5):
         self._count('o2v_fwd')
@@ -289,7 +290,7 @@ class EmulOps(CriticEmul):
             ds.copy_(sr[rows])
 
     def latent_psl_supported(self, T, P, H):
-        return self.fused_supported and T <= 32 and P <= 32 and H % 4 == 0
+        return self.fused_supported and limits.latent_psl(T, P, H)
 
     def latent_psl_fwd(self, ov, theta, gamma, beta, adj, u, out, stats, p=0.0, site=0, seed=0, eps=1e-5):
         B, T, H = ov.shape
@@ -308,7 +309,7 @@ class EmulOps(CriticEmul):
             self.latent_psl_bwd(**it)
 
     def latent_psl_bwd_supported(self, T, P, H):
-        return self.fused_supported and T <= 32 and P <= 8 and H % 4 == 0
+        return self.fused_supported and limits.latent_psl_bwd(T, P, H)
 
     def latent_psl_bwd(self, dout, u, stats, gamma, adj, ov, theta, dov, dtheta_part, part, p=0.0, site=0, seed=0):
         B, T, H = ov.shape
@@ -324,7 +325,7 @@ class EmulOps(CriticEmul):
         dtheta_part.copy_(dlg.transpose(1, 2) @ ov)
 
     def sa_core_supported(self, T, D):
-        return self.fused_supported and T <= 32 and D % 64 == 0
+        return self.fused_supported and limits.sa_core(T, D)
 
     def sa_core_fwd(self, K, Q, V, w, out, scale, mask=None):
         lg = (K @ Q.transpose(1, 2)) * scale
@@ -382,7 +383,7 @@ class EmulOps(CriticEmul):
                            seed=seed, eps=eps)
 
     def dec_tail_sample_supported(self, V, D):
-        return self.fused_supported and V * D <= (1 << 21)
+        return self.fused_supported and limits.dec_tail_sample(V, D)
 
     def dec_tail_fwd(self, slabs, b_ih, b_hh, c_prev, c, hd, gates, ln, dout, st_l, p, site, seed=0, eps=1e-5, sample=None):
         B, D = c.shape
