@@ -14,7 +14,10 @@ there is no back-trace; `beam_finalize` ranks the beams).  `ensemble_nbest` is t
 member steps its own state, `beam_select_ens` combines their logits and chooses the beams (`ensemble.Ensemble`).
 `constrained_nbest` is `beam_nbest` whose captions must contain given words: `beam_select_cons` shares the beams out over the
 banks "constraints met" (dynamic beam allocation) and recomputes what a beam has met from its token history; with phrases
-(`pack_phrases`) the same loop runs on `beam_select_phrases`, whose banks are (constraints met, progress into a phrase).
+(`pack_phrases`) the same loop runs on `beam_select_phrases`, whose banks are (constraints met, progress into a phrase).  Words
+and phrases share their host side: one packer (`_pack`; `pack_constraints` and `pack_phrases` are its two ways of reading a
+constraint's alternatives), one check of a packed tensor (`_check_packed`) and one search body, which differs by the tensor's
+rank in the step it launches and in how `_constraints_met` counts.
 """
 import torch
 
@@ -335,98 +338,16 @@ def importance_weights(logp, kappa):
     return phi.exp() / -torch.expm1(-(phi - kappa.double().unsqueeze(1)).exp())
 
 
-MAX_CONSTRAINTS, MAX_ALTERNATIVES = 8, 8          # DLSG_CONS_MAX, DLSG_CONS_ALT
+MAX_CONSTRAINTS, MAX_ALTERNATIVES, MAX_PHRASE = 8, 8, 4          # DLSG_CONS_MAX, DLSG_CONS_ALT, DLSG_PHRASE_MAX
 
 
-def pack_constraints(per_clip, vocab, device=None, skip_unknown=False):
-    """The constraint tensor of `constrained_nbest`: (B, C, W) int64 padded with -1.  per_clip: for every clip a list of
-    constraints, each a word, a word id or a list of alternatives (words or ids) of which the caption must contain one.
-    ValueError for more than 8 constraints per clip or 8 alternatives per constraint, for <end>, <start> or <pad> in a set, and
-    for a word outside the vocabulary -- unless skip_unknown: then the alternative is dropped, and a constraint left with none is
-    absent."""
+def _pack(per_clip, vocab, device, skip_unknown, phrases):
+    """The packer of both constraint tensors: (B, C, W, P) int64 padded with -1 from per-clip lists of constraints, each one
+    alternative or a collection of them.  phrases says how a constraint's alternatives are read: as phrases (a string is split on
+    whitespace, a tuple is one phrase of words or ids) or as single words (a tuple is a collection of alternatives; P is 1 and the
+    axis is dropped).  An alternative with a word outside the vocabulary is refused or, with skip_unknown, dropped whole."""
     special = {vocab(w) for w in ('<end>', '<start>', '<pad>') if w in vocab.word2idx}
-    packed = []
-    for b, clip in enumerate(per_clip):
-        if len(clip) > MAX_CONSTRAINTS:
-            raise ValueError('clip %d: %d constraints, at most %d per clip' % (b, len(clip), MAX_CONSTRAINTS))
-        sets = []
-        for con in clip:
-            alts = list(con) if isinstance(con, (list, tuple, set, frozenset)) else [con]
-            ids = []
-            for a in alts:
-                if isinstance(a, str):
-                    known = a in vocab.word2idx
-                    i = vocab.word2idx[a] if known else -1
-                else:
-                    i = int(a)
-                    known = 0 <= i < len(vocab)
-                if not known:
-                    if skip_unknown:
-                        continue
-                    raise ValueError('clip %d: %r is not in the vocabulary' % (b, a))
-                if i in special:
-                    raise ValueError('clip %d: %r cannot be required (<end>, <start> and <pad> are not words of a caption)' % (b, a))
-                if i not in ids:
-                    ids.append(i)
-            if len(ids) > MAX_ALTERNATIVES:
-                raise ValueError('clip %d: %d alternatives in one constraint, at most %d' % (b, len(ids), MAX_ALTERNATIVES))
-            sets.append(ids)
-        packed.append(sets)
-    C = max([len(s) for s in packed] + [0])
-    W = max([len(ids) for s in packed for ids in s] + [1])
-    out = torch.full((len(packed), C, W), -1, dtype=torch.int64)
-    for b, sets in enumerate(packed):
-        for c, ids in enumerate(sets):
-            out[b, c, :len(ids)] = torch.tensor(ids, dtype=torch.int64)
-    return out if device is None else out.to(device)
-
-
-def check_constrained_options(k, L, B, cons, device, n_best=None, length_penalty=0.0, no_repeat_ngram=0, min_len=0):
-    """ValueError for what `constrained_nbest` cannot run (what `check_nbest_options` refuses, and a constraint tensor of the wrong
-    shape, dtype or device, or with more constraints than words: a caption of max_words tokens holds max_words - 1 words and
-    <end>; the tensor's C counts, since nothing is read back); returns n"""
-    n = check_nbest_options(k, L, n_best, length_penalty, no_repeat_ngram, min_len)
-    if not torch.is_tensor(cons) or cons.dtype != torch.int64:
-        raise ValueError('constraints: an int64 tensor (B, C, W) (pack_constraints makes one), not %s'
-                         % (cons.dtype if torch.is_tensor(cons) else type(cons).__name__))
-    if cons.dim() != 3 or cons.shape[0] != B:
-        raise ValueError('constraints of shape %s: (B, C, W) with B = %d clips' % (tuple(cons.shape), B))
-    if cons.shape[1] > MAX_CONSTRAINTS or (cons.shape[1] > 0 and not 1 <= cons.shape[2] <= MAX_ALTERNATIVES):
-        raise ValueError('constraints of shape %s: at most %d constraints per clip of 1 to %d alternatives'
-                         % (tuple(cons.shape), MAX_CONSTRAINTS, MAX_ALTERNATIVES))
-    if cons.device != device:
-        raise ValueError('constraints on %s, the clips on %s' % (cons.device, device))
-    if cons.shape[1] + 1 > L:
-        raise ValueError('%d constraints and <end> do not fit into max_words %d' % (cons.shape[1], L))
-    return n
-
-
-MAX_PHRASE = 4                                     # DLSG_PHRASE_MAX
-
-
-def _is_phrase_string(x):
-    """a string that is more than one word"""
-    return isinstance(x, str) and x.split() != [x]
-
-
-def has_phrases(per_clip):
-    """whether per-clip constraint lists hold a string with whitespace in it: then they are phrases (`pack_phrases`), else the
-    words and sets of words of `pack_constraints`"""
-    for clip in per_clip:
-        for con in clip:
-            if any(_is_phrase_string(a) for a in (con if isinstance(con, (list, tuple, set, frozenset)) else [con])):
-                return True
-    return False
-
-
-def pack_phrases(per_clip, vocab, device=None, skip_unknown=False):
-    """The phrase tensor of `constrained_nbest`: (B, C, W, P) int64 padded with -1.  per_clip: for every clip a list of
-    constraints, each a phrase or a list (or set) of alternative phrases of which the caption must contain one as contiguous
-    words; a phrase is a string, split on whitespace, a tuple of words or word ids, or a single word or id.  ValueError for more
-    than 8 constraints per clip, 8 alternatives per constraint or 4 words per phrase, for an empty phrase, for <end>, <start> or
-    <pad> inside a phrase, and for a word outside the vocabulary -- unless skip_unknown: then the whole alternative is dropped, and
-    a constraint left with none is absent.  Alternatives that are equal are folded."""
-    special = {vocab(w) for w in ('<end>', '<start>', '<pad>') if w in vocab.word2idx}
+    collections = (list, set, frozenset) if phrases else (list, tuple, set, frozenset)
     packed = []
     for b, clip in enumerate(per_clip):
         if len(clip) > MAX_CONSTRAINTS:
@@ -434,8 +355,8 @@ def pack_phrases(per_clip, vocab, device=None, skip_unknown=False):
         sets = []
         for con in clip:
             alts = []
-            for a in (list(con) if isinstance(con, (list, set, frozenset)) else [con]):
-                words = a.split() if isinstance(a, str) else list(a) if isinstance(a, tuple) else [a]
+            for a in (list(con) if isinstance(con, collections) else [con]):
+                words = [a] if not phrases else a.split() if isinstance(a, str) else list(a) if isinstance(a, tuple) else [a]
                 if not words:
                     raise ValueError('clip %d: an empty phrase %r' % (b, a))
                 if len(words) > MAX_PHRASE:
@@ -467,27 +388,77 @@ def pack_phrases(per_clip, vocab, device=None, skip_unknown=False):
         for c, alts in enumerate(sets):
             for w, ids in enumerate(alts):
                 out[b, c, w, :len(ids)] = torch.tensor(ids, dtype=torch.int64)
+    out = out if phrases else out.squeeze(3)
     return out if device is None else out.to(device)
+
+
+def pack_constraints(per_clip, vocab, device=None, skip_unknown=False):
+    """The constraint tensor of `constrained_nbest`: (B, C, W) int64 padded with -1.  per_clip: for every clip a list of
+    constraints, each a word, a word id or a list of alternatives (words or ids) of which the caption must contain one.
+    ValueError for more than 8 constraints per clip or 8 alternatives per constraint, for <end>, <start> or <pad> in a set, and
+    for a word outside the vocabulary -- unless skip_unknown: then the alternative is dropped, and a constraint left with none is
+    absent."""
+    return _pack(per_clip, vocab, device, skip_unknown, phrases=False)
+
+
+def _check_packed(k, L, B, cons, device, phrases, n_best, length_penalty, no_repeat_ngram, min_len):
+    """ValueError for what `constrained_nbest` cannot run on a packed tensor, (B, C, W) words or (B, C, W, P) phrases: what
+    `check_nbest_options` refuses, a tensor of the wrong shape, dtype or device, or with more constraints than words; returns n"""
+    n = check_nbest_options(k, L, n_best, length_penalty, no_repeat_ngram, min_len)
+    axes, packer = ('(B, C, W, P)', 'pack_phrases') if phrases else ('(B, C, W)', 'pack_constraints')
+    if not torch.is_tensor(cons) or cons.dtype != torch.int64:
+        raise ValueError('constraints: an int64 tensor %s (%s makes one), not %s'
+                         % (axes, packer, cons.dtype if torch.is_tensor(cons) else type(cons).__name__))
+    if cons.dim() != (4 if phrases else 3) or cons.shape[0] != B:
+        raise ValueError('constraints of shape %s: %s with B = %d clips' % (tuple(cons.shape), axes, B))
+    limits = (MAX_ALTERNATIVES, MAX_PHRASE) if phrases else (MAX_ALTERNATIVES,)
+    if cons.shape[1] > MAX_CONSTRAINTS or (cons.shape[1] > 0 and not all(1 <= s <= m for s, m in zip(cons.shape[2:], limits))):
+        raise ValueError('constraints of shape %s: at most %d constraints per clip of 1 to %d alternative%s'
+                         % (tuple(cons.shape), MAX_CONSTRAINTS, MAX_ALTERNATIVES, ' phrases of 1 to %d words' % MAX_PHRASE if phrases else 's'))
+    if cons.device != device:
+        raise ValueError('constraints on %s, the clips on %s' % (cons.device, device))
+    if cons.shape[1] + 1 > L:
+        raise ValueError('%d constraints and <end> do not fit into max_words %d' % (cons.shape[1], L))
+    return n
+
+
+def check_constrained_options(k, L, B, cons, device, n_best=None, length_penalty=0.0, no_repeat_ngram=0, min_len=0):
+    """ValueError for what `constrained_nbest` cannot run (what `check_nbest_options` refuses, and a constraint tensor of the wrong
+    shape, dtype or device, or with more constraints than words: a caption of max_words tokens holds max_words - 1 words and
+    <end>; the tensor's C counts, since nothing is read back); returns n"""
+    return _check_packed(k, L, B, cons, device, False, n_best, length_penalty, no_repeat_ngram, min_len)
+
+
+def _is_phrase_string(x):
+    """a string that is more than one word"""
+    return isinstance(x, str) and x.split() != [x]
+
+
+def has_phrases(per_clip):
+    """whether per-clip constraint lists hold a string with whitespace in it: then they are phrases (`pack_phrases`), else the
+    words and sets of words of `pack_constraints`"""
+    for clip in per_clip:
+        for con in clip:
+            if any(_is_phrase_string(a) for a in (con if isinstance(con, (list, tuple, set, frozenset)) else [con])):
+                return True
+    return False
+
+
+def pack_phrases(per_clip, vocab, device=None, skip_unknown=False):
+    """The phrase tensor of `constrained_nbest`: (B, C, W, P) int64 padded with -1.  per_clip: for every clip a list of
+    constraints, each a phrase or a list (or set) of alternative phrases of which the caption must contain one as contiguous
+    words; a phrase is a string, split on whitespace, a tuple of words or word ids, or a single word or id.  ValueError for more
+    than 8 constraints per clip, 8 alternatives per constraint or 4 words per phrase, for an empty phrase, for <end>, <start> or
+    <pad> inside a phrase, and for a word outside the vocabulary -- unless skip_unknown: then the whole alternative is dropped, and
+    a constraint left with none is absent.  Alternatives that are equal are folded."""
+    return _pack(per_clip, vocab, device, skip_unknown, phrases=True)
 
 
 def check_phrase_options(k, L, B, phr, device, n_best=None, length_penalty=0.0, no_repeat_ngram=0, min_len=0):
     """ValueError for what `constrained_nbest` cannot run on a phrase tensor: what `check_nbest_options` refuses, a tensor of the
     wrong shape, dtype or device, or with more constraints than words (C + 1 > max_words: the tensor's C counts, since nothing is
     read back); returns n"""
-    n = check_nbest_options(k, L, n_best, length_penalty, no_repeat_ngram, min_len)
-    if not torch.is_tensor(phr) or phr.dtype != torch.int64:
-        raise ValueError('constraints: an int64 tensor (B, C, W, P) (pack_phrases makes one), not %s'
-                         % (phr.dtype if torch.is_tensor(phr) else type(phr).__name__))
-    if phr.dim() != 4 or phr.shape[0] != B:
-        raise ValueError('constraints of shape %s: (B, C, W, P) with B = %d clips' % (tuple(phr.shape), B))
-    if phr.shape[1] > MAX_CONSTRAINTS or (phr.shape[1] > 0 and not (1 <= phr.shape[2] <= MAX_ALTERNATIVES and 1 <= phr.shape[3] <= MAX_PHRASE)):
-        raise ValueError('constraints of shape %s: at most %d constraints per clip of 1 to %d alternative phrases of 1 to %d words'
-                         % (tuple(phr.shape), MAX_CONSTRAINTS, MAX_ALTERNATIVES, MAX_PHRASE))
-    if phr.device != device:
-        raise ValueError('constraints on %s, the clips on %s' % (phr.device, device))
-    if phr.shape[1] + 1 > L:
-        raise ValueError('%d constraints and <end> do not fit into max_words %d' % (phr.shape[1], L))
-    return n
+    return _check_packed(k, L, B, phr, device, True, n_best, length_penalty, no_repeat_ngram, min_len)
 
 
 def check_phrases_fit(phr, L):
@@ -522,6 +493,18 @@ def phrases_met(ids, phrases, vocab_size=None):
     return met if ids.dim() == 3 else met[:, 0]
 
 
+def _constraints_met(ids, cons, vocab_size):
+    """How many of its clip's constraints every row of ids (B, k, L) meets -> (B, k) int64: `phrases_met` for a (B, C, W, P) tensor;
+    for (B, C, W) words the same integers from a broadcast compare of the ids with the valid entries (padding never matches),
+    which is fewer launches inside a captured search"""
+    if cons.dim() == 4:
+        return phrases_met(ids, cons, vocab_size)
+    B, k, L = ids.shape
+    valid = (cons >= 0) & (cons < vocab_size)
+    hit = (ids.view(B, k, L, 1, 1) == cons.view(B, 1, 1, *cons.shape[1:])) & valid.view(B, 1, 1, *cons.shape[1:])
+    return hit.any(4).any(2).sum(2)
+
+
 @torch.no_grad()
 def constrained_nbest(model, visual_feats, region_feats, constraints, n_best=None, length_penalty=0.0, no_repeat_ngram=0, min_len=0,
                       beam_size=None, return_met=False):
@@ -535,34 +518,9 @@ def constrained_nbest(model, visual_feats, region_feats, constraints, n_best=Non
     The loop is `beam_nbest`'s: the same buffers, all L steps launched, nothing read back -- the met masks are recomputed from the
     token history, so there is no further state.  Without constraints the result is `beam_nbest`'s, bit for bit.
     Phrases: a (B, C, W, P) int64 tensor of `pack_phrases`, or per-clip lists in which some string holds whitespace ("hot dog"),
-    which are packed by it, require phrases as contiguous words (`_phrase_nbest`: one `beam_select_phrases` launch per word).  A
-    3-D tensor and lists without such a string run what they always ran."""
-    if (torch.is_tensor(constraints) and constraints.dim() == 4) or (not torch.is_tensor(constraints) and has_phrases(constraints)):
-        return _phrase_nbest(model, visual_feats, region_feats, constraints, n_best, length_penalty, no_repeat_ngram, min_len,
-                             beam_size, return_met)
-    dec = model.decoder
-    k, L = dec.beam_size if beam_size is None else beam_size, dec.max_words
-    B, dev = visual_feats.shape[0], visual_feats.device
-    cons = constraints if torch.is_tensor(constraints) else pack_constraints(constraints, dec.vocab, dev)
-    n = check_constrained_options(k, L, B, cons, dev, n_best, length_penalty, no_repeat_ngram, min_len)
-    cons = cons.contiguous()
-
-    def select(t, logits, step):
-        model.ops.beam_select_cons(logits[0], *step, cons, no_repeat_ngram, min_len)
-    ids, scores, lens = _finalize(model, *_hist_search([model], k, visual_feats, region_feats, select), k, k, length_penalty)
-    # constraints met per row: a broadcast compare of the final ids with the valid entries (padding never matches)
-    valid = (cons >= 0) & (cons < dec.vocab_size)
-    hit = (ids.view(B, k, L, 1, 1) == cons.view(B, 1, 1, *cons.shape[1:])) & valid.view(B, 1, 1, *cons.shape[1:])
-    met = hit.any(4).any(2).sum(2)                                 # (B, k)
-    order = met.sort(dim=1, descending=True, stable=True)[1][:, :n]
-    out = (ids.gather(1, order.unsqueeze(2).expand(B, n, L)), scores.gather(1, order), lens.gather(1, order))
-    return out + (met.gather(1, order),) if return_met else out
-
-
-def _phrase_nbest(model, visual_feats, region_feats, constraints, n_best, length_penalty, no_repeat_ngram, min_len, beam_size,
-                  return_met):
-    """`constrained_nbest` with phrases: the same loop on `beam_select_phrases`, whose banks are (constraints met, progress into a
-    phrase); what a beam has met and how far into a phrase it is are recomputed from its history row, so there is still no state
+    which are packed by it, require phrases as contiguous words: the same loop with one `beam_select_phrases` launch per word.  A
+    3-D tensor and lists without such a string run what they always ran.  With phrases the banks are (constraints met, progress
+    into a phrase); what a beam has met and how far into a phrase it is are recomputed from its history row, so there is still no state
     beside `_hist_search`'s and nothing is read back.  Lists are packed on the host, where the bound of the guarantee is checked:
     C_b constraints of up to n_max_b words meet within C_b * n_max_b words (no_repeat_ngram = 0, finite logits), which with <end>
     must fit into max_words.  With an n-gram ban the next word of a phrase can be banned although the phrase has not occurred: the
@@ -571,19 +529,22 @@ def _phrase_nbest(model, visual_feats, region_feats, constraints, n_best, length
     dec = model.decoder
     k, L = dec.beam_size if beam_size is None else beam_size, dec.max_words
     B, dev = visual_feats.shape[0], visual_feats.device
+    phrases = constraints.dim() == 4 if torch.is_tensor(constraints) else has_phrases(constraints)
     if torch.is_tensor(constraints):
-        phr = constraints
+        cons = constraints
+    elif phrases:
+        cons = pack_phrases(constraints, dec.vocab)
+        check_phrases_fit(cons, L)
+        cons = cons.to(dev)
     else:
-        phr = pack_phrases(constraints, dec.vocab)
-        check_phrases_fit(phr, L)
-        phr = phr.to(dev)
-    n = check_phrase_options(k, L, B, phr, dev, n_best, length_penalty, no_repeat_ngram, min_len)
-    phr = phr.contiguous()
+        cons = pack_constraints(constraints, dec.vocab, dev)
+    n = _check_packed(k, L, B, cons, dev, phrases, n_best, length_penalty, no_repeat_ngram, min_len)
+    cons = cons.contiguous()
 
-    def select(t, logits, step):
-        model.ops.beam_select_phrases(logits[0], *step, phr, no_repeat_ngram, min_len)
+    def select(t, logits, step):                                   # (a 3-D tensor never runs the phrase step, which is slower)
+        (model.ops.beam_select_phrases if phrases else model.ops.beam_select_cons)(logits[0], *step, cons, no_repeat_ngram, min_len)
     ids, scores, lens = _finalize(model, *_hist_search([model], k, visual_feats, region_feats, select), k, k, length_penalty)
-    met = phrases_met(ids, phr, dec.vocab_size)
+    met = _constraints_met(ids, cons, dec.vocab_size)              # (B, k)
     order = met.sort(dim=1, descending=True, stable=True)[1][:, :n]
     out = (ids.gather(1, order.unsqueeze(2).expand(B, n, L)), scores.gather(1, order), lens.gather(1, order))
     return out + (met.gather(1, order),) if return_met else out

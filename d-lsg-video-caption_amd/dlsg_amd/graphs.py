@@ -74,13 +74,22 @@ def expand_rows(x, n):
     return x.unsqueeze(1).expand(x.shape[0], n, *x.shape[1:]).reshape(x.shape[0] * n, *x.shape[1:])
 
 
+def _members(model_or_ensemble):
+    return list(getattr(model_or_ensemble, 'members', [model_or_ensemble]))
+
+
 class _InferenceGraph(object):
     """A no-grad pass of `model` over (frames, regions), captured once for a batch shape and replayed: a subclass says what to
     run (`_run`, on the static inputs self.frames / self.regions; its return value becomes self.out).  A captured graph holds raw
     addresses into the parameter arena of every model it runs and their train / eval modes at construction -- `models` lists
     them where there are several (an ensemble's members; self.model is the first): `valid_for` tells whether the graph still
     fits, and a replay after a model re-packed its parameters (load_encoder, load_state_dict into a copy, .to()) raises instead
-    of computing from the old arena."""
+    of computing from the old arena.
+    One more static input -- a seed word, a constraint tensor, caption ids: a subclass allocates its buffer before the capture,
+    names the attribute that holds it in `extra` and defines `_fitted(value)`: the caller's value as what is copied into the buffer
+    (a tensor like it, or host values), or ValueError; `graph(frames, regions, value)` then stages all three and replays."""
+
+    extra = None
 
     def __init__(self, model, frames, regions, models=None):
         models = [model] if models is None else list(models)
@@ -106,9 +115,24 @@ class _InferenceGraph(object):
         stage(self.frames, frames)
         stage(self.regions, regions)
 
+    def _like_captured(self, x, what):
+        """the tensor x if it has the shape, dtype and device of the `extra` buffer; ValueError otherwise"""
+        buf = getattr(self, self.extra)
+        if x.shape != buf.shape or x.dtype != buf.dtype or x.device != buf.device:
+            raise ValueError('%s: %s of shape %s %s on %s, captured with %s int64 on %s -- build a new graph'
+                             % (type(self).__name__, what, tuple(x.shape), x.dtype, x.device, tuple(buf.shape), buf.device))
+        return x
+
     @torch.no_grad()
-    def __call__(self, frames, regions):
+    def __call__(self, frames, regions, *value):
+        if len(value) != (self.extra is not None):
+            raise TypeError('%s takes (frames, regions%s)' % (type(self).__name__, ', ' + self.extra if self.extra else ''))
+        if value:
+            dst, src = getattr(self, self.extra), self._fitted(value[0])   # (refused before anything is staged)
         self._stage(frames, regions)
+        if value:
+            from .hip import copy_to_device
+            stage(dst, src) if torch.is_tensor(src) else copy_to_device(dst, src)
         self.graph.replay()
         return self.out
 
@@ -117,17 +141,14 @@ class _SeededGraph(_InferenceGraph):
     """An inference graph that draws: the seed is read from a device word, so every replay draws afresh, and a replay with seed s
     gives the bits of the eager call with seed=s"""
 
+    extra = 'seed'
+
     def __init__(self, model, frames, regions):
         self.seed = torch.zeros(1, dtype=torch.int64, device=frames.device)
         super().__init__(model, frames, regions)
 
-    @torch.no_grad()
-    def __call__(self, frames, regions, seed):
-        from .hip import copy_to_device
-        self._stage(frames, regions)
-        copy_to_device(self.seed, [int(seed)])
-        self.graph.replay()
-        return self.out
+    def _fitted(self, seed):
+        return [int(seed)]
 
 
 class GreedyGraph(_InferenceGraph):
@@ -207,6 +228,8 @@ class ConstrainedBeamGraph(_InferenceGraph):
     (packed to the captured shape, by `pack_phrases` where that is 4-D; ValueError for another shape).  A replay returns the eager
     call's (ids, scores, lens[, met]), static buffers, and synchronises nothing."""
 
+    extra = 'cons'
+
     def __init__(self, model, frames, regions, constraints, **options):
         self.options = options
         self.cons = self._packed(model, constraints, frames.device).clone()
@@ -233,18 +256,7 @@ class ConstrainedBeamGraph(_InferenceGraph):
             wide = torch.full_like(self.cons, -1)
             wide[tuple(slice(0, a) for a in cons.shape)] = cons
             cons = wide
-        if cons.shape != self.cons.shape or cons.dtype != self.cons.dtype or cons.device != self.cons.device:
-            raise ValueError('ConstrainedBeamGraph: constraints of shape %s %s on %s, captured with %s int64 on %s -- build a new graph'
-                             % (tuple(cons.shape), cons.dtype, cons.device, tuple(self.cons.shape), self.cons.device))
-        return cons
-
-    @torch.no_grad()
-    def __call__(self, frames, regions, constraints):
-        cons = self._fitted(constraints)
-        self._stage(frames, regions)
-        stage(self.cons, cons)
-        self.graph.replay()
-        return self.out
+        return self._like_captured(cons, 'constraints')
 
 
 class EnsembleBeamGraph(_InferenceGraph):
@@ -269,16 +281,12 @@ class ConsensusBeamGraph(_InferenceGraph):
 
     def __init__(self, model_or_ensemble, frames, regions, reward, **options):
         self.search, self.reward, self.options = model_or_ensemble, reward, options
-        members = list(getattr(model_or_ensemble, 'members', [model_or_ensemble]))
+        members = _members(model_or_ensemble)
         super().__init__(members[0], frames, regions, members)
 
     def _run(self):
         from .consensus import consensus_search
         return consensus_search(self.search, self.frames, self.regions, self.reward, **self.options)
-
-
-def _members(model_or_ensemble):
-    return list(getattr(model_or_ensemble, 'members', [model_or_ensemble]))
 
 
 class ScoreGraph(_InferenceGraph):
@@ -287,6 +295,8 @@ class ScoreGraph(_InferenceGraph):
     length_penalty, return_tokens, return_ranks, fixed at capture (lens are always counted from <end>).  A replay returns the eager
     call's tuple, static buffers, and synchronises nothing.  It holds the arena and train / eval mode of every member of the
     scorer."""
+
+    extra = 'ids'
 
     def __init__(self, scorer, frames, regions, ids, **options):
         if 'lens' in options:
@@ -300,15 +310,8 @@ class ScoreGraph(_InferenceGraph):
         from .rescore import score_captions
         return score_captions(self.scorer, self.frames, self.regions, self.ids, **self.options)
 
-    @torch.no_grad()
-    def __call__(self, frames, regions, ids):
-        if ids.shape != self.ids.shape or ids.dtype != self.ids.dtype or ids.device != self.ids.device:
-            raise ValueError('ScoreGraph: ids of shape %s %s on %s, captured with %s int64 on %s -- build a new graph'
-                             % (tuple(ids.shape), ids.dtype, ids.device, tuple(self.ids.shape), self.ids.device))
-        self._stage(frames, regions)
-        stage(self.ids, ids)
-        self.graph.replay()
-        return self.out
+    def _fitted(self, ids):
+        return self._like_captured(ids, 'ids')
 
 
 class RescoreBeamGraph(_InferenceGraph):

@@ -554,6 +554,22 @@ class HipOps(object):
         return R, V, ((C.c_void_p * M)(*[x.data_ptr() for x in logits_list]), (C.c_int64 * M)(*[x.stride(0) for x in logits_list]),
                       (C.c_float * M)(*w), (C.c_float * M)(*[math.log(x) for x in w]), M)
 
+    @staticmethod
+    def _cons_dims(cons, d, B, device):
+        """checks a constraint tensor of d dims on B clips, on the logits' device -> its dims behind the clips (None: no constraint)"""
+        if cons is None:
+            return (0,) + (1,) * (d - 2)
+        assert cons.dtype == torch.int64 and cons.is_contiguous() and cons.dim() == d and cons.shape[0] == B, (cons.dtype, cons.shape)
+        assert cons.device == device, (cons.device, device)
+        return tuple(cons.shape[1:])
+
+    @staticmethod
+    def _chk_row_words(R, *outs):
+        """checks the optional (R,) int32 outputs of a step"""
+        for o in outs:
+            if o is not None:
+                assert o.dtype == torch.int32 and o.is_contiguous() and o.numel() == R, (o.dtype, o.shape)
+
     def beam_select(self, logits, last, last_lp, pred, new_lp, back, rows, k, end, first=False, ended_count=None):
         """one beam-search step for every batch item (see include/dlsg.h): logits (B*k,V) -> pred/new_lp/back/rows (B*k)."""
         a = self._beam_args(*logits.shape, last, last_lp, pred, new_lp, back, rows, k, end, first, ended_count, logits)
@@ -577,13 +593,8 @@ class HipOps(object):
         R, V = logits.shape
         a, hist = self._hist_step(R, V, last, last_lp, pred, new_lp, back, rows, k, end, hist_in, hist_out, t, no_repeat_ngram, min_len,
                                   ended_count, logits)
-        Cn, W = 0, 1
-        if cons is not None:
-            assert cons.dtype == torch.int64 and cons.is_contiguous() and cons.dim() == 3 and cons.shape[0] == R // k, (cons.dtype, cons.shape)
-            assert cons.device == logits.device, (cons.device, logits.device)
-            Cn, W = cons.shape[1], cons.shape[2]
-        if met_out is not None:
-            assert met_out.dtype == torch.int32 and met_out.is_contiguous() and met_out.numel() == R, (met_out.dtype, met_out.shape)
+        Cn, W = self._cons_dims(cons, 3, R // k, logits.device)
+        self._chk_row_words(R, met_out)
         self._check(self.lib.dlsg_beam_select_cons(C.byref(a), *hist, _p(cons) if Cn else None, Cn, W, _p(met_out), self._stream()),
                     'dlsg_beam_select_cons')
 
@@ -597,14 +608,8 @@ class HipOps(object):
         R, V = logits.shape
         a, hist = self._hist_step(R, V, last, last_lp, pred, new_lp, back, rows, k, end, hist_in, hist_out, t, no_repeat_ngram, min_len,
                                   ended_count, logits)
-        Cn, W, P = 0, 1, 1
-        if phr is not None:
-            assert phr.dtype == torch.int64 and phr.is_contiguous() and phr.dim() == 4 and phr.shape[0] == R // k, (phr.dtype, phr.shape)
-            assert phr.device == logits.device, (phr.device, logits.device)
-            Cn, W, P = phr.shape[1:]
-        for o in (met_out, bank_out):
-            if o is not None:
-                assert o.dtype == torch.int32 and o.is_contiguous() and o.numel() == R, (o.dtype, o.shape)
+        Cn, W, P = self._cons_dims(phr, 4, R // k, logits.device)
+        self._chk_row_words(R, met_out, bank_out)
         self._check(self.lib.dlsg_beam_select_phrases(C.byref(a), *hist, _p(phr) if Cn else None, Cn, W, P, _p(met_out), _p(bank_out),
                                                       self._stream()), 'dlsg_beam_select_phrases')
 

@@ -1,5 +1,5 @@
 """`launch_traces.json`: for every path of tests/launch_trace.py (forward, backward, Trainer.step, greedy, the beam searches
-(the reference's, n-best, stochastic, constrained, ensemble with and without groups), sampling, SCST, Decoder.forward on its own, for the three model classes) the calls the host code makes into the kernels -- number
+(the reference's, n-best, stochastic, constrained by words and by phrases, ensemble with and without groups), sampling, SCST, Decoder.forward on its own, for the three model classes) the calls the host code makes into the kernels -- number
 of calls, calls per op, SHA-256 of the detailed trace (op names in order, shapes, strides, scalars) -- recorded through the kernel
 emulation.  The paths use the public API only: the fixture pins the launch sequence of the commit it was generated on,
 and a refactor of the host code is checked against it (tests/test_launch_traces.py).  Regenerate it only for a launch that is

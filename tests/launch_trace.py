@@ -15,7 +15,7 @@ import torch
 
 import dlsg_amd
 from dlsg_amd.synth import synth_batch, synth_state_dict
-from emul_constrained import ConsEmul
+from emul_phrases import PhraseEmul
 from emul_sbs import SbsEmul
 from helpers import load_case
 from test_scst_host import LengthReward
@@ -35,9 +35,9 @@ def describe(x):
     return type(x).__name__
 
 
-class TraceEmul(SeqEmul, SbsEmul, ConsEmul):
+class TraceEmul(SeqEmul, SbsEmul, PhraseEmul):
     """every emulated op (train step, sampling, seq_per_clip, the beam searches: SbsEmul brings the ensemble, group and consensus
-    ops with the stochastic step, ConsEmul the constrained one); `trace` (a list) collects the calls"""
+    ops with the stochastic step, PhraseEmul the constrained ones, words and phrases); `trace` (a list) collects the calls"""
 
     trace = None
 
@@ -151,6 +151,18 @@ def _constrained(options):
     return traced(net, lambda: net.constrained_beam_search(frames, regions, per_clip, beam_size=3, **kw))
 
 
+def _phrases(options, tensor=False):
+    """phrase constraints: a two-word string, a tuple of ids, a list of alternative phrases and an empty clip -- as the per-clip
+    lists, or (tensor) as the 4-D tensor `pack_phrases` makes of them"""
+    net, args, vocab, frames, regions, caps, lens = fresh('capgnn')
+    kw = dict(n_best=2, length_penalty=0.7, no_repeat_ngram=2, min_len=2, return_met=True) if options else {}
+    w = vocab.idx2word
+    cons = [['%s %s' % (w[5], w[6]), (7, 8, 9)], [], [[(10, 11), w[12], '%s %s' % (w[13], w[5])]]]
+    if tensor:
+        cons = dlsg_amd.pack_phrases(cons, vocab)
+    return traced(net, lambda: net.constrained_beam_search(frames, regions, cons, beam_size=3, **kw))
+
+
 def _ensemble(groups):
     """the three model classes as one ensemble on one traced op set"""
     nets = [fresh(kind) for kind in MODELS]
@@ -205,6 +217,9 @@ def _paths():
         P['capgnn/sample_without_replacement%s' % ('_threshold' if flag else '')] = lambda flag=flag: _sbs(flag)
         P['capgnn/constrained_beam_search_%s' % ('options' if flag else 'plain')] = lambda flag=flag: _constrained(flag)
         P['ensemble/beam_search%s' % ('_groups' if flag else '')] = lambda flag=flag: _ensemble(flag)
+    for flag in (False, True):
+        P['capgnn/constrained_beam_search_phrases_%s' % ('options' if flag else 'plain')] = lambda flag=flag: _phrases(flag)
+    P['capgnn/constrained_beam_search_phrases_tensor'] = lambda: _phrases(False, tensor=True)
     for kind, feats2 in (('capgnn', True), ('baseline1', False)):
         for step in (False, True):
             for mode in ('tf', 'greedy', 'beam'):

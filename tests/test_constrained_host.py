@@ -524,3 +524,81 @@ def test_constrained_graph_fits_constraints_to_the_captured_shape():
     for bad in (torch.full((2, 2, 2), -1, dtype=torch.int64), same.int(), [[10]], [[10, 11, 12, 13], []], [[[10, 11, 12]], []]):
         with pytest.raises(ValueError):
             graph._fitted(bad)
+
+
+class ReplayStub(object):
+    def __init__(self, log):
+        self.log = log
+
+    def replay(self):
+        self.log.append('replay')
+
+
+def hand_built_graph(cls, net, frames, regions, log, **extra):
+    """a graph object of `cls` without a capture: zeroed static inputs, the extra buffer given, a `graph` that notes its replays"""
+    graph = cls.__new__(cls)
+    graph.model, graph.held = net, []
+    graph.frames, graph.regions = torch.zeros_like(frames), torch.zeros_like(regions)
+    graph.graph, graph.out = ReplayStub(log), ('the', 'outputs')
+    for name, buf in extra.items():
+        setattr(graph, name, buf)
+    return graph
+
+
+def test_the_graph_base_stages_the_extra_static_input(monkeypatch):
+    """_SeededGraph, ConstrainedBeamGraph and ScoreGraph replay through the one `__call__` of their base: a call copies frames,
+    regions and the third input into their buffers, each once and before the replay, and returns `out`; an input that does not fit
+    raises the class's message and copies nothing"""
+    from dlsg_amd import graphs, hip
+    net, _, frames, regions = synth_pair(SEED, 2)
+    log, live = [], []
+
+    def noting(copy):
+        def noted(dst, src, *rest):
+            g = live[0]
+            log.append([nm for nm in ('frames', 'regions', g.extra) if getattr(g, nm) is dst][0])
+            return copy(dst, src, *rest)
+        return noted
+    monkeypatch.setattr(graphs, 'stage', noting(graphs.stage))
+    monkeypatch.setattr(hip, 'copy_to_device', noting(hip.copy_to_device))
+    ids = torch.arange(30).view(2, 3, 5)
+    cases = [(dlsg_amd.StochasticBeamGraph, 'seed', torch.zeros(1, dtype=torch.int64), 7, torch.tensor([7])),
+             (dlsg_amd.SampleGraph, 'seed', torch.zeros(1, dtype=torch.int64), torch.tensor(9), torch.tensor([9])),
+             (dlsg_amd.ConstrainedBeamGraph, 'cons', torch.full((2, 3, 2), -1, dtype=torch.int64), [[10], [[11, 12], 13]],
+              torch.tensor([[[10, -1], [-1, -1], [-1, -1]], [[11, 12], [13, -1], [-1, -1]]])),
+             (dlsg_amd.ConstrainedBeamGraph, 'cons', torch.full((2, 1, 1, 2), -1, dtype=torch.int64), torch.tensor([[[[4, 5]]], [[[6, -1]]]]),
+              torch.tensor([[[[4, 5]]], [[[6, -1]]]])),
+             (dlsg_amd.ScoreGraph, 'ids', torch.zeros(2, 3, 5, dtype=torch.int64), ids, ids)]
+    for cls, name, buf, value, want in cases:
+        assert cls.extra == name
+        graph = hand_built_graph(cls, net, frames, regions, log, **{name: buf})
+        live[:] = [graph]
+        del log[:]
+        assert graph(frames, regions, value) is graph.out
+        assert log == ['frames', 'regions', name, 'replay'], (cls.__name__, log)
+        assert torch.equal(graph.frames, frames) and torch.equal(graph.regions, regions) and torch.equal(getattr(graph, name), want)
+        assert getattr(graph, name) is buf
+        del log[:]
+        for args in ((frames, regions), (frames, regions, value, value)):
+            with pytest.raises(TypeError):
+                graph(*args)
+        assert log == []
+    refusals = [(dlsg_amd.ConstrainedBeamGraph, 'cons', torch.full((2, 3, 2), -1, dtype=torch.int64), torch.full((2, 2, 2), 5, dtype=torch.int64),
+                 'ConstrainedBeamGraph: constraints of shape (2, 2, 2) torch.int64 on cpu, captured with (2, 3, 2) int64 on cpu -- build a new graph'),
+                (dlsg_amd.ConstrainedBeamGraph, 'cons', torch.full((2, 3, 2), -1, dtype=torch.int64), torch.full((2, 3, 2, 1), 5, dtype=torch.int64),
+                 'ConstrainedBeamGraph: constraints of shape (2, 3, 2, 1) torch.int64 on cpu, captured with (2, 3, 2) int64 on cpu -- build a new graph'),
+                (dlsg_amd.ScoreGraph, 'ids', torch.zeros(2, 3, 5, dtype=torch.int64), ids[:, :2],
+                 'ScoreGraph: ids of shape (2, 2, 5) torch.int64 on cpu, captured with (2, 3, 5) int64 on cpu -- build a new graph'),
+                (dlsg_amd.ScoreGraph, 'ids', torch.zeros(2, 3, 5, dtype=torch.int64), ids.int(),
+                 'ScoreGraph: ids of shape (2, 3, 5) torch.int32 on cpu, captured with (2, 3, 5) int64 on cpu -- build a new graph')]
+    for cls, name, buf, value, message in refusals:
+        graph = hand_built_graph(cls, net, frames, regions, log, **{name: buf})
+        live[:] = [graph]
+        kept = buf.clone()
+        del log[:]
+        with pytest.raises(ValueError) as err:
+            graph(frames, regions, value)
+        assert str(err.value) == message
+        assert log == [] and torch.equal(buf, kept) and not bool(graph.frames.any())
+    with pytest.raises(ValueError, match='takes no lens'):
+        dlsg_amd.ScoreGraph(net, frames, regions, ids, lens=None)

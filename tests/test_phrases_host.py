@@ -590,6 +590,54 @@ def test_pack_phrases():
     assert has_phrases([[w[10]], [[w[11], w[12] + ' ' + w[13]]]]) and not has_phrases([[w[10], (11, 12)], [[w[11], 13]]])
 
 
+def test_word_lists_pack_alike():
+    """lists of words -- no tuple, which the two packers read differently -- give `pack_phrases` the tensor of `pack_constraints`
+    with a trailing axis of one, and what both refuse they refuse in the same words"""
+    vocab = dlsg_amd.make_vocab(50)
+    w = vocab.idx2word
+    lists = [[w[10], 11, [w[12], 13, w[12], 12], {14, 15}], [], [[w[16], 16, 17, 21], frozenset([18])], [19]]
+    got = pack_phrases(lists, vocab)
+    assert got.shape == (4, 4, 3, 1) and torch.equal(got[..., 0], pack_constraints(lists, vocab))
+    assert got[0, :3, :, 0].tolist() == [[10, -1, -1], [11, -1, -1], [12, 13, -1]] and sorted(got[0, 3, :, 0].tolist()) == [-1, 14, 15]
+    assert got[1:, :, :, 0].tolist() == [[[-1] * 3] * 4, [[16, 17, 21], [18, -1, -1]] + [[-1] * 3] * 2, [[19, -1, -1]] + [[-1] * 3] * 3]
+    unknown = [['no such word', [w[9], 'nor', 50, -1]], [[60], w[20]]]
+    got = pack_phrases(unknown, vocab, skip_unknown=True)
+    assert torch.equal(got[..., 0], pack_constraints(unknown, vocab, skip_unknown=True))
+    assert got[..., 0].tolist() == [[[-1], [9]], [[-1], [20]]]
+    empty = pack_phrases([[], []], vocab)
+    assert empty.shape == (2, 0, 1, 1) and torch.equal(empty[..., 0], pack_constraints([[], []], vocab))
+    refused = [[list(range(10, 19))], [[10], [list(range(10, 19))]], [['nope']], [[10, [11, 50]]], [[w[10]], ['<end>']], [[[10, vocab('<pad>')]]],
+               [[vocab('<start>')]]]
+    for bad in refused:
+        said = []
+        for pack in (pack_constraints, pack_phrases):
+            with pytest.raises(ValueError) as err:
+                pack(bad, vocab)
+            said.append(str(err.value))
+        assert said[0] == said[1], said
+
+
+@pytest.mark.parametrize('C', [0, 1, 3])
+@pytest.mark.parametrize('W', [1, 2])
+def test_the_word_count_of_met_is_phrases_met(C, W):
+    """what `constrained_nbest` counts on a (B, C, W) tensor is `phrases_met` of the same words as one-word phrases, and both are
+    the count by a loop; with -1 padding, ids outside the vocabulary and a constraint without a valid word"""
+    from dlsg_amd.beam import _constraints_met
+    B, k, L, V = 3, 3, 8, 12
+    gen = torch.Generator().manual_seed(10 * C + W)
+    ids = torch.randint(0, V, (B, k, L), generator=gen)
+    cons = torch.randint(-1, V + 2, (B, C, W), generator=gen)
+    if C:
+        cons[1, 0] = torch.tensor([-1, V + 1][:W])
+        cons[0, C - 1, 0] = ids[0, 1, 3]
+    got = _constraints_met(ids, cons, V)
+    assert got.shape == (B, k) and got.dtype == torch.int64
+    assert torch.equal(got, phrases_met(ids, cons.unsqueeze(3), V))
+    want = [[sum(any(0 <= a < V and a in row for a in con) for con in clip) for row in rows] for rows, clip in zip(ids.tolist(), cons.tolist())]
+    assert got.tolist() == want
+    assert C == 0 or 0 < sum(map(sum, want)) < B * k * C
+
+
 class Logged(PhraseEmul):
     """PhraseEmul that notes the name of every op called"""
     def __init__(self):
