@@ -732,64 +732,126 @@ __global__ void gather_rows_multi_kernel(const dlsg_gather_multi_args a) {
 
 // ------------------------------------------------------------------------------------------------ Adam
 // CLIP: the gradient is scaled by the clip record's coefficient and, with clipv > 0, clamped to +-clipv (dlsg_adam_clipped); the
-// CLIP = false instantiation is dlsg_adam's arithmetic, untouched
-template <bool CLIP>
+// CLIP = false instantiation is dlsg_adam's arithmetic, untouched.
+// DECAY (dlsg_adamw_ema): 0 none; 1 L2, gi += wdf * p behind the clip (torch.optim.Adam(weight_decay=), wdf = wd); 2 decoupled,
+// p *= wdf in front of the update (torch.optim.AdamW, wdf = 1 - lr * wd); `dec` says whether this element is decayed.
+// EMA: e += ew * (p_new - e), ew = 1 - d (torch.lerp's form for a weight below one half).  <CLIP, 0, false> is the arithmetic of
+// the two older entry points: the new terms are compiled out
+template <bool CLIP, int DECAY = 0, bool EMA = false>
 __device__ __forceinline__ void adam_one(float& p, float g, float& m, float& v, float lr_bc1, float b1, float b2, float eps,
-                                         float bc2s, float gscale, float coef, float clipv) {
+                                         float bc2s, float gscale, float coef, float clipv, float wdf = 0.f, bool dec = false,
+                                         float* e = nullptr, float ew = 0.f) {
     float gi = g * gscale;
     if (CLIP) {
         gi *= coef;                                        // coef == 1.0f: exact, dlsg_adam's bits
         if (clipv > 0.f) gi = fminf(fmaxf(gi, -clipv), clipv);
     }
+    if (DECAY == 1) { if (dec) gi += wdf * p; }
+    if (DECAY == 2) { if (dec) p *= wdf; }
     m = b1 * m + (1.f - b1) * gi;
     v = b2 * v + (1.f - b2) * gi * gi;
     const float denom = sqrtf(v) / bc2s + eps;
     p -= lr_bc1 * (m / denom);
+    if (EMA) *e += ew * (p - *e);
 }
-// NTM: bit 0 non-temporal loads of m, v, g; bit 1 non-temporal stores of m, v; bit 2 / 3 the same for the load / store of p.
-// 28 B of traffic per parameter: 16-byte accesses over the aligned body (the four arrays share one index, so one alignment),
-// scalar head and tail (a trainable range may start at any parameter boundary)
-template <int NTM, bool CLIP>
+// the decayed intervals of a dlsg_adamw_ema launch, staged once per workgroup: tab[2 r], tab[2 r + 1] = [lo, hi) of interval r,
+// sorted and disjoint, in elements relative to p
+extern __shared__ int64_t adam_tab[];
+// first interval that ends behind element i (nr when none does): bisection over the interval ends
+__device__ __forceinline__ int adam_tab_seek(int nr, int64_t i) {
+    int lo = 0, hi = nr;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (adam_tab[2 * mid + 1] <= i) lo = mid + 1; else hi = mid;
+    }
+    return lo;
+}
+// is element i decayed?  r: the cursor adam_tab_seek gave for an element <= i; it moves on over intervals that end at or before i
+__device__ __forceinline__ bool adam_tab_has(int nr, int& r, int64_t i) {
+    while (r < nr && adam_tab[2 * r + 1] <= i) ++r;
+    return r < nr && adam_tab[2 * r] <= i;
+}
+// NTM: bit 0 non-temporal loads of m, v, g (and ema); bit 1 non-temporal stores of m, v (and ema); bit 2 / 3 the same for the load /
+// store of p.  28 B of traffic per parameter, 36 B with EMA: 16-byte accesses over the aligned body (the arrays share one index, so
+// one alignment), scalar head and tail (a trainable range may start at any parameter boundary).  DECAY with nr > 0: only elements
+// inside one of the nr intervals of `ranges` are decayed -- one bisection per 16-byte group (per element in head and tail), then
+// the cursor walks, so a group that straddles an interval end is right element by element; nr == 0 decays the whole launch
+template <int NTM, bool CLIP, int DECAY = 0, bool EMA = false>
 __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                                                    float* __restrict__ v, int64_t n, float lr, float b1, float b2, float eps,
                                                    float bc1, float bc2s, float gscale, const float* __restrict__ hyper,
-                                                   const int32_t* __restrict__ guard, const float* __restrict__ record, float clipv) {
+                                                   const int32_t* __restrict__ guard, const float* __restrict__ record, float clipv,
+                                                   float* __restrict__ ema = nullptr, float wdf = 0.f, float ew = 0.f,
+                                                   const int64_t* __restrict__ ranges = nullptr, int nr = 0) {
     if (guard && *guard != 0) return;      // a persistent kernel reported a time-out in this step: its gradients are invalid
     float coef = 1.f;
     if (CLIP && record) {
-        if (record[DLSG_CLIP_NONFINITE] != 0.f) return;    // the step's gradient holds an inf or a NaN: p, m and v keep their bits
+        if (record[DLSG_CLIP_NONFINITE] != 0.f) return;    // the step's gradient holds an inf or a NaN: p, m, v and ema keep their bits
         coef = record[DLSG_CLIP_COEF];
     }
     if (hyper) { lr = hyper[0]; bc1 = 1.f; bc2s = hyper[1]; }
+    if ((DECAY || EMA) && hyper) { wdf = hyper[2]; ew = hyper[3]; }
+    if (DECAY && nr > 0) {
+        for (int i = threadIdx.x; i < 2 * nr; i += blockDim.x) adam_tab[i] = ranges[i];
+        __syncthreads();
+    }
     const float lr_bc1 = lr / bc1;
     const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, nth = (int64_t)gridDim.x * blockDim.x;
     const bool same = ((reinterpret_cast<uintptr_t>(p) ^ reinterpret_cast<uintptr_t>(g)) & 15) == 0 &&
                       ((reinterpret_cast<uintptr_t>(p) ^ reinterpret_cast<uintptr_t>(m)) & 15) == 0 &&
-                      ((reinterpret_cast<uintptr_t>(p) ^ reinterpret_cast<uintptr_t>(v)) & 15) == 0;
+                      ((reinterpret_cast<uintptr_t>(p) ^ reinterpret_cast<uintptr_t>(v)) & 15) == 0 &&
+                      (!EMA || ((reinterpret_cast<uintptr_t>(p) ^ reinterpret_cast<uintptr_t>(ema)) & 15) == 0);
     int64_t head = same ? (int64_t)((16 - (reinterpret_cast<uintptr_t>(p) & 15)) & 15) / 4 : n;
     if (head > n) head = n;
     const int64_t nv = (n - head) / 4;                     // float4 elements of the aligned body
-    for (int64_t i = tid; i < head; i += nth) adam_one<CLIP>(p[i], g[i], m[i], v[i], lr_bc1, b1, b2, eps, bc2s, gscale, coef, clipv);
+    // one element of the scalar head or tail
+    auto scalar = [&](int64_t i) {
+        bool dec = DECAY != 0;
+        if (DECAY && nr > 0) { int r = adam_tab_seek(nr, i); dec = adam_tab_has(nr, r, i); }
+        adam_one<CLIP, DECAY, EMA>(p[i], g[i], m[i], v[i], lr_bc1, b1, b2, eps, bc2s, gscale, coef, clipv, wdf, dec, EMA ? ema + i : nullptr, ew);
+    };
+    for (int64_t i = tid; i < head; i += nth) scalar(i);
     f32x4* p4 = reinterpret_cast<f32x4*>(p + head);
     const f32x4* g4 = reinterpret_cast<const f32x4*>(g + head);
     f32x4* m4 = reinterpret_cast<f32x4*>(m + head);
     f32x4* v4 = reinterpret_cast<f32x4*>(v + head);
+    f32x4* e4 = EMA ? reinterpret_cast<f32x4*>(ema + head) : nullptr;
     for (int64_t i = tid; i < nv; i += nth) {
-        f32x4 pp, mm, vv, gg;
+        f32x4 pp, mm, vv, gg, ee;
         if (NTM & 4) pp = __builtin_nontemporal_load(p4 + i); else pp = p4[i];
         if (NTM & 1) { mm = __builtin_nontemporal_load(m4 + i); vv = __builtin_nontemporal_load(v4 + i); gg = __builtin_nontemporal_load(g4 + i); }
         else { mm = m4[i]; vv = v4[i]; gg = g4[i]; }
+        if (EMA) { if (NTM & 1) ee = __builtin_nontemporal_load(e4 + i); else ee = e4[i]; }
+        int r = 0;
+        if (DECAY && nr > 0) r = adam_tab_seek(nr, head + 4 * i);
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-            float pe = pp[e], me = mm[e], ve = vv[e];
-            adam_one<CLIP>(pe, gg[e], me, ve, lr_bc1, b1, b2, eps, bc2s, gscale, coef, clipv);
+            float pe = pp[e], me = mm[e], ve = vv[e], ee1 = EMA ? ee[e] : 0.f;
+            bool dec = DECAY != 0;
+            if (DECAY && nr > 0) dec = adam_tab_has(nr, r, head + 4 * i + e);
+            adam_one<CLIP, DECAY, EMA>(pe, gg[e], me, ve, lr_bc1, b1, b2, eps, bc2s, gscale, coef, clipv, wdf, dec, &ee1, ew);
             pp[e] = pe; mm[e] = me; vv[e] = ve;
+            if (EMA) ee[e] = ee1;
         }
         if (NTM & 2) { __builtin_nontemporal_store(mm, m4 + i); __builtin_nontemporal_store(vv, v4 + i); }
         else { m4[i] = mm; v4[i] = vv; }
+        if (EMA) { if (NTM & 2) __builtin_nontemporal_store(ee, e4 + i); else e4[i] = ee; }
         if (NTM & 8) __builtin_nontemporal_store(pp, p4 + i); else p4[i] = pp;
     }
-    for (int64_t i = head + 4 * nv + tid; i < n; i += nth) adam_one<CLIP>(p[i], g[i], m[i], v[i], lr_bc1, b1, b2, eps, bc2s, gscale, coef, clipv);
+    for (int64_t i = head + 4 * nv + tid; i < n; i += nth) scalar(i);
+}
+// a <-> b over n floats: 16-byte accesses over the aligned body when the two share an alignment, scalar head and tail
+__global__ __launch_bounds__(256) void swap_kernel(float* __restrict__ a, float* __restrict__ b, int64_t n) {
+    const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, nth = (int64_t)gridDim.x * blockDim.x;
+    const bool same = ((reinterpret_cast<uintptr_t>(a) ^ reinterpret_cast<uintptr_t>(b)) & 15) == 0;
+    int64_t head = same ? (int64_t)((16 - (reinterpret_cast<uintptr_t>(a) & 15)) & 15) / 4 : n;
+    if (head > n) head = n;
+    const int64_t nv = (n - head) / 4;
+    for (int64_t i = tid; i < head; i += nth) { const float x = a[i]; a[i] = b[i]; b[i] = x; }
+    f32x4* a4 = reinterpret_cast<f32x4*>(a + head);
+    f32x4* b4 = reinterpret_cast<f32x4*>(b + head);
+    for (int64_t i = tid; i < nv; i += nth) { const f32x4 x = a4[i], y = b4[i]; a4[i] = y; b4[i] = x; }
+    for (int64_t i = head + 4 * nv + tid; i < n; i += nth) { const float x = a[i]; a[i] = b[i]; b[i] = x; }
 }
 
 // ------------------------------------------------------------------------------------------------ gradient clipping
@@ -1155,6 +1217,52 @@ extern "C" int dlsg_adam_clipped(float* p, const float* g, float* m, float* v, i
     // the same launch shape and cache policy as dlsg_adam: this is the last reader of g in the step
     hipLaunchKernelGGL((adam_kernel<3, true>), dim3(grid_for((n + 3) / 4, 256, 8192)), dim3(256), 0, ST(stream), p, g, m, v, n, lr, b1, b2,
                        eps, bc1, bc2s, grad_scale, hyper, guard, record, clip_value);
+    DLSG_CHECK_LAUNCH();
+    return DLSG_OK;
+}
+template <int DECAY, bool EMA>
+static void launch_adamw_ema(float* p, const float* g, float* m, float* v, float* ema, int64_t n, float lr, float b1, float b2, float eps,
+                             float bc1, float bc2s, float grad_scale, float wdf, float ew, const float* hyper, const int32_t* guard,
+                             const float* record, float clip_value, const int64_t* ranges, int nr, void* stream) {
+    hipLaunchKernelGGL((adam_kernel<3, true, DECAY, EMA>), dim3(grid_for((n + 3) / 4, 256, 8192)), dim3(256),
+                       DECAY ? (size_t)nr * 2 * sizeof(int64_t) : 0, ST(stream), p, g, m, v, n, lr, b1, b2, eps, bc1, bc2s, grad_scale,
+                       hyper, guard, record, clip_value, ema, wdf, ew, ranges, nr);
+}
+extern "C" int dlsg_adamw_ema(float* p, const float* g, float* m, float* v, float* ema, int64_t n, float lr, float b1, float b2,
+                              float eps, int step, float grad_scale, float weight_decay, int decoupled, float ema_decay,
+                              const float* hyper, const int32_t* guard, const float* record, float clip_value,
+                              const int64_t* decay_ranges, int n_ranges, void* stream) {
+    if (!(clip_value >= 0.f) || !(weight_decay >= 0.f) || n < 0) return DLSG_EINVAL;
+    if (n_ranges < 0 || n_ranges > DLSG_ADAM_MAX_RANGES || (n_ranges > 0 && !decay_ranges)) return DLSG_EINVAL;
+    if (ema && !(ema_decay >= 0.f && ema_decay <= 1.f)) return DLSG_EINVAL;
+    if (n == 0) return DLSG_OK;
+    const float bc1 = 1.f - powf(b1, (float)step);
+    const float bc2s = sqrtf(1.f - powf(b2, (float)step));
+    // the factors in float64, rounded once, as the host computes hyper[2] and hyper[3]
+    const float wdf = decoupled ? (float)(1.0 - (double)lr * (double)weight_decay) : weight_decay;
+    const float ew = (float)(1.0 - (double)ema_decay);
+    const int mode = weight_decay > 0.f ? (decoupled ? 2 : 1) : 0;     // no decay: the table is not read
+    const int nr = mode ? n_ranges : 0;
+#define DLSG_ADAMW_ARGS p, g, m, v, ema, n, lr, b1, b2, eps, bc1, bc2s, grad_scale, wdf, ew, hyper, guard, record, clip_value, decay_ranges, nr, stream
+    // the same launch shape and cache policy as dlsg_adam; (0, no ema) IS dlsg_adam_clipped's kernel
+    if (ema) {
+        if (mode == 0) launch_adamw_ema<0, true>(DLSG_ADAMW_ARGS);
+        else if (mode == 1) launch_adamw_ema<1, true>(DLSG_ADAMW_ARGS);
+        else launch_adamw_ema<2, true>(DLSG_ADAMW_ARGS);
+    } else {
+        if (mode == 0) launch_adamw_ema<0, false>(DLSG_ADAMW_ARGS);
+        else if (mode == 1) launch_adamw_ema<1, false>(DLSG_ADAMW_ARGS);
+        else launch_adamw_ema<2, false>(DLSG_ADAMW_ARGS);
+    }
+#undef DLSG_ADAMW_ARGS
+    DLSG_CHECK_LAUNCH();
+    return DLSG_OK;
+}
+extern "C" int dlsg_swap_f32(float* a, float* b, int64_t n, void* stream) {
+    if (n < 0 || ((!a || !b) && n > 0)) return DLSG_EINVAL;
+    if ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b)) & 3) return DLSG_EALIGN;
+    if (n == 0 || a == b) return DLSG_OK;
+    hipLaunchKernelGGL(swap_kernel, dim3(grid_for((n + 3) / 4, 256, 8192)), dim3(256), 0, ST(stream), a, b, n);
     DLSG_CHECK_LAUNCH();
     return DLSG_OK;
 }

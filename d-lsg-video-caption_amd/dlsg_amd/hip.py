@@ -32,6 +32,7 @@ F_SK, F_NOSK, F_SK_BM128, F_SK_BM256, F_SK_BN128, F_SK_NOXMAP = (_D['DLSG_GEMM_'
     'SK', 'NOSK', 'SK_BM128', 'SK_BM256', 'SK_BN128', 'SK_NOXMAP'))
 GRAD_SUMSQ_SLOTS = _D['DLSG_GRAD_SUMSQ_SLOTS']   # float64 partials one dlsg_grad_sumsq launch writes
 CLIP_NORM, CLIP_COEF, CLIP_NONFINITE, CLIP_RECORD_FLOATS = (_D['DLSG_CLIP_' + n] for n in ('NORM', 'COEF', 'NONFINITE', 'RECORD_FLOATS'))
+ADAM_MAX_RANGES = _D['DLSG_ADAM_MAX_RANGES']     # decayed intervals one dlsg_adamw_ema launch takes
 ENS_MAX = _D['DLSG_ENS_MAX']                    # members dlsg_beam_select_ens combines
 METRICS_STAGE = _D['DLSG_METRICS_STAGE']        # reference words dlsg_caption_metrics stages in LDS per pass
 F_SK_GIVEAWAY = _D['DLSG_GEMM_SK_GIVEAWAY']   # test hook (include/dlsg.h): the split tiles are finished by their last contributor alone
@@ -1699,3 +1700,30 @@ class HipOps(object):
         self._check(self.lib.dlsg_adam_clipped(_p(p), _p(g), _p(m), _p(v), i64(p.numel()), f32(lr), f32(b1), f32(b2), f32(eps),
                                                int(step), f32(grad_scale), _p(hyper), _p(self._persist_word(p.device)), _p(record),
                                                f32(clip_value), self._stream()), 'adam_clipped')
+
+    # ------------------------------------------------------------------ weight decay and averaged weights (include/dlsg.h)
+    def adamw_ema(self, p, g, m, v, lr, b1, b2, eps, step, grad_scale=1.0, weight_decay=0.0, decoupled=True, ema=None, ema_decay=0.0,
+                  hyper=None, record=None, clip_value=0.0, decay_ranges=None):
+        """`adam_clipped` with weight decay (decoupled: p *= 1 - lr * weight_decay in front of the update, AdamW; else
+        g += weight_decay * p behind the clip, Adam's L2) and, with ema (float32, laid out as p), ema += (1 - ema_decay) * (p_new - ema).
+        hyper: optional device tensor of FOUR floats {lr/(1-b1^step), sqrt(1-b2^step), 1 - lr*wd (decoupled) or wd, 1 - ema_decay}.
+        decay_ranges: optional device int64 (k, 2), sorted disjoint [lo, hi) element intervals of p that are decayed (None: all of
+        it), k <= ADAM_MAX_RANGES.  A skipped step (time-out word, non-finite record) leaves p, m, v and ema as they are."""
+        assert record is None or (record.dtype == torch.float32 and record.is_contiguous() and record.numel() == CLIP_RECORD_FLOATS)
+        assert hyper is None or (hyper.dtype == torch.float32 and hyper.numel() == 4 and hyper.is_contiguous()), 'hyper holds four floats'
+        assert ema is None or (ema.dtype == torch.float32 and ema.shape == p.shape and ema.device == p.device)
+        k = 0
+        if decay_ranges is not None:
+            assert decay_ranges.dtype == torch.int64 and decay_ranges.dim() == 2 and decay_ranges.shape[1] == 2 \
+                and decay_ranges.is_contiguous() and decay_ranges.device == p.device, (decay_ranges.dtype, decay_ranges.shape)
+            k = decay_ranges.shape[0]
+        self._check(self.lib.dlsg_adamw_ema(_p(p), _p(g), _p(m), _p(v), _p(ema), i64(p.numel()), f32(lr), f32(b1), f32(b2), f32(eps),
+                                            int(step), f32(grad_scale), f32(weight_decay), int(bool(decoupled)), f32(ema_decay),
+                                            _p(hyper), _p(self._persist_word(p.device)), _p(record), f32(clip_value),
+                                            _p(decay_ranges) if k else None, int(k), self._stream()), 'adamw_ema')
+
+    def swap(self, a, b):
+        """a <-> b in place: two 1-d float32 views of equal length"""
+        assert a.dtype == b.dtype == torch.float32 and a.dim() == b.dim() == 1 and a.numel() == b.numel() and a.device == b.device
+        assert (a.numel() <= 1 or a.stride(0) == 1) and (b.numel() <= 1 or b.stride(0) == 1)
+        self._check(self.lib.dlsg_swap_f32(_p(a), _p(b), i64(a.numel()), self._stream()), 'swap')

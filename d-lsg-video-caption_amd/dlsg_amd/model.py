@@ -7,6 +7,8 @@ forward() signatures (models/model.py:25-43,94-107), state_dict layout (SURVEY.m
 fused ragged cross-entropy, hand-scheduled backward into a flat gradient arena, bucketed RCCL all-reduce that
 overlaps the encoder backward, and one fused Adam kernel over the flat parameter arena.
 """
+import collections
+import contextlib
 import math
 import os
 import random
@@ -674,7 +676,8 @@ class Trainer(object):
 
     def __init__(self, model, lr=1.6e-4, betas=(0.5, 0.9), eps=1e-8, process_group=None, world_size=1, use_graphs=False,
                  device_coins=None, graph_fallback=False, comm='auto', check_every=100, rehearse_ranks=0, max_grad_norm=None,
-                 clip_grad_value=None, label_smoothing=0.0, teacher=None, distill_weight=0.0):
+                 clip_grad_value=None, label_smoothing=0.0, teacher=None, distill_weight=0.0, weight_decay=0.0,
+                 decoupled_weight_decay=True, decay_filter=None, ema_decay=None, ema_warmup=False):
         """comm: how the gradient buckets are summed over ranks.
           'rccl'  -- librccl through the C ABI (dlsg_allreduce_bucket) on a side stream forked by an event: the collectives
                      are part of the captured step, so one iteration is ONE hipGraph replay and a bucket's all-reduce runs
@@ -711,8 +714,33 @@ class Trainer(object):
           prefix).  With either option on, `step` returns the mixed loss and `last_loss_parts` is a 3-float device view {mixed
           loss, plain NLL of the targets, CrossEntropy against q} of the last step -- the NLL stays comparable with a run
           without the options.  seq_weights, seq_per_clip, extra_dlogits and clipping compose as before.  With the defaults
-          (0.0, None, 0.0) the step issues exactly the launches it issued before these options existed."""
+          (0.0, None, 0.0) the step issues exactly the launches it issued before these options existed.
+        weight_decay, decoupled_weight_decay: wd >= 0, applied inside Adam's launch (dlsg_adamw_ema).  Decoupled (the default,
+          torch.optim.AdamW): p *= 1 - lr * wd in front of the update, with the plain lr.  Not decoupled (torch.optim.Adam's
+          weight_decay, L2): g += wd * p behind the clip, so `last_grad_norm` never holds the decay term.
+        decay_filter: None decays every trainable parameter; else a callable (name, parameter) -> bool, e.g. lambda n, p: p.ndim > 1
+          for "no decay on biases and LayerNorm gains".  Parameters in `model.unused_parameters` are never decayed (torch skips
+          parameters without a gradient), frozen ones are outside the update altogether.
+        ema_decay: d in (0, 1) keeps `ema`, an fp32 arena laid out as the weights' (a copy of them at first), and moves it in the
+          same launch: ema += (1 - d) * (p_new - ema).  ema_warmup: d_t = min(d, (1 + t) / (10 + t)), t the step count, which
+          advances on a skipped step as the bias corrections do.  A skipped step (non-finite gradient, time-out word) leaves `ema`
+          as it is.  `averaged()`, `ema_state_dict()` and `load_ema_state_dict()` use the average.
+          With (0.0, None) the step issues exactly the launches it issued before these options existed."""
         assert comm in ('auto', 'rccl', 'torch'), comm
+        if not float(weight_decay) >= 0.0 or math.isinf(float(weight_decay)):
+            raise ValueError('weight_decay must be a finite number >= 0, not %r' % (weight_decay,))
+        if ema_decay is not None and not 0.0 < float(ema_decay) < 1.0:
+            raise ValueError('ema_decay must be in (0, 1), not %r' % (ema_decay,))
+        if ema_warmup and ema_decay is None:
+            raise ValueError('ema_warmup needs ema_decay')
+        if decay_filter is not None and not callable(decay_filter):
+            raise ValueError('decay_filter must be None or a callable (name, parameter) -> bool')
+        self.weight_decay, self.decoupled_weight_decay = float(weight_decay), bool(decoupled_weight_decay)
+        self.decay_filter = decay_filter
+        self.ema_decay, self.ema_warmup = None if ema_decay is None else float(ema_decay), bool(ema_warmup)
+        self.ema = None
+        self._decay_tabs = {}
+        self._averaging = False
         eps_ls, alpha = float(label_smoothing), float(distill_weight)
         if not 0.0 <= eps_ls < 1.0:
             raise ValueError('label_smoothing must be in [0, 1), not %r' % (label_smoothing,))
@@ -819,8 +847,12 @@ class Trainer(object):
         old_m, old_v = self.m, self.v
         self.m = torch.zeros_like(model._flat)
         self.v = torch.zeros_like(model._flat)
-        if old_m is not None and old_m.shape == self.m.shape and old_m.device == self.m.device:
+        same = old_m is not None and old_m.shape == self.m.shape and old_m.device == self.m.device
+        if same:
             self.m.copy_(old_m); self.v.copy_(old_v)      # same layout (only the frozen set changed): keep the moments
+        if self.ema_decay is not None and not (same and self.ema is not None and self.ema.shape == self.m.shape
+                                               and self.ema.device == self.m.device):
+            self.ema = model._flat.clone()                # the average starts at the weights; kept across a re-bind like m and v
         self._arena = model._flat
         self._graphs = None
         self._bind_teacher()
@@ -851,6 +883,7 @@ class Trainer(object):
         # maximal runs of trainable parameters: Adam and the all-reduces cover exactly these (torch.optim skips parameters
         # without a gradient; DDP does not reduce them)
         self._train_ranges = self._minus_frozen(0, model._flat.numel())
+        self._bind_decay()
         if self._clip:
             # scratch of the clip launches, allocated here and never inside a capture: one block of float64 partials per trainable
             # range (written in full by every dlsg_grad_sumsq launch), the record dlsg_clip_coef writes, the skipped-step counter
@@ -866,6 +899,46 @@ class Trainer(object):
                     self._skipped.copy_(old)
                 self.last_grad_norm = self._clip_rec[abi.defines['DLSG_CLIP_NORM']]
                 self.skipped_steps = self._skipped[0]
+
+    @property
+    def _ext(self):
+        """weight decay or the averaged weights are on: the update is dlsg_adamw_ema's, with four hyper words"""
+        return self.weight_decay > 0.0 or self.ema_decay is not None
+
+    def _decayed_names(self):
+        """the parameters `decay_filter` puts into the decayed param group, in named_parameters order (what
+        `torch.optim.AdamW([{'params': decayed}, {'params': rest, 'weight_decay': 0}])` would be given)"""
+        return [n for n, p in self.model.named_parameters() if self.decay_filter is None or self.decay_filter(n, p)]
+
+    def _bind_decay(self):
+        """per trainable range the device table of its decayed intervals (dlsg_adamw_ema's decay_ranges, relative to the range):
+        (weight decay of the range's launch, table or None for "all of it").  Uploaded here, never inside a capture."""
+        self._decay_tabs = {}
+        if not self.weight_decay > 0.0:
+            return
+        model = self.model
+        chosen = set(self._decayed_names())
+        runs = []                                         # [lo, hi, padded end]: runs of decayed parameters, joined over the padding
+        for name, p in model.named_parameters():
+            if name not in chosen or name in model.unused_parameters or not p.requires_grad or p.numel() == 0:
+                continue
+            o = model._offsets[name]
+            end = o + (p.numel() + _ALIGN - 1) // _ALIGN * _ALIGN
+            if runs and runs[-1][2] == o:
+                runs[-1][1:] = [o + p.numel(), end]
+            else:
+                runs.append([o, o + p.numel(), end])
+        limit = abi.defines['DLSG_ADAM_MAX_RANGES']
+        for lo, hi in self._train_ranges:
+            tab = [(a - lo, b - lo) for a, b, _ in runs if a >= lo and b <= hi]
+            if not tab:
+                self._decay_tabs[(lo, hi)] = (0.0, None)
+            elif len(tab) == 1 and tab[0][0] == 0 and (tab[0][1] + _ALIGN - 1) // _ALIGN * _ALIGN == hi - lo:
+                self._decay_tabs[(lo, hi)] = (self.weight_decay, None)
+            else:
+                if len(tab) > limit:
+                    raise ValueError('%d decayed intervals in one trainable range: dlsg_adamw_ema takes %d' % (len(tab), limit))
+                self._decay_tabs[(lo, hi)] = (self.weight_decay, _h2d(tab, torch.int64, model._flat.device).view(-1, 2))
 
     def _minus_frozen(self, lo, hi):
         out, cur = [], lo
@@ -915,7 +988,17 @@ class Trainer(object):
 
     def _adam(self, step, hyper=None, ranges=None):
         model, ops = self.model, self.model.ops
+        ext = self._ext
         for lo, hi in (self._train_ranges if ranges is None else ranges):
+            if ext:
+                # weight decay and / or the averaged weights: one launch does clip, decay, update and average
+                wd, tab = self._decay_tabs[(lo, hi)] if self.weight_decay > 0.0 else (0.0, None)
+                ops.adamw_ema(model._flat[lo:hi], model._gflat[lo:hi], self.m[lo:hi], self.v[lo:hi], self.lr, self.betas[0],
+                              self.betas[1], self.eps, step, 1.0 / self.world_size, weight_decay=wd,
+                              decoupled=self.decoupled_weight_decay, ema=None if self.ema is None else self.ema[lo:hi],
+                              ema_decay=self._ema_decay_at(step), hyper=hyper, record=self._clip_rec if self._clip else None,
+                              clip_value=self.clip_grad_value or 0.0, decay_ranges=tab)
+                continue
             if self._clip:
                 ops.adam_clipped(model._flat[lo:hi], model._gflat[lo:hi], self.m[lo:hi], self.v[lo:hi], self.lr, self.betas[0],
                                  self.betas[1], self.eps, step, 1.0 / self.world_size, hyper=hyper, record=self._clip_rec,
@@ -931,27 +1014,57 @@ class Trainer(object):
         as in torch (Adam creates state lazily for parameters with a gradient)."""
         model = self.model
         state = {}
-        names = [n for n, _ in model.named_parameters()]
-        for i, (name, p) in enumerate(model.named_parameters()):
+        params = dict(model.named_parameters())
+        order, split = self._state_order()
+        for i, name in enumerate(order):
+            p = params[name]
             if name in model.unused_parameters or not p.requires_grad or self.t == 0:
                 continue
             o = model._offsets[name]
             state[i] = {'step': torch.tensor(float(self.t)),
                         'exp_avg': self.m[o:o + p.numel()].view(p.shape).clone(),
                         'exp_avg_sq': self.v[o:o + p.numel()].view(p.shape).clone()}
-        group = {'lr': self.lr, 'betas': tuple(self.betas), 'eps': self.eps, 'weight_decay': 0, 'amsgrad': False,
+        wd = self.weight_decay if self.weight_decay > 0.0 else 0
+        group = {'lr': self.lr, 'betas': tuple(self.betas), 'eps': self.eps, 'weight_decay': wd, 'amsgrad': False,
                  'maximize': False, 'foreach': None, 'capturable': False, 'differentiable': False, 'fused': None,
-                 'decoupled_weight_decay': False, 'params': list(range(len(names)))}
-        return {'state': state, 'param_groups': [group]}
+                 'decoupled_weight_decay': bool(wd and self.decoupled_weight_decay), 'params': list(range(len(order)))}
+        if split is None:
+            return {'state': state, 'param_groups': [group]}
+        # with a filter: torch's idiom AdamW([{'params': decayed}, {'params': rest, 'weight_decay': 0}]) -- two groups, the state
+        # numbered over their concatenation
+        rest = dict(group, weight_decay=0, params=list(range(split, len(order))))
+        group['params'] = list(range(split))
+        return {'state': state, 'param_groups': [group, rest]}
+
+    def _state_order(self):
+        """-> (parameter names in the order torch numbers the optimizer state, size of the decayed group or None for one group)"""
+        names = [n for n, _ in self.model.named_parameters()]
+        if self.decay_filter is None:
+            return names, None
+        chosen = self._decayed_names()
+        seen = set(chosen)
+        return chosen + [n for n in names if n not in seen], len(chosen)
 
     def load_optimizer_state_dict(self, sd):
-        """Resume from a reference checkpoint's `optimizer_state_dict` (torch.optim.Adam layout)."""
+        """Resume from a reference checkpoint's `optimizer_state_dict` (torch.optim.Adam layout: one param group), or from what
+        `optimizer_state_dict` wrote with a decay_filter (two groups, decayed parameters first; this trainer's filter says which
+        they are).  lr, betas, eps, weight_decay and decoupled_weight_decay are taken from group 0."""
         model = self.model
         model.flatten_parameters_()
+        groups = sd['param_groups']
+        params = dict(model.named_parameters())
+        if len(groups) == 1:
+            order = list(params)
+        else:
+            order, split = self._state_order()
+            if len(groups) != 2 or split is None or [len(g['params']) for g in groups] != [split, len(order) - split]:
+                raise ValueError('%d param groups of %s parameters: not a layout this trainer (decay_filter %s) can resume'
+                                 % (len(groups), [len(g['params']) for g in groups], 'set' if split is not None else 'None'))
         self.m.zero_()
         self.v.zero_()
         steps = set()
-        for i, (name, p) in enumerate(model.named_parameters()):
+        for i, name in enumerate(order):
+            p = params[name]
             st = sd['state'].get(i, sd['state'].get(str(i)))
             if st is None:
                 continue
@@ -964,7 +1077,71 @@ class Trainer(object):
         self.t = steps.pop() if steps else 0
         g = sd['param_groups'][0]
         self.lr, self.betas, self.eps = g['lr'], tuple(g['betas']), g['eps']
+        wd = float(g.get('weight_decay', 0))
+        if wd != self.weight_decay or (wd > 0.0 and 'decoupled_weight_decay' in g
+                                       and bool(g['decoupled_weight_decay']) != self.decoupled_weight_decay):
+            if not wd >= 0.0:
+                raise ValueError('weight_decay %r in the state dict' % (g.get('weight_decay'),))
+            self.weight_decay = wd
+            if wd > 0.0:
+                self.decoupled_weight_decay = bool(g.get('decoupled_weight_decay', self.decoupled_weight_decay))
+            self._bind_decay()
         self._graphs = None          # captured graphs bake nothing of this state, but recapture keeps the invariants simple
+
+    # ------------------------------------------------------------------ the averaged weights
+    def _ema_decay_at(self, t):
+        if self.ema_decay is None:
+            return 0.0
+        return min(self.ema_decay, (1.0 + t) / (10.0 + t)) if self.ema_warmup else self.ema_decay
+
+    def _need_ema(self):
+        if self.ema is None:
+            raise RuntimeError('this trainer keeps no averaged weights: build it with ema_decay')
+        self._check_binding()
+
+    @contextlib.contextmanager
+    def averaged(self):
+        """`with tr.averaged():` -- the model computes with the averaged weights inside the block: the bits of the weight arena
+        and of `ema` are exchanged in place (dlsg_swap_f32) and exchanged back on exit, also when the block raises.  No address
+        changes, so every captured graph -- this trainer's and the inference graphs of graphs.py -- sees the averaged weights
+        without recapture.  What `scoring.evaluate`, `gather_results` and `perplexity` run under; `step` inside raises."""
+        self._need_ema()
+        if self._averaging:
+            raise RuntimeError('averaged() is already active')
+        ops, flat, ema = self.model.ops, self.model._flat, self.ema
+        ops.swap(flat, ema)
+        self._averaging = True
+        try:
+            yield self.model
+        finally:
+            self._averaging = False
+            ops.swap(flat, ema)
+
+    def ema_state_dict(self):
+        """the model's state dict (its keys and shapes) with every parameter taken from `ema`, as clones: loads with
+        `load_state_dict` into a `copy.deepcopy(model)`, e.g. to put the averaged model into an `Ensemble` beside the raw one"""
+        self._need_ema()
+        if self._averaging:
+            raise RuntimeError('inside averaged() the arenas are exchanged: take the state dict outside the block')
+        model = self.model
+        sd = collections.OrderedDict((k, v.detach().clone()) for k, v in model.state_dict().items())
+        for name, p in model.named_parameters():
+            o = model._offsets[name]
+            sd[name] = self.ema[o:o + p.numel()].view(p.shape).clone()
+        return sd
+
+    def load_ema_state_dict(self, sd):
+        """restore the average from what `ema_state_dict` returned (resume)"""
+        self._need_ema()
+        if self._averaging:
+            raise RuntimeError('inside averaged() the arenas are exchanged: load the average outside the block')
+        model = self.model
+        missing = [n for n, _ in model.named_parameters() if n not in sd]
+        if missing:
+            raise KeyError('the EMA state dict lacks %s' % missing[:5])
+        for name, p in model.named_parameters():
+            o = model._offsets[name]
+            self.ema[o:o + p.numel()].view(p.shape).copy_(sd[name])
 
     # ------------------------------------------------------------------ collectives
     def _comm_mode(self):
@@ -1179,7 +1356,13 @@ class Trainer(object):
 
     def _hyper(self):
         b1, b2 = self.betas
-        return [self.lr / (1.0 - b1 ** self.t), math.sqrt(1.0 - b2 ** self.t)]
+        h = [self.lr / (1.0 - b1 ** self.t), math.sqrt(1.0 - b2 ** self.t)]
+        if self._ext:
+            # dlsg_adamw_ema's two further words, in float64 like the first two and rounded once on the way to the device: the decay
+            # factor (of the plain lr) and the average's weight 1 - d_t
+            h += [1.0 - self.lr * self.weight_decay if self.decoupled_weight_decay else self.weight_decay,
+                  1.0 - self._ema_decay_at(self.t)]
+        return h
 
     @torch.no_grad()
     def step(self, frames, regions, captions, cap_lens, tf_ratio, max_len=26, extra_dlogits=None, seed=None, seq_weights=None,
@@ -1199,6 +1382,8 @@ class Trainer(object):
         any step.  Encoder dropout is keyed by the clip row, decoder and word dropout by the caption row.  With use_graphs the
         captured step is for one n and one pair of row counts; other batches run kernel by kernel."""
         model, ops = self.model, self.model.ops
+        if self._averaging:
+            raise RuntimeError('step inside `with trainer.averaged():` -- the weight arena holds the averaged weights')
         n_seq = model._check_seq_per_clip(seq_per_clip, frames.shape[0], captions)
         self._check_binding()
         captions = captions[:, :max_len].contiguous()
@@ -1239,10 +1424,10 @@ class Trainer(object):
         for w in self._works:
             w.wait()
         self._join_comm()
-        if not self._clip and not self._soft:
+        if not self._clip and not self._soft and not self._ext:
             self._adam(self.t)
             return loss
-        # a clipping (or label-smoothing / distilling) trainer's eager step (a batch of another shape than the captured one, or
+        # a clipping (or label-smoothing / distilling / decaying / averaging) trainer's eager step (a batch of another shape than the captured one, or
         # use_graphs=False) reads the bias corrections from device words the host computed, as the captured step does: one arithmetic for both, so the two forms
         # of a step give the same bits (dlsg_adam's own float powf / sqrtf differ from them in the last place)
         hyper = _h2d(self._hyper(), torch.float32, captions.device)
@@ -1261,13 +1446,15 @@ class Trainer(object):
                                  lens=cap_lens.clone())
         st['weights'] = torch.ones(captions.shape[0], dtype=torch.float32, device=dev) if weighted else None
         # what changes every step besides the batch -- the scheduled-sampling coins, the dropout seed, Adam's bias corrections --
-        # lives in ONE device buffer (int32 words: coins | seed (int64) | hyper (2 x float32)), so that a step sends it as one copy
+        # lives in ONE device buffer (int32 words: coins | seed (int64) | hyper (2 x float32; 4 with weight decay or averaged
+        # weights)), so that a step sends it as one copy
         Lp = (L + 1) // 2 * 2
-        st['scalars'] = torch.zeros(Lp + 4, dtype=torch.int32, device=dev)
+        nh = st['n_hyper'] = 4 if self._ext else 2
+        st['scalars'] = torch.zeros(Lp + 2 + nh, dtype=torch.int32, device=dev)
         st['coins'] = st['scalars'][:L]
         st['coins'].fill_(1)
         st['seed'] = st['scalars'][Lp:Lp + 2].view(torch.int64)
-        st['hyper'] = st['scalars'][Lp + 2:Lp + 4].view(torch.float32)
+        st['hyper'] = st['scalars'][Lp + 2:Lp + 2 + nh].view(torch.float32)
         mode = self._comm_mode()
         # host-issued collectives need the capture cut at every bucket; RCCL's own launches are captured with the step
         cuts = mode == 'torch' or self.force_graph_cuts
@@ -1377,14 +1564,15 @@ class Trainer(object):
         st = self._static
         n = st['scalars'].numel()
         L = st['coins'].numel()
+        nh = st['n_hyper']
         host = torch.empty(n, dtype=torch.int32)
         host[:L] = torch.tensor([int(c) for c in coins], dtype=torch.int32)
-        host[L:n - 4] = 0
-        host[n - 4:n - 2].view(torch.int64)[0] = seed
+        host[L:n - nh - 2] = 0
+        host[n - nh - 2:n - nh].view(torch.int64)[0] = seed
         if hyper is None:
-            _copy_h2d(st['scalars'][:n - 2], host[:n - 2])
+            _copy_h2d(st['scalars'][:n - nh], host[:n - nh])
             return
-        host[n - 2:].view(torch.float32).copy_(torch.tensor(hyper, dtype=torch.float32))
+        host[n - nh:].view(torch.float32).copy_(torch.tensor(hyper, dtype=torch.float32))
         _copy_h2d(st['scalars'], host)
 
     def static_inputs(self):

@@ -23,7 +23,8 @@ class SCSTTrainer(object):
     BLEU-1..4 and ROUGE_L.
     baseline: 'mean' -- the leave-one-out mean of the clip's other n - 1 rewards (needs n_samples >= 2); 'greedy' -- the reward
     of the clip's eval-mode greedy caption.  The remaining keywords go to the owned `Trainer` (lr, use_graphs, data parallel,
-    ...), whose Adam state, gradient buckets and graphs the step reuses.
+    clipping, weight_decay / decay_filter / ema_decay, ...), whose Adam state, gradient buckets and graphs the step reuses;
+    `self.trainer.averaged()` and `self.trainer.ema_state_dict()` give the averaged weights.
     share_encoder=True: the n samples and the train pass run the encoder once per clip -- `sample(..., share_encoder=True)`,
     then `Trainer.step(frames, regions, ids, lens, ..., seq_per_clip=n)` on the B clips and their B*n sampled captions -- instead
     of on the clips repeated n times.  The encoder's dropout masks are then shared by a clip's n samples (keyed by the clip

@@ -1047,6 +1047,30 @@ int dlsg_clip_coef(const double* slots, int count, float grad_scale, float max_n
 int dlsg_adam_clipped(float* p, const float* g, float* m, float* v, int64_t n, float lr, float b1, float b2, float eps, int step,
                       float grad_scale, const float* hyper, const int32_t* guard, const float* record, float clip_value, void* stream);
 
+/* ---------------------------------------------------------------- weight decay and an averaged copy of the weights, in Adam's pass
+ * dlsg_adamw_ema: dlsg_adam_clipped with two further terms, per element and in torch's order:
+ *   gi = (g * grad_scale) * record[DLSG_CLIP_COEF], clamped to +-clip_value when clip_value > 0       (dlsg_adam_clipped)
+ *   decoupled == 0 (torch.optim.Adam(weight_decay=)):  gi += weight_decay * p     -- behind the clip: the record's norm has no decay term
+ *   decoupled != 0 (torch.optim.AdamW):                p *= 1 - lr * weight_decay -- the plain lr, in front of the update
+ *   m, v, p: dlsg_adam's update
+ *   ema (optional, device, laid out as p): ema += (1 - ema_decay) * (p_new - ema)                    (torch.lerp, small weight)
+ * hyper (optional, device) is FOUR floats here: {lr / (1 - b1^step), sqrt(1 - b2^step), the decay factor (1 - lr * weight_decay when
+ *   decoupled, else weight_decay), 1 - ema_decay}, each computed in float64 and rounded once; without it the kernel takes the same
+ *   four from its scalar arguments.  weight_decay == 0 compiles the decay out (hyper[2] is then not read), ema == NULL the average.
+ * decay_ranges (optional, device): n_ranges <= DLSG_ADAM_MAX_RANGES intervals [lo, hi) as (n_ranges, 2) int64, in elements relative
+ *   to p, sorted and disjoint, ends at any element: only elements inside one are decayed.  NULL / 0: the whole launch is decayed.
+ *   The table is staged in LDS (16 B per interval) and searched by bisection once per 16-byte group.
+ * guard != 0 or record[DLSG_CLIP_NONFINITE] != 0: p, m, v AND ema keep their bits.  p, g, m, v, ema at any float offset that they
+ *   share; m, v, g and ema stream non-temporally, p does not (the next forward reads it).
+ * With weight_decay == 0 and ema == NULL the launch is dlsg_adam_clipped's kernel: the same bits.
+ * dlsg_swap_f32: a[i] <-> b[i] for i < n, in place (the weights against their average: addresses, and every captured graph that
+ *   holds them, stay valid). */
+#define DLSG_ADAM_MAX_RANGES 1024
+int dlsg_adamw_ema(float* p, const float* g, float* m, float* v, float* ema, int64_t n, float lr, float b1, float b2, float eps,
+                   int step, float grad_scale, float weight_decay, int decoupled, float ema_decay, const float* hyper,
+                   const int32_t* guard, const float* record, float clip_value, const int64_t* decay_ranges, int n_ranges, void* stream);
+int dlsg_swap_f32(float* a, float* b, int64_t n, void* stream);
+
 
 /* ---------------------------------------------------------------- persistent BiLSTM recurrence (csrc/bilstm.hip)
  * Replaces the time loop of `nn.LSTM(H, H, bidirectional=True, batch_first=True)` in EncoderVisual (models/layer.py:26,52)
