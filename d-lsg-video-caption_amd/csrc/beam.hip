@@ -1,5 +1,5 @@
 // The beam-search step (gfx950): dlsg_beam_select and its variants with a token history, lexical constraints (dynamic beam
-// allocation), Gumbel-perturbed selection (stochastic beam search), an ensemble of members and beam groups, and dlsg_beam_finalize.  One workgroup per batch item, one wave per live
+// allocation), Gumbel-perturbed selection (stochastic beam search), an ensemble of members, beam groups and exclusions, and dlsg_beam_finalize.  One workgroup per batch item, one wave per live
 // beam (BeamSearch.search, allennlp_beamsearch.py:140-260 with per_node_beam_size == beam_size): log-softmax of the beam's logits
 // row, its top-k classes (a finished beam offers <end> at log-prob 0 and nothing else), then the top-k of the k*k summed
 // candidates, back-pointers and the row indices that reorder the recurrent state.  Ties resolve to the lower index.  The step kernels are compositions of the
@@ -333,6 +333,50 @@ __global__ __launch_bounds__(64 * K) void beam_select_groups_kernel(const dlsg_b
     }
 }
 
+// The step with exclusions (dlsg_beam_select_excl): beam_select_ens_kernel's step whose live rows may not choose the last word of
+// an excluded entry behind the entry's other words.  Phase 0 stages the NS shared entries and the clip's NC own in LDS
+// (beam_stage_exclusions); phase 1, wave w for row w: the ban list of beam_select_ens_kernel with the matching entries' last words
+// behind it, a longer list sorted by residue so that a lane scans only the classes it can meet (beam_row_bans_excl), then that kernel's
+// candidates; phase 2, wave 0: beam_flat_merge.  NS = NC = 0 gives the bits of beam_select_ens_kernel.
+template <int K>
+__global__ __launch_bounds__(64 * K) void beam_select_excl_kernel(const dlsg_beam_select_args a, const EnsPack e,
+                                                                    const int64_t* __restrict__ hist_in, int64_t* __restrict__ hist_out,
+                                                                    int L, int t, int g, int min_len,
+                                                                    const int64_t* __restrict__ excl_shared, int NS,
+                                                                    const int64_t* __restrict__ excl_clip, int NC, int P) {
+    __shared__ float cand_lp[K * K];
+    __shared__ int cand_cls[K * K];
+    __shared__ int hist[K][BEAM_MAXL];
+    __shared__ int ban[K][BEAM_BAN_EXCL];
+    __shared__ int sorted[K][BEAM_BAN_EXCL];
+    __shared__ int nban[K];
+    __shared__ float lse_s[K][DLSG_ENS_MAX];
+    __shared__ int ex_s[EXCL_SLOTS * DLSG_PHRASE_MAX];
+    __shared__ int exn_s[EXCL_SLOTS];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const int nbeam = a.first ? 1 : K;
+    const int64_t row = (int64_t)blockIdx.x * K + w;
+    const bool ended = !a.first && a.last[row] == a.end;
+    const int tok = lane < t ? (int)hist_in[row * L + lane] : -1;     // (asked for before the tables: one wait for both)
+    beam_stage_exclusions(excl_shared, NS, excl_clip + (int64_t)blockIdx.x * (NC * P), NC, P, a.V, ex_s, exn_s);
+    int cnt;                                                  // what this lane scans: list[0 .. cnt)
+    const int* list = beam_row_bans_excl(tok, t, g, min_len, a.end, w < nbeam && !ended, ex_s, exn_s, NS + NC, P, hist, ban, nban, sorted,
+                                         cnt);
+    if (w < nbeam) {
+        const float base = a.first ? 0.f : a.last_lp[row];
+        if (ended) {
+            beam_offer_ended<K>(a, lane, base, cand_lp + w * K, cand_cls + w * K);
+        } else {
+            float bv[K];
+            int bi[K];
+            beam_ens_row_topk<K>(e, row, a.V, lane, lse_s[w], list, cnt, bv, bi);
+            beam_offer_live<K>(lane, bv, bi, base, cand_lp + w * K, cand_cls + w * K);
+        }
+    }
+    __syncthreads();
+    if (w == 0) beam_flat_merge<K, true>(a, nbeam, lane, cand_lp, cand_cls, hist_in, hist_out, L, t);
+}
+
 // The n best of each clip's k finished beams, by score = lp / len^alpha (double, stored as float), descending, ties to the lower
 // beam: one wave per clip.  len = tokens up to and including the first `end` of the beam's history row, L without one.
 __global__ __launch_bounds__(64) void beam_finalize_kernel(const int64_t* __restrict__ hist, const float* __restrict__ lp, int k, int L,
@@ -468,6 +512,23 @@ extern "C" int dlsg_beam_select_groups(const dlsg_beam_select_args* a, const flo
     if (groups < 1 || a->k % groups != 0 || !(diversity >= 0.f)) return DLSG_EINVAL;     // (NaN fails the comparison)
     if (a->B == 0) return DLSG_OK;
     BEAM_LAUNCH(beam_select_groups_kernel, e, hist_in, hist_out, L, t, no_repeat_ngram, min_len, groups, diversity);
+    DLSG_CHECK_LAUNCH();
+    return DLSG_OK;
+}
+extern "C" int dlsg_beam_select_excl(const dlsg_beam_select_args* a, const float* const* logits, const int64_t* ld, const float* w,
+                                     const float* logw, int M, int mode, const int64_t* hist_in, int64_t* hist_out, int L, int t,
+                                     int no_repeat_ngram, int min_len, const int64_t* excl_shared, int NS, const int64_t* excl_clip,
+                                     int NC, int P, void* stream) {
+    EnsPack e;
+    if (!beam_hist_ok(a, hist_in, hist_out, L, t, no_repeat_ngram, min_len) ||
+        !beam_ens_pack(logits, ld, w, logw, M, mode, e))
+        return DLSG_EINVAL;
+    if (NS < 0 || NS > DLSG_EXCL_SHARED || NC < 0 || NC > DLSG_EXCL_CLIP || (NS > 0 && !excl_shared) || (NC > 0 && !excl_clip))
+        return DLSG_EINVAL;
+    if (NS + NC > 0 && (P < 1 || P > DLSG_PHRASE_MAX)) return DLSG_EINVAL;
+    if (a->B == 0) return DLSG_OK;
+    if (NS + NC == 0) P = 1;
+    BEAM_LAUNCH(beam_select_excl_kernel, e, hist_in, hist_out, L, t, no_repeat_ngram, min_len, excl_shared, NS, excl_clip, NC, P);
     DLSG_CHECK_LAUNCH();
     return DLSG_OK;
 }

@@ -670,4 +670,130 @@ __device__ __forceinline__ void beam_phrase_merge(const dlsg_beam_select_args& a
     if (lane == 0 && a.ended_count) atomicAdd(a.ended_count, n_end);
 }
 
+// ------------------------------------------------------------------------------------------------ exclusions
+// A clip's exclusions are NE = NS + NC entries of up to P <= DLSG_PHRASE_MAX words, the NS shared ones first: entry a lies in LDS as
+// ex[a * P + j], cut behind its leading run of ids in [0, V) as beam_stage_phrases cuts an alternative, with its length in n[a]
+// (0: absent).  The last word of an entry is banned for a row whose history ends with the words before it.
+constexpr int EXCL_SLOTS = DLSG_EXCL_SHARED + DLSG_EXCL_CLIP;
+constexpr int BEAM_BAN_EXCL = BEAM_MAXL + 1 + EXCL_SLOTS;      // a row's ban list with every entry matching at once
+
+// Phase 0, the whole workgroup (one wave has fewer threads than there are entries): entry a from global memory, `shared` (NS, P)
+// or `clip`, the clip's own (NC, P)
+__device__ __forceinline__ void beam_stage_exclusions(const int64_t* __restrict__ shared, int NS, const int64_t* __restrict__ clip,
+                                                      int NC, int P, int V, int* ex_s, int* n_s) {
+    for (int a = threadIdx.x; a < NS + NC; a += blockDim.x) {
+        const int64_t* e = a < NS ? shared + (int64_t)a * P : clip + (int64_t)(a - NS) * P;
+        int n = 0;
+        bool run = true;
+        for (int j = 0; j < P; ++j) {
+            const int64_t id = e[j];
+            run = run && id >= 0 && id < V;
+            ex_s[a * P + j] = run ? (int)id : -1;
+            n += run;
+        }
+        n_s[a] = n;
+    }
+}
+
+// The bans of the exclusions, ONE wave, appended to the list beam_ban_list has made (ban[0 .. *nban)): lane i of a round tests entry
+// a = 64 * round + i -- n - 1 <= t and hist[t - n + 1 .. t - 1] == ex[a][0 .. n - 2], which a one-word entry meets at every step --
+// and the entries that match put their last word behind the list, in entry order.  A word can stand in the list twice.
+__device__ __forceinline__ void beam_ban_exclusions(const int* hist, int t, const int* ex_s, const int* n_s, int NE, int P, int* ban,
+                                                    int* nban) {
+    const int lane = threadIdx.x & 63;
+    __builtin_amdgcn_wave_barrier();                           // (lane 0 of this wave has just stored the count)
+    int cnt = *nban;
+    for (int a0 = 0; a0 < NE; a0 += 64) {
+        const int a = a0 + lane;
+        const int n = a < NE ? n_s[a] : 0;
+        bool hit = n > 0 && n - 1 <= t;
+        for (int j = 0; j < P - 1; ++j) hit = hit && (j >= n - 1 || hist[t - n + 1 + j] == ex_s[a * P + j]);
+        const unsigned long long m = __ballot(hit);
+        if (hit) ban[cnt + __popcll(m & ((1ull << lane) - 1ull))] = ex_s[a * P + n - 1];
+        cnt += __popcll(m);
+    }
+    __builtin_amdgcn_wave_barrier();
+    if (lane == 0) *nban = cnt;
+}
+
+// A ban list by residue, ONE wave.  The row's wave gives lane l the classes l, l + 64, ... (beam_row_topk, beam_ens_row_topk), so
+// a lane needs only the banned classes congruent to it: ban[0 .. n) is copied into `sorted` as a counting sort by class & 63 -- lane
+// i of a round holds entry 64 * round + i, six ballots over the bits of its residue tell every lane which entries of the round share
+// a residue -- and lane l gets its own stretch sorted[off .. off + cnt).  A lane scans its stretch, typically none or one class,
+// where it would scan all n.
+__device__ __forceinline__ void beam_ban_buckets(const int* ban, int n, int* sorted, int& off, int& cnt) {
+    const int lane = threadIdx.x & 63;
+    const unsigned long long below = (1ull << lane) - 1ull;
+    // the entries (lanes) of a round whose residue is `want`
+    auto same = [](const unsigned long long* bit, unsigned long long valid, int want) {
+        unsigned long long m = valid;
+#pragma unroll
+        for (int b = 0; b < 6; ++b) m &= ((want >> b) & 1) ? bit[b] : ~bit[b];
+        return m;
+    };
+    __builtin_amdgcn_wave_barrier();                           // (the list was stored by lanes of this wave)
+    n = __builtin_amdgcn_readfirstlane(n);
+    cnt = 0;
+    for (int a0 = 0; a0 < n; a0 += 64) {
+        const bool have = a0 + lane < n;
+        const int r = have ? ban[a0 + lane] & 63 : 0;
+        unsigned long long bit[6];
+#pragma unroll
+        for (int b = 0; b < 6; ++b) bit[b] = __ballot(have && ((r >> b) & 1));
+        cnt += __popcll(same(bit, __ballot(have), lane));
+    }
+    int incl = cnt;                                            // the stretches lie in residue order
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const int up = __shfl_up(incl, o, 64);
+        incl += lane >= o ? up : 0;
+    }
+    off = incl - cnt;
+    int fill = off;                                            // lane l: where the next class of residue l goes
+    for (int a0 = 0; a0 < n; a0 += 64) {
+        const bool have = a0 + lane < n;
+        const int c = have ? ban[a0 + lane] : 0;
+        const int r = c & 63;
+        unsigned long long bit[6];
+#pragma unroll
+        for (int b = 0; b < 6; ++b) bit[b] = __ballot(have && ((r >> b) & 1));
+        const unsigned long long valid = __ballot(have);
+        const int dst = __shfl(fill, r, 64) + __popcll(same(bit, valid, r) & below);
+        if (have) sorted[dst] = c;
+        fill += __popcll(same(bit, valid, lane));
+    }
+    __builtin_amdgcn_wave_barrier();
+}
+
+// beam_row_bans for the wider list (every wave calls it: two barriers, the first of which also ends phase 0).  tok: token `lane` of
+// the row's history (-1 behind it), which goes into LDS whatever g is -- a context is matched against it; the caller loads it
+// before it stages the tables, so that the two trips to memory overlap.  Then beam_ban_list and beam_ban_exclusions for a row that
+// is `live`.  -> the list the calling lane scans and its length: the whole list while it is short, from BEAM_BUCKET_MIN classes on
+// the lane's stretch of the list by residue (beam_ban_buckets into sorted[w]), which costs about as much as scanning two classes.
+constexpr int BEAM_BUCKET_MIN = 3;
+template <int K>
+__device__ __forceinline__ const int* beam_row_bans_excl(int tok, int t, int g, int min_len, int end, bool live, const int* ex_s,
+                                                         const int* n_s, int NE, int P, int (&hist)[K][BEAM_MAXL],
+                                                         int (&ban)[K][BEAM_BAN_EXCL], int (&nban)[K], int (&sorted)[K][BEAM_BAN_EXCL],
+                                                         int& cnt) {
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    hist[w][lane] = tok;
+    const int* list = ban[w];
+    cnt = 0;
+    __syncthreads();
+    if (live) {
+        beam_ban_list(hist[w], t, g, min_len, end, ban[w], &nban[w]);
+        beam_ban_exclusions(hist[w], t, ex_s, n_s, NE, P, ban[w], &nban[w]);
+        __builtin_amdgcn_wave_barrier();
+        cnt = nban[w];
+        if (cnt >= BEAM_BUCKET_MIN) {
+            int off;
+            beam_ban_buckets(ban[w], cnt, sorted[w], off, cnt);
+            list = sorted[w] + off;
+        }
+    }
+    __syncthreads();
+    return list;
+}
+
 }  // namespace dlsg

@@ -18,7 +18,12 @@ banks "constraints met" (dynamic beam allocation) and recomputes what a beam has
 and phrases share their host side: one packer (`_pack`; `pack_constraints` and `pack_phrases` are its two ways of reading a
 constraint's alternatives), one check of a packed tensor (`_check_packed`) and one search body, which differs by the tensor's
 rank in the step it launches and in how `_constraints_met` counts.
+`beam_nbest(exclude=...)` and `ensemble_nbest(exclude=...)` are those searches under exclusions -- words, phrases and endings a caption
+must not contain (`pack_exclusions`): `beam_select_excl` adds the last word of every excluded entry that a beam's history leads up to
+to the beam's ban list; `exclusions_hit` counts what a caption contains of them.
 """
+import collections
+
 import torch
 
 from . import engine as E
@@ -227,15 +232,19 @@ def _finalize(model, hist, lps, k, n, length_penalty):
 
 
 def _nbest_search(models, weights, mode, visual_feats, region_feats, n_best, length_penalty, no_repeat_ngram, min_len, beam_size,
-                  num_groups, diversity_penalty):
+                  num_groups, diversity_penalty, exclude=None):
     """The search of `beam_nbest` (weights None: one model) and `ensemble_nbest`: `_hist_search` on the step kernel the options
     ask for, `beam_finalize` ranks the beams."""
     dec, ops = models[0].decoder, models[0].ops
     k = dec.beam_size if beam_size is None else beam_size
     n = check_nbest_options(k, dec.max_words, n_best, length_penalty, no_repeat_ngram, min_len, num_groups, diversity_penalty)
+    if exclude is not None:
+        shared, per_clip = check_exclusions(exclude, visual_feats.shape[0], visual_feats.device, num_groups)
 
     def select(t, logits, step):
-        if num_groups > 1:                                             # (a single model: one member of weight 1)
+        if exclude is not None:                                        # (never with groups: check_exclusions)
+            ops.beam_select_excl(logits, [1.0] if weights is None else weights, mode, *step, shared, per_clip, no_repeat_ngram, min_len)
+        elif num_groups > 1:                                           # (a single model: one member of weight 1)
             ops.beam_select_groups(logits, [1.0] if weights is None else weights, mode, *step, no_repeat_ngram, min_len, num_groups,
                                    float(diversity_penalty))
         elif weights is None:
@@ -247,7 +256,7 @@ def _nbest_search(models, weights, mode, visual_feats, region_feats, n_best, len
 
 @torch.no_grad()
 def beam_nbest(model, visual_feats, region_feats, n_best=None, length_penalty=0.0, no_repeat_ngram=0, min_len=0, beam_size=None,
-               num_groups=1, diversity_penalty=0.0):
+               num_groups=1, diversity_penalty=0.0, exclude=None):
     """The n best of the k beams of every clip: (ids (B, n, L) int64, padded with <end>; scores (B, n) float32 =
     log-prob / len^length_penalty, descending; lens (B, n) int64 = tokens up to and including the first <end>, else L), device
     tensors.  no_repeat_ngram = g: no caption repeats a g-gram; min_len: no <end> before that many words.  A banned word takes
@@ -259,22 +268,27 @@ def beam_nbest(model, visual_feats, region_feats, n_best=None, length_penalty=0.
     num_groups = G > 1: diverse beam search (Vijayakumar et al. 2016) -- the beams are G groups of beam_size / G, chosen one
     group after another at every word; a word that earlier groups chose at that step costs a later group `diversity_penalty` per
     choice (inf: it is excluded).  The penalty steers the choice only: scores stay log-prob / len^length_penalty, and the n best
-    are ranked over all groups together.  One `beam_select_groups` launch per step; num_groups = 1 launches what it always did."""
+    are ranked over all groups together.  One `beam_select_groups` launch per step; num_groups = 1 launches what it always did.
+    exclude: the `Exclusions` of `pack_exclusions` -- words and phrases no caption may contain, for all clips or per clip: a beam may
+    not choose the last word of an entry behind the entry's other words (`<unk>` is a one-word entry, a bad ending the pair
+    (word, <end>)).  One `beam_select_excl` launch per step, the model as one member of weight 1; not together with num_groups > 1.
+    exclude=None launches what it always did."""
     return _nbest_search([model], None, 0, visual_feats, region_feats, n_best, length_penalty, no_repeat_ngram, min_len, beam_size,
-                         num_groups, diversity_penalty)
+                         num_groups, diversity_penalty, exclude)
 
 
 @torch.no_grad()
 def ensemble_nbest(models, weights, mode, visual_feats, region_feats, n_best=None, length_penalty=0.0, no_repeat_ngram=0, min_len=0,
-                   beam_size=None, num_groups=1, diversity_penalty=0.0):
+                   beam_size=None, num_groups=1, diversity_penalty=0.0, exclude=None):
     """`beam_nbest` with several models that decode one caption: every member runs its own encoder and its own decode step on the
     shared words and back-pointer rows (its own state slots; any of the model classes, any hidden sizes), and one
     `beam_select_ens` launch per step combines the members' logit rows -- mode 0: log of the weighted mean probability, mode 1:
     weighted mean log-probability -- and chooses the beams.  One set of preds / hist / back / rows / lps; no host synchronisation.
     The members share vocabulary, max_words and device (`ensemble.Ensemble` checks that); beam_size defaults to the first member's.
-    num_groups, diversity_penalty: diverse beam search as in `beam_nbest`, on the combined values (`beam_select_groups`)."""
+    num_groups, diversity_penalty: diverse beam search as in `beam_nbest`, on the combined values (`beam_select_groups`).
+    exclude: exclusions as in `beam_nbest` (`beam_select_excl` in place of `beam_select_ens`)."""
     return _nbest_search(models, weights, mode, visual_feats, region_feats, n_best, length_penalty, no_repeat_ngram, min_len, beam_size,
-                         num_groups, diversity_penalty)
+                         num_groups, diversity_penalty, exclude)
 
 
 def check_stochastic_options(n, L, V, temperature, min_len=0, no_repeat_ngram=0, return_threshold=False):
@@ -503,6 +517,159 @@ def _constraints_met(ids, cons, vocab_size):
     valid = (cons >= 0) & (cons < vocab_size)
     hit = (ids.view(B, k, L, 1, 1) == cons.view(B, 1, 1, *cons.shape[1:])) & valid.view(B, 1, 1, *cons.shape[1:])
     return hit.any(4).any(2).sum(2)
+
+
+# ---------------------------------------------------------------------------------------------- exclusions
+MAX_EXCL_SHARED, MAX_EXCL_CLIP = 64, 32                          # DLSG_EXCL_SHARED, DLSG_EXCL_CLIP
+# the words a caption should not stop behind (self-critical.pytorch, utils/misc.py: bad_endings)
+BAD_ENDINGS = ('a', 'an', 'the', 'in', 'for', 'at', 'of', 'with', 'before', 'after', 'on', 'upon', 'near', 'to', 'is', 'are', 'am')
+
+Exclusions = collections.namedtuple('Exclusions', ['shared', 'per_clip'])
+Exclusions.__doc__ = """What `beam_search(exclude=...)` must not emit, as `beam_select_excl` reads it: shared (NS <= 64, P) int64 or None,
+the entries that hold for every clip, and per_clip (B, NC <= 32, P) int64 or None, each clip's own; an entry is a row of up to P <= 4
+word ids padded with -1, whose last word is banned behind its other words.  `pack_exclusions` makes one."""
+
+
+def _excluded_entry(phrase, vocab, where, skip_unknown):
+    """one excluded phrase -- a string, split on whitespace, a tuple of words or ids, or one word or id -- as a list of ids; None
+    for a phrase with a word outside the vocabulary under skip_unknown; ValueError for what cannot be excluded"""
+    words = phrase.split() if isinstance(phrase, str) else list(phrase) if isinstance(phrase, (tuple, list)) else [phrase]
+    if not words:
+        raise ValueError('%san empty phrase %r' % (where, phrase))
+    if len(words) > MAX_PHRASE:
+        raise ValueError('%s%r has %d words, at most %d per phrase' % (where, phrase, len(words), MAX_PHRASE))
+    never = {vocab.word2idx[w] for w in ('<start>', '<pad>') if w in vocab.word2idx}
+    end = vocab.word2idx.get('<end>', -1)
+    ids = []
+    for j, wd in enumerate(words):
+        if isinstance(wd, str):
+            i = vocab.word2idx.get(wd, -1)                              # (<unk> written out is a word of the vocabulary)
+        else:
+            i = int(wd) if 0 <= int(wd) < len(vocab) else -1
+        if i < 0:
+            if skip_unknown:
+                return None
+            raise ValueError('%s%r is not in the vocabulary' % (where, wd))
+        if i in never:
+            raise ValueError('%s%r cannot be excluded (<start> and <pad> are never chosen)' % (where, wd))
+        if i == end and (j + 1 < len(words) or len(words) < 2):
+            raise ValueError('%s%r: <end> can only be the last of at least two words (a bad ending)' % (where, phrase))
+        ids.append(i)
+    return ids
+
+
+def pack_exclusions(vocab, words=(), phrases=(), bad_endings=False, suppress_unk=False, per_clip=None, device=None, skip_unknown=False):
+    """The `Exclusions` of `beam_search(exclude=...)`: two int64 tensors padded with -1, shared (NS, P) -- None without a shared
+    entry -- and per_clip (B, NC, P) -- None without the argument.  words: words or ids no caption may contain; phrases: phrases no
+    caption may contain as contiguous words, each a string, split on whitespace, a tuple of words or ids, or one word or id;
+    bad_endings=True: no caption stops behind a word of `BAD_ENDINGS` (those the vocabulary has), a sequence of words in its place:
+    behind one of those; suppress_unk: `<unk>` is never emitted; per_clip: for every clip a list of further phrases.  Equal entries
+    are folded.  ValueError for more than 64 shared or 32 per-clip entries, more than 4 words in a phrase, an empty phrase, <start>
+    or <pad> in a phrase, <end> anywhere but as the last of at least two words, and for a word outside the vocabulary (`<unk>`
+    written out is allowed) -- unless skip_unknown: then that entry is dropped."""
+    def entries(items, where):
+        out = []
+        for it in items:
+            ids = _excluded_entry(it, vocab, where, skip_unknown)
+            if ids is not None and ids not in out:
+                out.append(ids)
+        return out
+    shared = [(w,) if isinstance(w, str) else w for w in words] + list(phrases)
+    if suppress_unk:
+        shared.append(('<unk>',))
+    if bad_endings is True:
+        shared += [(w, '<end>') for w in BAD_ENDINGS if w in vocab.word2idx]
+    elif bad_endings:
+        shared += [(w, '<end>') for w in bad_endings]
+    shared = entries(shared, '')
+    if len(shared) > MAX_EXCL_SHARED:
+        raise ValueError('%d shared exclusions, at most %d' % (len(shared), MAX_EXCL_SHARED))
+    clips = None if per_clip is None else [entries(clip, 'clip %d: ' % b) for b, clip in enumerate(per_clip)]
+    for b, clip in enumerate(clips or []):
+        if len(clip) > MAX_EXCL_CLIP:
+            raise ValueError('clip %d: %d exclusions, at most %d per clip' % (b, len(clip), MAX_EXCL_CLIP))
+    P = max([len(e) for e in shared] + [len(e) for clip in clips or [] for e in clip] + [1])
+
+    def table(rows, n):
+        out = torch.full((n, P), -1, dtype=torch.int64)
+        for a, ids in enumerate(rows):
+            out[a, :len(ids)] = torch.tensor(ids, dtype=torch.int64)
+        return out
+    sh = table(shared, len(shared)) if shared else None
+    pc = None
+    if clips is not None:
+        NC = max([len(clip) for clip in clips] + [0])
+        pc = torch.stack([table(clip, NC) for clip in clips]) if clips else torch.full((0, NC, P), -1, dtype=torch.int64)
+    if device is not None:
+        sh, pc = (None if x is None else x.to(device) for x in (sh, pc))
+    return Exclusions(sh, pc)
+
+
+def check_exclusions(exclude, B, device, num_groups=1):
+    """ValueError for an `exclude` the n-best search cannot run on B clips on `device`: not an `Exclusions`, a table of the wrong
+    dtype, rank, device or size, a per-clip table whose first dimension is not the batch, two tables of different P, or together
+    with beam groups; returns the two tables, contiguous (None for an absent or empty one)"""
+    if num_groups > 1:
+        raise ValueError('exclude and num_groups = %d: exclusions are not covered in diverse beam search' % num_groups)
+    if not isinstance(exclude, tuple) or len(exclude) != 2:
+        raise ValueError('exclude: an Exclusions(shared, per_clip) (pack_exclusions makes one), not %s' % type(exclude).__name__)
+    out, P = [], None
+    for tab, d, lim, what in ((exclude[0], 2, MAX_EXCL_SHARED, 'shared'), (exclude[1], 3, MAX_EXCL_CLIP, 'per-clip')):
+        if tab is None:
+            out.append(None)
+            continue
+        axes = '(NS, P)' if d == 2 else '(B, NC, P)'
+        if not torch.is_tensor(tab) or tab.dtype != torch.int64 or tab.dim() != d:
+            raise ValueError('exclude: the %s table is an int64 tensor %s, not %s'
+                             % (what, axes, '%s %s' % (tab.dtype, tuple(tab.shape)) if torch.is_tensor(tab) else type(tab).__name__))
+        if d == 3 and tab.shape[0] != B:
+            raise ValueError('exclude: the per-clip table of shape %s holds %d clips, the batch %d' % (tuple(tab.shape), tab.shape[0], B))
+        if tab.shape[-2] > lim or (tab.shape[-2] > 0 and not 1 <= tab.shape[-1] <= MAX_PHRASE):
+            raise ValueError('exclude: the %s table of shape %s: at most %d entries of 1 to %d words' % (what, tuple(tab.shape), lim, MAX_PHRASE))
+        if tab.device != device:
+            raise ValueError('exclude: the %s table on %s, the clips on %s' % (what, tab.device, device))
+        if tab.shape[-2] == 0:
+            out.append(None)
+            continue
+        if P not in (None, tab.shape[-1]):
+            raise ValueError('exclude: the shared table has %d words per entry, the per-clip table %d' % (P, tab.shape[-1]))
+        P = tab.shape[-1]
+        out.append(tab.contiguous())
+    return out
+
+
+def exclusions_hit(ids, lens, exclusions, vocab_size=None):
+    """How often captions contain what is excluded: ids (B, n, L) or (B, L) int64, lens (B, n) or (B,) int64 as a search returns
+    them, exclusions an `Exclusions` (an entry: the leading run of ids in [0, vocab_size), of any id >= 0 without vocab_size) ->
+    (B, n) or (B,) int64, the number of positions p < lens at which an entry ends, that is ids[p - n + 1 .. p] equals an entry of n
+    words -- a bad ending ends at the caption's <end>, which lens counts.  0 everywhere is what `beam_search(exclude=...)` owes for
+    every caption of finite score.  Torch operations on the tensors' device, nothing is read back; any captions, not only a search's."""
+    rows, ln = (ids, lens) if ids.dim() == 3 else (ids.unsqueeze(1), lens.unsqueeze(1))
+    B, n, L = rows.shape
+    tabs = []
+    if exclusions[0] is not None and exclusions[0].shape[0]:
+        tabs.append(exclusions[0].to(rows.device).unsqueeze(0).expand(B, *exclusions[0].shape))
+    if exclusions[1] is not None and exclusions[1].shape[1]:
+        if exclusions[1].shape[0] != B:
+            raise ValueError('exclusions_hit: the per-clip table holds %d clips, ids %d' % (exclusions[1].shape[0], B))
+        tabs.append(exclusions[1].to(rows.device))
+    hits = torch.zeros(B, n, L, dtype=torch.bool, device=rows.device)
+    for tab in tabs:                                                   # (B, N, P)
+        P = tab.shape[2]
+        valid = tab >= 0 if vocab_size is None else (tab >= 0) & (tab < vocab_size)
+        run = valid.long().cumprod(2)
+        m = run.sum(2)                                                 # (B, N): the entries' lengths
+        # the entry right-aligned in its P slots: slot s holds word s - (P - m)
+        src = torch.arange(P, device=rows.device).view(1, 1, P) - (P - m).unsqueeze(2)
+        right = tab.gather(2, src.clamp(min=0))
+        used = src >= 0
+        # the P tokens that end at every position, -2 before the caption's start
+        win = torch.cat([rows.new_full((B, n, P - 1), -2), rows], 2).unfold(2, P, 1)       # (B, n, L, P)
+        same = (win.unsqueeze(3) == right.view(B, 1, 1, -1, P)) | ~used.view(B, 1, 1, -1, P)
+        hits |= (same.all(4) & (m > 0).view(B, 1, 1, -1)).any(3)
+    below = torch.arange(L, device=rows.device).view(1, 1, L) < ln.unsqueeze(2)
+    out = (hits & below).sum(2)
+    return out if ids.dim() == 3 else out[:, 0]
 
 
 @torch.no_grad()

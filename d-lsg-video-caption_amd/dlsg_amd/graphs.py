@@ -78,6 +78,17 @@ def _members(model_or_ensemble):
     return list(getattr(model_or_ensemble, 'members', [model_or_ensemble]))
 
 
+def _held_exclusions(options):
+    """takes `exclude` out of a search's options -> (the other options, the graph's own copy of the two tables or None, the options
+    the captured search runs with): the copies are static buffers like the inputs"""
+    options = dict(options)
+    exclude = options.pop('exclude', None)
+    if exclude is None:
+        return options, None, options
+    exclude = type(exclude)(*[None if x is None else x.clone() for x in exclude])
+    return options, exclude, dict(options, exclude=exclude)
+
+
 class _InferenceGraph(object):
     """A no-grad pass of `model` over (frames, regions), captured once for a batch shape and replayed: a subclass says what to
     run (`_run`, on the static inputs self.frames / self.regions; its return value becomes self.out).  A captured graph holds raw
@@ -197,14 +208,17 @@ class BeamGraph(_InferenceGraph):
 class NBestBeamGraph(_InferenceGraph):
     """hipGraph-captured `model.beam_search(frames, regions, **options)` for one batch shape: encoder, all max_words steps with
     the beams' token history, and the ranking.  A replay returns (ids, scores, lens) -- static buffers, valid until the next
-    replay -- and synchronises nothing (call `model.ops.check_persistent()` where the ids are read back)."""
+    replay -- and synchronises nothing (call `model.ops.check_persistent()` where the ids are read back).
+    exclude=Exclusions (`pack_exclusions`): the graph keeps its own copy of the two tables as `graph.exclude` and captures their
+    addresses: `graph.exclude.per_clip.copy_(new)` (or `.shared`) changes what the next replay bans; another shape needs a new
+    graph."""
 
     def __init__(self, model, frames, regions, **options):
-        self.options = options
+        self.options, self.exclude, self._search = _held_exclusions(options)
         super().__init__(model, frames, regions)
 
     def _run(self):
-        return self.model.beam_search(self.frames, self.regions, **self.options)
+        return self.model.beam_search(self.frames, self.regions, **self._search)
 
 
 class StochasticBeamGraph(_SeededGraph):
@@ -263,14 +277,15 @@ class EnsembleBeamGraph(_InferenceGraph):
     """hipGraph-captured `ensemble.beam_search(frames, regions, **options)` (ensemble.Ensemble) for one batch shape: every member's
     encoder and decode steps, one `beam_select_ens` per word, the ranking.  The graph holds addresses into EVERY member's arena and
     every member's train / eval mode: `valid_for` and the stale-arena error cover all of them.  A replay returns (ids, scores,
-    lens), static buffers, and synchronises nothing."""
+    lens), static buffers, and synchronises nothing.  exclude=Exclusions: kept as `graph.exclude`, as NBestBeamGraph keeps it."""
 
     def __init__(self, ensemble, frames, regions, **options):
-        self.ensemble, self.options = ensemble, options
+        self.ensemble = ensemble
+        self.options, self.exclude, self._search = _held_exclusions(options)
         super().__init__(ensemble.members[0], frames, regions, ensemble.members)
 
     def _run(self):
-        return self.ensemble.beam_search(self.frames, self.regions, **self.options)
+        return self.ensemble.beam_search(self.frames, self.regions, **self._search)
 
 
 class ConsensusBeamGraph(_InferenceGraph):

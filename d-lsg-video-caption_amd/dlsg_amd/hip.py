@@ -651,6 +651,38 @@ class HipOps(object):
         self._check(self.lib.dlsg_beam_select_groups(C.byref(a), *members, int(mode), *hist, int(num_groups),
                                                      C.c_float(diversity_penalty), self._stream()), 'dlsg_beam_select_groups')
 
+    @staticmethod
+    def _excl_tables(shared, per_clip, B, device):
+        """checks the two exclusion tables, (NS, P) shared and (B, NC, P) per clip, int64 on the logits' device, either None ->
+        the ctypes arguments (shared, NS, per_clip, NC, P) of dlsg_beam_select_excl; an empty table goes as NULL with count 0"""
+        P = None
+        for tab, d, lim, what in ((shared, 2, abi.defines['DLSG_EXCL_SHARED'], 'shared'), (per_clip, 3, abi.defines['DLSG_EXCL_CLIP'], 'per-clip')):
+            if tab is None:
+                continue
+            assert tab.dtype == torch.int64 and tab.is_contiguous() and tab.dim() == d, (what, tab.dtype, tab.shape)
+            assert tab.device == device, (what, tab.device, device)
+            assert d == 2 or tab.shape[0] == B, (what, tab.shape, B)
+            assert tab.shape[-2] <= lim, (what, tab.shape, lim)
+            if tab.shape[-2] > 0:
+                assert 1 <= tab.shape[-1] <= abi.defines['DLSG_PHRASE_MAX'] and P in (None, tab.shape[-1]), (what, tab.shape, P)
+                P = tab.shape[-1]
+        NS = 0 if shared is None else shared.shape[0]
+        NC = 0 if per_clip is None else per_clip.shape[1]
+        return _p(shared) if NS else None, NS, _p(per_clip) if NC else None, NC, P or 1
+
+    def beam_select_excl(self, logits_list, weights, mode, last, last_lp, pred, new_lp, back, rows, k, end, hist_in, hist_out, t,
+                         excl_shared=None, excl_clip=None, no_repeat_ngram=0, min_len=0, ended_count=None):
+        """`beam_select_ens` with exclusions: excl_shared (NS <= 64, P) int64 holds entries of up to P <= 4 word ids that no clip's
+        caption may contain, excl_clip (B, NC <= 32, P) each clip's own (an entry is the leading run of ids in [0, V)); a live beam
+        may not choose the last word of an entry whose other words are the last words of its history (see include/dlsg.h).  Both
+        None or empty: the bits of `beam_select_ens`.  A single model passes one logits array and weights [1.0]."""
+        R, V, members = self._beam_members(logits_list, weights, hist_out.device)
+        a, hist = self._hist_step(R, V, last, last_lp, pred, new_lp, back, rows, k, end, hist_in, hist_out, t, no_repeat_ngram, min_len,
+                                  ended_count)
+        tables = self._excl_tables(excl_shared, excl_clip, R // k, hist_out.device)
+        self._check(self.lib.dlsg_beam_select_excl(C.byref(a), *members, int(mode), *hist, *tables, self._stream()),
+                    'dlsg_beam_select_excl')
+
     def beam_finalize(self, hist, lp, k, end, alpha, ids, scores, lens):
         """the n = ids.shape[1] best of each clip's k beams by lp / len^alpha: ids (B, n, L), scores (B, n), lens (B, n)."""
         R, L = hist.shape

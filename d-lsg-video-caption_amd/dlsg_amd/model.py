@@ -263,17 +263,20 @@ class _HipModel(_ArenaModule):
         raise NotImplementedError('sampled decoding (self-critical training) is implemented for CapGnnModel only')
 
     def beam_search(self, visual_feats, region_feats, beam_size=None, n_best=None, length_penalty=0.0, no_repeat_ngram=0, min_len=0,
-                    num_groups=1, diversity_penalty=0.0):
+                    num_groups=1, diversity_penalty=0.0, exclude=None):
         """The n_best (default: all) of `beam_size` (default: the decoder's, at most 8) beams per clip, entirely on the device:
         (ids (B, n, L) int64 padded with <end>, scores (B, n) float32 = log-prob / len^length_penalty in descending order, lens
         (B, n) int64 counting the <end>).  no_repeat_ngram = g > 0: no caption repeats a g-gram; min_len: at least that many words
         before <end>.  With the options off, row 0 is `model(frames, regions, None)` padded with <end> (`beam.beam_nbest`).
         num_groups = G > 1: diverse beam search -- G groups of beam_size / G beams, chosen in turn at every word; a word that
         earlier groups chose at that step costs a later group `diversity_penalty` per choice (inf: excluded).  scores do not
-        contain the penalty.  Nothing synchronises with the host, so call `model.ops.check_persistent()` where the ids are read back."""
+        contain the penalty.  exclude: the `Exclusions` `dlsg_amd.pack_exclusions` makes -- words and phrases no caption may contain,
+        `<unk>`, bad endings, for all clips or per clip; a banned word takes log-prob -inf, nothing is renormalised (not together
+        with num_groups > 1).  Nothing synchronises with the host, so call `model.ops.check_persistent()` where the ids are read back."""
         from .beam import beam_search
         return beam_search(self, visual_feats, region_feats, beam_size, n_best=n_best, length_penalty=length_penalty,
-                           no_repeat_ngram=no_repeat_ngram, min_len=min_len, num_groups=num_groups, diversity_penalty=diversity_penalty)
+                           no_repeat_ngram=no_repeat_ngram, min_len=min_len, num_groups=num_groups, diversity_penalty=diversity_penalty,
+                           exclude=exclude)
 
     def sample_without_replacement(self, visual_feats, region_feats, n=5, temperature=1.0, seed=None, min_len=0, no_repeat_ngram=0,
                                    return_threshold=False):

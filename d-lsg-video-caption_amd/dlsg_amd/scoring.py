@@ -663,11 +663,21 @@ def gather_results(net, eval_loader, decode=None):
     `constrained_beam_search` with the other options: it contains a word of every constraint (not together with consensus); fn may
     as well return phrases -- lists with strings such as "hot dog", or the tensor of `beam.pack_phrases` --, which that call dispatches.
     With the key rescore=scorer (a model or an `Ensemble`; optionally rescore_mix) every beam of that search is kept and the
-    caption is the one the scorer ranks first: row 0 of `rescore.rescore_search` (not together with consensus or constraints)."""
+    caption is the one the scorer ranks first: row 0 of `rescore.rescore_search` (not together with consensus or constraints).
+    With the key exclude=X the search runs under exclusions (`beam.pack_exclusions`): X is an `Exclusions` without a per-clip part,
+    which holds for every batch, or fn(video_ids) -> the batch's `Exclusions`; consensus and rescore searches pass it on to their
+    beam search, constraints do not take it."""
     import torch
     result = collections.OrderedDict()
     dec = (net.module if hasattr(net, 'module') else net).decoder
-    consensus, constraints, rescorer = None, None, None
+    consensus, constraints, rescorer, exclude = None, None, None, None
+    if decode is not None and decode.get('exclude') is not None:
+        decode = dict(decode)
+        exclude = decode.pop('exclude')
+        if 'constraints' in decode:
+            raise ValueError('decode: exclude and constraints cannot be combined (constrained_beam_search takes no exclusions)')
+        if not callable(exclude) and (not isinstance(exclude, tuple) or len(exclude) != 2 or exclude[1] is not None):
+            raise ValueError('decode: exclude is an Exclusions without a per-clip part, or fn(video_ids) -> Exclusions')
     if decode is not None and 'rescore' in decode:
         decode = dict(decode)
         rescorer = dict(scorer=decode.pop('rescore'), mix=decode.pop('rescore_mix', 1.0))
@@ -685,6 +695,9 @@ def gather_results(net, eval_loader, decode=None):
                          temperature=decode.pop('consensus_temperature', 1.0))
     with torch.no_grad():
         for frames, regions, spatials, video_ids in eval_loader:
+            if exclude is not None:
+                ex = exclude(video_ids) if callable(exclude) else exclude
+                decode['exclude'] = type(ex)(*[None if x is None else x.to(frames.device) for x in ex])
             if decode is None:
                 outputs = net(frames, regions, None)[0]
             elif consensus is not None:

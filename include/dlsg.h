@@ -974,6 +974,27 @@ int dlsg_beam_select_cons(const dlsg_beam_select_args* a, const int64_t* hist_in
 int dlsg_beam_select_phrases(const dlsg_beam_select_args* a, const int64_t* hist_in, int64_t* hist_out, int L, int t,
                              int no_repeat_ngram, int min_len, const int64_t* phr, int C, int W, int P, int32_t* met_out,
                              int32_t* bank_out, void* stream);
+/* dlsg_beam_select_ens with EXCLUSIONS: words and phrases a caption must not contain.  excl_shared (NS, P) int64, device: NS <=
+ * DLSG_EXCL_SHARED entries that hold for every clip; excl_clip (B, NC, P) int64, device: NC <= DLSG_EXCL_CLIP entries of each
+ * clip's own; 1 <= P <= DLSG_PHRASE_MAX; either table may be NULL with its count 0.  An entry e is the leading run of ids in
+ * [0, V) of its row of P words -- it is cut at the first id outside that range, as dlsg_beam_select_phrases cuts an alternative --,
+ * n its length, n == 0: absent.  For a live row at step t with history h[0 .. t), the word e[n-1] is banned iff n - 1 <= t and
+ * h[t-n+1 .. t-1] == e[0 .. n-2]: a one-word entry bans its word at every step (`<unk>`), the two-word entry (w, end) forbids a
+ * caption to stop behind w (a bad ending).  The context never matches the start token, which is not part of the history, and an
+ * entry longer than the caption so far bans nothing.  These bans join the row's list behind those of no_repeat_ngram and min_len
+ * (a word may stand there twice); a banned class counts as -inf in the row's k best while the log-sum-exp stays that of the whole
+ * row; a row that has ended is untouched.  Everything else -- the members and their combination in `mode`, the (value, index)
+ * order, step 0 reading the clip's first row, the k*k merge, pred / new_lp / back / rows, hist_out, ended_count -- is
+ * dlsg_beam_select_ens's: with NS == NC == 0 the launch returns that call's bits, and with M == 1, w = {1} besides those of
+ * dlsg_beam_select_hist.  One workgroup per clip, one wave per row; no atomics but ended_count's; deterministic.  EINVAL for what
+ * dlsg_beam_select_ens refuses, NS outside 0..DLSG_EXCL_SHARED, NC outside 0..DLSG_EXCL_CLIP, a count above 0 with a NULL table,
+ * and, with a count above 0, P outside 1..DLSG_PHRASE_MAX. */
+#define DLSG_EXCL_SHARED 64   /* excluded entries shared by all clips */
+#define DLSG_EXCL_CLIP 32     /* excluded entries of one clip */
+int dlsg_beam_select_excl(const dlsg_beam_select_args* a, const float* const* logits, const int64_t* ld, const float* w,
+                          const float* logw, int M, int mode, const int64_t* hist_in, int64_t* hist_out, int L, int t,
+                          int no_repeat_ngram, int min_len, const int64_t* excl_shared, int NS, const int64_t* excl_clip, int NC,
+                          int P, void* stream);
 /* After the last step: the n <= k best beams of every clip by score = lp / len^alpha (computed in double, stored as float),
  * descending, ties to the lower beam.  hist (B*k, L) the final history, lp (B*k) the final log-probs; len = tokens up to and
  * including the first `end`, L without one.  Out: ids (B, n, L) int64, scores (B, n), lens (B, n) int64.  One wave per clip. */
