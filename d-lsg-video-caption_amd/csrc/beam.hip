@@ -1,5 +1,5 @@
 // The beam-search step (gfx950): dlsg_beam_select and its variants with a token history, lexical constraints (dynamic beam
-// allocation), Gumbel-perturbed selection (stochastic beam search), an ensemble of members, beam groups and exclusions, and dlsg_beam_finalize.  One workgroup per batch item, one wave per live
+// allocation), Gumbel-perturbed selection (stochastic beam search, also under exclusions), an ensemble of members, beam groups and exclusions, and dlsg_beam_finalize.  One workgroup per batch item, one wave per live
 // beam (BeamSearch.search, allennlp_beamsearch.py:140-260 with per_node_beam_size == beam_size): log-softmax of the beam's logits
 // row, its top-k classes (a finished beam offers <end> at log-prob 0 and nothing else), then the top-k of the k*k summed
 // candidates, back-pointers and the row indices that reorder the recurrent state.  Ties resolve to the lower index.  The step kernels are compositions of the
@@ -377,6 +377,52 @@ __global__ __launch_bounds__(64 * K) void beam_select_excl_kernel(const dlsg_bea
     if (w == 0) beam_flat_merge<K, true>(a, nbeam, lane, cand_lp, cand_cls, hist_in, hist_out, L, t);
 }
 
+// The stochastic step under exclusions (dlsg_beam_select_gumbel_excl): beam_select_gumbel_kernel with phase 0 and the ban list of
+// beam_select_excl_kernel.  beam_offer_gumbel looks every class up in the list, since its log-sum-exp leaves the banned classes out,
+// so the list by residue (beam_row_bans_excl) saves it more than it saves the beam step.  The keys, the conditioning in float64, the
+// merge and G_in / G_out are beam_select_gumbel_kernel's; NS = NC = 0 gives its bits.
+template <int K>
+__global__ __launch_bounds__(64 * K) void beam_select_gumbel_excl_kernel(const dlsg_beam_select_args a, const int64_t* __restrict__ hist_in,
+                                                                           int64_t* __restrict__ hist_out, int L, int t, int g, int min_len,
+                                                                           float tau, uint64_t seed, const uint64_t* __restrict__ seed_ptr,
+                                                                           uint32_t site_sample, const double* __restrict__ G_in,
+                                                                           double* __restrict__ G_out, const int64_t* __restrict__ excl_shared,
+                                                                           int NS, const int64_t* __restrict__ excl_clip, int NC, int P) {
+    __shared__ float cand_lp[K * K];
+    __shared__ int cand_cls[K * K];
+    __shared__ double cand_g[K * K];
+    __shared__ int hist[K][BEAM_MAXL];
+    __shared__ int ban[K][BEAM_BAN_EXCL];
+    __shared__ int sorted[K][BEAM_BAN_EXCL];
+    __shared__ int nban[K];
+    __shared__ int ex_s[EXCL_SLOTS * DLSG_PHRASE_MAX];
+    __shared__ int exn_s[EXCL_SLOTS];
+    if (seed_ptr) seed += *seed_ptr;
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const int nbeam = a.first ? 1 : K;
+    const int64_t row = (int64_t)blockIdx.x * K + w;
+    const bool ended = !a.first && a.last[row] == a.end;
+    const int tok = lane < t ? (int)hist_in[row * L + lane] : -1;     // (asked for before the tables: one wait for both)
+    beam_stage_exclusions(excl_shared, NS, excl_clip + (int64_t)blockIdx.x * (NC * P), NC, P, a.V, ex_s, exn_s);
+    int cnt;                                                  // what this lane scans: list[0 .. cnt)
+    const int* list = beam_row_bans_excl(tok, t, g, min_len, a.end, w < nbeam && !ended, ex_s, exn_s, NS + NC, P, hist, ban, nban, sorted,
+                                         cnt);
+    if (w < nbeam) {
+        const float base = a.first ? 0.f : a.last_lp[row];
+        const double T = a.first ? gumbel_noise64(seed, site_sample, (uint64_t)row * (uint64_t)a.V) : G_in[row];
+        if (ended) {
+            beam_offer_ended<K>(a, lane, base, cand_lp + w * K, cand_cls + w * K);
+            if (lane < K) cand_g[w * K + lane] = lane == 0 ? T : -INFINITY;
+        } else {
+            const uint64_t key0 = ((uint64_t)(t + 1) * ((uint64_t)a.B * K) + (uint64_t)row) * (uint64_t)a.V;
+            beam_offer_gumbel<K>(a.logits + row * a.ld, a.V, lane, 1.f / tau, seed, site_sample, key0, list, cnt, base, T,
+                                 cand_lp + w * K, cand_cls + w * K, cand_g + w * K);
+        }
+    }
+    __syncthreads();
+    if (w == 0) beam_flat_merge<K, true, double>(a, nbeam, lane, cand_g, cand_cls, hist_in, hist_out, L, t, cand_lp, G_out);
+}
+
 // The n best of each clip's k finished beams, by score = lp / len^alpha (double, stored as float), descending, ties to the lower
 // beam: one wave per clip.  len = tokens up to and including the first `end` of the beam's history row, L without one.
 __global__ __launch_bounds__(64) void beam_finalize_kernel(const int64_t* __restrict__ hist, const float* __restrict__ lp, int k, int L,
@@ -417,6 +463,11 @@ bool beam_ens_pack(const float* const* logits, const int64_t* ld, const float* w
     }
     e.M = M; e.mode = mode;
     return true;
+}
+// what the steps under exclusions ask of their two tables
+bool beam_excl_ok(const int64_t* excl_shared, int NS, const int64_t* excl_clip, int NC, int P) {
+    if (NS < 0 || NS > DLSG_EXCL_SHARED || NC < 0 || NC > DLSG_EXCL_CLIP || (NS > 0 && !excl_shared) || (NC > 0 && !excl_clip)) return false;
+    return NS + NC == 0 || (P >= 1 && P <= DLSG_PHRASE_MAX);
 }
 // launch(integral_constant<int, k>) for k = 1 .. BEAM_MAXK (checked by beam_args_ok)
 template <typename F>
@@ -523,12 +574,24 @@ extern "C" int dlsg_beam_select_excl(const dlsg_beam_select_args* a, const float
     if (!beam_hist_ok(a, hist_in, hist_out, L, t, no_repeat_ngram, min_len) ||
         !beam_ens_pack(logits, ld, w, logw, M, mode, e))
         return DLSG_EINVAL;
-    if (NS < 0 || NS > DLSG_EXCL_SHARED || NC < 0 || NC > DLSG_EXCL_CLIP || (NS > 0 && !excl_shared) || (NC > 0 && !excl_clip))
-        return DLSG_EINVAL;
-    if (NS + NC > 0 && (P < 1 || P > DLSG_PHRASE_MAX)) return DLSG_EINVAL;
+    if (!beam_excl_ok(excl_shared, NS, excl_clip, NC, P)) return DLSG_EINVAL;
     if (a->B == 0) return DLSG_OK;
     if (NS + NC == 0) P = 1;
     BEAM_LAUNCH(beam_select_excl_kernel, e, hist_in, hist_out, L, t, no_repeat_ngram, min_len, excl_shared, NS, excl_clip, NC, P);
+    DLSG_CHECK_LAUNCH();
+    return DLSG_OK;
+}
+extern "C" int dlsg_beam_select_gumbel_excl(const dlsg_beam_select_args* a, const int64_t* hist_in, int64_t* hist_out, int L, int t,
+                                            int no_repeat_ngram, int min_len, float temperature, uint64_t seed, const uint64_t* seed_ptr,
+                                            uint32_t site_sample, const double* G_in, double* G_out, const int64_t* excl_shared, int NS,
+                                            const int64_t* excl_clip, int NC, int P, void* stream) {
+    if (!beam_hist_ok(a, hist_in, hist_out, L, t, no_repeat_ngram, min_len)) return DLSG_EINVAL;
+    if (!(temperature > 0.f) || !G_out || (t > 0 && (!G_in || G_in == G_out))) return DLSG_EINVAL;     // (NaN fails the comparison)
+    if (!beam_excl_ok(excl_shared, NS, excl_clip, NC, P)) return DLSG_EINVAL;
+    if (a->B == 0) return DLSG_OK;
+    if (NS + NC == 0) P = 1;
+    BEAM_LAUNCH(beam_select_gumbel_excl_kernel, hist_in, hist_out, L, t, no_repeat_ngram, min_len, temperature, seed, seed_ptr,
+                site_sample, G_in, G_out, excl_shared, NS, excl_clip, NC, P);
     DLSG_CHECK_LAUNCH();
     return DLSG_OK;
 }

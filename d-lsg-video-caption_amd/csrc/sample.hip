@@ -1,7 +1,8 @@
 // The kernels that choose the next word from a row of logits and write its embedding (gfx950), one workgroup of 256 per row, each
 // a composition of the phases of wordpick.hpp: dlsg_argmax (greedy), dlsg_select_embed (scheduled sampling: the caption's word or
 // the greedy one), dlsg_sample_embed (Gumbel-max draw with its log-prob) and dlsg_sample_filter_embed, the draw behind a
-// repeated-n-gram ban, a minimum length, top-k and nucleus (top-p) truncation.  The filtered step holds the row's tempered logits in
+// repeated-n-gram ban, a minimum length, top-k and nucleus (top-p) truncation, and dlsg_sample_excl_embed, that step's body once more
+// with the bans of the exclusion tables (beam.hpp) in the row's list.  The filtered step holds the row's tempered logits in
 // LDS and finds the two thresholds without sorting: a descent over an order-preserving uint32 image of the float, two bits per
 // round, each round one pass over the candidates still undecided and one fixed-order block reduction (an integer count for top-k,
 // a float mass for top-p).  No atomics anywhere: two launches, or an eager launch and a graph replay, give the same bits.
@@ -183,15 +184,28 @@ __global__ __launch_bounds__(256) void sample_embed_kernel(const float* __restri
     embed_row(E, chosen, out, ldo, W, r, p, seed, site_word, row0, blockDim.x);
 }
 
+// The exclusion tables of the step under exclusions (dlsg_sample_excl_embed): beam.hpp's two tables; row r reads the own entries of
+// clip r / rows_per_clip
+struct SampleExcl {
+    const int64_t* shared;
+    const int64_t* clip;
+    int NS, NC, P, rows_per_clip;
+};
+
 // The filtered step.  hist: the row's earlier words, time-major: word i of row r at hist[i * hist_stride + r], i < t.
-__global__ __launch_bounds__(SF_THREADS) void sample_filter_embed_kernel(
+// EXCL: the step under exclusions -- phase 0 stages the two tables in LDS (beam_stage_exclusions), the history row is loaded whenever
+// an entry can look at it, and wave 0 puts the last words of the matching entries behind the list of beam_ban_list
+// (beam_ban_exclusions); everything behind the list is the one body.  Without EXCL `e` is not looked at.
+template <bool EXCL>
+__device__ __forceinline__ void sample_filter_embed_body(
     const float* __restrict__ logits, int64_t ld, int V, float tau, const float* __restrict__ E, int64_t* __restrict__ ids_out,
     float* __restrict__ out, int64_t ldo, int W, float* __restrict__ logp, int64_t* __restrict__ lens, int t, int64_t end_id, float p,
     uint64_t seed, uint32_t site_word, uint32_t site_sample, int64_t row0, const uint64_t* seed_ptr, int top_k, float top_p,
-    int min_len, int g, const int64_t* hist, int64_t hist_stride, int32_t* __restrict__ kept) {
+    int min_len, int g, const int64_t* hist, int64_t hist_stride, int32_t* __restrict__ kept, const SampleExcl& e) {
     extern __shared__ float zs[];                            // V floats: the threads' candidate lists (descend)
     __shared__ Red red;
-    __shared__ int hs[SF_MAXL], ban[SF_MAXL + 1], nban_s;
+    __shared__ int hs[SF_MAXL], ban[EXCL ? BEAM_BAN_EXCL : SF_MAXL + 1], nban_s;
+    __shared__ int ex_s[EXCL ? EXCL_SLOTS * DLSG_PHRASE_MAX : 1], exn_s[EXCL ? EXCL_SLOTS : 1];
     __shared__ float bv[4], bm[4], bs[4];
     __shared__ int bi[4], bn[4];
     __shared__ int64_t chosen;
@@ -202,9 +216,22 @@ __global__ __launch_bounds__(SF_THREADS) void sample_filter_embed_kernel(
     int par = 0;
 
     // ---- the classes this row may not choose: the beam search's rule (beam_ban_list, beam.hpp) on the row's own words
-    if (g > 0 && t >= g && tid < SF_MAXL) hs[tid] = tid < t ? (int)hist[(int64_t)tid * hist_stride + r] : -1;
-    __syncthreads();
-    if (w == 0) beam_ban_list(hs, t, g, min_len, (int)end_id, ban, &nban_s);
+    if constexpr (EXCL) {
+        const int NE = e.NS + e.NC;
+        const bool need = ((g > 0 && t >= g) || (NE > 0 && t >= 1)) && tid < SF_MAXL;
+        const int tok = need && tid < t ? (int)hist[(int64_t)tid * hist_stride + r] : -1;   // (asked for before the tables: one wait)
+        beam_stage_exclusions(e.shared, e.NS, e.clip + (int64_t)(r / e.rows_per_clip) * (e.NC * e.P), e.NC, e.P, V, ex_s, exn_s);
+        if (need) hs[tid] = tok;
+        __syncthreads();
+        if (w == 0) {
+            beam_ban_list(hs, t, g, min_len, (int)end_id, ban, &nban_s);
+            beam_ban_exclusions(hs, t, ex_s, exn_s, NE, e.P, ban, &nban_s);
+        }
+    } else {
+        if (g > 0 && t >= g && tid < SF_MAXL) hs[tid] = tid < t ? (int)hist[(int64_t)tid * hist_stride + r] : -1;
+        __syncthreads();
+        if (w == 0) beam_ban_list(hs, t, g, min_len, (int)end_id, ban, &nban_s);
+    }
     __syncthreads();
     const int nban = nban_s;
 
@@ -278,8 +305,33 @@ __global__ __launch_bounds__(SF_THREADS) void sample_filter_embed_kernel(
     embed_row(E, chosen, out, ldo, W, r, p, seed, site_word, row0, SF_THREADS);
 }
 
+__global__ __launch_bounds__(SF_THREADS) void sample_filter_embed_kernel(
+    const float* __restrict__ logits, int64_t ld, int V, float tau, const float* __restrict__ E, int64_t* __restrict__ ids_out,
+    float* __restrict__ out, int64_t ldo, int W, float* __restrict__ logp, int64_t* __restrict__ lens, int t, int64_t end_id, float p,
+    uint64_t seed, uint32_t site_word, uint32_t site_sample, int64_t row0, const uint64_t* seed_ptr, int top_k, float top_p,
+    int min_len, int g, const int64_t* hist, int64_t hist_stride, int32_t* __restrict__ kept) {
+    sample_filter_embed_body<false>(logits, ld, V, tau, E, ids_out, out, ldo, W, logp, lens, t, end_id, p, seed, site_word, site_sample,
+                                    row0, seed_ptr, top_k, top_p, min_len, g, hist, hist_stride, kept, SampleExcl{});
+}
+
+// The filtered step under exclusions (dlsg_sample_excl_embed): the same body with the tables' bans in the row's list.
+__global__ __launch_bounds__(SF_THREADS) void sample_excl_embed_kernel(
+    const float* __restrict__ logits, int64_t ld, int V, float tau, const float* __restrict__ E, int64_t* __restrict__ ids_out,
+    float* __restrict__ out, int64_t ldo, int W, float* __restrict__ logp, int64_t* __restrict__ lens, int t, int64_t end_id, float p,
+    uint64_t seed, uint32_t site_word, uint32_t site_sample, int64_t row0, const uint64_t* seed_ptr, int top_k, float top_p,
+    int min_len, int g, const int64_t* hist, int64_t hist_stride, int32_t* __restrict__ kept, const SampleExcl e) {
+    sample_filter_embed_body<true>(logits, ld, V, tau, E, ids_out, out, ldo, W, logp, lens, t, end_id, p, seed, site_word, site_sample,
+                                   row0, seed_ptr, top_k, top_p, min_len, g, hist, hist_stride, kept, e);
+}
+
 // what the two sampled steps ask of their common arguments
 bool sample_args_ok(int V, int W, float temperature) { return V >= 1 && W >= 0 && temperature >= 0.f; }
+// and the two filtered steps of theirs; reads_hist: something looks at the row's earlier words from step 1 on
+bool sample_filter_args_ok(int V, int W, float temperature, int top_k, float top_p, int min_len, int no_repeat_ngram, int t, int rows,
+                           bool reads_hist, const int64_t* hist, int64_t hist_stride) {
+    return sample_args_ok(V, W, temperature) && V <= DLSG_SAMPLE_FILTER_MAXV && top_k >= 0 && top_p > 0.f && top_p <= 1.f &&
+           min_len >= 0 && no_repeat_ngram >= 0 && t >= 0 && t < SF_MAXL && !(reads_hist && t > 0 && (!hist || hist_stride < rows));
+}
 #define ST(s) reinterpret_cast<hipStream_t>(s)
 
 }  // namespace
@@ -317,8 +369,7 @@ extern "C" int dlsg_sample_filter_embed(const float* logits, int64_t ld, int V, 
                                         const uint64_t* seed_ptr, int top_k, float top_p, int min_len, int no_repeat_ngram,
                                         const int64_t* hist, int64_t hist_stride, int32_t* kept, void* stream) {
     if (rows == 0) return DLSG_OK;
-    if (!sample_args_ok(V, W, temperature) || V > DLSG_SAMPLE_FILTER_MAXV || top_k < 0 || !(top_p > 0.f && top_p <= 1.f) ||
-        min_len < 0 || no_repeat_ngram < 0 || t < 0 || t >= SF_MAXL || (no_repeat_ngram > 0 && t > 0 && (!hist || hist_stride < rows)))
+    if (!sample_filter_args_ok(V, W, temperature, top_k, top_p, min_len, no_repeat_ngram, t, rows, no_repeat_ngram > 0, hist, hist_stride))
         return DLSG_EINVAL;
     static std::once_flag once;
     static hipError_t attr_rc = hipSuccess;
@@ -330,6 +381,36 @@ extern "C" int dlsg_sample_filter_embed(const float* logits, int64_t ld, int V, 
     hipLaunchKernelGGL(sample_filter_embed_kernel, dim3(rows), dim3(SF_THREADS), (size_t)V * 4, ST(stream),
                        logits, ld, V, temperature, E, ids_out, out, ldo, W, logp, lens, t, end_id, p, seed, site_word, site_sample,
                        row0, seed_ptr, top_k, top_p, min_len, no_repeat_ngram, hist, hist_stride, kept);
+    DLSG_CHECK_LAUNCH();
+    return DLSG_OK;
+}
+
+extern "C" int dlsg_sample_excl_embed(const float* logits, int64_t ld, int V, float temperature, const float* E, int64_t* ids_out,
+                                      float* out, int64_t ldo, int W, float* logp, int64_t* lens, int t, int64_t end_id, int rows,
+                                      float p, uint64_t seed, uint32_t site_word, uint32_t site_sample, int64_t row0,
+                                      const uint64_t* seed_ptr, int top_k, float top_p, int min_len, int no_repeat_ngram,
+                                      const int64_t* hist, int64_t hist_stride, int32_t* kept, const int64_t* excl_shared, int NS,
+                                      const int64_t* excl_clip, int NC, int P, int rows_per_clip, void* stream) {
+    if (rows == 0) return DLSG_OK;
+    if (NS < 0 || NS > DLSG_EXCL_SHARED || NC < 0 || NC > DLSG_EXCL_CLIP || (NS > 0 && !excl_shared) || (NC > 0 && !excl_clip))
+        return DLSG_EINVAL;
+    if (NS + NC > 0 && (P < 1 || P > DLSG_PHRASE_MAX)) return DLSG_EINVAL;
+    if (rows_per_clip < 1 || rows % rows_per_clip != 0) return DLSG_EINVAL;
+    if (!sample_filter_args_ok(V, W, temperature, top_k, top_p, min_len, no_repeat_ngram, t, rows, no_repeat_ngram > 0 || NS + NC > 0, hist,
+                               hist_stride))
+        return DLSG_EINVAL;
+    if (NS + NC == 0) P = 1;
+    static std::once_flag once;
+    static hipError_t attr_rc = hipSuccess;
+    std::call_once(once, [] {
+        attr_rc = hipFuncSetAttribute(reinterpret_cast<const void*>(&sample_excl_embed_kernel),
+                                      hipFuncAttributeMaxDynamicSharedMemorySize, DLSG_SAMPLE_FILTER_MAXV * 4);
+    });
+    if (attr_rc != hipSuccess) return DLSG_ELAUNCH;
+    const SampleExcl e{NS > 0 ? excl_shared : nullptr, NC > 0 ? excl_clip : nullptr, NS, NC, P, rows_per_clip};
+    hipLaunchKernelGGL(sample_excl_embed_kernel, dim3(rows), dim3(SF_THREADS), (size_t)V * 4, ST(stream),
+                       logits, ld, V, temperature, E, ids_out, out, ldo, W, logp, lens, t, end_id, p, seed, site_word, site_sample,
+                       row0, seed_ptr, top_k, top_p, min_len, no_repeat_ngram, hist, hist_stride, kept, e);
     DLSG_CHECK_LAUNCH();
     return DLSG_OK;
 }

@@ -20,7 +20,8 @@ constraint's alternatives), one check of a packed tensor (`_check_packed`) and o
 rank in the step it launches and in how `_constraints_met` counts.
 `beam_nbest(exclude=...)` and `ensemble_nbest(exclude=...)` are those searches under exclusions -- words, phrases and endings a caption
 must not contain (`pack_exclusions`): `beam_select_excl` adds the last word of every excluded entry that a beam's history leads up to
-to the beam's ban list; `exclusions_hit` counts what a caption contains of them.
+to the beam's ban list; `exclusions_hit` counts what a caption contains of them.  `stochastic_nbest(exclude=...)` draws its captions
+under the same tables (`beam_select_gumbel_excl`), the model renormalised over the words that are left, as its other bans do.
 """
 import collections
 
@@ -309,7 +310,7 @@ def check_stochastic_options(n, L, V, temperature, min_len=0, no_repeat_ngram=0,
 
 @torch.no_grad()
 def stochastic_nbest(model, visual_feats, region_feats, n=5, temperature=1.0, seed=None, min_len=0, no_repeat_ngram=0,
-                     return_threshold=False):
+                     return_threshold=False, exclude=None):
     """Stochastic beam search (Kool, van Hoof & Welling 2019): n DISTINCT captions per clip that are an exact ordered sample without
     replacement from softmax(logits / temperature), renormalised over the words min_len and no_repeat_ngram leave -- row 0 is
     distributed as one ordinary sample, rows 0 .. m-1 as a without-replacement sample of size m.  Returns (ids (B, n, L) int64
@@ -319,10 +320,17 @@ def stochastic_nbest(model, visual_feats, region_feats, n=5, temperature=1.0, se
     estimator of any expectation under the model.
     The search is `beam_nbest`'s -- eval-mode decode, state ping-pong, one select launch per word, all L steps launched, nothing read
     back -- on `beam_select_gumbel`, whose noise is `sample`'s: with n = 1 the words are those of `model.eval().sample(n=1,
-    temperature, seed)`.  seed None draws the model's next seed; it may be a device word (a captured graph)."""
+    temperature, seed)`.  seed None draws the model's next seed; it may be a device word (a captured graph).
+    exclude: the `Exclusions` of `pack_exclusions` -- the step is `beam_select_gumbel_excl`, whose banned words are those of the
+    two other bans and the last words of the entries a beam's history leads up to; the model is renormalised over the words that
+    are left, as with the other two (the beam search under exclusions does not renormalise).  None, or two empty tables, launches
+    what the call launched without the keyword."""
     dec = model.decoder
     L = dec.max_words
     k = check_stochastic_options(n, L, dec.vocab_size, temperature, min_len, no_repeat_ngram, return_threshold)
+    shared, per_clip = (None, None) if exclude is None else check_exclusions(exclude, visual_feats.shape[0], visual_feats.device)
+    if shared is not None or per_clip is not None:
+        require_excl_step(model.ops, 'beam_select_gumbel_excl')
     if seed is None:
         seed = model.next_seed()                                       # (before the encoder draws its own)
     G = []                                                             # the beams' perturbed values (2, R), ping-pong
@@ -330,8 +338,11 @@ def stochastic_nbest(model, visual_feats, region_feats, n=5, temperature=1.0, se
     def select(t, logits, step):
         if t == 0:                                                     # (beside the search's buffers, behind the encoder)
             G.append(torch.zeros(2, step[0].shape[0], dtype=torch.float64, device=step[0].device))
-        model.ops.beam_select_gumbel(logits[0], *step, G[0][t % 2], G[0][(t + 1) % 2], temperature=float(temperature), seed=seed,
-                                     site_sample=E.SITE_SAMPLE, no_repeat_ngram=no_repeat_ngram, min_len=min_len)
+        options = dict(temperature=float(temperature), seed=seed, site_sample=E.SITE_SAMPLE, no_repeat_ngram=no_repeat_ngram, min_len=min_len)
+        if shared is None and per_clip is None:
+            model.ops.beam_select_gumbel(logits[0], *step, G[0][t % 2], G[0][(t + 1) % 2], **options)
+        else:
+            model.ops.beam_select_gumbel_excl(logits[0], *step, G[0][t % 2], G[0][(t + 1) % 2], shared, per_clip, **options)
     hist, lps = _hist_search([model], k, visual_feats, region_feats, select)
     ids = hist.view(-1, k, L)
     B = ids.shape[0]
@@ -605,6 +616,19 @@ def pack_exclusions(vocab, words=(), phrases=(), bad_endings=False, suppress_unk
     return Exclusions(sh, pc)
 
 
+class ExcludeNotCovered(TypeError, ValueError):
+    """`exclude` where it cannot be honoured: given to a search that does not cover exclusions, or to a model whose ops object has
+    no step under exclusions.  A ValueError that names the combination -- and a TypeError, which is what these calls raised while they
+    took no such keyword, so that code written against them keeps catching it."""
+
+
+def require_excl_step(ops, step):
+    """ExcludeNotCovered unless `ops` implements `step`, the launch a decode under exclusions makes at every word (HipOps does; an
+    ops object written before the step existed does not): raised before the encoder runs, not as an AttributeError at the first word"""
+    if not hasattr(ops, step):
+        raise ExcludeNotCovered('exclude: %s has no %s, the word step under exclusions' % (type(ops).__name__, step))
+
+
 def check_exclusions(exclude, B, device, num_groups=1):
     """ValueError for an `exclude` the n-best search cannot run on B clips on `device`: not an `Exclusions`, a table of the wrong
     dtype, rank, device or size, a per-clip table whose first dimension is not the batch, two tables of different P, or together
@@ -674,7 +698,7 @@ def exclusions_hit(ids, lens, exclusions, vocab_size=None):
 
 @torch.no_grad()
 def constrained_nbest(model, visual_feats, region_feats, constraints, n_best=None, length_penalty=0.0, no_repeat_ngram=0, min_len=0,
-                      beam_size=None, return_met=False):
+                      beam_size=None, return_met=False, exclude=None):
     """Lexically constrained beam search (dynamic beam allocation, Post & Vilar 2018): `beam_nbest` whose captions must contain a
     word of every constraint of their clip.  constraints: the (B, C, W) int64 tensor of `pack_constraints` on the clips' device
     (C sets of W alternative word ids per clip, -1 or an id outside the vocabulary for padding), or the per-clip lists, which are
@@ -692,7 +716,10 @@ def constrained_nbest(model, visual_feats, region_feats, constraints, n_best=Non
     C_b constraints of up to n_max_b words meet within C_b * n_max_b words (no_repeat_ngram = 0, finite logits), which with <end>
     must fit into max_words.  With an n-gram ban the next word of a phrase can be banned although the phrase has not occurred: the
     search is then best effort, and a beam that cannot finish runs to max_words without <end>.  The rows of a clip are ordered by
-    `phrases_met` of the final ids, most first, then by score."""
+    `phrases_met` of the final ids, most first, then by score.
+    exclude: not covered -- anything but None is an `ExcludeNotCovered`, a ValueError (a required word could be an excluded one)."""
+    if exclude is not None:
+        raise ExcludeNotCovered('exclude and constraints: exclusions are not covered in constrained beam search')
     dec = model.decoder
     k, L = dec.beam_size if beam_size is None else beam_size, dec.max_words
     B, dev = visual_feats.shape[0], visual_feats.device

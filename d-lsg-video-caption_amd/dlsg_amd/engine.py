@@ -1121,7 +1121,25 @@ def check_sample_options(L, top_k=0, top_p=1.0, min_len=0, no_repeat_ngram=0, vo
     return on
 
 
-def dec_sample(ops, dec, mems, sv, L, training, seed, temperature, top_k=0, top_p=1.0, min_len=0, no_repeat_ngram=0):
+def sample_exclusions(exclude, clips, device, L, vocab_size=None):
+    """the two tables of `exclude` for a sampled decode of `clips` clips (`beam.check_exclusions`), or None when there is nothing to
+    exclude -- exclude None, or an `Exclusions` whose tables are both absent or empty; ValueError for a table the step cannot take,
+    and for a history or a vocabulary the step under exclusions does not hold"""
+    if exclude is None:
+        return None
+    from .beam import check_exclusions
+    shared, per_clip = check_exclusions(exclude, clips, device)
+    if shared is None and per_clip is None:
+        return None
+    if L > SAMPLE_FILTER_MAXL:
+        raise ValueError('sampling under exclusions keeps at most %d words of history, max_words is %d' % (SAMPLE_FILTER_MAXL, L))
+    if vocab_size is not None and vocab_size > SAMPLE_FILTER_MAXV:
+        raise ValueError('sampling under exclusions holds a row of logits in LDS: vocabulary %d > %d' % (vocab_size, SAMPLE_FILTER_MAXV))
+    return shared, per_clip
+
+
+def dec_sample(ops, dec, mems, sv, L, training, seed, temperature, top_k=0, top_p=1.0, min_len=0, no_repeat_ngram=0, exclude=None,
+               rows_per_clip=1):
     """Sampled decoding for self-critical training: step t feeds a word drawn from softmax(logits_t / temperature) to step t+1
     (`sample_embed`, Gumbel noise keyed by (seed, SITE_SAMPLE, row); temperature 0 is greedy).  Fills IDS (slots 1..L: the
     words), LOGP (L, B) their log-probabilities and LENS (B,): first <end> position + 1, else L.  The word-dropout rows are those
@@ -1129,18 +1147,31 @@ def dec_sample(ops, dec, mems, sv, L, training, seed, temperature, top_k=0, top_
     synchronisation: capturable, the seed may be a device word.
     With one of the controls on (top_k, top_p, min_len, no_repeat_ngram) the step draws with `sample_filter_embed` instead --
     from what the bans, top-k and the nucleus leave, LOGP under that truncated distribution -- and KEPT (L, B) int32 holds the
-    number of words each draw chose from.  With all of them off the launches are the ones above."""
+    number of words each draw chose from.  With all of them off the launches are the ones above.
+    exclude: an `Exclusions` (beam.pack_exclusions) with at least one entry -- the step is `sample_excl_embed`, whatever the other
+    controls are: the last word of an entry is banned behind the entry's other words, before top_k and top_p, renormalised like
+    the other bans; row r reads the per-clip entries of clip r // rows_per_clip.  None, or two empty tables: the launches above."""
     filtered = check_sample_options(L, top_k, top_p, min_len, no_repeat_ngram, dec.vocab_size)
     s, ref, B, E, ids, pw = dec_begin(ops, dec, mems, sv, L, training, seed)
+    if rows_per_clip < 1 or B % rows_per_clip:
+        raise ValueError('dec_sample: %d rows are not clips of rows_per_clip = %r rows' % (B, rows_per_clip))
+    tables = sample_exclusions(exclude, B // rows_per_clip, ref.device, L, dec.vocab_size)
     s['LOGP'] = _empty(ref, L, B)
     s['LENS'] = torch.full((B,), L, dtype=torch.int64, device=ref.device)
-    if filtered:
+    if filtered or tables is not None:
         s['KEPT'] = torch.empty(L, B, dtype=torch.int32, device=ref.device)
     end = dec.vocab('<end>')
     ops.embed_fwd(E, ids[0], s['WE'][0], p=pw, seed=seed, site=SITE_WORD, row0=0)
     for t in range(L):
         dec_step(ops, dec, s, t, ref, training, seed, B)
         dec_logits(ops, dec, s, t, t + 1)
+        if tables is not None:
+            ops.sample_excl_embed(s['LOGITS'][t], E, ids[t + 1], s['WE'][t + 1], s['LOGP'][t], s['LENS'], t, end,
+                                  temperature=temperature, p=pw, seed=seed, site=SITE_WORD, site_sample=SITE_SAMPLE,
+                                  row0=(t + 1) * B, top_k=top_k, top_p=top_p, min_len=min_len, no_repeat_ngram=no_repeat_ngram,
+                                  hist=ids[1:], kept=s['KEPT'][t], excl_shared=tables[0], excl_clip=tables[1],
+                                  rows_per_clip=rows_per_clip)
+            continue
         if filtered:
             ops.sample_filter_embed(s['LOGITS'][t], E, ids[t + 1], s['WE'][t + 1], s['LOGP'][t], s['LENS'], t, end,
                                     temperature=temperature, p=pw, seed=seed, site=SITE_WORD, site_sample=SITE_SAMPLE,

@@ -178,16 +178,19 @@ class SampleGraph(_SeededGraph):
     `model.sample(frames, regions, n, temperature, seed=s)`.  Outputs are static buffers, valid until the next replay.
     share_encoder=True captures `model.sample(..., share_encoder=True)` instead: the encoder on the B clips, their proposals
     fanned out in-graph (`rows_repeat`), the sampled decode steps on B*n rows; a replay with seed s gives that call's bits.
-    top_k, top_p, min_len, no_repeat_ngram, return_kept: the sampling controls of `CapGnnModel.sample`, fixed at capture."""
+    top_k, top_p, min_len, no_repeat_ngram, return_kept: the sampling controls of `CapGnnModel.sample`, fixed at capture.
+    exclude=Exclusions (`pack_exclusions`): kept as `graph.exclude`, the graph's own copy of the two tables, as NBestBeamGraph keeps
+    it: `graph.exclude.shared.copy_(new)` changes what the next replay bans; the tables' shapes are fixed at capture."""
 
     def __init__(self, model, frames, regions, n=1, temperature=1.0, share_encoder=False, top_k=0, top_p=1.0, min_len=0,
-                 no_repeat_ngram=0, return_kept=False):
+                 no_repeat_ngram=0, return_kept=False, exclude=None):
         self.n, self.temperature, self.share_encoder = n, temperature, bool(share_encoder)
-        self.options = dict(top_k=top_k, top_p=top_p, min_len=min_len, no_repeat_ngram=no_repeat_ngram, return_kept=return_kept)
+        self.options, self.exclude, self._draw = _held_exclusions(dict(
+            top_k=top_k, top_p=top_p, min_len=min_len, no_repeat_ngram=no_repeat_ngram, return_kept=return_kept, exclude=exclude))
         super().__init__(model, frames, regions)
 
     def _run(self):
-        return self.model.sample(self.frames, self.regions, self.n, self.temperature, self.seed, self.share_encoder, **self.options)
+        return self.model.sample(self.frames, self.regions, self.n, self.temperature, self.seed, self.share_encoder, **self._draw)
 
 
 class BeamGraph(_InferenceGraph):
@@ -225,14 +228,16 @@ class StochasticBeamGraph(_SeededGraph):
     """hipGraph-captured `model.sample_without_replacement(frames, regions, n, temperature, **options)` for one batch shape: encoder
     and all max_words steps of stochastic beam search.  The seed is read from a device word, like SampleGraph's, so every replay
     draws afresh; a replay with seed s gives the bits of the eager call with seed=s.  options: min_len, no_repeat_ngram,
-    return_threshold, fixed at capture.  Outputs are static buffers, valid until the next replay; nothing synchronises."""
+    return_threshold, fixed at capture.  Outputs are static buffers, valid until the next replay; nothing synchronises.
+    exclude=Exclusions: kept as `graph.exclude`, as NBestBeamGraph keeps it."""
 
     def __init__(self, model, frames, regions, n=5, temperature=1.0, **options):
-        self.n, self.temperature, self.options = n, temperature, options
+        self.n, self.temperature = n, temperature
+        self.options, self.exclude, self._search = _held_exclusions(options)
         super().__init__(model, frames, regions)
 
     def _run(self):
-        return self.model.sample_without_replacement(self.frames, self.regions, self.n, self.temperature, self.seed, **self.options)
+        return self.model.sample_without_replacement(self.frames, self.regions, self.n, self.temperature, self.seed, **self._search)
 
 
 class ConstrainedBeamGraph(_InferenceGraph):

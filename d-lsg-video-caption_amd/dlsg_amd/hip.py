@@ -683,6 +683,22 @@ class HipOps(object):
         self._check(self.lib.dlsg_beam_select_excl(C.byref(a), *members, int(mode), *hist, *tables, self._stream()),
                     'dlsg_beam_select_excl')
 
+    def beam_select_gumbel_excl(self, logits, last, last_lp, pred, new_lp, back, rows, k, end, hist_in, hist_out, t, G_in, G_out,
+                                excl_shared=None, excl_clip=None, temperature=1.0, seed=0, site_sample=0, no_repeat_ngram=0, min_len=0,
+                                ended_count=None):
+        """`beam_select_gumbel` with the exclusion tables of `beam_select_excl`: the last words of the entries a live row's history
+        leads up to join its ban list, and the log-probs are renormalised over the words that are left, as that step's other bans
+        are (see include/dlsg.h).  Both tables None or empty: the bits of `beam_select_gumbel`."""
+        R, V = logits.shape
+        for G in (G_in, G_out):
+            assert G.dtype == torch.float64 and G.is_contiguous() and G.numel() == R, (G.dtype, G.shape)
+        a, hist = self._hist_step(R, V, last, last_lp, pred, new_lp, back, rows, k, end, hist_in, hist_out, t, no_repeat_ngram, min_len,
+                                  ended_count, logits)
+        tables = self._excl_tables(excl_shared, excl_clip, R // k, logits.device)
+        sd, sp = _seed(seed)
+        self._check(self.lib.dlsg_beam_select_gumbel_excl(C.byref(a), *hist, f32(temperature), u64(sd), sp, u32(site_sample), _p(G_in),
+                                                          _p(G_out), *tables, self._stream()), 'dlsg_beam_select_gumbel_excl')
+
     def beam_finalize(self, hist, lp, k, end, alpha, ids, scores, lens):
         """the n = ids.shape[1] best of each clip's k beams by lp / len^alpha: ids (B, n, L), scores (B, n), lens (B, n)."""
         R, L = hist.shape
@@ -1254,6 +1270,30 @@ class HipOps(object):
             *args, int(top_k), f32(top_p), int(min_len), int(no_repeat_ngram), _p(hist) if hist is not None else None,
             i64(hist.stride(0) if hist is not None else 0), _p(kept) if kept is not None else None, self._stream()),
             'sample_filter_embed')
+
+    def sample_excl_embed(self, logits, E, ids_out, out, logp, lens, t, end_id, temperature=1.0, p=0.0, seed=0, site=0, site_sample=0,
+                          row0=0, top_k=0, top_p=1.0, min_len=0, no_repeat_ngram=0, hist=None, kept=None, excl_shared=None,
+                          excl_clip=None, rows_per_clip=1):
+        """`sample_filter_embed` under the exclusion tables of `beam_select_excl`: excl_shared (NS <= 64, P) int64 for every row,
+        excl_clip (rows / rows_per_clip, NC <= 32, P) of which row r reads clip r // rows_per_clip's; the last word of an entry is
+        banned behind its other words, before top_k and top_p, and logp is renormalised over the words that are left (see
+        include/dlsg.h).  hist as there, needed from t = 1 on with an entry.  Both tables None or empty: the bits of
+        `sample_filter_embed`."""
+        rows, V = logits.shape
+        if V > SAMPLE_FILTER_MAXV:
+            raise ValueError('sample_excl_embed holds a row of logits in LDS: vocabulary %d > %d' % (V, SAMPLE_FILTER_MAXV))
+        if rows_per_clip < 1 or rows % rows_per_clip:
+            raise ValueError('sample_excl_embed: %d rows are not clips of rows_per_clip = %r rows' % (rows, rows_per_clip))
+        args = self._sample_args(logits, E, ids_out, out, logp, lens, t, end_id, temperature, p, seed, site, site_sample, row0)
+        assert kept is None or (kept.dtype == torch.int32 and kept.numel() == rows and kept.is_contiguous())
+        tables = self._excl_tables(excl_shared, excl_clip, rows // rows_per_clip, logits.device)
+        if (no_repeat_ngram > 0 or tables[1] + tables[3] > 0) and t > 0:
+            assert hist is not None and hist.dtype == torch.int64 and hist.shape[0] >= t and hist.shape[1] == rows and \
+                hist.stride(1) == 1, 'hist: the rows\' earlier words, (>= t, rows) int64'
+        self._check(self.lib.dlsg_sample_excl_embed(
+            *args, int(top_k), f32(top_p), int(min_len), int(no_repeat_ngram), _p(hist) if hist is not None else None,
+            i64(hist.stride(0) if hist is not None else 0), _p(kept) if kept is not None else None, *tables, int(rows_per_clip),
+            self._stream()), 'sample_excl_embed')
 
     def copy2d(self, src, dst, accum=False):
         rows, n = src.shape

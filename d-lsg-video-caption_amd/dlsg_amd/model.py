@@ -259,7 +259,7 @@ class _HipModel(_ArenaModule):
         return self._public(out[0], out[1:3], out[3])
 
     def sample(self, visual_feats, region_feats, n=1, temperature=1.0, seed=None, share_encoder=False, top_k=0, top_p=1.0,
-               min_len=0, no_repeat_ngram=0, return_kept=False):
+               min_len=0, no_repeat_ngram=0, return_kept=False, exclude=None):
         raise NotImplementedError('sampled decoding (self-critical training) is implemented for CapGnnModel only')
 
     def beam_search(self, visual_feats, region_feats, beam_size=None, n_best=None, length_penalty=0.0, no_repeat_ngram=0, min_len=0,
@@ -279,20 +279,22 @@ class _HipModel(_ArenaModule):
                            exclude=exclude)
 
     def sample_without_replacement(self, visual_feats, region_feats, n=5, temperature=1.0, seed=None, min_len=0, no_repeat_ngram=0,
-                                   return_threshold=False):
+                                   return_threshold=False, exclude=None):
         """n (at most 8) DISTINCT captions per clip, an exact ordered sample without replacement from softmax(logits /
         temperature) by stochastic beam search, entirely on the device: (ids (B, n, L) int64 padded with <end>, logp (B, n) float32
         the captions' log-probabilities, lens (B, n) int64 counting the <end>), rows in sampling order -- row 0 is distributed as
         one ordinary sample.  min_len, no_repeat_ngram as in `sample`: the model is renormalised over the words they leave.
         return_threshold=True (n at most 7) adds (gumbel (B, n) float64, kappa (B,) float64) for `dlsg_amd.importance_weights`.
+        exclude: the `Exclusions` of `dlsg_amd.pack_exclusions`, as in `beam_search` -- but here the model is renormalised over the
+        words the exclusions leave, like the other two bans, and the sample is one without replacement from that model.
         seed None draws the model's next seed, a given seed reproduces the draw.  The decode runs in eval mode whatever
         `self.training` is (`beam.stochastic_nbest`); nothing synchronises with the host."""
         from .beam import stochastic_nbest
         return stochastic_nbest(self, visual_feats, region_feats, n=n, temperature=temperature, seed=seed, min_len=min_len,
-                                no_repeat_ngram=no_repeat_ngram, return_threshold=return_threshold)
+                                no_repeat_ngram=no_repeat_ngram, return_threshold=return_threshold, exclude=exclude)
 
     def constrained_beam_search(self, visual_feats, region_feats, constraints, beam_size=None, n_best=None, length_penalty=0.0,
-                                no_repeat_ngram=0, min_len=0, return_met=False):
+                                no_repeat_ngram=0, min_len=0, return_met=False, exclude=None):
         """`beam_search` whose captions must contain given words (lexically constrained beam search by dynamic beam allocation).
         constraints: per clip a list of constraints, each a word, a word id or a list of alternatives of which one must appear
         (at most 8 constraints of 8 alternatives), or the (B, C, W) int64 device tensor `dlsg_amd.pack_constraints` makes of them.
@@ -303,10 +305,12 @@ class _HipModel(_ArenaModule):
         alternative phrases, a phrase a string, a tuple of words or ids, or one word, at most 4 words), or the (B, C, W, P) tensor
         `dlsg_amd.pack_phrases` makes, require phrases as contiguous words; met then counts the constraints with a phrase in the row
         (`dlsg_amd.phrases_met`).  C_b phrase constraints of up to n words need C_b * n + 1 <= max_words; with no_repeat_ngram the
-        next word of a phrase can be banned, the search is then best effort and a beam that cannot finish runs to max_words."""
+        next word of a phrase can be banned, the search is then best effort and a beam that cannot finish runs to max_words.
+        exclude: exclusions are not covered here; anything but None is a ValueError."""
         from .beam import constrained_nbest
         return constrained_nbest(self, visual_feats, region_feats, constraints, n_best=n_best, length_penalty=length_penalty,
-                                 no_repeat_ngram=no_repeat_ngram, min_len=min_len, beam_size=beam_size, return_met=return_met)
+                                 no_repeat_ngram=no_repeat_ngram, min_len=min_len, beam_size=beam_size, return_met=return_met,
+                                 exclude=exclude)
 
     def score(self, visual_feats, region_feats, ids, **options):
         """The log-probability of GIVEN captions under this model: `rescore.score_captions(self, ...)` -- ids (B, L) or (B, n, L)
@@ -517,7 +521,7 @@ class CapGnnModel(_HipModel):
 
     @torch.no_grad()
     def sample(self, visual_feats, region_feats, n=1, temperature=1.0, seed=None, share_encoder=False, top_k=0, top_p=1.0,
-               min_len=0, no_repeat_ngram=0, return_kept=False):
+               min_len=0, no_repeat_ngram=0, return_kept=False, exclude=None):
         """Draw n captions per clip from softmax(logits / temperature) (self-critical training; temperature 0 is greedy).
         Returns (ids (B*n, L) int64, logp (B*n, L) float32 log-probabilities of the drawn words, lens (B*n,) int64: first
         <end> position + 1, else L); clip b's samples are rows b*n .. b*n + n - 1.  The clips are repeated n times before the
@@ -533,20 +537,32 @@ class CapGnnModel(_HipModel):
         words; no_repeat_ngram = g > 0 -- no caption repeats a g-gram; top_k > 0 -- only the k likeliest words (ties at the k-th
         kept); top_p < 1 -- of those, the smallest set of likeliest words whose probability reaches top_p.  logp is then the
         log-probability under the truncated, renormalised distribution.  A word's Gumbel noise does not depend on the controls.
-        return_kept=True adds a fourth value, (B*n, L) int32: how many words each draw chose from (needs a control on)."""
+        return_kept=True adds a fourth value, (B*n, L) int32: how many words each draw chose from (needs a control on).
+        exclude: the `Exclusions` of `dlsg_amd.pack_exclusions` -- words and phrases no sample may contain, `<unk>`, bad endings, for
+        all clips (shared) or per clip (per_clip (B, NC, P): the B clips, not their B*n rows).  A word is banned for a row when it
+        would complete an entry whose earlier words are the row's last words; the bans join those of min_len and no_repeat_ngram,
+        come before top_k and top_p and renormalise like them (`dlsg_sample_excl_embed`; `beam_search` does not renormalise).  It is
+        a control of its own: the others may be off.  Words behind a row's first <end> are not part of its caption.  None, or
+        two empty tables, launches what the call launched without the keyword."""
         L = self.decoder.max_words
         filtered = E.check_sample_options(L, top_k, top_p, min_len, no_repeat_ngram, self.decoder.vocab_size)
-        if return_kept and not filtered:
-            raise ValueError('return_kept needs one of top_k, top_p, min_len, no_repeat_ngram switched on')
+        excluding = E.sample_exclusions(exclude, visual_feats.shape[0], visual_feats.device, L, self.decoder.vocab_size) is not None
+        if excluding:
+            from .beam import require_excl_step
+            require_excl_step(self.ops, 'sample_excl_embed')
+        if return_kept and not (filtered or excluding):
+            raise ValueError('return_kept needs one of top_k, top_p, min_len, no_repeat_ngram, exclude switched on')
         self.flatten_parameters_()
         if seed is None:
             seed = self.next_seed()
+        per_clip = int(n)               # rows of one clip, whichever form runs
         if not share_encoder:           # the clips repeated n times, then the shared form with one row per clip
             visual_feats, region_feats, n = expand_rows(visual_feats, n), expand_rows(region_feats, n), 1
         sv = {}
         _, mems = self._encoder_pass(visual_feats, region_feats, self.training, seed, sv, int(n))
         s = E.dec_sample(self.ops, self.decoder, list(mems), sv, L, self.training, seed, temperature, top_k=top_k, top_p=top_p,
-                         min_len=min_len, no_repeat_ngram=no_repeat_ngram)
+                         min_len=min_len, no_repeat_ngram=no_repeat_ngram, exclude=exclude if excluding else None,
+                         rows_per_clip=per_clip)
         out = s['IDS'][1:].t().contiguous(), s['LOGP'].t().contiguous(), s['LENS']
         return out + (s['KEPT'].t().contiguous(),) if return_kept else out
 

@@ -11,6 +11,7 @@ on-policy up to the tiling of the vocabulary product.
 import numpy as np
 import torch
 
+from .beam import check_exclusions
 from .engine import check_sample_options
 from .graphs import GreedyGraph, SampleGraph, expand_rows
 from .model import Trainer, _h2d
@@ -33,7 +34,12 @@ class SCSTTrainer(object):
     sample_options: a dict of `CapGnnModel.sample`'s sampling controls (top_k, top_p, min_len, no_repeat_ngram), forwarded to
     `sample` / `SampleGraph`: the captions are then drawn from the truncated policy (the `train_sample_method = top<k> / top<p>`
     recipe of the usual captioning toolkits).  The train pass is unchanged: it differentiates the FULL-softmax log-probabilities
-    of the words drawn from the truncated policy -- the usual, biased, estimator.  Without the keyword the step is the plain one."""
+    of the words drawn from the truncated policy -- the usual, biased, estimator.  Without the keyword the step is the plain one.
+    sample_options may also hold exclude=X, an `Exclusions` (`beam.pack_exclusions`) without a per-clip part (a captured step has no
+    per-batch table input): the captions are drawn under it -- no `<unk>`, no bad ending, none of the words and phrases listed --
+    and with baseline='greedy' the baseline is the eval-mode greedy caption under the same exclusions (`sample(n=1,
+    temperature=0, exclude=X)` with dropout off, captured as a `SampleGraph` when the Trainer uses graphs): the caption
+    `evaluate(decode=dict(exclude=X))` scores at beam size 1.  The train pass is unchanged here too."""
 
     def __init__(self, model, reward, n_samples=5, baseline='mean', temperature=1.0, share_encoder=False, sample_options=None,
                  **trainer_kwargs):
@@ -45,10 +51,24 @@ class SCSTTrainer(object):
         self.n, self.baseline, self.temperature = int(n_samples), baseline, float(temperature)
         self.share_encoder = bool(share_encoder)
         self.sample_options = dict(sample_options or {})
-        unknown = sorted(set(self.sample_options) - {'top_k', 'top_p', 'min_len', 'no_repeat_ngram'})
+        # the keys the model's ops can run: `exclude` needs the sampled step under exclusions
+        # (an ops object written before that step existed does not take the key; the ops are looked at only when it is given)
+        can_exclude = 'exclude' not in self.sample_options or hasattr(model.ops, 'sample_excl_embed')
+        known = ['top_k', 'top_p', 'min_len', 'no_repeat_ngram'] + ['exclude'] * can_exclude
+        unknown = sorted(set(self.sample_options) - set(known))
         if unknown:
-            raise ValueError('sample_options: unknown keys %s (top_k, top_p, min_len, no_repeat_ngram)' % unknown)
-        check_sample_options(model.decoder.max_words, vocab_size=model.decoder.vocab_size, **self.sample_options)
+            raise ValueError('sample_options: unknown keys %s (%s)' % (unknown, ', '.join(known)))
+        self.exclude = self.sample_options.get('exclude')
+        check_sample_options(model.decoder.max_words, vocab_size=model.decoder.vocab_size,
+                             **{k: v for k, v in self.sample_options.items() if k != 'exclude'})
+        if self.exclude is not None:
+            pair = self.exclude if isinstance(self.exclude, tuple) and len(self.exclude) == 2 else (None, None)
+            if pair[1] is not None:
+                raise ValueError('sample_options: exclude with a per-clip part is not covered in SCSTTrainer (a captured step has no '
+                                 'per-batch table input): pass an Exclusions without one')
+            # (anything but an Exclusions, or a shared table the steps cannot take: ValueError here, not at the first step)
+            if check_exclusions(self.exclude, 0, pair[0].device if torch.is_tensor(pair[0]) else None)[0] is None:
+                self.exclude = None                                 # nothing to exclude: the plain step, the plain greedy baseline
         if trainer_kwargs.get('label_smoothing') or trainer_kwargs.get('teacher') is not None or trainer_kwargs.get('distill_weight'):
             raise ValueError('label_smoothing / teacher / distill_weight are options of the CrossEntropy step (Trainer): the '
                              'policy gradient against a smoothed or a teacher\'s target row is not one')
@@ -71,11 +91,27 @@ class SCSTTrainer(object):
         """eval-mode greedy captions of the B clips (no dropout, so the seed is immaterial)"""
         model = self.model
         model.flatten_parameters_()
+        if self.exclude is not None:
+            return self._greedy_excluding(frames, regions)
         if self.trainer.use_graphs:
             if not self._graph_ok(self._greedy, frames, regions):
                 self._greedy = GreedyGraph(model, frames, regions)
             return self._greedy(frames, regions)
         return model._greedy_ids(frames, regions, 0)[0]
+
+    def _greedy_excluding(self, frames, regions):
+        """the greedy captions under the exclusions: the sampled step at temperature 0, one row per clip, in eval mode"""
+        model = self.model
+        was_training = model.training
+        model.eval()
+        try:
+            if not self.trainer.use_graphs:
+                return model.sample(frames, regions, 1, 0.0, 0, exclude=self.exclude)[0]
+            if not self._graph_ok(self._greedy, frames, regions):
+                self._greedy = SampleGraph(model, frames, regions, 1, 0.0, exclude=self.exclude)
+            return self._greedy(frames, regions, 0)[0]
+        finally:
+            model.train(was_training)
 
     def _expanded_inputs(self, frames, regions):
         """the batch repeated n times, written straight into the Trainer's static graph inputs when they have that shape"""

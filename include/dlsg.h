@@ -995,6 +995,36 @@ int dlsg_beam_select_excl(const dlsg_beam_select_args* a, const float* const* lo
                           const float* logw, int M, int mode, const int64_t* hist_in, int64_t* hist_out, int L, int t,
                           int no_repeat_ngram, int min_len, const int64_t* excl_shared, int NS, const int64_t* excl_clip, int NC,
                           int P, void* stream);
+/* dlsg_sample_filter_embed under EXCLUSIONS: that call's arguments, then the two tables of dlsg_beam_select_excl -- excl_shared
+ * (NS, P) for every row, excl_clip (rows / rows_per_clip, NC, P), of which row r reads the entries of clip r / rows_per_clip (the n
+ * samples of a clip are consecutive rows).  With h the row's own words (h[i] = hist[i * hist_stride + r], i < t) the word e[n-1] of
+ * an entry e of length n is banned by dlsg_beam_select_excl's rule: n - 1 <= t and h[t-n+1 .. t-1] == e[0 .. n-2].  These bans join
+ * those of step 1 of dlsg_sample_filter_embed (a word may stand in the list twice) and, like them, come before top_k and top_p and
+ * RENORMALISE: logp is the log-probability over the words that are left, kept their number behind top_k / top_p.  (The beam step
+ * does not renormalise.)  A word's noise does not depend on the bans: the launch draws what dlsg_sample_filter_embed draws from
+ * the same rows with the logits of the words the tables ban set to -inf, with that call's ids, lens, kept and embedded rows.
+ * temperature 0: the first maximum over the words that are not banned.  A row with no word left gives word 0 and kept 0.  A row
+ * that has drawn end_id goes on drawing under the same rule.  hist may be NULL only when no_repeat_ngram == 0 and NS + NC == 0,
+ * or t == 0.  The tables and the longer list take about 3 KB of LDS beside the row's V floats.  No atomics; two launches, or a
+ * launch and a graph replay, give the same bits; NS == NC == 0 gives the bits of dlsg_sample_filter_embed.  EINVAL for what
+ * dlsg_sample_filter_embed refuses, for what dlsg_beam_select_excl refuses of its tables, rows_per_clip < 1, rows not a multiple
+ * of rows_per_clip, and t > 0 with an entry and hist NULL or hist_stride < rows. */
+int dlsg_sample_excl_embed(const float* logits, int64_t ld, int V, float temperature, const float* E, int64_t* ids_out, float* out,
+                           int64_t ldo, int W, float* logp, int64_t* lens, int t, int64_t end_id, int rows, float p, uint64_t seed,
+                           uint32_t site_word, uint32_t site_sample, int64_t row0, const uint64_t* seed_ptr, int top_k, float top_p,
+                           int min_len, int no_repeat_ngram, const int64_t* hist, int64_t hist_stride, int32_t* kept,
+                           const int64_t* excl_shared, int NS, const int64_t* excl_clip, int NC, int P, int rows_per_clip, void* stream);
+/* dlsg_beam_select_gumbel under EXCLUSIONS: that call's arguments, then the two tables as dlsg_beam_select_excl takes them
+ * (excl_clip (B, NC, P): the entries of the clip whose k rows the workgroup holds).  A live row's banned classes are those of
+ * no_repeat_ngram and min_len and the last words of the entries its history row leads up to, by dlsg_beam_select_excl's rule; as in
+ * dlsg_beam_select_gumbel a banned class counts as -inf in the keys AND in the log-sum-exp, so phi stays the log-prob under the
+ * model renormalised over the words that are left.  The launch returns what dlsg_beam_select_gumbel returns on the same rows with
+ * the logits of those words set to -inf; a row that has ended is untouched; NS == NC == 0 gives that call's bits.  EINVAL for what
+ * dlsg_beam_select_gumbel refuses and for what dlsg_beam_select_excl refuses of its tables. */
+int dlsg_beam_select_gumbel_excl(const dlsg_beam_select_args* a, const int64_t* hist_in, int64_t* hist_out, int L, int t,
+                                 int no_repeat_ngram, int min_len, float temperature, uint64_t seed, const uint64_t* seed_ptr,
+                                 uint32_t site_sample, const double* G_in, double* G_out, const int64_t* excl_shared, int NS,
+                                 const int64_t* excl_clip, int NC, int P, void* stream);
 /* After the last step: the n <= k best beams of every clip by score = lp / len^alpha (computed in double, stored as float),
  * descending, ties to the lower beam.  hist (B*k, L) the final history, lp (B*k) the final log-probs; len = tokens up to and
  * including the first `end`, L without one.  Out: ids (B, n, L) int64, scores (B, n), lens (B, n) int64.  One wave per clip. */
