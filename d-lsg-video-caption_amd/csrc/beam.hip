@@ -464,10 +464,9 @@ bool beam_ens_pack(const float* const* logits, const int64_t* ld, const float* w
     e.M = M; e.mode = mode;
     return true;
 }
-// what the steps under exclusions ask of their two tables
-bool beam_excl_ok(const int64_t* excl_shared, int NS, const int64_t* excl_clip, int NC, int P) {
-    if (NS < 0 || NS > DLSG_EXCL_SHARED || NC < 0 || NC > DLSG_EXCL_CLIP || (NS > 0 && !excl_shared) || (NC > 0 && !excl_clip)) return false;
-    return NS + NC == 0 || (P >= 1 && P <= DLSG_PHRASE_MAX);
+// what the two stochastic steps ask beyond the history step
+bool beam_gumbel_ok(float temperature, const double* G_in, const double* G_out, int t) {
+    return temperature > 0.f && G_out && (t == 0 || (G_in && G_in != G_out));     // (NaN fails the comparison)
 }
 // launch(integral_constant<int, k>) for k = 1 .. BEAM_MAXK (checked by beam_args_ok)
 template <typename F>
@@ -534,7 +533,7 @@ extern "C" int dlsg_beam_select_gumbel(const dlsg_beam_select_args* a, const int
                                        int no_repeat_ngram, int min_len, float temperature, uint64_t seed, const uint64_t* seed_ptr,
                                        uint32_t site_sample, const double* G_in, double* G_out, void* stream) {
     if (!beam_hist_ok(a, hist_in, hist_out, L, t, no_repeat_ngram, min_len)) return DLSG_EINVAL;
-    if (!(temperature > 0.f) || !G_out || (t > 0 && (!G_in || G_in == G_out))) return DLSG_EINVAL;     // (NaN fails the comparison)
+    if (!beam_gumbel_ok(temperature, G_in, G_out, t)) return DLSG_EINVAL;
     if (a->B == 0) return DLSG_OK;
     BEAM_LAUNCH(beam_select_gumbel_kernel, hist_in, hist_out, L, t, no_repeat_ngram, min_len, temperature, seed, seed_ptr, site_sample,
                 G_in, G_out);
@@ -586,7 +585,7 @@ extern "C" int dlsg_beam_select_gumbel_excl(const dlsg_beam_select_args* a, cons
                                             uint32_t site_sample, const double* G_in, double* G_out, const int64_t* excl_shared, int NS,
                                             const int64_t* excl_clip, int NC, int P, void* stream) {
     if (!beam_hist_ok(a, hist_in, hist_out, L, t, no_repeat_ngram, min_len)) return DLSG_EINVAL;
-    if (!(temperature > 0.f) || !G_out || (t > 0 && (!G_in || G_in == G_out))) return DLSG_EINVAL;     // (NaN fails the comparison)
+    if (!beam_gumbel_ok(temperature, G_in, G_out, t)) return DLSG_EINVAL;
     if (!beam_excl_ok(excl_shared, NS, excl_clip, NC, P)) return DLSG_EINVAL;
     if (a->B == 0) return DLSG_OK;
     if (NS + NC == 0) P = 1;

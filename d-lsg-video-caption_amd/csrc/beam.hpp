@@ -676,6 +676,11 @@ __device__ __forceinline__ void beam_phrase_merge(const dlsg_beam_select_args& a
 // (0: absent).  The last word of an entry is banned for a row whose history ends with the words before it.
 constexpr int EXCL_SLOTS = DLSG_EXCL_SHARED + DLSG_EXCL_CLIP;
 constexpr int BEAM_BAN_EXCL = BEAM_MAXL + 1 + EXCL_SLOTS;      // a row's ban list with every entry matching at once
+// what a launcher asks of the two tables (host): the steps under exclusions here and the sampler's in sample.hip
+inline bool beam_excl_ok(const int64_t* excl_shared, int NS, const int64_t* excl_clip, int NC, int P) {
+    if (NS < 0 || NS > DLSG_EXCL_SHARED || NC < 0 || NC > DLSG_EXCL_CLIP || (NS > 0 && !excl_shared) || (NC > 0 && !excl_clip)) return false;
+    return NS + NC == 0 || (P >= 1 && P <= DLSG_PHRASE_MAX);
+}
 
 // Phase 0, the whole workgroup (one wave has fewer threads than there are entries): entry a from global memory, `shared` (NS, P)
 // or `clip`, the clip's own (NC, P)

@@ -392,9 +392,7 @@ extern "C" int dlsg_sample_excl_embed(const float* logits, int64_t ld, int V, fl
                                       const int64_t* hist, int64_t hist_stride, int32_t* kept, const int64_t* excl_shared, int NS,
                                       const int64_t* excl_clip, int NC, int P, int rows_per_clip, void* stream) {
     if (rows == 0) return DLSG_OK;
-    if (NS < 0 || NS > DLSG_EXCL_SHARED || NC < 0 || NC > DLSG_EXCL_CLIP || (NS > 0 && !excl_shared) || (NC > 0 && !excl_clip))
-        return DLSG_EINVAL;
-    if (NS + NC > 0 && (P < 1 || P > DLSG_PHRASE_MAX)) return DLSG_EINVAL;
+    if (!beam_excl_ok(excl_shared, NS, excl_clip, NC, P)) return DLSG_EINVAL;
     if (rows_per_clip < 1 || rows % rows_per_clip != 0) return DLSG_EINVAL;
     if (!sample_filter_args_ok(V, W, temperature, top_k, top_p, min_len, no_repeat_ngram, t, rows, no_repeat_ngram > 0 || NS + NC > 0, hist,
                                hist_stride))

@@ -620,24 +620,40 @@ class HipOps(object):
         (B*k), two buffers like last_lp / new_lp), rows in sampling order; last_lp / new_lp are log-probs under the tempered model
         renormalised over the unbanned words; the noise is `sample_embed`'s, keyed (seed, site_sample, ((t+1) R + r) V + j); seed an
         int or a device word (see include/dlsg.h)."""
+        self._gumbel_step('dlsg_beam_select_gumbel', logits, last, last_lp, pred, new_lp, back, rows, k, end, hist_in, hist_out, t, G_in,
+                          G_out, temperature, seed, site_sample, no_repeat_ngram, min_len, ended_count)
+
+    def _gumbel_step(self, entry, logits, last, last_lp, pred, new_lp, back, rows, k, end, hist_in, hist_out, t, G_in, G_out, temperature,
+                     seed, site_sample, no_repeat_ngram, min_len, ended_count, tables=None):
+        """the body of `beam_select_gumbel` and `beam_select_gumbel_excl`: `entry` with the (excl_shared, excl_clip) of `tables`
+        behind its arguments"""
         R, V = logits.shape
         for G in (G_in, G_out):
             assert G.dtype == torch.float64 and G.is_contiguous() and G.numel() == R, (G.dtype, G.shape)
         a, hist = self._hist_step(R, V, last, last_lp, pred, new_lp, back, rows, k, end, hist_in, hist_out, t, no_repeat_ngram, min_len,
                                   ended_count, logits)
+        tail = () if tables is None else self._excl_tables(*tables, R // k, logits.device)
         sd, sp = _seed(seed)
-        self._check(self.lib.dlsg_beam_select_gumbel(C.byref(a), *hist, f32(temperature), u64(sd), sp, u32(site_sample), _p(G_in),
-                                                     _p(G_out), self._stream()), 'dlsg_beam_select_gumbel')
+        self._check(getattr(self.lib, entry)(C.byref(a), *hist, f32(temperature), u64(sd), sp, u32(site_sample), _p(G_in), _p(G_out),
+                                             *tail, self._stream()), entry)
 
     def beam_select_ens(self, logits_list, weights, mode, last, last_lp, pred, new_lp, back, rows, k, end, hist_in, hist_out, t,
                         no_repeat_ngram=0, min_len=0, ended_count=None):
         """`beam_select_hist` for an ensemble: the candidates of beam row r are combined from logits_list[m][r], one (R, V) float32
         array per member, with `weights` (positive, normalised here in float64) -- mode 0: log of the weighted mean probability,
         mode 1: weighted mean log-probability (see include/dlsg.h)."""
+        self._ens_step('dlsg_beam_select_ens', logits_list, weights, mode, last, last_lp, pred, new_lp, back, rows, k, end, hist_in,
+                       hist_out, t, no_repeat_ngram, min_len, ended_count)
+
+    def _ens_step(self, entry, logits_list, weights, mode, last, last_lp, pred, new_lp, back, rows, k, end, hist_in, hist_out, t,
+                  no_repeat_ngram, min_len, ended_count, tables=None):
+        """the body of `beam_select_ens` and `beam_select_excl`: `entry` with the (excl_shared, excl_clip) of `tables` behind its
+        arguments"""
         R, V, members = self._beam_members(logits_list, weights, hist_out.device)
         a, hist = self._hist_step(R, V, last, last_lp, pred, new_lp, back, rows, k, end, hist_in, hist_out, t, no_repeat_ngram, min_len,
                                   ended_count)
-        self._check(self.lib.dlsg_beam_select_ens(C.byref(a), *members, int(mode), *hist, self._stream()), 'dlsg_beam_select_ens')
+        tail = () if tables is None else self._excl_tables(*tables, R // k, hist_out.device)
+        self._check(getattr(self.lib, entry)(C.byref(a), *members, int(mode), *hist, *tail, self._stream()), entry)
 
     def beam_select_groups(self, logits_list, weights, mode, last, last_lp, pred, new_lp, back, rows, k, end, hist_in, hist_out, t,
                            no_repeat_ngram=0, min_len=0, num_groups=1, diversity_penalty=0.0, ended_count=None):
@@ -676,12 +692,8 @@ class HipOps(object):
         caption may contain, excl_clip (B, NC <= 32, P) each clip's own (an entry is the leading run of ids in [0, V)); a live beam
         may not choose the last word of an entry whose other words are the last words of its history (see include/dlsg.h).  Both
         None or empty: the bits of `beam_select_ens`.  A single model passes one logits array and weights [1.0]."""
-        R, V, members = self._beam_members(logits_list, weights, hist_out.device)
-        a, hist = self._hist_step(R, V, last, last_lp, pred, new_lp, back, rows, k, end, hist_in, hist_out, t, no_repeat_ngram, min_len,
-                                  ended_count)
-        tables = self._excl_tables(excl_shared, excl_clip, R // k, hist_out.device)
-        self._check(self.lib.dlsg_beam_select_excl(C.byref(a), *members, int(mode), *hist, *tables, self._stream()),
-                    'dlsg_beam_select_excl')
+        self._ens_step('dlsg_beam_select_excl', logits_list, weights, mode, last, last_lp, pred, new_lp, back, rows, k, end, hist_in,
+                       hist_out, t, no_repeat_ngram, min_len, ended_count, (excl_shared, excl_clip))
 
     def beam_select_gumbel_excl(self, logits, last, last_lp, pred, new_lp, back, rows, k, end, hist_in, hist_out, t, G_in, G_out,
                                 excl_shared=None, excl_clip=None, temperature=1.0, seed=0, site_sample=0, no_repeat_ngram=0, min_len=0,
@@ -689,15 +701,8 @@ class HipOps(object):
         """`beam_select_gumbel` with the exclusion tables of `beam_select_excl`: the last words of the entries a live row's history
         leads up to join its ban list, and the log-probs are renormalised over the words that are left, as that step's other bans
         are (see include/dlsg.h).  Both tables None or empty: the bits of `beam_select_gumbel`."""
-        R, V = logits.shape
-        for G in (G_in, G_out):
-            assert G.dtype == torch.float64 and G.is_contiguous() and G.numel() == R, (G.dtype, G.shape)
-        a, hist = self._hist_step(R, V, last, last_lp, pred, new_lp, back, rows, k, end, hist_in, hist_out, t, no_repeat_ngram, min_len,
-                                  ended_count, logits)
-        tables = self._excl_tables(excl_shared, excl_clip, R // k, logits.device)
-        sd, sp = _seed(seed)
-        self._check(self.lib.dlsg_beam_select_gumbel_excl(C.byref(a), *hist, f32(temperature), u64(sd), sp, u32(site_sample), _p(G_in),
-                                                          _p(G_out), *tables, self._stream()), 'dlsg_beam_select_gumbel_excl')
+        self._gumbel_step('dlsg_beam_select_gumbel_excl', logits, last, last_lp, pred, new_lp, back, rows, k, end, hist_in, hist_out, t,
+                          G_in, G_out, temperature, seed, site_sample, no_repeat_ngram, min_len, ended_count, (excl_shared, excl_clip))
 
     def beam_finalize(self, hist, lp, k, end, alpha, ids, scores, lens):
         """the n = ids.shape[1] best of each clip's k beams by lp / len^alpha: ids (B, n, L), scores (B, n), lens (B, n)."""
