@@ -324,6 +324,43 @@ __global__ __launch_bounds__(SF_THREADS) void sample_excl_embed_kernel(
                                    row0, seed_ptr, top_k, top_p, min_len, g, hist, hist_stride, kept, e);
 }
 
+// A forced prefix behind a sampled step (dlsg_sample_force_prefix): launched behind whichever of the three steps ran, on its
+// arguments.  Row r reads the prefix of clip r / rows_per_clip and is forced at step t iff words 0 .. t of that row of the table
+// all lie in [0, V); every other row returns at once.  A forced row's outputs are rewritten as sample_embed_kernel writes them for
+// a word it draws: the word, its log-prob under softmax(x / tau) with the row's (max, sum-exp) in WordDraw's reduction order (each
+// thread's strided online pair, wave(), block()'s merge) and commit()'s expression, the embedding under the same dropout stream;
+// lens[r] goes back to L (a prefix holds no end_id and every earlier step of the row was forced) and kept[r] is 1.
+__global__ __launch_bounds__(256) void sample_force_prefix_kernel(const float* __restrict__ logits, int64_t ld, int V, float tau,
+                                                                  const float* __restrict__ E, int64_t* __restrict__ ids_out,
+                                                                  float* __restrict__ out, int64_t ldo, int W, float* __restrict__ logp,
+                                                                  int64_t* __restrict__ lens, int t, float p, uint64_t seed,
+                                                                  uint32_t site_word, int64_t row0, const uint64_t* seed_ptr,
+                                                                  const int64_t* __restrict__ prefix, int P, int rows_per_clip, int L,
+                                                                  int32_t* __restrict__ kept) {
+    __shared__ float bv[4], bm[4], bs[4];
+    __shared__ int bi[4];
+    const int r = blockIdx.x;
+    const int64_t* px = prefix + (int64_t)(r / rows_per_clip) * P;
+    int64_t id = -1;
+    for (int j = 0; j <= t; ++j) {                           // (t < P: the launcher checks; every thread reads the same words)
+        id = px[j];
+        if (!(id >= 0 && id < V)) return;
+    }
+    if (seed_ptr) seed += *seed_ptr;
+    const float* x = logits + (int64_t)r * ld;
+    WordDraw d(tau, seed, 0u, row0 + r, V);
+    d.gumbel = false;                                        // (no noise is drawn: the step keeps up the pair (m, s) of x * sc)
+    for (int j = threadIdx.x; j < V; j += blockDim.x) d.step<false>(j, x[j]);
+    d.wave();
+    d.block(bv, bi, bm, bs);
+    if (threadIdx.x == 0) {
+        d.commit(id, x, false, r, ids_out, logp, lens, t, -1);
+        lens[r] = L;
+        if (kept) kept[r] = 1;
+    }
+    embed_row(E, id, out, ldo, W, r, p, seed, site_word, row0, blockDim.x);
+}
+
 // what the two sampled steps ask of their common arguments
 bool sample_args_ok(int V, int W, float temperature) { return V >= 1 && W >= 0 && temperature >= 0.f; }
 // and the two filtered steps of theirs; reads_hist: something looks at the row's earlier words from step 1 on
@@ -353,6 +390,20 @@ extern "C" int dlsg_sample_embed(const float* logits, int64_t ld, int V, float t
     if (!sample_args_ok(V, W, temperature)) return DLSG_EINVAL;
     hipLaunchKernelGGL(sample_embed_kernel, dim3(rows), dim3(256), 0, ST(stream), logits, ld, V, temperature, E, ids_out, out, ldo, W,
                        logp, lens, t, end_id, p, seed, site_word, site_sample, row0, seed_ptr);
+    DLSG_CHECK_LAUNCH();
+    return DLSG_OK;
+}
+extern "C" int dlsg_sample_force_prefix(const float* logits, int64_t ld, int V, float temperature, const float* E, int64_t* ids_out,
+                                        float* out, int64_t ldo, int W, float* logp, int64_t* lens, int t, int rows, float p,
+                                        uint64_t seed, uint32_t site_word, int64_t row0, const uint64_t* seed_ptr,
+                                        const int64_t* prefix, int P, int rows_per_clip, int L, int32_t* kept, void* stream) {
+    if (!sample_args_ok(V, W, temperature) || rows < 0 || L < 1 || t < 0 || t >= L || P < 0 || P > L - 1 || (P > 0 && !prefix))
+        return DLSG_EINVAL;
+    if (rows_per_clip < 1 || rows % rows_per_clip != 0) return DLSG_EINVAL;
+    if (rows == 0 || t >= P) return DLSG_OK;                 // (no row is forced at a step behind the table's width)
+    if (!logits || !E || !ids_out || !out || !logp || !lens) return DLSG_EINVAL;
+    hipLaunchKernelGGL(sample_force_prefix_kernel, dim3(rows), dim3(256), 0, ST(stream), logits, ld, V, temperature, E, ids_out, out,
+                       ldo, W, logp, lens, t, p, seed, site_word, row0, seed_ptr, prefix, P, rows_per_clip, L, kept);
     DLSG_CHECK_LAUNCH();
     return DLSG_OK;
 }

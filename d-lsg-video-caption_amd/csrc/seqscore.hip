@@ -148,6 +148,50 @@ __global__ __launch_bounds__(64 * SEQ_WAVES) void seq_logprob_kernel(const SeqPa
     }
 }
 
+// A forced prefix behind a history step (dlsg_beam_force_prefix): one workgroup of ONE wave per clip, launched behind the step's
+// select launch on its argument block and history buffers.  Lane j holds word j of the clip's prefix row; the clip is forced at
+// step t iff words 0 .. t all lie in [0, V) -- otherwise the workgroup returns and the select launch's outputs stand.  A forced
+// clip's K output slots are rewritten: the word, parent row b*K, the parent's history with the word at t (beam_write_hist); slot 0
+// carries the parent's log-prob plus the word's value -- seq_logprob_kernel's, by the two functions above -- the other slots -inf,
+// so that the first free step expands beam 0 alone, as step 0 does.  e.ld_t is not looked at.
+__global__ __launch_bounds__(64) void beam_force_prefix_kernel(const dlsg_beam_select_args a, const SeqPack e,
+                                                               const int64_t* __restrict__ hist_in, int64_t* __restrict__ hist_out,
+                                                               int L, int t, const int64_t* __restrict__ prefix, int P) {
+    __shared__ float lse_s[DLSG_ENS_MAX];
+    const int lane = threadIdx.x, K = a.k;
+    const int64_t b = blockIdx.x, row = b * K;
+    const int64_t id = lane < P ? prefix[b * P + lane] : -1;
+    if (__ballot(lane <= t && !(id >= 0 && id < a.V))) return;       // t >= p_b: nothing of this clip is written
+    const int wd = (int)lane_u64((uint64_t)id, t);
+    float val;
+    if (e.M == 1) {
+        const float* x = e.x[0] + row * e.ld_r[0];
+        val = x[wd] - beam_row_lse(x, a.V, lane);
+    } else {
+        for (int m = 0; m < e.M; ++m)                         // (not unrolled; every lane reads back its own store)
+            lse_s[m] = beam_row_lse(e.x[m] + row * e.ld_r[m], a.V, lane);
+        const float* x[DLSG_ENS_MAX];
+        float lse[DLSG_ENS_MAX];
+#pragma unroll
+        for (int m = 0; m < DLSG_ENS_MAX; ++m) {
+            x[m] = m < e.M ? e.x[m] + row * e.ld_r[m] : nullptr;
+            lse[m] = m < e.M ? lse_s[m] : 0.f;
+        }
+        val = beam_ens_combine(x, lse, e.w, e.logw, e.M, e.mode, wd);
+    }
+    val = val + (t == 0 ? 0.f : a.last_lp[row]);              // the searches' order: new_lp = word + last_lp
+    for (int c = 0; c < K; ++c) {
+        const int64_t o = row + c;
+        if (lane == 0) {
+            a.pred[o] = wd;
+            a.new_lp[o] = c == 0 ? val : -INFINITY;
+            a.back[o] = 0;
+            a.rows[o] = row;
+        }
+        beam_write_hist(hist_in, hist_out, o, row, L, t, lane, wd, a.end);
+    }
+}
+
 }  // namespace
 
 #define ST(s) reinterpret_cast<hipStream_t>(s)
@@ -172,6 +216,25 @@ extern "C" int dlsg_seq_logprob(const float* const* logits, const int64_t* ld_t,
     else
         hipLaunchKernelGGL(seq_logprob_kernel<false>, dim3(R), dim3(64 * SEQ_WAVES), 0, ST(stream), e, ids, ids_ld, lens_in, L, V, end,
                            alpha, tok_lp, tok_rank, lp, scores, lens_out);
+    DLSG_CHECK_LAUNCH();
+    return DLSG_OK;
+}
+
+extern "C" int dlsg_beam_force_prefix(const dlsg_beam_select_args* a, const float* const* logits, const int64_t* ld, const float* w,
+                                      const float* logw, int M, int mode, const int64_t* hist_in, int64_t* hist_out, int L, int t,
+                                      const int64_t* prefix, int P, void* stream) {
+    if (!a || a->k < 1 || a->k > BEAM_MAXK || a->V < 1 || a->B < 0 || L < 1 || L > BEAM_MAXL || t < 0 || t >= L) return DLSG_EINVAL;
+    if (P < 0 || P > L - 1 || (P > 0 && !prefix)) return DLSG_EINVAL;
+    if (!logits || !ld || !w || !logw || M < 1 || M > DLSG_ENS_MAX || (mode != 0 && mode != 1)) return DLSG_EINVAL;
+    if (!hist_out || (t > 0 && (!hist_in || hist_in == hist_out))) return DLSG_EINVAL;
+    SeqPack e = {};
+    for (int m = 0; m < M; ++m) {
+        if (!logits[m]) return DLSG_EINVAL;
+        e.x[m] = logits[m]; e.ld_r[m] = ld[m]; e.w[m] = w[m]; e.logw[m] = logw[m];
+    }
+    e.M = M; e.mode = mode;
+    if (P == 0 || a->B == 0 || t >= P) return DLSG_OK;         // (no clip is forced at a step behind the table's width)
+    hipLaunchKernelGGL(beam_force_prefix_kernel, dim3(a->B), dim3(64), 0, ST(stream), *a, e, hist_in, hist_out, L, t, prefix, P);
     DLSG_CHECK_LAUNCH();
     return DLSG_OK;
 }

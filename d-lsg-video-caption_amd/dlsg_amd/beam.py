@@ -22,6 +22,9 @@ rank in the step it launches and in how `_constraints_met` counts.
 must not contain (`pack_exclusions`): `beam_select_excl` adds the last word of every excluded entry that a beam's history leads up to
 to the beam's ban list; `exclusions_hit` counts what a caption contains of them.  `stochastic_nbest(exclude=...)` draws its captions
 under the same tables (`beam_select_gumbel_excl`), the model renormalised over the words that are left, as its other bans do.
+`prefix=` makes the history searches continue a given beginning (`pack_prefix`): behind the select launch of each of the first P
+steps `beam_force_prefix` rewrites the clips whose prefix reaches that step -- the forced word in every slot, its value on beam 0,
+-inf on the others -- and since bans and constraint state are recomputed from the history row, the prefix is seen by all of them.
 """
 import collections
 
@@ -197,11 +200,13 @@ def check_nbest_options(k, L, n_best=None, length_penalty=0.0, no_repeat_ngram=0
     return n
 
 
-def _hist_search(models, k, visual_feats, region_feats, select):
+def _hist_search(models, k, visual_feats, region_feats, select, prefix=None, weights=None, mode=0):
     """The search every history step kernel runs in: each model encodes its clips and steps its own state on the shared words and
     back-pointer rows; at every word `select(t, logits, step)` makes the one launch that chooses the beams -- `logits` the models'
     (R, V) rows, `step` the arguments every history step takes after the logits (words, the log-prob and pred ping-pong, back, rows,
-    k, <end>, the history ping-pong, t).  All L steps are launched, nothing is read back.  -> the last step's (hist (R, L), lps (R,))"""
+    k, <end>, the history ping-pong, t).  All L steps are launched, nothing is read back.  -> the last step's (hist (R, L), lps (R,))
+    prefix (B, P) int64 (`check_prefix`): behind the select launch of each of the first P steps one `beam_force_prefix` launch
+    rewrites the clips whose prefix reaches that step, with the models as members of `weights` (None: one model) in `mode`."""
     steps = []
     for model in models:
         mems, sv, seed, _ = _encode(model, visual_feats, region_feats)
@@ -217,7 +222,10 @@ def _hist_search(models, k, visual_feats, region_feats, select):
     words = torch.full((R,), dec.vocab('<start>'), dtype=torch.int64, device=dev)
     for t in range(L):
         logits = [advance(t, words, rows) for advance in steps]
-        select(t, logits, (words, lps[t % 2], preds[t % 2], lps[(t + 1) % 2], back, rows, k, end, hist[t % 2], hist[(t + 1) % 2], t))
+        step = (words, lps[t % 2], preds[t % 2], lps[(t + 1) % 2], back, rows, k, end, hist[t % 2], hist[(t + 1) % 2], t)
+        select(t, logits, step)
+        if prefix is not None and t < prefix.shape[1]:                 # (the table's width: nothing is read back)
+            models[0].ops.beam_force_prefix(logits, [1.0] if weights is None else weights, mode, *step, prefix)
         words = preds[t % 2]
     return hist[L % 2], lps[L % 2]
 
@@ -233,12 +241,13 @@ def _finalize(model, hist, lps, k, n, length_penalty):
 
 
 def _nbest_search(models, weights, mode, visual_feats, region_feats, n_best, length_penalty, no_repeat_ngram, min_len, beam_size,
-                  num_groups, diversity_penalty, exclude=None):
+                  num_groups, diversity_penalty, exclude=None, prefix=None):
     """The search of `beam_nbest` (weights None: one model) and `ensemble_nbest`: `_hist_search` on the step kernel the options
     ask for, `beam_finalize` ranks the beams."""
     dec, ops = models[0].decoder, models[0].ops
     k = dec.beam_size if beam_size is None else beam_size
     n = check_nbest_options(k, dec.max_words, n_best, length_penalty, no_repeat_ngram, min_len, num_groups, diversity_penalty)
+    prefix = search_prefix(ops, prefix, visual_feats.shape[0], visual_feats.device, dec, num_groups)
     if exclude is not None:
         shared, per_clip = check_exclusions(exclude, visual_feats.shape[0], visual_feats.device, num_groups)
 
@@ -252,12 +261,12 @@ def _nbest_search(models, weights, mode, visual_feats, region_feats, n_best, len
             ops.beam_select_hist(logits[0], *step, no_repeat_ngram, min_len)   # (reads a logit row twice, the ensemble step three times)
         else:
             ops.beam_select_ens(logits, weights, mode, *step, no_repeat_ngram, min_len)
-    return _finalize(models[0], *_hist_search(models, k, visual_feats, region_feats, select), k, n, length_penalty)
+    return _finalize(models[0], *_hist_search(models, k, visual_feats, region_feats, select, prefix, weights, mode), k, n, length_penalty)
 
 
 @torch.no_grad()
 def beam_nbest(model, visual_feats, region_feats, n_best=None, length_penalty=0.0, no_repeat_ngram=0, min_len=0, beam_size=None,
-               num_groups=1, diversity_penalty=0.0, exclude=None):
+               num_groups=1, diversity_penalty=0.0, exclude=None, prefix=None):
     """The n best of the k beams of every clip: (ids (B, n, L) int64, padded with <end>; scores (B, n) float32 =
     log-prob / len^length_penalty, descending; lens (B, n) int64 = tokens up to and including the first <end>, else L), device
     tensors.  no_repeat_ngram = g: no caption repeats a g-gram; min_len: no <end> before that many words.  A banned word takes
@@ -273,23 +282,32 @@ def beam_nbest(model, visual_feats, region_feats, n_best=None, length_penalty=0.
     exclude: the `Exclusions` of `pack_exclusions` -- words and phrases no caption may contain, for all clips or per clip: a beam may
     not choose the last word of an entry behind the entry's other words (`<unk>` is a one-word entry, a bad ending the pair
     (word, <end>)).  One `beam_select_excl` launch per step, the model as one member of weight 1; not together with num_groups > 1.
-    exclude=None launches what it always did."""
+    exclude=None launches what it always did.
+    prefix: how every caption begins -- the (B, P) int64 tensor of `pack_prefix` on the clips' device (clip b's prefix: the leading run
+    of ids in [0, V) of row b, any other id, normally -1, ends it; lengths may differ and may be 0), or the per-clip list `pack_prefix`
+    takes, which is packed here.  At the steps t < p_b the caption's word is prefix[b, t] whatever the bans say; from p_b on the
+    search goes on as it would behind these words had it chosen them: the n-gram ban and the exclusions see the prefix (an entry can
+    be completed across the boundary and is banned there), min_len counts it.  The caller's own words are not checked against
+    `exclude`: `exclusions_hit` can be non-zero because of the prefix alone.  The scores include the forced words' log-probs and lens
+    count them, so `score(ids)` returns the search's scores and lens.  One `beam_force_prefix` launch behind the select launch of
+    each of the first P steps; not together with num_groups > 1.  prefix None, or P == 0, launches what it always did."""
     return _nbest_search([model], None, 0, visual_feats, region_feats, n_best, length_penalty, no_repeat_ngram, min_len, beam_size,
-                         num_groups, diversity_penalty, exclude)
+                         num_groups, diversity_penalty, exclude, prefix)
 
 
 @torch.no_grad()
 def ensemble_nbest(models, weights, mode, visual_feats, region_feats, n_best=None, length_penalty=0.0, no_repeat_ngram=0, min_len=0,
-                   beam_size=None, num_groups=1, diversity_penalty=0.0, exclude=None):
+                   beam_size=None, num_groups=1, diversity_penalty=0.0, exclude=None, prefix=None):
     """`beam_nbest` with several models that decode one caption: every member runs its own encoder and its own decode step on the
     shared words and back-pointer rows (its own state slots; any of the model classes, any hidden sizes), and one
     `beam_select_ens` launch per step combines the members' logit rows -- mode 0: log of the weighted mean probability, mode 1:
     weighted mean log-probability -- and chooses the beams.  One set of preds / hist / back / rows / lps; no host synchronisation.
     The members share vocabulary, max_words and device (`ensemble.Ensemble` checks that); beam_size defaults to the first member's.
     num_groups, diversity_penalty: diverse beam search as in `beam_nbest`, on the combined values (`beam_select_groups`).
-    exclude: exclusions as in `beam_nbest` (`beam_select_excl` in place of `beam_select_ens`)."""
+    exclude: exclusions as in `beam_nbest` (`beam_select_excl` in place of `beam_select_ens`).
+    prefix: a forced beginning as in `beam_nbest`; a forced word's value is the members' combined one."""
     return _nbest_search(models, weights, mode, visual_feats, region_feats, n_best, length_penalty, no_repeat_ngram, min_len, beam_size,
-                         num_groups, diversity_penalty, exclude)
+                         num_groups, diversity_penalty, exclude, prefix)
 
 
 def check_stochastic_options(n, L, V, temperature, min_len=0, no_repeat_ngram=0, return_threshold=False):
@@ -310,7 +328,7 @@ def check_stochastic_options(n, L, V, temperature, min_len=0, no_repeat_ngram=0,
 
 @torch.no_grad()
 def stochastic_nbest(model, visual_feats, region_feats, n=5, temperature=1.0, seed=None, min_len=0, no_repeat_ngram=0,
-                     return_threshold=False, exclude=None):
+                     return_threshold=False, exclude=None, prefix=None):
     """Stochastic beam search (Kool, van Hoof & Welling 2019): n DISTINCT captions per clip that are an exact ordered sample without
     replacement from softmax(logits / temperature), renormalised over the words min_len and no_repeat_ngram leave -- row 0 is
     distributed as one ordinary sample, rows 0 .. m-1 as a without-replacement sample of size m.  Returns (ids (B, n, L) int64
@@ -324,7 +342,10 @@ def stochastic_nbest(model, visual_feats, region_feats, n=5, temperature=1.0, se
     exclude: the `Exclusions` of `pack_exclusions` -- the step is `beam_select_gumbel_excl`, whose banned words are those of the
     two other bans and the last words of the entries a beam's history leads up to; the model is renormalised over the words that
     are left, as with the other two (the beam search under exclusions does not renormalise).  None, or two empty tables, launches
-    what the call launched without the keyword."""
+    what the call launched without the keyword.
+    prefix: not covered -- anything but None is a ValueError (the perturbed value of a forced node is a design of its own)."""
+    if prefix is not None:
+        raise PrefixNotCovered('prefix and sample_without_replacement: a forced beginning is not covered in stochastic beam search')
     dec = model.decoder
     L = dec.max_words
     k = check_stochastic_options(n, L, dec.vocab_size, temperature, min_len, no_repeat_ngram, return_threshold)
@@ -696,9 +717,89 @@ def exclusions_hit(ids, lens, exclusions, vocab_size=None):
     return out if ids.dim() == 3 else out[:, 0]
 
 
+# ---------------------------------------------------------------------------------------------- forced prefixes
+def pack_prefix(per_clip, vocab, device=None, max_words=None, allow_unk=False):
+    """The prefix tensor of `beam_search(prefix=...)` and `sample(prefix=...)`: (B, P) int64 padded with -1, P the longest prefix
+    (0 when no clip has one).  per_clip: for every clip how its captions begin -- a string, split on whitespace, a tuple or list
+    of words or ids, or None / '' for no prefix.  ValueError for <end>, <start> or <pad> in a prefix, for a word outside the
+    vocabulary -- unless allow_unk: then it becomes `<unk>` (`<unk>` written out is always allowed) --, and, with max_words, for a
+    prefix longer than max_words - 1 (a caption of max_words tokens holds max_words - 1 words and <end>)."""
+    special = {vocab(w) for w in ('<end>', '<start>', '<pad>') if w in vocab.word2idx}
+    rows = []
+    for b, item in enumerate(per_clip):
+        words = [] if item is None else item.split() if isinstance(item, str) else list(item) if isinstance(item, (tuple, list)) else None
+        if words is None:
+            raise ValueError('clip %d: a prefix is a string, a tuple or list of words or ids, or None, not %s' % (b, type(item).__name__))
+        ids = []
+        for wd in words:
+            if isinstance(wd, str):
+                i = vocab.word2idx.get(wd, -1)
+            else:
+                i = int(wd) if 0 <= int(wd) < len(vocab) else -1
+            if i < 0 and allow_unk and '<unk>' in vocab.word2idx:
+                i = vocab.word2idx['<unk>']
+            if i < 0:
+                raise ValueError('clip %d: %r is not in the vocabulary' % (b, wd))
+            if i in special:
+                raise ValueError('clip %d: %r cannot stand in a prefix (<end>, <start> and <pad> are not words of a caption)' % (b, wd))
+            ids.append(i)
+        if max_words is not None and len(ids) > max_words - 1:
+            raise ValueError('clip %d: a prefix of %d words and <end> do not fit into max_words %d' % (b, len(ids), max_words))
+        rows.append(ids)
+    out = torch.full((len(rows), max([len(ids) for ids in rows] + [0])), -1, dtype=torch.int64)
+    for b, ids in enumerate(rows):
+        out[b, :len(ids)] = torch.tensor(ids, dtype=torch.int64)
+    return out if device is None else out.to(device)
+
+
+def check_prefix(prefix, B, device, L, vocab=None):
+    """ValueError for a `prefix` a decode of B clips on `device` with max_words L cannot run on: not an int64 tensor (B, P) on that
+    device, or P > L - 1; returns the tensor, contiguous, or None for P == 0.  With `vocab` a list in place of a tensor is packed
+    first (`pack_prefix` with max_words L)."""
+    if vocab is not None and isinstance(prefix, (list, tuple)):
+        prefix = pack_prefix(prefix, vocab, device, max_words=L)
+    if not torch.is_tensor(prefix) or prefix.dtype != torch.int64 or prefix.dim() != 2:
+        raise ValueError('prefix: an int64 tensor (B, P) (pack_prefix makes one), not %s'
+                         % ('%s %s' % (prefix.dtype, tuple(prefix.shape)) if torch.is_tensor(prefix) else type(prefix).__name__))
+    if prefix.shape[0] != B:
+        raise ValueError('prefix of shape %s holds %d clips, the batch %d' % (tuple(prefix.shape), prefix.shape[0], B))
+    if prefix.device != device:
+        raise ValueError('prefix on %s, the clips on %s' % (prefix.device, device))
+    if prefix.shape[1] > L - 1:
+        raise ValueError('prefix of %d words and <end> do not fit into max_words %d' % (prefix.shape[1], L))
+    return prefix.contiguous() if prefix.shape[1] else None
+
+
+class PrefixNotCovered(ValueError):
+    """`prefix` where it cannot be honoured: given to a decode that does not cover a forced beginning, or to a model whose ops
+    object has no force launch.  A ValueError that names the combination."""
+
+
+def require_prefix_step(ops, step):
+    """PrefixNotCovered unless `ops` implements `step`, the launch a decode under a forced prefix makes behind its word step (HipOps
+    does; an ops object written before the launch existed does not): raised before the encoder runs"""
+    if not hasattr(ops, step):
+        raise PrefixNotCovered('prefix: %s has no %s, the launch behind the word step under a forced prefix' % (type(ops).__name__, step))
+
+
+def search_prefix(ops, prefix, B, device, dec, num_groups=1):
+    """what a history search does with its `prefix` keyword before the encoder runs: None stays None; otherwise beam groups are
+    refused, the tensor (or list) is checked (`check_prefix`) and the ops object must have the force launch -> the tensor, or None
+    for P == 0"""
+    if prefix is None:
+        return None
+    if num_groups > 1:
+        raise PrefixNotCovered('prefix and num_groups = %d: a forced beginning is not covered in diverse beam search (the later '
+                               'groups\' beams would start at -inf)' % num_groups)
+    prefix = check_prefix(prefix, B, device, dec.max_words, dec.vocab)
+    if prefix is not None:
+        require_prefix_step(ops, 'beam_force_prefix')
+    return prefix
+
+
 @torch.no_grad()
 def constrained_nbest(model, visual_feats, region_feats, constraints, n_best=None, length_penalty=0.0, no_repeat_ngram=0, min_len=0,
-                      beam_size=None, return_met=False, exclude=None):
+                      beam_size=None, return_met=False, exclude=None, prefix=None):
     """Lexically constrained beam search (dynamic beam allocation, Post & Vilar 2018): `beam_nbest` whose captions must contain a
     word of every constraint of their clip.  constraints: the (B, C, W) int64 tensor of `pack_constraints` on the clips' device
     (C sets of W alternative word ids per clip, -1 or an id outside the vocabulary for padding), or the per-clip lists, which are
@@ -717,7 +818,10 @@ def constrained_nbest(model, visual_feats, region_feats, constraints, n_best=Non
     must fit into max_words.  With an n-gram ban the next word of a phrase can be banned although the phrase has not occurred: the
     search is then best effort, and a beam that cannot finish runs to max_words without <end>.  The rows of a clip are ordered by
     `phrases_met` of the final ids, most first, then by score.
-    exclude: not covered -- anything but None is an `ExcludeNotCovered`, a ValueError (a required word could be an excluded one)."""
+    exclude: not covered -- anything but None is an `ExcludeNotCovered`, a ValueError (a required word could be an excluded one).
+    prefix: a forced beginning as in `beam_nbest`.  A prefix word meets a constraint or advances a phrase like a word the search
+    chose (what a beam has met is recomputed from its history row), and it overrides the <end> ban of unmet constraints as it does
+    every other ban; return_met counts it."""
     if exclude is not None:
         raise ExcludeNotCovered('exclude and constraints: exclusions are not covered in constrained beam search')
     dec = model.decoder
@@ -734,10 +838,11 @@ def constrained_nbest(model, visual_feats, region_feats, constraints, n_best=Non
         cons = pack_constraints(constraints, dec.vocab, dev)
     n = _check_packed(k, L, B, cons, dev, phrases, n_best, length_penalty, no_repeat_ngram, min_len)
     cons = cons.contiguous()
+    prefix = search_prefix(model.ops, prefix, B, dev, dec)
 
     def select(t, logits, step):                                   # (a 3-D tensor never runs the phrase step, which is slower)
         (model.ops.beam_select_phrases if phrases else model.ops.beam_select_cons)(logits[0], *step, cons, no_repeat_ngram, min_len)
-    ids, scores, lens = _finalize(model, *_hist_search([model], k, visual_feats, region_feats, select), k, k, length_penalty)
+    ids, scores, lens = _finalize(model, *_hist_search([model], k, visual_feats, region_feats, select, prefix), k, k, length_penalty)
     met = _constraints_met(ids, cons, dec.vocab_size)              # (B, k)
     order = met.sort(dim=1, descending=True, stable=True)[1][:, :n]
     out = (ids.gather(1, order.unsqueeze(2).expand(B, n, L)), scores.gather(1, order), lens.gather(1, order))

@@ -43,13 +43,16 @@ def consensus_search(model_or_ensemble, frames, regions, reward, n_best=1, weigh
                      **beam_options):
     """`beam_search` of a model (CapGnnModel, the baselines) or an `ensemble.Ensemble` with every beam kept, then
     `consensus_rerank`: (ids (B, n_best, L), expected, lens, order).  beam_options: beam_size, length_penalty, no_repeat_ngram,
-    min_len, num_groups, diversity_penalty -- diverse groups give the consensus something to choose from.  The search's launches
-    plus one.
+    min_len, num_groups, diversity_penalty, exclude, prefix -- diverse groups give the consensus something to choose from, a prefix
+    (`beam.pack_prefix`) makes the candidates n endings of one beginning.  The search's launches plus one.
     stochastic=dict(n=..., temperature=..., seed=..., min_len=..., no_repeat_ngram=...): the candidates are the n distinct
     captions of `model.sample_without_replacement` instead (a model, not an ensemble), their log-probabilities the scores: a
     without-replacement sample of the model as the candidate list of the Monte Carlo estimate, with no row spent on a duplicate.
-    beam_options must then be empty."""
+    beam_options must then be empty, and a prefix is refused in either place."""
     if stochastic is not None:
+        if stochastic.get('prefix') is not None or beam_options.get('prefix') is not None:
+            raise ValueError('prefix and consensus_search(stochastic=...): a forced beginning is not covered in sampling without '
+                             'replacement')
         if beam_options:
             raise ValueError('consensus_search(stochastic=...) takes no beam options (%s): the candidates come from '
                              'sample_without_replacement' % ', '.join(sorted(beam_options)))

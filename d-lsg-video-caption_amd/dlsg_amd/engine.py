@@ -1139,7 +1139,7 @@ def sample_exclusions(exclude, clips, device, L, vocab_size=None):
 
 
 def dec_sample(ops, dec, mems, sv, L, training, seed, temperature, top_k=0, top_p=1.0, min_len=0, no_repeat_ngram=0, exclude=None,
-               rows_per_clip=1):
+               rows_per_clip=1, prefix=None):
     """Sampled decoding for self-critical training: step t feeds a word drawn from softmax(logits_t / temperature) to step t+1
     (`sample_embed`, Gumbel noise keyed by (seed, SITE_SAMPLE, row); temperature 0 is greedy).  Fills IDS (slots 1..L: the
     words), LOGP (L, B) their log-probabilities and LENS (B,): first <end> position + 1, else L.  The word-dropout rows are those
@@ -1150,7 +1150,10 @@ def dec_sample(ops, dec, mems, sv, L, training, seed, temperature, top_k=0, top_
     number of words each draw chose from.  With all of them off the launches are the ones above.
     exclude: an `Exclusions` (beam.pack_exclusions) with at least one entry -- the step is `sample_excl_embed`, whatever the other
     controls are: the last word of an entry is banned behind the entry's other words, before top_k and top_p, renormalised like
-    the other bans; row r reads the per-clip entries of clip r // rows_per_clip.  None, or two empty tables: the launches above."""
+    the other bans; row r reads the per-clip entries of clip r // rows_per_clip.  None, or two empty tables: the launches above.
+    prefix: a (clips, P) int64 table (beam.check_prefix) -- behind the step of each of the first P words one `sample_force_prefix`
+    launch rewrites the rows whose clip's prefix reaches that word (row r reads clip r // rows_per_clip): the word, its plain
+    log-probability, its embedding, LENS back to L, KEPT 1.  None: the launches above."""
     filtered = check_sample_options(L, top_k, top_p, min_len, no_repeat_ngram, dec.vocab_size)
     s, ref, B, E, ids, pw = dec_begin(ops, dec, mems, sv, L, training, seed)
     if rows_per_clip < 1 or B % rows_per_clip:
@@ -1161,6 +1164,14 @@ def dec_sample(ops, dec, mems, sv, L, training, seed, temperature, top_k=0, top_
     if filtered or tables is not None:
         s['KEPT'] = torch.empty(L, B, dtype=torch.int32, device=ref.device)
     end = dec.vocab('<end>')
+    if prefix is not None and prefix.shape[0] != B // rows_per_clip:
+        raise ValueError('dec_sample: the prefix holds %d clips, the rows %d' % (prefix.shape[0], B // rows_per_clip))
+
+    def force(t):
+        if prefix is not None and t < prefix.shape[1]:                 # (the table's width: nothing is read back)
+            ops.sample_force_prefix(s['LOGITS'][t], E, ids[t + 1], s['WE'][t + 1], s['LOGP'][t], s['LENS'], t, prefix, L,
+                                    temperature=temperature, p=pw, seed=seed, site=SITE_WORD, row0=(t + 1) * B,
+                                    rows_per_clip=rows_per_clip, kept=s['KEPT'][t] if 'KEPT' in s else None)
     ops.embed_fwd(E, ids[0], s['WE'][0], p=pw, seed=seed, site=SITE_WORD, row0=0)
     for t in range(L):
         dec_step(ops, dec, s, t, ref, training, seed, B)
@@ -1171,15 +1182,18 @@ def dec_sample(ops, dec, mems, sv, L, training, seed, temperature, top_k=0, top_
                                   row0=(t + 1) * B, top_k=top_k, top_p=top_p, min_len=min_len, no_repeat_ngram=no_repeat_ngram,
                                   hist=ids[1:], kept=s['KEPT'][t], excl_shared=tables[0], excl_clip=tables[1],
                                   rows_per_clip=rows_per_clip)
+            force(t)
             continue
         if filtered:
             ops.sample_filter_embed(s['LOGITS'][t], E, ids[t + 1], s['WE'][t + 1], s['LOGP'][t], s['LENS'], t, end,
                                     temperature=temperature, p=pw, seed=seed, site=SITE_WORD, site_sample=SITE_SAMPLE,
                                     row0=(t + 1) * B, top_k=top_k, top_p=top_p, min_len=min_len, no_repeat_ngram=no_repeat_ngram,
                                     hist=ids[1:], kept=s['KEPT'][t])
+            force(t)
             continue
         ops.sample_embed(s['LOGITS'][t], E, ids[t + 1], s['WE'][t + 1], s['LOGP'][t], s['LENS'], t, end, temperature=temperature,
                          p=pw, seed=seed, site=SITE_WORD, site_sample=SITE_SAMPLE, row0=(t + 1) * B)
+        force(t)
     return s
 
 

@@ -48,14 +48,15 @@ class Ensemble(object):
         return self.members[0].ops
 
     def beam_search(self, visual_feats, region_feats, beam_size=None, n_best=None, length_penalty=0.0, no_repeat_ngram=0, min_len=0,
-                    num_groups=1, diversity_penalty=0.0, exclude=None):
+                    num_groups=1, diversity_penalty=0.0, exclude=None, prefix=None):
         """`model.beam_search` of the ensemble: (ids (B, n, L), scores (B, n), lens (B, n)), device tensors, nothing read back.
         beam_size None: the first member's; no member's decoder.beam_size is changed.  num_groups, diversity_penalty: diverse
-        beam search on the combined values, as in `model.beam_search`; exclude: exclusions, as there."""
+        beam search on the combined values, as in `model.beam_search`; exclude: exclusions, as there; prefix: a forced beginning,
+        as there, a forced word's value being the members' combined one."""
         from .beam import ensemble_nbest
         return ensemble_nbest(self.members, self.weights, MODES[self.mode], visual_feats, region_feats, n_best=n_best,
                               length_penalty=length_penalty, no_repeat_ngram=no_repeat_ngram, min_len=min_len, beam_size=beam_size,
-                              num_groups=num_groups, diversity_penalty=diversity_penalty, exclude=exclude)
+                              num_groups=num_groups, diversity_penalty=diversity_penalty, exclude=exclude, prefix=prefix)
 
     def greedy(self, visual_feats, region_feats):
         """(B, L) ids, <end>-padded: the search with one beam"""

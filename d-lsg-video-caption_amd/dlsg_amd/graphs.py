@@ -89,6 +89,19 @@ def _held_exclusions(options):
     return options, exclude, dict(options, exclude=exclude)
 
 
+def _held_prefix(model, options, device):
+    """takes `prefix` out of the options a captured decode runs with -> (those options with the graph's own copy of the table in its
+    place, the copy or None): a static buffer like the inputs; per-clip lists are packed here (`beam.pack_prefix`)"""
+    prefix = options.get('prefix')
+    if prefix is None:
+        return options, None
+    if not torch.is_tensor(prefix):
+        from .beam import pack_prefix
+        prefix = pack_prefix(prefix, model.decoder.vocab, device, max_words=model.decoder.max_words)
+    prefix = prefix.clone()
+    return dict(options, prefix=prefix), prefix
+
+
 class _InferenceGraph(object):
     """A no-grad pass of `model` over (frames, regions), captured once for a batch shape and replayed: a subclass says what to
     run (`_run`, on the static inputs self.frames / self.regions; its return value becomes self.out).  A captured graph holds raw
@@ -180,13 +193,16 @@ class SampleGraph(_SeededGraph):
     fanned out in-graph (`rows_repeat`), the sampled decode steps on B*n rows; a replay with seed s gives that call's bits.
     top_k, top_p, min_len, no_repeat_ngram, return_kept: the sampling controls of `CapGnnModel.sample`, fixed at capture.
     exclude=Exclusions (`pack_exclusions`): kept as `graph.exclude`, the graph's own copy of the two tables, as NBestBeamGraph keeps
-    it: `graph.exclude.shared.copy_(new)` changes what the next replay bans; the tables' shapes are fixed at capture."""
+    it: `graph.exclude.shared.copy_(new)` changes what the next replay bans; the tables' shapes are fixed at capture.
+    prefix=(B, P) int64 (`pack_prefix`, or the per-clip list it takes): kept as `graph.prefix`, the graph's own copy:
+    `graph.prefix.copy_(new)` changes what the next replay's samples begin with; the shape is fixed at capture."""
 
     def __init__(self, model, frames, regions, n=1, temperature=1.0, share_encoder=False, top_k=0, top_p=1.0, min_len=0,
-                 no_repeat_ngram=0, return_kept=False, exclude=None):
+                 no_repeat_ngram=0, return_kept=False, exclude=None, prefix=None):
         self.n, self.temperature, self.share_encoder = n, temperature, bool(share_encoder)
         self.options, self.exclude, self._draw = _held_exclusions(dict(
             top_k=top_k, top_p=top_p, min_len=min_len, no_repeat_ngram=no_repeat_ngram, return_kept=return_kept, exclude=exclude))
+        self._draw, self.prefix = _held_prefix(model, self._draw if prefix is None else dict(self._draw, prefix=prefix), frames.device)
         super().__init__(model, frames, regions)
 
     def _run(self):
@@ -214,10 +230,14 @@ class NBestBeamGraph(_InferenceGraph):
     replay -- and synchronises nothing (call `model.ops.check_persistent()` where the ids are read back).
     exclude=Exclusions (`pack_exclusions`): the graph keeps its own copy of the two tables as `graph.exclude` and captures their
     addresses: `graph.exclude.per_clip.copy_(new)` (or `.shared`) changes what the next replay bans; another shape needs a new
-    graph."""
+    graph.
+    prefix=(B, P) int64 (`pack_prefix`, or the per-clip list it takes): the graph keeps its own copy as `graph.prefix`, like
+    `graph.exclude`: `graph.prefix.copy_(new)` changes what the next replay's captions begin with (a row of -1 frees its clip);
+    another P needs a new graph."""
 
     def __init__(self, model, frames, regions, **options):
         self.options, self.exclude, self._search = _held_exclusions(options)
+        self._search, self.prefix = _held_prefix(model, self._search, frames.device)
         super().__init__(model, frames, regions)
 
     def _run(self):
@@ -229,9 +249,13 @@ class StochasticBeamGraph(_SeededGraph):
     and all max_words steps of stochastic beam search.  The seed is read from a device word, like SampleGraph's, so every replay
     draws afresh; a replay with seed s gives the bits of the eager call with seed=s.  options: min_len, no_repeat_ngram,
     return_threshold, fixed at capture.  Outputs are static buffers, valid until the next replay; nothing synchronises.
-    exclude=Exclusions: kept as `graph.exclude`, as NBestBeamGraph keeps it."""
+    exclude=Exclusions: kept as `graph.exclude`, as NBestBeamGraph keeps it.  prefix: a forced beginning is not covered in sampling
+    without replacement; anything but None is a ValueError."""
 
     def __init__(self, model, frames, regions, n=5, temperature=1.0, **options):
+        if options.get('prefix') is not None:
+            from .beam import PrefixNotCovered
+            raise PrefixNotCovered('prefix and StochasticBeamGraph: a forced beginning is not covered in stochastic beam search')
         self.n, self.temperature = n, temperature
         self.options, self.exclude, self._search = _held_exclusions(options)
         super().__init__(model, frames, regions)
@@ -245,12 +269,13 @@ class ConstrainedBeamGraph(_InferenceGraph):
     of the constraint tensor -- (B, C, W) words or (B, C, W, P) phrases --, which is a static buffer like the inputs:
     `graph(frames, regions, constraints)` stages all three and replays; constraints are the packed int64 tensor or the per-clip lists
     (packed to the captured shape, by `pack_phrases` where that is 4-D; ValueError for another shape).  A replay returns the eager
-    call's (ids, scores, lens[, met]), static buffers, and synchronises nothing."""
+    call's (ids, scores, lens[, met]), static buffers, and synchronises nothing.  prefix=: kept as `graph.prefix`, as
+    NBestBeamGraph keeps it."""
 
     extra = 'cons'
 
     def __init__(self, model, frames, regions, constraints, **options):
-        self.options = options
+        self.options, self.prefix = _held_prefix(model, options, frames.device)
         self.cons = self._packed(model, constraints, frames.device).clone()
         super().__init__(model, frames, regions)
 
@@ -282,11 +307,13 @@ class EnsembleBeamGraph(_InferenceGraph):
     """hipGraph-captured `ensemble.beam_search(frames, regions, **options)` (ensemble.Ensemble) for one batch shape: every member's
     encoder and decode steps, one `beam_select_ens` per word, the ranking.  The graph holds addresses into EVERY member's arena and
     every member's train / eval mode: `valid_for` and the stale-arena error cover all of them.  A replay returns (ids, scores,
-    lens), static buffers, and synchronises nothing.  exclude=Exclusions: kept as `graph.exclude`, as NBestBeamGraph keeps it."""
+    lens), static buffers, and synchronises nothing.  exclude=Exclusions: kept as `graph.exclude`, as NBestBeamGraph keeps it;
+    prefix=: kept as `graph.prefix`, likewise."""
 
     def __init__(self, ensemble, frames, regions, **options):
         self.ensemble = ensemble
         self.options, self.exclude, self._search = _held_exclusions(options)
+        self._search, self.prefix = _held_prefix(ensemble.members[0], self._search, frames.device)
         super().__init__(ensemble.members[0], frames, regions, ensemble.members)
 
     def _run(self):

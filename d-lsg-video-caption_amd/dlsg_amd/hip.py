@@ -704,6 +704,31 @@ class HipOps(object):
         self._gumbel_step('dlsg_beam_select_gumbel_excl', logits, last, last_lp, pred, new_lp, back, rows, k, end, hist_in, hist_out, t,
                           G_in, G_out, temperature, seed, site_sample, no_repeat_ngram, min_len, ended_count, (excl_shared, excl_clip))
 
+    @staticmethod
+    def _prefix_table(prefix, clips, device, what):
+        """checks a prefix table, (clips, P) int64 on the logits' device -> P"""
+        if not torch.is_tensor(prefix) or prefix.dtype != torch.int64 or prefix.dim() != 2 or not prefix.is_contiguous():
+            raise ValueError('%s: prefix is a contiguous int64 tensor (B, P), not %s'
+                             % (what, '%s %s' % (prefix.dtype, tuple(prefix.shape)) if torch.is_tensor(prefix) else type(prefix).__name__))
+        if prefix.shape[0] != clips:
+            raise ValueError('%s: the prefix of shape %s holds %d clips, the step %d' % (what, tuple(prefix.shape), prefix.shape[0], clips))
+        if prefix.device != device:
+            raise ValueError('%s: the prefix on %s, the logits on %s' % (what, prefix.device, device))
+        return prefix.shape[1]
+
+    def beam_force_prefix(self, logits_list, weights, mode, last, last_lp, pred, new_lp, back, rows, k, end, hist_in, hist_out, t,
+                          prefix):
+        """A forced prefix behind a history step: called behind the step's select launch with that call's members and step
+        arguments.  prefix (B, P) int64: a clip whose row holds ids in [0, V) at 0 .. t gets pred = prefix[b, t] in all its k slots,
+        parent row b*k, that row's history with the word at t, new_lp = the parent's log-prob plus the word's value (`seq_logprob`'s
+        bits) in slot 0 and -inf in the others; every other clip keeps what the select launch wrote (see include/dlsg.h).  A single
+        model passes one logits array and weights [1.0]."""
+        R, V, members = self._beam_members(logits_list, weights, hist_out.device)
+        P = self._prefix_table(prefix, R // k, hist_out.device, 'beam_force_prefix')
+        a, hist = self._hist_step(R, V, last, last_lp, pred, new_lp, back, rows, k, end, hist_in, hist_out, t, 0, 0, None)
+        self._check(self.lib.dlsg_beam_force_prefix(C.byref(a), *members, int(mode), *hist[:4], _p(prefix) if P else None, P,
+                                                    self._stream()), 'dlsg_beam_force_prefix')
+
     def beam_finalize(self, hist, lp, k, end, alpha, ids, scores, lens):
         """the n = ids.shape[1] best of each clip's k beams by lp / len^alpha: ids (B, n, L), scores (B, n), lens (B, n)."""
         R, L = hist.shape
@@ -1299,6 +1324,28 @@ class HipOps(object):
             *args, int(top_k), f32(top_p), int(min_len), int(no_repeat_ngram), _p(hist) if hist is not None else None,
             i64(hist.stride(0) if hist is not None else 0), _p(kept) if kept is not None else None, *tables, int(rows_per_clip),
             self._stream()), 'sample_excl_embed')
+
+    def sample_force_prefix(self, logits, E, ids_out, out, logp, lens, t, prefix, L, temperature=1.0, p=0.0, seed=0, site=0, row0=0,
+                            rows_per_clip=1, kept=None):
+        """A forced prefix behind a sampled step: called behind `sample_embed`, `sample_filter_embed` or `sample_excl_embed` with
+        that call's logits, E, ids_out, out, logp, lens, t, temperature, p, seed, site and row0.  prefix (rows / rows_per_clip, P)
+        int64, of which row r reads clip r // rows_per_clip's: a row whose clip holds ids in [0, V) at 0 .. t gets ids_out =
+        prefix[., t], logp = that word's plain log-probability under softmax(logits / temperature) -- `sample_embed`'s bits for a
+        word it draws --, out = drop(E[word]), lens = L and kept = 1; every other row keeps what the step wrote (see
+        include/dlsg.h)."""
+        rows, V = logits.shape
+        if rows_per_clip < 1 or rows % rows_per_clip:
+            raise ValueError('sample_force_prefix: %d rows are not clips of rows_per_clip = %r rows' % (rows, rows_per_clip))
+        P = self._prefix_table(prefix, rows // rows_per_clip, logits.device, 'sample_force_prefix')
+        assert logits.dtype == torch.float32 and logits.stride(1) == 1 and logp.dtype == torch.float32, (logits.dtype, logits.stride())
+        assert E.shape[0] >= V and E.is_contiguous() and ids_out.numel() == rows and logp.numel() == rows and lens.numel() == rows
+        assert ids_out.dtype == torch.int64 and lens.dtype == torch.int64 and out.shape == (rows, E.shape[1])
+        assert kept is None or (kept.dtype == torch.int32 and kept.numel() == rows and kept.is_contiguous())
+        sd, sp = _seed(seed)
+        self._check(self.lib.dlsg_sample_force_prefix(
+            _p(logits), i64(logits.stride(0)), V, f32(temperature), _p(E), _p(ids_out), _p(out), i64(out.stride(0)), out.shape[1],
+            _p(logp), _p(lens), int(t), rows, f32(p), u64(sd), u32(site), i64(row0), sp, _p(prefix) if P else None, P,
+            int(rows_per_clip), int(L), _p(kept), self._stream()), 'sample_force_prefix')
 
     def copy2d(self, src, dst, accum=False):
         rows, n = src.shape

@@ -259,11 +259,11 @@ class _HipModel(_ArenaModule):
         return self._public(out[0], out[1:3], out[3])
 
     def sample(self, visual_feats, region_feats, n=1, temperature=1.0, seed=None, share_encoder=False, top_k=0, top_p=1.0,
-               min_len=0, no_repeat_ngram=0, return_kept=False, exclude=None):
+               min_len=0, no_repeat_ngram=0, return_kept=False, exclude=None, prefix=None):
         raise NotImplementedError('sampled decoding (self-critical training) is implemented for CapGnnModel only')
 
     def beam_search(self, visual_feats, region_feats, beam_size=None, n_best=None, length_penalty=0.0, no_repeat_ngram=0, min_len=0,
-                    num_groups=1, diversity_penalty=0.0, exclude=None):
+                    num_groups=1, diversity_penalty=0.0, exclude=None, prefix=None):
         """The n_best (default: all) of `beam_size` (default: the decoder's, at most 8) beams per clip, entirely on the device:
         (ids (B, n, L) int64 padded with <end>, scores (B, n) float32 = log-prob / len^length_penalty in descending order, lens
         (B, n) int64 counting the <end>).  no_repeat_ngram = g > 0: no caption repeats a g-gram; min_len: at least that many words
@@ -272,14 +272,18 @@ class _HipModel(_ArenaModule):
         earlier groups chose at that step costs a later group `diversity_penalty` per choice (inf: excluded).  scores do not
         contain the penalty.  exclude: the `Exclusions` `dlsg_amd.pack_exclusions` makes -- words and phrases no caption may contain,
         `<unk>`, bad endings, for all clips or per clip; a banned word takes log-prob -inf, nothing is renormalised (not together
-        with num_groups > 1).  Nothing synchronises with the host, so call `model.ops.check_persistent()` where the ids are read back."""
+        with num_groups > 1).  prefix: how every caption begins -- the (B, P) int64 tensor `dlsg_amd.pack_prefix` makes (-1 ends a
+        clip's prefix; lengths may differ) or the per-clip list it takes: the words are forced whatever the bans say, the search goes
+        on behind them as if it had chosen them (bans, min_len and exclusions see the prefix; the caller's own words are not checked
+        against `exclude`), scores include their log-probs and lens count them (not together with num_groups > 1).
+        Nothing synchronises with the host, so call `model.ops.check_persistent()` where the ids are read back."""
         from .beam import beam_search
         return beam_search(self, visual_feats, region_feats, beam_size, n_best=n_best, length_penalty=length_penalty,
                            no_repeat_ngram=no_repeat_ngram, min_len=min_len, num_groups=num_groups, diversity_penalty=diversity_penalty,
-                           exclude=exclude)
+                           exclude=exclude, prefix=prefix)
 
     def sample_without_replacement(self, visual_feats, region_feats, n=5, temperature=1.0, seed=None, min_len=0, no_repeat_ngram=0,
-                                   return_threshold=False, exclude=None):
+                                   return_threshold=False, exclude=None, prefix=None):
         """n (at most 8) DISTINCT captions per clip, an exact ordered sample without replacement from softmax(logits /
         temperature) by stochastic beam search, entirely on the device: (ids (B, n, L) int64 padded with <end>, logp (B, n) float32
         the captions' log-probabilities, lens (B, n) int64 counting the <end>), rows in sampling order -- row 0 is distributed as
@@ -288,13 +292,14 @@ class _HipModel(_ArenaModule):
         exclude: the `Exclusions` of `dlsg_amd.pack_exclusions`, as in `beam_search` -- but here the model is renormalised over the
         words the exclusions leave, like the other two bans, and the sample is one without replacement from that model.
         seed None draws the model's next seed, a given seed reproduces the draw.  The decode runs in eval mode whatever
-        `self.training` is (`beam.stochastic_nbest`); nothing synchronises with the host."""
+        `self.training` is (`beam.stochastic_nbest`); nothing synchronises with the host.
+        prefix: a forced beginning is not covered here; anything but None is a ValueError."""
         from .beam import stochastic_nbest
         return stochastic_nbest(self, visual_feats, region_feats, n=n, temperature=temperature, seed=seed, min_len=min_len,
-                                no_repeat_ngram=no_repeat_ngram, return_threshold=return_threshold, exclude=exclude)
+                                no_repeat_ngram=no_repeat_ngram, return_threshold=return_threshold, exclude=exclude, prefix=prefix)
 
     def constrained_beam_search(self, visual_feats, region_feats, constraints, beam_size=None, n_best=None, length_penalty=0.0,
-                                no_repeat_ngram=0, min_len=0, return_met=False, exclude=None):
+                                no_repeat_ngram=0, min_len=0, return_met=False, exclude=None, prefix=None):
         """`beam_search` whose captions must contain given words (lexically constrained beam search by dynamic beam allocation).
         constraints: per clip a list of constraints, each a word, a word id or a list of alternatives of which one must appear
         (at most 8 constraints of 8 alternatives), or the (B, C, W) int64 device tensor `dlsg_amd.pack_constraints` makes of them.
@@ -306,11 +311,12 @@ class _HipModel(_ArenaModule):
         `dlsg_amd.pack_phrases` makes, require phrases as contiguous words; met then counts the constraints with a phrase in the row
         (`dlsg_amd.phrases_met`).  C_b phrase constraints of up to n words need C_b * n + 1 <= max_words; with no_repeat_ngram the
         next word of a phrase can be banned, the search is then best effort and a beam that cannot finish runs to max_words.
-        exclude: exclusions are not covered here; anything but None is a ValueError."""
+        exclude: exclusions are not covered here; anything but None is a ValueError.  prefix: a forced beginning as in
+        `beam_search`; a prefix word meets a constraint or advances a phrase, and met counts it."""
         from .beam import constrained_nbest
         return constrained_nbest(self, visual_feats, region_feats, constraints, n_best=n_best, length_penalty=length_penalty,
                                  no_repeat_ngram=no_repeat_ngram, min_len=min_len, beam_size=beam_size, return_met=return_met,
-                                 exclude=exclude)
+                                 exclude=exclude, prefix=prefix)
 
     def score(self, visual_feats, region_feats, ids, **options):
         """The log-probability of GIVEN captions under this model: `rescore.score_captions(self, ...)` -- ids (B, L) or (B, n, L)
@@ -521,7 +527,7 @@ class CapGnnModel(_HipModel):
 
     @torch.no_grad()
     def sample(self, visual_feats, region_feats, n=1, temperature=1.0, seed=None, share_encoder=False, top_k=0, top_p=1.0,
-               min_len=0, no_repeat_ngram=0, return_kept=False, exclude=None):
+               min_len=0, no_repeat_ngram=0, return_kept=False, exclude=None, prefix=None):
         """Draw n captions per clip from softmax(logits / temperature) (self-critical training; temperature 0 is greedy).
         Returns (ids (B*n, L) int64, logp (B*n, L) float32 log-probabilities of the drawn words, lens (B*n,) int64: first
         <end> position + 1, else L); clip b's samples are rows b*n .. b*n + n - 1.  The clips are repeated n times before the
@@ -543,13 +549,26 @@ class CapGnnModel(_HipModel):
         would complete an entry whose earlier words are the row's last words; the bans join those of min_len and no_repeat_ngram,
         come before top_k and top_p and renormalise like them (`dlsg_sample_excl_embed`; `beam_search` does not renormalise).  It is
         a control of its own: the others may be off.  Words behind a row's first <end> are not part of its caption.  None, or
-        two empty tables, launches what the call launched without the keyword."""
+        two empty tables, launches what the call launched without the keyword.
+        prefix: how the samples begin -- the (B, P) int64 tensor `dlsg_amd.pack_prefix` makes, for the B clips, not their B*n rows
+        (-1 ends a clip's prefix; lengths may differ), or the per-clip list it takes.  The n rows of clip b hold prefix[b, t] at the
+        steps t < p_b whatever the controls say, and draw from p_b on as they would behind these words: the n-gram ban, min_len and
+        the exclusions see the prefix (the caller's own words are not checked against `exclude`).  logp at a forced position is the
+        word's plain log-probability under softmax(logits / temperature) -- no control applied, at temperature 0 under the
+        untempered softmax: what the plain sampler reports for a word it draws -- so the sum from p_b on is the conditional
+        log-probability; kept is 1 there.  One `sample_force_prefix` launch behind the step of each of the first P words; None, or
+        P == 0, launches what the call launched without the keyword."""
         L = self.decoder.max_words
         filtered = E.check_sample_options(L, top_k, top_p, min_len, no_repeat_ngram, self.decoder.vocab_size)
         excluding = E.sample_exclusions(exclude, visual_feats.shape[0], visual_feats.device, L, self.decoder.vocab_size) is not None
         if excluding:
             from .beam import require_excl_step
             require_excl_step(self.ops, 'sample_excl_embed')
+        if prefix is not None:
+            from .beam import check_prefix, require_prefix_step
+            prefix = check_prefix(prefix, visual_feats.shape[0], visual_feats.device, L, self.decoder.vocab)
+            if prefix is not None:
+                require_prefix_step(self.ops, 'sample_force_prefix')
         if return_kept and not (filtered or excluding):
             raise ValueError('return_kept needs one of top_k, top_p, min_len, no_repeat_ngram, exclude switched on')
         self.flatten_parameters_()
@@ -562,7 +581,7 @@ class CapGnnModel(_HipModel):
         _, mems = self._encoder_pass(visual_feats, region_feats, self.training, seed, sv, int(n))
         s = E.dec_sample(self.ops, self.decoder, list(mems), sv, L, self.training, seed, temperature, top_k=top_k, top_p=top_p,
                          min_len=min_len, no_repeat_ngram=no_repeat_ngram, exclude=exclude if excluding else None,
-                         rows_per_clip=per_clip)
+                         rows_per_clip=per_clip, prefix=prefix)
         out = s['IDS'][1:].t().contiguous(), s['LOGP'].t().contiguous(), s['LENS']
         return out + (s['KEPT'].t().contiguous(),) if return_kept else out
 

@@ -666,11 +666,19 @@ def gather_results(net, eval_loader, decode=None):
     caption is the one the scorer ranks first: row 0 of `rescore.rescore_search` (not together with consensus or constraints).
     With the key exclude=X the search runs under exclusions (`beam.pack_exclusions`): X is an `Exclusions` without a per-clip part,
     which holds for every batch, or fn(video_ids) -> the batch's `Exclusions`; consensus and rescore searches pass it on to their
-    beam search, constraints do not take it."""
+    beam search, constraints do not take it.
+    With the key prefix=X every caption continues a given beginning (`beam.pack_prefix`): X is a (B, P) int64 tensor, which then
+    holds for every batch of that size, or fn(video_ids) -> the batch's tensor or per-clip list; every search above passes it on
+    to its beam search."""
     import torch
     result = collections.OrderedDict()
     dec = (net.module if hasattr(net, 'module') else net).decoder
-    consensus, constraints, rescorer, exclude = None, None, None, None
+    consensus, constraints, rescorer, exclude, prefix = None, None, None, None, None
+    if decode is not None and decode.get('prefix') is not None:
+        decode = dict(decode)
+        prefix = decode.pop('prefix')
+        if not callable(prefix) and not torch.is_tensor(prefix):
+            raise ValueError('decode: prefix is an int64 tensor (B, P) for every batch, or fn(video_ids) -> prefix')
     if decode is not None and decode.get('exclude') is not None:
         decode = dict(decode)
         exclude = decode.pop('exclude')
@@ -698,6 +706,9 @@ def gather_results(net, eval_loader, decode=None):
             if exclude is not None:
                 ex = exclude(video_ids) if callable(exclude) else exclude
                 decode['exclude'] = type(ex)(*[None if x is None else x.to(frames.device) for x in ex])
+            if prefix is not None:
+                px = prefix(video_ids) if callable(prefix) else prefix
+                decode['prefix'] = px.to(frames.device) if torch.is_tensor(px) else px
             if decode is None:
                 outputs = net(frames, regions, None)[0]
             elif consensus is not None:

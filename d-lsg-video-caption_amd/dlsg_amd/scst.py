@@ -39,7 +39,8 @@ class SCSTTrainer(object):
     per-batch table input): the captions are drawn under it -- no `<unk>`, no bad ending, none of the words and phrases listed --
     and with baseline='greedy' the baseline is the eval-mode greedy caption under the same exclusions (`sample(n=1,
     temperature=0, exclude=X)` with dropout off, captured as a `SampleGraph` when the Trainer uses graphs): the caption
-    `evaluate(decode=dict(exclude=X))` scores at beam size 1.  The train pass is unchanged here too."""
+    `evaluate(decode=dict(exclude=X))` scores at beam size 1.  The train pass is unchanged here too.  `sample`'s prefix= is
+    refused: the train pass would differentiate words the policy did not choose."""
 
     def __init__(self, model, reward, n_samples=5, baseline='mean', temperature=1.0, share_encoder=False, sample_options=None,
                  **trainer_kwargs):
@@ -51,6 +52,9 @@ class SCSTTrainer(object):
         self.n, self.baseline, self.temperature = int(n_samples), baseline, float(temperature)
         self.share_encoder = bool(share_encoder)
         self.sample_options = dict(sample_options or {})
+        if 'prefix' in self.sample_options:
+            raise ValueError('sample_options: prefix is not covered in SCSTTrainer (the train pass would differentiate words the '
+                             'policy did not choose)')
         # the keys the model's ops can run: `exclude` needs the sampled step under exclusions
         # (an ops object written before that step existed does not take the key; the ops are looked at only when it is given)
         can_exclude = 'exclude' not in self.sample_options or hasattr(model.ops, 'sample_excl_embed')

@@ -1058,6 +1058,36 @@ int dlsg_beam_finalize(const int64_t* hist, const float* lp, int B, int k, int L
 int dlsg_seq_logprob(const float* const* logits, const int64_t* ld_t, const int64_t* ld_r, const float* w, const float* logw, int M,
                      int mode, const int64_t* ids, int64_t ids_ld, const int64_t* lens_in, int R, int L, int V, int64_t end,
                      double alpha, float* tok_lp, int32_t* tok_rank, float* lp, float* scores, int64_t* lens_out, void* stream);
+/* A FORCED PREFIX behind a history step: launched behind the step's select launch (any of dlsg_beam_select_hist / _ens / _excl /
+ * _cons / _phrases) on the same argument block `a`, the same hist_in / hist_out, L and t, with the members as
+ * dlsg_beam_select_ens takes them (a single model: M == 1, w = {1}, logw = {0}; a->logits and a->ld are ignored).  prefix (B, P)
+ * int64: clip b's prefix is the leading run of ids in [0, V) of its row, p_b words (0 .. P); any other id, normally -1, ends it.
+ * One workgroup of one wave per clip.  t >= p_b: the workgroup returns and nothing of the clip is written -- the select launch's
+ * outputs stand.  t < p_b, with w = prefix[b, t] and the clip's first row b*k as the parent: all k output slots b*k + c get
+ * pred = w, back = 0, rows = b*k and the history row hist_in[b*k][0 .. t), w, then `end` (dlsg_beam_select_hist's rule); slot 0
+ * gets new_lp = c(w) + (t == 0 ? 0 : last_lp[b*k]), c(w) the combined value of class w on row b*k exactly as dlsg_seq_logprob
+ * computes tok_lp (with M == 1 x - lse, the bits dlsg_beam_select_hist adds for that class); slots 1 .. k-1 get new_lp = -inf, so
+ * the first free step expands beam 0 alone, as step 0 does.  No ban applies to a forced word; a forced word whose value is -inf or
+ * NaN gives the clip that log-prob.  ended_count is not touched.  EINVAL and no launch for k outside 1..8, L outside 1..64, t
+ * outside [0, L), P outside 0..L-1, M outside 1..DLSG_ENS_MAX, mode outside {0, 1}, prefix NULL with P > 0, hist_out NULL, and
+ * t > 0 with hist_in NULL or equal to hist_out.  P == 0, B == 0 or t >= P launches nothing. */
+int dlsg_beam_force_prefix(const dlsg_beam_select_args* a, const float* const* logits, const int64_t* ld, const float* w,
+                           const float* logw, int M, int mode, const int64_t* hist_in, int64_t* hist_out, int L, int t,
+                           const int64_t* prefix, int P, void* stream);
+/* A FORCED PREFIX behind a sampled step: launched behind dlsg_sample_embed, dlsg_sample_filter_embed or dlsg_sample_excl_embed
+ * on that call's logits, E, ids_out, out, logp, lens, t, temperature, p, seed / seed_ptr, site_word and row0.  prefix
+ * (rows / rows_per_clip, P) int64 as dlsg_beam_force_prefix reads it; row r reads clip r / rows_per_clip.  A row whose clip has
+ * p_b <= t returns at once.  A forced row gets ids_out[r] = w = prefix[., t]; logp[r] = the log-probability of w under
+ * softmax(logits[r] / temperature) (temperature 0: the untempered softmax) in the operations of dlsg_sample_embed, so forcing the
+ * word that call drew leaves its bits; no control of the filtered steps applies; out[r] = E[w] under the word-dropout stream
+ * (seed, site_word, row0 + r); lens[r] = L (a prefix holds no end_id and every earlier step of the row was forced, so it was L
+ * on entry to step t); kept[r] = 1 (kept may be NULL).  EINVAL and no launch for V < 1, W < 0, temperature < 0, L < 1, t outside
+ * [0, L), P outside 0..L-1, prefix NULL with P > 0, rows_per_clip < 1 and rows not a multiple of it.  rows == 0 or t >= P
+ * launches nothing. */
+int dlsg_sample_force_prefix(const float* logits, int64_t ld, int V, float temperature, const float* E, int64_t* ids_out, float* out,
+                             int64_t ldo, int W, float* logp, int64_t* lens, int t, int rows, float p, uint64_t seed,
+                             uint32_t site_word, int64_t row0, const uint64_t* seed_ptr, const int64_t* prefix, int P,
+                             int rows_per_clip, int L, int32_t* kept, void* stream);
 /* dst_i[r,:] = src_i[rows[r],:] (dense rows of n[i] floats) for count <= 4 arrays in one launch */
 typedef struct {
     const float* src[4]; float* dst[4]; int32_t n[4];
