@@ -454,16 +454,6 @@ bool beam_hist_ok(const dlsg_beam_select_args* a, const int64_t* hist_in, const 
     if (!beam_args_ok(a) || !hist_out || L < 1 || L > BEAM_MAXL || t < 0 || t >= L || g < 0 || min_len < 0) return false;
     return (a->first != 0) == (t == 0) && (t == 0 || (hist_in && hist_in != hist_out));
 }
-bool beam_ens_pack(const float* const* logits, const int64_t* ld, const float* w, const float* logw, int M, int mode, EnsPack& e) {
-    if (!logits || !ld || !w || !logw || M < 1 || M > DLSG_ENS_MAX || (mode != 0 && mode != 1)) return false;
-    e = {};
-    for (int m = 0; m < M; ++m) {
-        if (!logits[m]) return false;
-        e.x[m] = logits[m]; e.ld[m] = ld[m]; e.w[m] = w[m]; e.logw[m] = logw[m];
-    }
-    e.M = M; e.mode = mode;
-    return true;
-}
 // what the two stochastic steps ask beyond the history step
 bool beam_gumbel_ok(float temperature, const double* G_in, const double* G_out, int t) {
     return temperature > 0.f && G_out && (t == 0 || (G_in && G_in != G_out));     // (NaN fails the comparison)

@@ -180,6 +180,55 @@ struct EnsPack {
     float w[DLSG_ENS_MAX], logw[DLSG_ENS_MAX];
     int M, mode;
 };
+// the members' host arrays into the block a launcher passes by value (host); false for what every ensemble entry point refuses
+inline bool beam_ens_pack(const float* const* logits, const int64_t* ld, const float* w, const float* logw, int M, int mode, EnsPack& e) {
+    if (!logits || !ld || !w || !logw || M < 1 || M > DLSG_ENS_MAX || (mode != 0 && mode != 1)) return false;
+    e = {};
+    for (int m = 0; m < M; ++m) {
+        if (!logits[m]) return false;
+        e.x[m] = logits[m]; e.ld[m] = ld[m]; e.w[m] = w[m]; e.logw[m] = logw[m];
+    }
+    e.M = M; e.mode = mode;
+    return true;
+}
+// The two steps of beam_ens_row_topk for the kernels that want the combined value without the K best (dlsg_seq_logprob,
+// dlsg_beam_force_prefix, dlsg_sample_ens), operation for operation: that function keeps its own statement of them, because calling
+// these from it changed the code the compiler emits for the ensemble and group step kernels, and those stay as they are.
+// tests/test_gpu_rescore.py holds the two statements together: a word's value here equals the new_lp of dlsg_beam_select_hist /
+// dlsg_beam_select_ens bit for bit.
+// a member's row: its log-sum-exp, ONE wave, to every lane
+__device__ __forceinline__ float beam_row_lse(const float* x, int V, int lane) {
+    float mx = -INFINITY;
+    for (int j = lane; j < V; j += 64) mx = fmaxf(mx, x[j]);
+    mx = dlsg::wave_max(mx);
+    float sum = 0.f;
+    for (int j = lane; j < V; j += 64) sum += expf(x[j] - mx);
+    sum = dlsg::wave_sum(sum);
+    return logf(sum) + mx;
+}
+// class j's combined value from the members' rows x and their log-sum-exps
+__device__ __forceinline__ float beam_ens_combine(const float* const (&x)[DLSG_ENS_MAX], const float (&lse)[DLSG_ENS_MAX],
+                                                  const float (&w)[DLSG_ENS_MAX], const float (&logw)[DLSG_ENS_MAX], int M, int mode,
+                                                  int j) {
+    float c;
+    if (mode == 0) {
+        float v[DLSG_ENS_MAX], mx = -INFINITY, sum = 0.f;
+#pragma unroll
+        for (int m = 0; m < DLSG_ENS_MAX; ++m)
+            if (m < M) { v[m] = (x[m][j] - lse[m]) + logw[m]; mx = fmaxf(mx, v[m]); }
+#pragma unroll
+        for (int m = 0; m < DLSG_ENS_MAX; ++m)
+            if (m < M) sum += expf(v[m] - mx);
+        c = mx == -INFINITY ? -INFINITY : mx + logf(sum);
+    } else {
+        c = 0.f;
+#pragma unroll
+        for (int m = 0; m < DLSG_ENS_MAX; ++m)
+            if (m < M) c += w[m] * (x[m][j] - lse[m]);
+    }
+    return c;
+}
+
 template <int K>
 __device__ __forceinline__ void beam_ens_row_topk(const EnsPack& e, int64_t row, int V, int lane, float* lse_s, const int* ban,
                                                   int nban, float (&bv)[K], int (&bi)[K]) {

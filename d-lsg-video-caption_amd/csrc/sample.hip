@@ -2,7 +2,8 @@
 // a composition of the phases of wordpick.hpp: dlsg_argmax (greedy), dlsg_select_embed (scheduled sampling: the caption's word or
 // the greedy one), dlsg_sample_embed (Gumbel-max draw with its log-prob) and dlsg_sample_filter_embed, the draw behind a
 // repeated-n-gram ban, a minimum length, top-k and nucleus (top-p) truncation, and dlsg_sample_excl_embed, that step's body once more
-// with the bans of the exclusion tables (beam.hpp) in the row's list.  The filtered step holds the row's tempered logits in
+// with the bans of the exclusion tables (beam.hpp) in the row's list, and dlsg_sample_ens, which combines an ensemble's M logit rows
+// into one row of values and runs that body on it without the embedding.  The filtered step holds the row's tempered logits in
 // LDS and finds the two thresholds without sorting: a descent over an order-preserving uint32 image of the float, two bits per
 // round, each round one pass over the candidates still undecided and one fixed-order block reduction (an integer count for top-k,
 // a float mass for top-p).  No atomics anywhere: two launches, or an eager launch and a graph replay, give the same bits.
@@ -12,6 +13,7 @@
 #include "beam.hpp"
 #include "common.hpp"
 #include "dlsg.h"
+#include "dlsg_sample_ens.h"
 #include "wordpick.hpp"
 
 using namespace dlsg;
@@ -195,8 +197,10 @@ struct SampleExcl {
 // The filtered step.  hist: the row's earlier words, time-major: word i of row r at hist[i * hist_stride + r], i < t.
 // EXCL: the step under exclusions -- phase 0 stages the two tables in LDS (beam_stage_exclusions), the history row is loaded whenever
 // an entry can look at it, and wave 0 puts the last words of the matching entries behind the list of beam_ban_list
-// (beam_ban_exclusions); everything behind the list is the one body.  Without EXCL `e` is not looked at.
-template <bool EXCL>
+// (beam_ban_exclusions); everything behind the list is the one body.  Without EXCL `e` is not looked at.  EMBED: the chosen word's
+// embedding row is written behind the draw; without it (dlsg_sample_ens: every member embeds the word itself) E, out, ldo, W, p and
+// site_word are not looked at and the step ends with thread 0's commit.
+template <bool EXCL, bool EMBED = true>
 __device__ __forceinline__ void sample_filter_embed_body(
     const float* __restrict__ logits, int64_t ld, int V, float tau, const float* __restrict__ E, int64_t* __restrict__ ids_out,
     float* __restrict__ out, int64_t ldo, int W, float* __restrict__ logp, int64_t* __restrict__ lens, int t, int64_t end_id, float p,
@@ -297,12 +301,14 @@ __device__ __forceinline__ void sample_filter_embed_body(
     const int64_t id = d.block(bv, bi, bm, bs);              // (nothing kept: word 0)
     if (tid == 0) {
         const int nkept = (bn[0] + bn[1]) + (bn[2] + bn[3]);
-        chosen = id;
+        if constexpr (EMBED) chosen = id;
         if (kept) kept[r] = nkept;
         d.commit(id, x, nkept == 1, r, ids_out, logp, lens, t, end_id);
     }
-    __syncthreads();
-    embed_row(E, chosen, out, ldo, W, r, p, seed, site_word, row0, SF_THREADS);
+    if constexpr (EMBED) {
+        __syncthreads();
+        embed_row(E, chosen, out, ldo, W, r, p, seed, site_word, row0, SF_THREADS);
+    }
 }
 
 __global__ __launch_bounds__(SF_THREADS) void sample_filter_embed_kernel(
@@ -322,6 +328,42 @@ __global__ __launch_bounds__(SF_THREADS) void sample_excl_embed_kernel(
     int min_len, int g, const int64_t* hist, int64_t hist_stride, int32_t* __restrict__ kept, const SampleExcl e) {
     sample_filter_embed_body<true>(logits, ld, V, tau, E, ids_out, out, ldo, W, logp, lens, t, end_id, p, seed, site_word, site_sample,
                                    row0, seed_ptr, top_k, top_p, min_len, g, hist, hist_stride, kept, e);
+}
+
+// An ensemble's sampled step (dlsg_sample_ens).  Phase A: the row's V combined values into comb[r], in the operations of the
+// ensemble beam step -- wave w takes the log-sum-exp of the members w, w + 4 (beam_row_lse: one wave per row, so the sum keeps that
+// step's order), then every thread combines the classes tid, tid + 256, ... (beam_ens_combine; one member: x - lse, as
+// dlsg_seq_logprob takes it).  Phase B: the filtered body under exclusions on comb[r] as its logits, without the embedding.  The
+// barrier between the two is all the hand-over needs: comb[r] is written and read by this workgroup alone, a workgroup's waves share
+// their CU's vector L1, which is write-through, and __syncthreads() waits for the stores (vmcnt(0)) in front of s_barrier.  comb is
+// not __restrict__ and the body's loads of it all lie behind the barrier.
+__global__ __launch_bounds__(SF_THREADS) void sample_ens_kernel(
+    const EnsPack e, int V, float tau, float* comb, int64_t* __restrict__ ids_out, float* __restrict__ logp, int64_t* __restrict__ lens,
+    int t, int64_t end_id, uint64_t seed, uint32_t site_sample, int64_t row0, const uint64_t* seed_ptr, int top_k, float top_p,
+    int min_len, int g, const int64_t* hist, int64_t hist_stride, int32_t* __restrict__ kept, const SampleExcl excl) {
+    __shared__ float lse_s[DLSG_ENS_MAX];
+    const int r = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    for (int m = w; m < e.M; m += SF_THREADS / 64) {         // (not unrolled: the member's pointer is read from the argument block)
+        const float l = beam_row_lse(e.x[m] + (int64_t)r * e.ld[m], V, lane);
+        if (lane == 0) lse_s[m] = l;
+    }
+    __syncthreads();
+    const float* x[DLSG_ENS_MAX];
+    float lse[DLSG_ENS_MAX];
+#pragma unroll
+    for (int m = 0; m < DLSG_ENS_MAX; ++m) {
+        x[m] = m < e.M ? e.x[m] + (int64_t)r * e.ld[m] : nullptr;
+        lse[m] = m < e.M ? lse_s[m] : 0.f;
+    }
+    float* c = comb + (int64_t)r * V;
+    if (e.M == 1) {
+        for (int j = tid; j < V; j += SF_THREADS) c[j] = x[0][j] - lse[0];
+    } else {
+        for (int j = tid; j < V; j += SF_THREADS) c[j] = beam_ens_combine(x, lse, e.w, e.logw, e.M, e.mode, j);
+    }
+    __syncthreads();
+    sample_filter_embed_body<true, false>(comb, V, V, tau, nullptr, ids_out, nullptr, 0, 0, logp, lens, t, end_id, 0.f, seed, 0u,
+                                          site_sample, row0, seed_ptr, top_k, top_p, min_len, g, hist, hist_stride, kept, excl);
 }
 
 // A forced prefix behind a sampled step (dlsg_sample_force_prefix): launched behind whichever of the three steps ran, on its
@@ -363,10 +405,11 @@ __global__ __launch_bounds__(256) void sample_force_prefix_kernel(const float* _
 
 // what the two sampled steps ask of their common arguments
 bool sample_args_ok(int V, int W, float temperature) { return V >= 1 && W >= 0 && temperature >= 0.f; }
-// and the two filtered steps of theirs; reads_hist: something looks at the row's earlier words from step 1 on
+// and the filtered steps of theirs; reads_hist: something looks at the row's earlier words from step 1 on; maxv: the widest row the
+// step holds in LDS
 bool sample_filter_args_ok(int V, int W, float temperature, int top_k, float top_p, int min_len, int no_repeat_ngram, int t, int rows,
-                           bool reads_hist, const int64_t* hist, int64_t hist_stride) {
-    return sample_args_ok(V, W, temperature) && V <= DLSG_SAMPLE_FILTER_MAXV && top_k >= 0 && top_p > 0.f && top_p <= 1.f &&
+                           bool reads_hist, const int64_t* hist, int64_t hist_stride, int maxv = DLSG_SAMPLE_FILTER_MAXV) {
+    return sample_args_ok(V, W, temperature) && V <= maxv && top_k >= 0 && top_p > 0.f && top_p <= 1.f &&
            min_len >= 0 && no_repeat_ngram >= 0 && t >= 0 && t < SF_MAXL && !(reads_hist && t > 0 && (!hist || hist_stride < rows));
 }
 #define ST(s) reinterpret_cast<hipStream_t>(s)
@@ -460,6 +503,39 @@ extern "C" int dlsg_sample_excl_embed(const float* logits, int64_t ld, int V, fl
     hipLaunchKernelGGL(sample_excl_embed_kernel, dim3(rows), dim3(SF_THREADS), (size_t)V * 4, ST(stream),
                        logits, ld, V, temperature, E, ids_out, out, ldo, W, logp, lens, t, end_id, p, seed, site_word, site_sample,
                        row0, seed_ptr, top_k, top_p, min_len, no_repeat_ngram, hist, hist_stride, kept, e);
+    DLSG_CHECK_LAUNCH();
+    return DLSG_OK;
+}
+
+extern "C" int dlsg_sample_ens(const float* const* logits, const int64_t* ld, const float* w, const float* logw, int M, int mode, int V,
+                               float temperature, float* comb, int64_t* ids_out, float* logp, int64_t* lens, int t, int64_t end_id,
+                               int rows, uint64_t seed, uint32_t site_sample, int64_t row0, const uint64_t* seed_ptr, int top_k,
+                               float top_p, int min_len, int no_repeat_ngram, const int64_t* hist, int64_t hist_stride, int32_t* kept,
+                               const int64_t* excl_shared, int NS, const int64_t* excl_clip, int NC, int P, int rows_per_clip,
+                               void* stream) {
+    EnsPack e;
+    if (!beam_ens_pack(logits, ld, w, logw, M, mode, e) || !beam_excl_ok(excl_shared, NS, excl_clip, NC, P)) return DLSG_EINVAL;
+    if (rows < 0 || rows_per_clip < 1 || rows % rows_per_clip != 0) return DLSG_EINVAL;
+    // a control: what makes the one-model sampler leave dlsg_sample_embed for a step that holds the row in LDS
+    const bool control = top_k > 0 || top_p < 1.f || min_len > 0 || no_repeat_ngram > 0 || NS + NC > 0;
+    if (!sample_filter_args_ok(V, 0, temperature, top_k, top_p, min_len, no_repeat_ngram, t, rows, no_repeat_ngram > 0 || NS + NC > 0, hist,
+                               hist_stride, control ? DLSG_SAMPLE_FILTER_MAXV : 0x7fffffff))
+        return DLSG_EINVAL;
+    if (rows == 0) return DLSG_OK;
+    if (!comb || !ids_out || !logp || !lens) return DLSG_EINVAL;
+    if (NS + NC == 0) P = 1;
+    static std::once_flag once;
+    static hipError_t attr_rc = hipSuccess;
+    std::call_once(once, [] {
+        attr_rc = hipFuncSetAttribute(reinterpret_cast<const void*>(&sample_ens_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                      DLSG_SAMPLE_FILTER_MAXV * 4);
+    });
+    if (attr_rc != hipSuccess) return DLSG_ELAUNCH;
+    const SampleExcl x{NS > 0 ? excl_shared : nullptr, NC > 0 ? excl_clip : nullptr, NS, NC, P, rows_per_clip};
+    // the candidate lists of the two threshold searches are the only use of the dynamic LDS
+    const size_t lds = temperature > 0.f && (top_k > 0 || top_p < 1.f) ? (size_t)V * 4 : 0;
+    hipLaunchKernelGGL(sample_ens_kernel, dim3(rows), dim3(SF_THREADS), lds, ST(stream), e, V, temperature, comb, ids_out, logp, lens, t,
+                       end_id, seed, site_sample, row0, seed_ptr, top_k, top_p, min_len, no_repeat_ngram, hist, hist_stride, kept, x);
     DLSG_CHECK_LAUNCH();
     return DLSG_OK;
 }

@@ -22,42 +22,7 @@ struct SeqPack {
     int M, mode;
 };
 
-// beam_ens_row_topk's two steps (beam.hpp), RESTATED here operation for operation: taking them out of that function as shared
-// helpers changed the code the compiler emits for the ensemble and group step kernels, and those stay as they are.
-// tests/test_gpu_rescore.py holds the two statements together: a word's value here equals the new_lp of dlsg_beam_select_hist /
-// dlsg_beam_select_ens bit for bit.
-// a member's row: its log-sum-exp, ONE wave, to every lane
-__device__ __forceinline__ float beam_row_lse(const float* x, int V, int lane) {
-    float mx = -INFINITY;
-    for (int j = lane; j < V; j += 64) mx = fmaxf(mx, x[j]);
-    mx = dlsg::wave_max(mx);
-    float sum = 0.f;
-    for (int j = lane; j < V; j += 64) sum += expf(x[j] - mx);
-    sum = dlsg::wave_sum(sum);
-    return logf(sum) + mx;
-}
-// class j's combined value from the members' rows x and their log-sum-exps
-__device__ __forceinline__ float beam_ens_combine(const float* const (&x)[DLSG_ENS_MAX], const float (&lse)[DLSG_ENS_MAX],
-                                                  const float (&w)[DLSG_ENS_MAX], const float (&logw)[DLSG_ENS_MAX], int M, int mode,
-                                                  int j) {
-    float c;
-    if (mode == 0) {
-        float v[DLSG_ENS_MAX], mx = -INFINITY, sum = 0.f;
-#pragma unroll
-        for (int m = 0; m < DLSG_ENS_MAX; ++m)
-            if (m < M) { v[m] = (x[m][j] - lse[m]) + logw[m]; mx = fmaxf(mx, v[m]); }
-#pragma unroll
-        for (int m = 0; m < DLSG_ENS_MAX; ++m)
-            if (m < M) sum += expf(v[m] - mx);
-        c = mx == -INFINITY ? -INFINITY : mx + logf(sum);
-    } else {
-        c = 0.f;
-#pragma unroll
-        for (int m = 0; m < DLSG_ENS_MAX; ++m)
-            if (m < M) c += w[m] * (x[m][j] - lse[m]);
-    }
-    return c;
-}
+// A member row's log-sum-exp and a class's combined value: beam_row_lse and beam_ens_combine (beam.hpp).
 
 // RANK: tok_rank is wanted.  With one member the count rides on the maximum pass over the raw logits (the row is read twice, as
 // without it); with several it is a third pass per member over the combined values.

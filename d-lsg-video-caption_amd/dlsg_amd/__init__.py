@@ -8,9 +8,10 @@ from .scst import SCSTTrainer  # noqa: F401
 from .beam import beam_search, beam_nbest, stochastic_nbest, sample_without_replacement, importance_weights  # noqa: F401
 from .beam import pack_exclusions, exclusions_hit, Exclusions, ExcludeNotCovered, BAD_ENDINGS  # noqa: F401
 from .beam import pack_prefix, check_prefix, PrefixNotCovered  # noqa: F401
+from .beam import sample, ensemble_sample, EnsembleSampleNotCovered  # noqa: F401
 from .beam import constrained_beam_search, constrained_nbest, pack_constraints, pack_phrases, phrases_met  # noqa: F401
 from .ensemble import Ensemble  # noqa: F401
-from .graphs import EnsembleBeamGraph, ConsensusBeamGraph, StochasticBeamGraph, ConstrainedBeamGraph  # noqa: F401
+from .graphs import EnsembleBeamGraph, EnsembleSampleGraph, ConsensusBeamGraph, StochasticBeamGraph, ConstrainedBeamGraph  # noqa: F401
 from .consensus import consensus_rerank, consensus_search  # noqa: F401
 from .rescore import score_captions, rescore, rescore_search  # noqa: F401
 from .graphs import ScoreGraph, RescoreBeamGraph  # noqa: F401

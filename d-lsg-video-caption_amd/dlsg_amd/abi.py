@@ -7,6 +7,7 @@ behind it).  The module parses the header once, when it is imported, and offers
   defines    {'DLSG_ABI_VERSION': 8, 'DLSG_GEMM_ACCUM': 1, ...}   every #define with an integer value
   structs    {'dlsg_gemm_args': <ctypes.Structure subclass>, ...}  also module attributes: abi.dlsg_gemm_args
   functions  {'dlsg_gemm': (restype, [argtypes]), ...}
+  extensions {'dlsg_sample_ens': (restype, [argtypes])}            the prototypes of the headers beside dlsg.h (EXTENSION_HEADERS)
 
 Types: the fixed-width integers, int, float and double map to their ctypes scalars; a pointer to a struct of the header
 is POINTER(that struct); every other pointer is c_void_p.
@@ -103,3 +104,14 @@ if not os.path.exists(HEADER):
 with open(HEADER) as _f:
     defines, structs, functions = parse(_f.read())
 globals().update(structs)
+
+# Entry points beside the versioned ABI: dlsg.h's list is what DLSG_ABI_VERSION counts; an addition that changes no existing entry point
+# stands in a header of its own next to it, in the same subset of C (prototypes only: no struct, no define), and is read the same way.
+EXTENSION_HEADERS = ('dlsg_sample_ens.h',)
+extensions = {}
+for _name in EXTENSION_HEADERS:
+    with open(os.path.join(os.path.dirname(HEADER), _name)) as _f:
+        _d, _s, _fn = parse(_f.read())
+    if _d or _s or set(_fn) & (set(functions) | set(extensions)):
+        raise RuntimeError('include/%s: an extension header declares new prototypes only' % _name)
+    extensions.update(_fn)

@@ -22,6 +22,8 @@ rank in the step it launches and in how `_constraints_met` counts.
 must not contain (`pack_exclusions`): `beam_select_excl` adds the last word of every excluded entry that a beam's history leads up to
 to the beam's ban list; `exclusions_hit` counts what a caption contains of them.  `stochastic_nbest(exclude=...)` draws its captions
 under the same tables (`beam_select_gumbel_excl`), the model renormalised over the words that are left, as its other bans do.
+`ensemble_sample` draws from an ensemble instead of searching with it: the members step as in `ensemble_nbest`, on rows that never
+change parents, and one `sample_ens` launch per word combines their rows and draws from the combined distribution.
 `prefix=` makes the history searches continue a given beginning (`pack_prefix`): behind the select launch of each of the first P
 steps `beam_force_prefix` rewrites the clips whose prefix reaches that step -- the forced word in every slot, its value on beam 0,
 -inf on the others -- and since bans and constraint state are recomputed from the history row, the prefix is seen by all of them.
@@ -308,6 +310,81 @@ def ensemble_nbest(models, weights, mode, visual_feats, region_feats, n_best=Non
     prefix: a forced beginning as in `beam_nbest`; a forced word's value is the members' combined one."""
     return _nbest_search(models, weights, mode, visual_feats, region_feats, n_best, length_penalty, no_repeat_ngram, min_len, beam_size,
                          num_groups, diversity_penalty, exclude, prefix)
+
+
+class EnsembleSampleNotCovered(ValueError):
+    """`Ensemble.sample` where it cannot run: with a keyword the sampled ensemble loop does not cover (prefix, share_encoder), or on
+    members whose ops object has no `sample_ens`.  A ValueError that names the combination."""
+
+
+def check_ensemble_sample(ops, dec, B, device, n, temperature, top_k=0, top_p=1.0, min_len=0, no_repeat_ngram=0, exclude=None,
+                          prefix=None, share_encoder=None):
+    """ValueError for what `ensemble_sample` cannot run, before any encoder does; returns the two exclusion tables (None, None without)"""
+    if prefix is not None:
+        raise EnsembleSampleNotCovered('prefix and Ensemble.sample: a forced beginning is not covered (the force launch writes one '
+                                       'member\'s embedding, and a forced word under c / temperature is a design of its own)')
+    if share_encoder is not None:
+        raise EnsembleSampleNotCovered('share_encoder and Ensemble.sample: the ensemble\'s loop always runs every member\'s encoder '
+                                       'once per clip; there is nothing to switch')
+    if int(n) != n or n < 1:
+        raise ValueError('n (%r): Ensemble.sample draws 1 or more captions per clip' % (n,))
+    if not temperature >= 0.0:                                         # (NaN fails the comparison)
+        raise ValueError('temperature (%r) must not be negative or NaN (0: greedy)' % (temperature,))
+    _check_max_words(dec.max_words, 'the ensemble\'s sampled step')
+    E.check_sample_options(dec.max_words, top_k, top_p, min_len, no_repeat_ngram, dec.vocab_size)
+    tables = E.sample_exclusions(exclude, B, device, dec.max_words, dec.vocab_size)
+    if not hasattr(ops, 'sample_ens'):
+        raise EnsembleSampleNotCovered('Ensemble.sample: %s has no sample_ens, the word step that draws from the members\' combined '
+                                       'distribution' % type(ops).__name__)
+    return tables if tables is not None else (None, None)
+
+
+@torch.no_grad()
+def ensemble_sample(models, weights, mode, visual_feats, region_feats, n=1, temperature=1.0, seed=None, top_k=0, top_p=1.0, min_len=0,
+                    no_repeat_ngram=0, exclude=None, return_kept=False, prefix=None, share_encoder=None):
+    """n captions per clip drawn from the ENSEMBLE's distribution: at every word the members' logit rows are combined into c
+    (`beam_select_ens`'s rule: mode 0 the log of the weighted mean probability, mode 1 the weighted mean log-probability) and the
+    word is drawn with probability proportional to exp(c / temperature) over the words the controls keep -- the temperature tempers
+    the combined distribution, not each member's; temperature 0 is greedy on c.  -> (ids (B*n, L) int64, logp (B*n, L) float32,
+    lens (B*n,) int64[, kept (B*n, L) int32]) as `CapGnnModel.sample` returns them, clip b owning rows b*n .. b*n + n - 1; logp is
+    the drawn word's log-probability under the renormalised distribution it was drawn from, kept the number of words it was drawn
+    from (always written here, so return_kept needs no control on).
+    The loop is the ensemble search's on rows that never change parents: every member encodes its B clips once and steps its own
+    state on R = B*n rows in eval mode (`_beam_setup` with k = n, the state gather on identity rows), and ONE `sample_ens` launch
+    per word combines the members' rows and draws -- row t of a time-major (L, R) id buffer, which is also the rows' history.  The
+    noise of row r at word t is keyed ((t + 1) R + r) V + j under (seed, SITE_SAMPLE): the noise `CapGnnModel.sample` gives that row
+    (an ensemble of one model ranks x - lse + noise where the model's own sampler ranks x + noise: the same draw up to the rounding
+    of the subtraction).  seed None draws the first
+    member's next seed; it may be a device word (a captured graph).  Nothing is read back.
+    top_k, top_p, min_len, no_repeat_ngram, exclude: the controls of `CapGnnModel.sample`, on the combined values; per-clip exclusions
+    are indexed by clip.  prefix and share_encoder are refused (`EnsembleSampleNotCovered`)."""
+    dec, ops = models[0].decoder, models[0].ops
+    shared, per_clip = check_ensemble_sample(ops, dec, visual_feats.shape[0], visual_feats.device, n, temperature, top_k, top_p, min_len,
+                                             no_repeat_ngram, exclude, prefix, share_encoder)
+    n = int(n)
+    if seed is None:
+        seed = models[0].next_seed()                                   # (before the encoders draw their own)
+    steps = []
+    for model in models:
+        mems, sv, own, _ = _encode(model, visual_feats, region_feats)
+        advance, B, R, L = _beam_setup(model, mems, sv, own, n)
+        steps.append(advance)
+    dev, end = mems[0].device, dec.vocab('<end>')
+    ids = torch.empty(L, R, dtype=torch.int64, device=dev)             # time-major: row t is step t's words, rows < t its history
+    logp = torch.empty(L, R, dtype=torch.float32, device=dev)
+    kept = torch.empty(L, R, dtype=torch.int32, device=dev)
+    lens = torch.full((R,), L, dtype=torch.int64, device=dev)
+    comb = torch.empty(R, dec.vocab_size, dtype=torch.float32, device=dev)
+    rows = torch.arange(R, dtype=torch.int64, device=dev)             # a row is its own parent at every step
+    words = torch.full((R,), dec.vocab('<start>'), dtype=torch.int64, device=dev)
+    for t in range(L):
+        logits = [advance(t, words, rows) for advance in steps]
+        ops.sample_ens(logits, weights, mode, comb, ids[t], logp[t], lens, t, end, temperature=float(temperature), seed=seed,
+                       site_sample=E.SITE_SAMPLE, row0=(t + 1) * R, top_k=top_k, top_p=top_p, min_len=min_len,
+                       no_repeat_ngram=no_repeat_ngram, hist=ids, kept=kept[t], excl_shared=shared, excl_clip=per_clip, rows_per_clip=n)
+        words = ids[t]
+    out = ids.t().contiguous(), logp.t().contiguous(), lens
+    return out + (kept.t().contiguous(),) if return_kept else out
 
 
 def check_stochastic_options(n, L, V, temperature, min_len=0, no_repeat_ngram=0, return_threshold=False):
@@ -862,3 +939,9 @@ def sample_without_replacement(model, visual_feats, region_feats, **options):
 def beam_search(model, visual_feats, region_feats, beam_size=None, **options):
     """`beam_nbest` with `beam_size` beams (default: the decoder's own, which is not changed)"""
     return beam_nbest(model, visual_feats, region_feats, beam_size=beam_size, **options)
+
+
+def sample(model_or_ensemble, visual_feats, region_feats, **options):
+    """the function form of `model.sample` and `Ensemble.sample`: the object's own sampler with `options` -- a CapGnnModel's sampled
+    decode, an ensemble's draw from its members' combined distribution (`ensemble_sample`)"""
+    return model_or_ensemble.sample(visual_feats, region_feats, **options)

@@ -1,8 +1,9 @@
 """Ensemble decoding: several trained models -- seeds of one configuration, CapGnnModel beside a baseline, the checkpoints a GAN run
 and an SCST run leave behind -- decode one caption per clip in ONE beam search.  Every member runs its own encoder and decode
 step; `dlsg_beam_select_ens` combines their logit rows on the device at every word (`beam.ensemble_nbest`), so the search has the
-launches of the members' searches plus nothing that touches the host.  An ensemble decodes, and it teaches: `teacher_logits`
-gives a `Trainer(teacher=...)` the members' teacher-forced rows, which `dlsg_ce_ragged_soft` combines by the same rule into the
+launches of the members' searches plus nothing that touches the host.  An ensemble decodes, it samples -- `sample` draws captions
+from the members' combined distribution, one `dlsg_sample_ens` launch per word (`beam.ensemble_sample`) -- and it teaches:
+`teacher_logits` gives a `Trainer(teacher=...)` the members' teacher-forced rows, which `dlsg_ce_ragged_soft` combines by the same rule into the
 word distribution a student is distilled towards; its own members it does not train."""
 import torch
 
@@ -61,6 +62,25 @@ class Ensemble(object):
     def greedy(self, visual_feats, region_feats):
         """(B, L) ids, <end>-padded: the search with one beam"""
         return self.beam_search(visual_feats, region_feats, beam_size=1, n_best=1)[0][:, 0]
+
+    def sample(self, visual_feats, region_feats, n=1, temperature=1.0, seed=None, top_k=0, top_p=1.0, min_len=0, no_repeat_ngram=0,
+               exclude=None, return_kept=False, **refused):
+        """n captions per clip drawn from the ensemble's own distribution: (ids (B*n, L), logp (B*n, L), lens (B*n,)[, kept]) with
+        the shapes and meanings of `CapGnnModel.sample`, clip b owning rows b*n .. b*n + n - 1.  At every word the members' rows are
+        combined as the beam search combines them and the word is drawn with probability proportional to exp(c / temperature) over
+        the words the controls keep (`beam.ensemble_sample`): the temperature tempers the ENSEMBLE's distribution; temperature 0 is
+        `greedy` up to lens.  Every member runs in eval mode, whatever its `.training` says, and encodes each clip once; the members
+        may be any of the three model classes, so `Ensemble([CapBaseline1(...)]).sample(...)` is the sampler those classes lack.
+        seed None draws the first member's next seed; a given seed reproduces the draw.  top_k, top_p, min_len, no_repeat_ngram,
+        exclude (per_clip indexed by clip), return_kept: as in `CapGnnModel.sample`.  prefix= and share_encoder= are refused with a
+        ValueError that names the combination, before any encoder runs."""
+        unknown = sorted(set(refused) - {'prefix', 'share_encoder'})
+        if unknown:
+            raise TypeError('Ensemble.sample got unexpected keyword arguments %s' % unknown)
+        from .beam import ensemble_sample
+        return ensemble_sample(self.members, self.weights, MODES[self.mode], visual_feats, region_feats, n=n, temperature=temperature,
+                               seed=seed, top_k=top_k, top_p=top_p, min_len=min_len, no_repeat_ngram=no_repeat_ngram, exclude=exclude,
+                               return_kept=return_kept, **refused)
 
     @torch.no_grad()
     def teacher_logits(self, frames, regions, captions, max_words=None, seq_per_clip=1):

@@ -1,7 +1,7 @@
 """hipGraph capture and replay, in one place: entering and leaving the process's capture stream, the eager warm-up, capturing one
 graph or a chain of segments, dropping a capture whose body raised, staging inputs into the static buffers a graph reads --
 and the captured forms of inference built on it (GreedyGraph, SampleGraph, BeamGraph, NBestBeamGraph, StochasticBeamGraph,
-ConstrainedBeamGraph, EnsembleBeamGraph, ConsensusBeamGraph, ScoreGraph, RescoreBeamGraph).  The Trainer (model.py), the GanTrainer (gan.py) and the SCSTTrainer (scst.py) capture through `capture` /
+ConstrainedBeamGraph, EnsembleBeamGraph, EnsembleSampleGraph, ConsensusBeamGraph, ScoreGraph, RescoreBeamGraph).  The Trainer (model.py), the GanTrainer (gan.py) and the SCSTTrainer (scst.py) capture through `capture` /
 `capture_segments`."""
 import torch
 
@@ -167,9 +167,9 @@ class _SeededGraph(_InferenceGraph):
 
     extra = 'seed'
 
-    def __init__(self, model, frames, regions):
+    def __init__(self, model, frames, regions, models=None):
         self.seed = torch.zeros(1, dtype=torch.int64, device=frames.device)
-        super().__init__(model, frames, regions)
+        super().__init__(model, frames, regions, models)
 
     def _fitted(self, seed):
         return [int(seed)]
@@ -318,6 +318,27 @@ class EnsembleBeamGraph(_InferenceGraph):
 
     def _run(self):
         return self.ensemble.beam_search(self.frames, self.regions, **self._search)
+
+
+class EnsembleSampleGraph(_SeededGraph):
+    """hipGraph-captured `ensemble.sample(frames, regions, n, temperature, **options)` (ensemble.Ensemble) for one batch shape: every
+    member's encoder and decode steps and one `sample_ens` per word.  The seed is read from a device word, like SampleGraph's, so every
+    replay draws afresh; a replay with seed s gives the bits of the eager call with seed=s.  options: top_k, top_p, min_len,
+    no_repeat_ngram, return_kept, fixed at capture; exclude=Exclusions: kept as `graph.exclude`, the graph's own copy of the two
+    tables, as SampleGraph keeps it.  Like EnsembleBeamGraph it holds addresses into EVERY member's arena and every member's train /
+    eval mode.  prefix= and share_encoder= are refused as `Ensemble.sample` refuses them.  Outputs are static buffers, valid until the
+    next replay; nothing synchronises."""
+
+    def __init__(self, ensemble, frames, regions, n=1, temperature=1.0, **options):
+        from .beam import check_ensemble_sample
+        self.ensemble, self.n, self.temperature = ensemble, n, temperature
+        check_ensemble_sample(ensemble.ops, ensemble.decoder, frames.shape[0], frames.device, n, temperature,
+                              **{key: v for key, v in options.items() if key != 'return_kept'})      # (refused before the warm-up runs)
+        self.options, self.exclude, self._draw = _held_exclusions(options)
+        super().__init__(ensemble.members[0], frames, regions, ensemble.members)
+
+    def _run(self):
+        return self.ensemble.sample(self.frames, self.regions, self.n, self.temperature, self.seed, **self._draw)
 
 
 class ConsensusBeamGraph(_InferenceGraph):

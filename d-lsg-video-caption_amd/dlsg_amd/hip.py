@@ -41,13 +41,14 @@ i64, u32, u64, f32 = C.c_int64, C.c_uint32, C.c_uint64, C.c_float
 
 
 def load_library(path=LIB_PATH):
-    """libdlsg_hip.so with the argtypes and restype of every entry point include/dlsg.h declares (dlsg_amd/abi.py reads them)"""
+    """libdlsg_hip.so with the argtypes and restype of every entry point include/dlsg.h and the extension headers beside it declare
+    (dlsg_amd/abi.py reads them)"""
     if not os.path.exists(path):
         raise RuntimeError('libdlsg_hip.so not built (%s): run `python -c "import __graft_entry__ as g; g.build()"` '
                            'or `make -C d-lsg-video-caption_amd/csrc`; there is no fallback path' % path)
     lib = C.CDLL(path)
-    for name, (restype, argtypes) in abi.functions.items():
-        fn = getattr(lib, name)  # AttributeError if the library does not export what the header declares
+    for name, (restype, argtypes) in list(abi.functions.items()) + list(abi.extensions.items()):
+        fn = getattr(lib, name)  # AttributeError if the library does not export what a header declares
         fn.restype, fn.argtypes = restype, argtypes
     if lib.dlsg_abi_version() != ABI_VERSION:
         raise RuntimeError('libdlsg_hip.so ABI mismatch: library %d, include/dlsg.h %d (rebuild: make -C d-lsg-video-caption_amd/csrc)'
@@ -1324,6 +1325,35 @@ class HipOps(object):
             *args, int(top_k), f32(top_p), int(min_len), int(no_repeat_ngram), _p(hist) if hist is not None else None,
             i64(hist.stride(0) if hist is not None else 0), _p(kept) if kept is not None else None, *tables, int(rows_per_clip),
             self._stream()), 'sample_excl_embed')
+
+    def sample_ens(self, logits_list, weights, mode, comb, ids_out, logp, lens, t, end_id, temperature=1.0, seed=0, site_sample=0, row0=0,
+                   top_k=0, top_p=1.0, min_len=0, no_repeat_ngram=0, hist=None, kept=None, excl_shared=None, excl_clip=None,
+                   rows_per_clip=1):
+        """A sampled word step of an ensemble: logits_list, weights, mode as `beam_select_ens` takes them; comb (rows, V) float32,
+        contiguous: the caller's workspace, which holds the rows' combined values on return; then ids_out[r] drawn from
+        exp(comb[r] / temperature) under the controls and tables of `sample_excl_embed`, with that step's noise, logp, lens and kept --
+        the bits of that step on comb as its logits -- and no embedding: the members embed the word themselves (see
+        include/dlsg_sample_ens.h)."""
+        rows, V, members = self._beam_members(logits_list, weights, comb.device)
+        control = top_k > 0 or top_p < 1.0 or min_len > 0 or no_repeat_ngram > 0
+        tables = self._excl_tables(excl_shared, excl_clip, rows // rows_per_clip if rows_per_clip >= 1 else 0, comb.device)
+        if V > SAMPLE_FILTER_MAXV and (control or tables[1] + tables[3] > 0):
+            raise ValueError('sample_ens holds a row of combined values in LDS under a control: vocabulary %d > %d' % (V, SAMPLE_FILTER_MAXV))
+        if rows_per_clip < 1 or rows % rows_per_clip:
+            raise ValueError('sample_ens: %d rows are not clips of rows_per_clip = %r rows' % (rows, rows_per_clip))
+        assert comb.dtype == torch.float32 and comb.shape == (rows, V) and comb.is_contiguous(), (comb.dtype, comb.shape)
+        assert ids_out.numel() == rows and logp.numel() == rows and lens.numel() == rows
+        assert ids_out.dtype == torch.int64 and lens.dtype == torch.int64 and logp.dtype == torch.float32
+        assert kept is None or (kept.dtype == torch.int32 and kept.numel() == rows and kept.is_contiguous())
+        if (no_repeat_ngram > 0 or tables[1] + tables[3] > 0) and t > 0:
+            assert hist is not None and hist.dtype == torch.int64 and hist.shape[0] >= t and hist.shape[1] == rows and \
+                hist.stride(1) == 1, 'hist: the rows\' earlier words, (>= t, rows) int64'
+        sd, sp = _seed(seed)
+        self._check(self.lib.dlsg_sample_ens(
+            *members, int(mode), V, f32(temperature), _p(comb), _p(ids_out), _p(logp), _p(lens), int(t), i64(end_id), rows, u64(sd),
+            u32(site_sample), i64(row0), sp, int(top_k), f32(top_p), int(min_len), int(no_repeat_ngram),
+            _p(hist) if hist is not None else None, i64(hist.stride(0) if hist is not None else 0), _p(kept), *tables,
+            int(rows_per_clip), self._stream()), 'sample_ens')
 
     def sample_force_prefix(self, logits, E, ids_out, out, logp, lens, t, prefix, L, temperature=1.0, p=0.0, seed=0, site=0, row0=0,
                             rows_per_clip=1, kept=None):

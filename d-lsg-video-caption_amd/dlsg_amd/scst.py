@@ -44,6 +44,9 @@ class SCSTTrainer(object):
 
     def __init__(self, model, reward, n_samples=5, baseline='mean', temperature=1.0, share_encoder=False, sample_options=None,
                  **trainer_kwargs):
+        if hasattr(model, 'members'):
+            raise ValueError('an Ensemble in SCSTTrainer: an ensemble samples in eval mode and trains none of its members; the policy '
+                             'gradient needs one model whose train pass reproduces the draw')
         if baseline not in ('mean', 'greedy'):
             raise ValueError("baseline must be 'mean' or 'greedy', not %r" % (baseline,))
         if baseline == 'mean' and n_samples < 2:
