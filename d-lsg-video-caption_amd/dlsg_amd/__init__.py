@@ -5,6 +5,7 @@ from .model import CapGnnModel, CapBaseline1, CapBaselineModel, Trainer, GreedyG
 from .gan import DiscV2, GanTrainer, GANLambdaHandler, save_checkpoint, load_checkpoint  # noqa: F401
 from .data import H5File, CaptionSet, ResidentFeatures, StreamedFeatures, TrainLoader, EvalLoader, distributed_indices  # noqa: F401
 from .scst import SCSTTrainer  # noqa: F401
+from .mrt import MRTTrainer, risk_loss_reference  # noqa: F401
 from .beam import beam_search, beam_nbest, stochastic_nbest, sample_without_replacement, importance_weights  # noqa: F401
 from .beam import pack_exclusions, exclusions_hit, Exclusions, ExcludeNotCovered, BAD_ENDINGS  # noqa: F401
 from .beam import pack_prefix, check_prefix, PrefixNotCovered  # noqa: F401

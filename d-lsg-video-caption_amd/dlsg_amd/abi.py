@@ -8,6 +8,7 @@ behind it).  The module parses the header once, when it is imported, and offers
   structs    {'dlsg_gemm_args': <ctypes.Structure subclass>, ...}  also module attributes: abi.dlsg_gemm_args
   functions  {'dlsg_gemm': (restype, [argtypes]), ...}
   extensions {'dlsg_sample_ens': (restype, [argtypes])}            the prototypes of the headers beside dlsg.h (EXTENSION_HEADERS)
+  addons     {'dlsg_risk_rows': (restype, [argtypes]), ...}        the prototypes of include/addons/*.h, read in sorted order
 
 Types: the fixed-width integers, int, float and double map to their ctypes scalars; a pointer to a struct of the header
 is POINTER(that struct); every other pointer is c_void_p.
@@ -115,3 +116,36 @@ for _name in EXTENSION_HEADERS:
     if _d or _s or set(_fn) & (set(functions) | set(extensions)):
         raise RuntimeError('include/%s: an extension header declares new prototypes only' % _name)
     extensions.update(_fn)
+
+
+# Every later entry point: one header per addition under include/addons/, prototypes only, read in sorted order.  A test pins the names
+# it owns ({'dlsg_x'} <= set(abi.addons)), never a total, so an addition leaves every earlier pin alone.
+ADDONS_DIR = os.path.join(os.path.dirname(HEADER), 'addons')
+
+
+def read_addons(directory, taken):
+    """{name: (restype, [argtypes])} of the *.h under `directory`; a struct, an integer #define, or a name in `taken` or in an earlier
+    addon header is an error that names the header and the line"""
+    out = {}
+    for name in sorted(os.listdir(directory)) if os.path.isdir(directory) else ():
+        if not name.endswith('.h'):
+            continue
+        with open(os.path.join(directory, name)) as f:
+            text = f.read()
+        d, s, fn = parse(text)
+
+        bare = re.sub(r'/\*.*?\*/|//[^\n]*', lambda c: '\n' * c.group(0).count('\n'), text, flags=re.S)   # (comments blanked, lines kept)
+
+        def line_of(word):
+            return bare.count('\n', 0, re.search(r'\b%s\b' % re.escape(word), bare).start()) + 1
+
+        for word in list(d) + list(s):
+            raise ValueError('include/addons/%s line %d: %s -- an addon header declares prototypes only' % (name, line_of(word), word))
+        for word in fn:
+            if word in taken or word in out:
+                raise ValueError('include/addons/%s line %d: %s is already declared' % (name, line_of(word), word))
+        out.update(fn)
+    return out
+
+
+addons = read_addons(ADDONS_DIR, set(functions) | set(extensions))

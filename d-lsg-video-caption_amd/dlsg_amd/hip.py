@@ -41,13 +41,13 @@ i64, u32, u64, f32 = C.c_int64, C.c_uint32, C.c_uint64, C.c_float
 
 
 def load_library(path=LIB_PATH):
-    """libdlsg_hip.so with the argtypes and restype of every entry point include/dlsg.h and the extension headers beside it declare
-    (dlsg_amd/abi.py reads them)"""
+    """libdlsg_hip.so with the argtypes and restype of every entry point include/dlsg.h, the extension headers beside it and the
+    headers under include/addons/ declare (dlsg_amd/abi.py reads them)"""
     if not os.path.exists(path):
         raise RuntimeError('libdlsg_hip.so not built (%s): run `python -c "import __graft_entry__ as g; g.build()"` '
                            'or `make -C d-lsg-video-caption_amd/csrc`; there is no fallback path' % path)
     lib = C.CDLL(path)
-    for name, (restype, argtypes) in list(abi.functions.items()) + list(abi.extensions.items()):
+    for name, (restype, argtypes) in list(abi.functions.items()) + list(abi.extensions.items()) + list(abi.addons.items()):
         fn = getattr(lib, name)  # AttributeError if the library does not export what a header declares
         fn.restype, fn.argtypes = restype, argtypes
     if lib.dlsg_abi_version() != ABI_VERSION:
@@ -1747,6 +1747,45 @@ class HipOps(object):
         self._check(self.lib.dlsg_ce_ragged_soft(_p(logits), _p(targets), _p(lens), _p(weights), _p(dlogits), _p(row_loss), _p(loss),
                                                  B, L, V, int(time_major), f32(smoothing), f32(alpha), ptrs, lds, ws, logws, M, int(mode),
                                                  self._stream()), 'ce_ragged_soft')
+
+    @staticmethod
+    def _risk_shape(logits, targets, lens, lse, tok_lp, n, time_major):
+        if time_major:
+            L, rows, V = logits.shape
+        else:
+            rows, L, V = logits.shape
+        assert logits.dtype == torch.float32 and logits.is_contiguous(), (logits.dtype, logits.stride())
+        assert targets.dtype == torch.int64 and targets.is_contiguous() and targets.shape == (rows, L), (targets.dtype, targets.shape)
+        assert lens.dtype == torch.int64 and lens.is_contiguous() and lens.numel() == rows
+        for x in (lse, tok_lp):
+            assert x.dtype == torch.float32 and x.is_contiguous() and x.numel() == rows * L, (x.dtype, x.shape)
+        assert int(n) == n, n
+        return rows, L, V
+
+    def risk_rows(self, logits, targets, lens, lse, tok_lp, n, time_major):
+        """the first launch of the minimum-risk loss (include/addons/dlsg_risk.h): lse and tok_lp (rows * L float32, the logits' row
+        order) of logits (rows, L, V) or, time_major, (L, rows, V); targets (rows, L) int64; lens (rows,) int64; n candidates per clip"""
+        rows, L, V = self._risk_shape(logits, targets, lens, lse, tok_lp, n, time_major)
+        self._check(self.lib.dlsg_risk_rows(_p(logits), _p(targets), _p(lens), _p(lse), _p(tok_lp), rows, int(n), L, V, int(time_major),
+                                            self._stream()), 'risk_rows')
+
+    def risk_grad(self, logits, targets, lens, lse, tok_lp, rewards, valid, dlogits, Q, s, R, loss, stats, n, time_major, alpha,
+                  length_penalty=0.0):
+        """the second launch, on what `risk_rows` wrote for the same logits: dlogits (as logits), Q and s (rows,) float64, R (rows / n,)
+        float64, loss (1,) float32, stats (4,) float64 {loss, mean reward and mean length of the counted candidates, mean R_b}.
+        rewards (rows,) float64; valid (rows,) bool or uint8, or None."""
+        rows, L, V = self._risk_shape(logits, targets, lens, lse, tok_lp, n, time_major)
+        assert dlogits.dtype == torch.float32 and dlogits.is_contiguous() and dlogits.shape == logits.shape, (dlogits.dtype, dlogits.shape)
+        assert rewards.dtype == torch.float64 and rewards.is_contiguous() and rewards.numel() == rows, (rewards.dtype, rewards.shape)
+        assert valid is None or (valid.dtype in (torch.bool, torch.uint8) and valid.is_contiguous() and valid.numel() == rows)
+        for x in (Q, s):
+            assert x.dtype == torch.float64 and x.is_contiguous() and x.numel() == rows, (x.dtype, x.shape)
+        assert R.dtype == torch.float64 and R.is_contiguous() and int(n) >= 1 and R.numel() >= rows // int(n), (R.dtype, R.shape, rows, n)
+        assert loss.dtype == torch.float32 and loss.is_contiguous() and loss.numel() == 1
+        assert stats.dtype == torch.float64 and stats.is_contiguous() and stats.numel() == 4
+        self._check(self.lib.dlsg_risk_grad(_p(logits), _p(targets), _p(lens), _p(lse), _p(tok_lp), _p(rewards), _p(valid), _p(dlogits),
+                                            _p(Q), _p(s), _p(R), _p(loss), _p(stats), rows, int(n), L, V, int(time_major), float(alpha),
+                                            float(length_penalty), self._stream()), 'risk_grad')
 
     def cider_d(self, ids, clip_idx, end_id, tables, out):
         """out[r] (float64) = CIDEr-D of the words of ids[r] (int64 (R, L), L <= 64, unit column stride; the words before the first

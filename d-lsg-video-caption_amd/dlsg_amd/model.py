@@ -841,6 +841,8 @@ class Trainer(object):
         self._hook_mode, self._hook_sv = False, None
         self._weighted_mode = False     # the captured graphs weight the CrossEntropy per caption (step(seq_weights=...))
         self._spc_mode = 1              # captions per clip of the captured graphs (step(seq_per_clip=...))
+        self._risk_mode = None          # (n, alpha, length_penalty) of the captured graphs' minimum-risk loss (step(risk=...)), or None
+        self.last_risk = None           # step(risk=...): device views {'Q', 's', 'R', 'stats'} of the last such step
         self.m = self.v = None
         if world_size > 1 or self.rehearse_ranks > 1:
             assert world_size == 1 or not self.rehearse_ranks, 'rehearse_ranks is for one-rank runs'
@@ -1352,7 +1354,7 @@ class Trainer(object):
 
     # ------------------------------------------------------------------ one step, as a schedule
     def _schedule(self, frames, regions, captions, cap_lens, coins, seed, dev_coins, on_bucket, extra_dlogits=None, seq_weights=None,
-                  seq_per_clip=1):
+                  seq_per_clip=1, risk=None):
         model, ops = self.model, self.model.ops
         L = captions.shape[1]
         sv = {}
@@ -1368,6 +1370,21 @@ class Trainer(object):
         s = sv['dec']
         Bn = captions.shape[0]
         dl = torch.empty_like(s['LOGITS'])
+        if risk is not None:
+            # minimum-risk training: the expected reward over each clip's n candidate rows; its two launches stand where the
+            # CrossEntropy's one stood (the weights depend on this pass's log-probabilities: they cannot be handed in)
+            n = risk['n']
+            f64 = dict(dtype=torch.float64, device=dl.device)
+            lse, tok_lp = (torch.empty(L * Bn, dtype=torch.float32, device=dl.device) for _ in range(2))
+            out = dict(Q=torch.empty(Bn // n, n, **f64), s=torch.empty(Bn // n, n, **f64), R=torch.empty(Bn // n, **f64),
+                       stats=torch.empty(4, **f64))
+            loss = torch.empty(1, dtype=torch.float32, device=dl.device)
+            ops.risk_rows(s['LOGITS'], captions, cap_lens, lse, tok_lp, n, time_major=True)
+            ops.risk_grad(s['LOGITS'], captions, cap_lens, lse, tok_lp, risk['rewards'], risk['mask'], dl, out['Q'], out['s'], out['R'],
+                          loss, out['stats'], n, time_major=True, alpha=risk['alpha'], length_penalty=risk['length_penalty'])
+            self.last_risk = out
+            model._engine_backward(sv, dl, None, None, None, training, seed, on_bucket=on_bucket, seq_per_clip=seq_per_clip)
+            return loss
         row_loss = torch.empty((3 if self._soft else 1) * L * Bn, dtype=torch.float32, device=dl.device)
         loss = torch.empty(3 if self._soft else 1, dtype=torch.float32, device=dl.device)
         if self._soft:
@@ -1404,7 +1421,7 @@ class Trainer(object):
 
     @torch.no_grad()
     def step(self, frames, regions, captions, cap_lens, tf_ratio, max_len=26, extra_dlogits=None, seed=None, seq_weights=None,
-             seq_per_clip=1):
+             seq_per_clip=1, risk=None):
         """One optimisation step.  Returns the (device) scalar loss of this rank's shard.
         extra_dlogits: optional callable (logits (L,B,V) time-major, saved-state dict) -> (L,B,V) gradient of an additional
         loss on the logits, added to the CrossEntropy's before the backward.  With use_graphs the captured step is cut at
@@ -1418,8 +1435,21 @@ class Trainer(object):
         rows, clip b's in rows b*n .. b*n+n-1.  The encoder and its backward run once per clip (`CapGnnModel.forward`), the loss
         is the same ragged CrossEntropy over all B*n captions, and the gradient arena, buckets, clipping and Adam are those of
         any step.  Encoder dropout is keyed by the clip row, decoder and word dropout by the caption row.  With use_graphs the
-        captured step is for one n and one pair of row counts; other batches run kernel by kernel."""
+        captured step is for one n and one pair of row counts; other batches run kernel by kernel.
+        risk: dict(rewards=, n=, mask=None, alpha=, length_penalty=0.0) -- minimum-risk training (Shen et al. 2016): captions holds
+        n candidate captions per clip, clip b's in rows b*n .. b*n+n-1, rewards (rows,) float64 or float32 their rewards and mask
+        (rows,) bool which of them count (None: all).  The loss is the negative expected reward under the model renormalised
+        over each clip's list, Q_bi ~ exp(alpha * s_bi / len_bi^length_penalty) with s_bi the caption's log-probability in THIS
+        pass; its two launches (`risk_rows`, `risk_grad`; include/addons/dlsg_risk.h has the arithmetic and the rules for masked
+        candidates and bad targets) replace the CrossEntropy's and everything else is the step as it was: seq_per_clip (= n: one
+        encoder pass per clip) or rows expanded n-fold, clipping, weight decay, the averaged weights, the data-parallel schedule.
+        The step returns the loss and `last_risk` holds device views 'Q' and 's' (B, n) float64, 'R' (B,) float64 and 'stats' (4,)
+        float64 {loss, mean reward and mean length of the counted candidates, mean R_b}.  With use_graphs this form of the step
+        is captured on its own for one (n, alpha, length_penalty), rewards and mask read from static buffers.  seq_weights,
+        extra_dlogits, label_smoothing, a teacher and tf_ratio != 1 are refused with it."""
         model, ops = self.model, self.model.ops
+        if risk is not None:
+            risk = self._check_risk(risk, captions, max_len, tf_ratio, extra_dlogits, seq_weights)
         if self._averaging:
             raise RuntimeError('step inside `with trainer.averaged():` -- the weight arena holds the averaged weights')
         n_seq = model._check_seq_per_clip(seq_per_clip, frames.shape[0], captions)
@@ -1436,19 +1466,53 @@ class Trainer(object):
         if weighted and not (torch.is_tensor(seq_weights) and seq_weights.device == captions.device
                              and seq_weights.dtype == torch.float32):
             seq_weights = _h2d(seq_weights, torch.float32, captions.device)
+        risk_key = None if risk is None else (risk['n'], risk['alpha'], risk['length_penalty'])
         if self.use_graphs and (self._graphs is None or (self._hook_mode == hook and self._weighted_mode == weighted
-                                                         and self._spc_mode == n_seq)):
-            loss = self._step_graphs(frames, regions, captions, cap_lens, coins, seed, extra_dlogits, seq_weights, n_seq)
+                                                         and self._spc_mode == n_seq and self._risk_mode == risk_key)):
+            loss = self._step_graphs(frames, regions, captions, cap_lens, coins, seed, extra_dlogits, seq_weights, n_seq, risk)
         else:
             # (a trainer's graphs are captured for one form of the step; the other forms run kernel by kernel)
             loss = self._eager_step(frames, regions, captions, cap_lens, coins, seed, counted=True, extra_dlogits=extra_dlogits,
-                                    seq_weights=seq_weights, seq_per_clip=n_seq)
+                                    seq_weights=seq_weights, seq_per_clip=n_seq, risk=risk)
         if self.check_every and self.t % self.check_every == 0:
             self.check()
         return loss
 
+    RISK_MAX_N, RISK_MAX_L = 32, 64    # csrc/risk.hip: one lane per candidate, words per caption
+
+    def _check_risk(self, risk, captions, max_len, tf_ratio, extra_dlogits, seq_weights):
+        """step(risk=...) as `_schedule` takes it: n int, alpha and length_penalty floats, rewards float64 and mask bool (or None)
+        on the captions' device; ValueError for what the minimum-risk step does not cover"""
+        for what, on in (('seq_weights', seq_weights is not None), ('extra_dlogits', extra_dlogits is not None),
+                         ('label_smoothing', self.label_smoothing > 0.0), ('teacher', self.teacher is not None),
+                         ('tf_ratio != 1', float(tf_ratio) != 1.0)):
+            if on:
+                raise ValueError('risk with %s: the minimum-risk loss replaces the CrossEntropy, teacher-forced on the candidates; '
+                                 '%s belongs to the CrossEntropy step' % (what, what))
+        if not isinstance(risk, dict) or set(risk) - {'rewards', 'n', 'mask', 'alpha', 'length_penalty'} \
+                or not {'rewards', 'n', 'alpha'} <= set(risk):
+            raise ValueError('risk must be dict(rewards=, n=, mask=None, alpha=, length_penalty=0.0), not %r'
+                             % (sorted(risk) if isinstance(risk, dict) else risk,))
+        n, alpha, lp = int(risk['n']), float(risk['alpha']), float(risk.get('length_penalty', 0.0))
+        rows, L = captions.shape[0], min(captions.shape[1], max_len)
+        if not 1 <= n <= self.RISK_MAX_N or n != risk['n'] or rows % n:
+            raise ValueError('risk: n must be in 1..%d and divide the %d caption rows, not %r' % (self.RISK_MAX_N, rows, risk['n']))
+        if L > self.RISK_MAX_L:
+            raise ValueError('risk: captions of %d words; the minimum-risk kernels take %d' % (L, self.RISK_MAX_L))
+        if not (alpha >= 0.0 and math.isfinite(alpha) and math.isfinite(lp)):
+            raise ValueError('risk: alpha must be finite and >= 0 and length_penalty finite, not %r, %r' % (risk['alpha'], lp))
+        rewards, mask = risk['rewards'], risk.get('mask')
+        if not (torch.is_tensor(rewards) and rewards.device == captions.device and rewards.shape == (rows,)
+                and rewards.dtype in (torch.float64, torch.float32)):
+            raise ValueError('risk: rewards must be a (%d,) float64 or float32 tensor on %s' % (rows, captions.device))
+        if mask is not None and not (torch.is_tensor(mask) and mask.device == captions.device and mask.shape == (rows,)
+                                     and mask.dtype == torch.bool):
+            raise ValueError('risk: mask must be None or a (%d,) bool tensor on %s' % (rows, captions.device))
+        return dict(rewards=rewards.to(torch.float64).contiguous(), mask=None if mask is None else mask.contiguous(), n=n,
+                    alpha=alpha, length_penalty=lp)
+
     def _eager_step(self, frames, regions, captions, cap_lens, coins, seed, counted=False, extra_dlogits=None, seq_weights=None,
-                    seq_per_clip=1):
+                    seq_per_clip=1, risk=None):
         model, ops = self.model, self.model.ops
         if not counted:
             self.t += 1
@@ -1457,7 +1521,7 @@ class Trainer(object):
             dev_coins = _h2d([int(c) for c in coins], torch.int32, captions.device)
         self._works = []
         loss = self._schedule(frames, regions, captions, cap_lens, coins, seed, dev_coins, self._allreduce, extra_dlogits, seq_weights,
-                              seq_per_clip)
+                              seq_per_clip, risk)
         self._reduce_guard()
         for w in self._works:
             w.wait()
@@ -1474,15 +1538,20 @@ class Trainer(object):
         return loss
 
     # ------------------------------------------------------------------ hipGraph path
-    def _capture(self, frames, regions, captions, cap_lens, hook=False, weighted=False, seq_per_clip=1):
+    def _capture(self, frames, regions, captions, cap_lens, hook=False, weighted=False, seq_per_clip=1, risk=None):
         dev = frames.device
         L = captions.shape[1]
         self._hook_mode, self._hook_sv = hook, None
         self._weighted_mode = weighted
         self._spc_mode = seq_per_clip
+        self._risk_mode = None if risk is None else (risk['n'], risk['alpha'], risk['length_penalty'])
         st = self._static = dict(frames=frames.clone(), regions=regions.clone(), captions=captions.clone(),
                                  lens=cap_lens.clone())
         st['weights'] = torch.ones(captions.shape[0], dtype=torch.float32, device=dev) if weighted else None
+        # the minimum-risk form reads rewards and mask from static buffers (a step without a mask fills it with True: every
+        # candidate counts, the bits of mask=None); n, alpha and length_penalty are constants of the captured launches
+        st['risk'] = None if risk is None else dict(risk, rewards=torch.zeros(captions.shape[0], dtype=torch.float64, device=dev),
+                                                    mask=torch.ones(captions.shape[0], dtype=torch.bool, device=dev))
         # what changes every step besides the batch -- the scheduled-sampling coins, the dropout seed, Adam's bias corrections --
         # lives in ONE device buffer (int32 words: coins | seed (int64) | hyper (2 x float32; 4 with weight decay or averaged
         # weights)), so that a step sends it as one copy
@@ -1503,7 +1572,8 @@ class Trainer(object):
             # (with RCCL the warm-up also runs the collectives once: channel buffers are set up before the capture;
             #  nothing is updated: Adam is not part of the schedule)
             self._schedule(st['frames'], st['regions'], st['captions'], st['lens'], None, st['seed'], st['coins'],
-                           self._allreduce if mode == 'rccl' else None, seq_weights=st['weights'], seq_per_clip=seq_per_clip)
+                           self._allreduce if mode == 'rccl' else None, seq_weights=st['weights'], seq_per_clip=seq_per_clip,
+                           risk=st['risk'])
             if mode == 'rccl':
                 self._reduce_guard()
             self._join_comm()
@@ -1530,7 +1600,7 @@ class Trainer(object):
                 return st['extra']
 
             loss = self._schedule(st['frames'], st['regions'], st['captions'], st['lens'], None, st['seed'], st['coins'], cut,
-                                  placeholder if hook else None, st['weights'], seq_per_clip)
+                                  placeholder if hook else None, st['weights'], seq_per_clip, st['risk'])
             if mode != 'torch':
                 # no host-issued collective between backward and update: Adam is part of the graph, behind the join of the
                 # side stream's collectives; with host-issued collectives it follows their waits
@@ -1549,15 +1619,16 @@ class Trainer(object):
             raise
         self._graphs, self._loss = graphs, loss
         st['parts'] = self.last_loss_parts        # (the captured launch's three floats: every replay rewrites them)
+        st['risk_out'] = self.last_risk if risk is not None else None
         self._adam_in_graph = mode != 'torch'
 
-    def _capture_agreed(self, frames, regions, captions, cap_lens, hook, weighted=False, seq_per_clip=1):
+    def _capture_agreed(self, frames, regions, captions, cap_lens, hook, weighted=False, seq_per_clip=1, risk=None):
         """`_capture`, and with several ranks the agreement on its outcome: returns None when EVERY rank captured, else the error
         (this rank's own, or a stand-in when only another rank failed) after dropping this rank's graphs -- so that all ranks take
         the same fallback together"""
         err = None
         try:
-            self._capture(frames, regions, captions, cap_lens, hook, weighted, seq_per_clip)
+            self._capture(frames, regions, captions, cap_lens, hook, weighted, seq_per_clip, risk)
         except Exception as e:            # (any failure votes: an AssertionError on one rank must not leave the others in the vote)
             err = e
         if self.world_size > 1:
@@ -1623,12 +1694,13 @@ class Trainer(object):
         st = self._static
         return st['frames'], st['regions'], st['captions'], st['lens']
 
-    def _step_graphs(self, frames, regions, captions, cap_lens, coins, seed, extra_dlogits=None, seq_weights=None, seq_per_clip=1):
+    def _step_graphs(self, frames, regions, captions, cap_lens, coins, seed, extra_dlogits=None, seq_weights=None, seq_per_clip=1,
+                     risk=None):
         model, ops = self.model, self.model.ops
         hook = extra_dlogits is not None
         weighted = seq_weights is not None
         if self._graphs is None:
-            err = self._capture_agreed(frames, regions, captions, cap_lens, hook, weighted, seq_per_clip)
+            err = self._capture_agreed(frames, regions, captions, cap_lens, hook, weighted, seq_per_clip, risk)
             if err is not None and self.graph_fallback and self._comm_mode() == 'rccl' and self.world_size > 1:
                 # the in-graph RCCL capture was refused somewhere: EVERY rank retries the segmented form (torch.distributed
                 # collectives issued by the host between graph segments) -- a rank replaying graphs that hold private-communicator
@@ -1638,7 +1710,7 @@ class Trainer(object):
                               'torch.distributed collectives between graph segments' % (type(err).__name__, err))
                 torch.cuda.synchronize()
                 self.comm = 'torch'
-                err = self._capture_agreed(frames, regions, captions, cap_lens, hook, weighted, seq_per_clip)
+                err = self._capture_agreed(frames, regions, captions, cap_lens, hook, weighted, seq_per_clip, risk)
             if err is not None:
                 if not self.graph_fallback:
                     raise err
@@ -1648,17 +1720,24 @@ class Trainer(object):
                 torch.cuda.synchronize()
                 self.use_graphs, self._graphs = False, None
                 return self._eager_step(frames, regions, captions, cap_lens, coins, seed, counted=True, extra_dlogits=extra_dlogits,
-                                        seq_weights=seq_weights, seq_per_clip=seq_per_clip)
+                                        seq_weights=seq_weights, seq_per_clip=seq_per_clip, risk=risk)
         st = self._static
         if (frames.shape, regions.shape, captions.shape) != (st['frames'].shape, st['regions'].shape, st['captions'].shape):
             # a batch of another shape (the short last batch of an epoch; other clip or caption row counts): the captured graphs
             # are for one shape only
             return self._eager_step(frames, regions, captions, cap_lens, coins, seed, counted=True, extra_dlogits=extra_dlogits,
-                                    seq_weights=seq_weights, seq_per_clip=seq_per_clip)
+                                    seq_weights=seq_weights, seq_per_clip=seq_per_clip, risk=risk)
         for k, src in (('frames', frames), ('regions', regions), ('captions', captions), ('lens', cap_lens)):
             stage(st[k], src)
         if weighted:
             st['weights'].copy_(seq_weights, non_blocking=True)
+        if risk is not None:
+            st['risk']['rewards'].copy_(risk['rewards'], non_blocking=True)
+            if risk['mask'] is None:
+                st['risk']['mask'].fill_(True)
+            else:
+                st['risk']['mask'].copy_(risk['mask'], non_blocking=True)
+            self.last_risk = st['risk_out']
         self._send_scalars(coins, seed, self._hyper())
         self.last_loss_parts = st['parts']
         self._works = []
